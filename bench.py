@@ -28,10 +28,15 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
             config.dense_64k_roofline / config.c4_roofline.  The HBM view (counter traffic / time / 8 TB/s) is
             kept as roofline.hbm_frac; SURVEY §8(d)'s "bytes the reference's flat traversal streams" is a
             property of the workload, reported in config, not a rate.
-  config.c4_strong = BASELINE config 5 measured in the same run at whatever N the driver chose: the 4x4 bunny grid
+  config.c4_strong = (--full) BASELINE config 5 measured in the same run at whatever N the driver chose: the 4x4 bunny grid
             @4096x4096, one frame per step row-tiled over the N ranks, gathered to rank 0 (frame ms, Mrays/s).
-  cpu_baseline = the CPU checker (oracle/_ref = the reference's own headers built for the host
+  cpu_baseline = (--full) the CPU checker (oracle/_ref = the reference's own headers built for the host
             when present, else the plain-C port) on a bounded row sample of the same workload.
+
+  A plain run sets up, warms up, times the K steps and prints the line (its roofline comes from this run's kernel
+  events and the committed profiles).  --full adds every side measurement: the image-order probe, config.c4_strong,
+  config.two_steps_in_flight, the untimed extras, cpu_baseline and config.dense_64k_roofline / c4_roofline.
+  --dump-outputs DIR writes the frames of the last timed step (see dump_outputs) for output-by-output comparisons.
 """
 import argparse
 import json
@@ -79,7 +84,38 @@ def parse_args():
     p.add_argument("--counters-json", default="", help="PMC-derived per-launch counters (default profiles/r02/counters.json)")
     p.add_argument("--no-extras", action="store_true", help="skip the untimed extra measurements (first launch, host-buffer "
                    "call, lane statistics, dense mesh): profiling runs")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the image-order probe, the C4 strong leg, two steps in "
+                        "flight, the untimed extras, the CPU baseline and the roofline constants of the other scenes "
+                        "(--skip-probe, --no-extras and --no-cpu-baseline still drop their part).  Off: set up, warm up, time the "
+                        "steps, write --dump-outputs, print the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps write what the last one computed (the frame(s) rank 0 assembled: depth, color, "
+                        "normal; the step's ray count) as DIR/<name>.npy, float32 / float64; above %d MB in all a fixed, "
+                        "seeded sample of the pixels (DIR/pixel_index.npy)" % (DUMP_LIMIT_BYTES // 10**6))
     return p.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, frames, rays_step):
+    """Write the last timed step's outputs: depth (F, h, w), color / normal (F, h, w, 3) in float32 and ray_count (1,) in
+    float64.  When the frames exceed DUMP_LIMIT_BYTES, the same seeded sample of pixels (flat index over frame, row,
+    column; pixel_index.npy) is taken from each array, so two runs with the same arguments write the same pixels."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in frames.items()}
+    n_px = arrays["depth"].size
+    px_bytes = sum(a.size // n_px for a in arrays.values()) * 4
+    if n_px * px_bytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - 10**6) // (px_bytes + 8)   # (+ 8: the pixel's float64 index; 1 MB for headers and rays)
+        idx = np.sort(np.random.default_rng(20251016).choice(n_px, size=keep, replace=False))
+        arrays = {k: a.reshape(n_px, -1)[idx].reshape((keep,) + a.shape[3:]) for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    arrays["ray_count"] = np.array([rays_step], dtype=np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
 
 
 def cpu_baseline(ca, host_scene, bounces, div):
@@ -481,9 +517,12 @@ def main():
         hs.set_size(args.width, args.height)
     w, h = hs.size
     sim = args.of if (world == 1 and args.of > 1) else 0
+    if sim and args.dump_outputs:
+        raise SystemExit("bench.py --dump-outputs: --of renders one rank's rows and assembles no frame")
 
-    def measure(hs, scaling, roots, steps, warmup, probe, in_flight=1):
-        """One workload through the tiler: -> (ds, tiler, frames, dt_max, rays_step, kern_avg, kern_io)."""
+    def measure(hs, scaling, roots, steps, warmup, probe, in_flight=1, snapshot=None):
+        """One workload through the tiler: -> (ds, tiler, frames, dt_max, rays_step, kern_avg, kern_io).  `snapshot` (a dict):
+        filled with host copies of the frames this rank assembled in the last timed step, before anything else runs."""
         w, h = hs.size
         # in_flight == 2: two scene handles (each keeps its own counters, tile costs and dispatch order: launches on ONE handle
         # must not overlap) on two streams, used alternately
@@ -560,6 +599,8 @@ def main():
             render_step(events)
         barrier()
         dt = time.perf_counter() - t0
+        if snapshot is not None and tiler.final_frames:
+            snapshot.update({k: v.cpu().numpy() for k, v in tiler.final.items()})
 
         kern_ms = [a.elapsed_time(b) for a, b in events]
         # for the record (untimed): the same launch with tiles dispatched in image order, i.e. what the
@@ -586,8 +627,12 @@ def main():
             dt_max, rays_step, kern_avg = dt, float(rays_rank_step), float(t[2])
         return ds, tiler, frames, dt_max, rays_step, kern_avg, kern_io
 
+    last_step = {} if args.dump_outputs else None
     ds, tiler, frames, dt_max, rays_step, kern_avg, kern_io = measure(hs, args.scaling, args.roots, args.steps, args.warmup,
-                                                                       not args.skip_probe, args.in_flight)
+                                                                       args.full and not args.skip_probe, args.in_flight,
+                                                                       last_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step, rays_step)
 
     if args.check and not sim:
         import numpy as np
@@ -627,7 +672,7 @@ def main():
                   "frame_ms": dt_max / args.steps * 1e3 / frames,
                   "unique_mrays_per_s": (rays_step - frames * w * h) * args.steps / dt_max / 1e6,
                   "steps_in_flight": args.in_flight}
-        for tag, key in (("dense64k", "dense_64k_roofline"), ("c4", "c4_roofline")):
+        for tag, key in ((("dense64k", "dense_64k_roofline"), ("c4", "c4_roofline")) if args.full else ()):
             r_ = roofline_from_profiles(PROFILE_WORKLOADS[tag], 0.0, "")
             if r_.get("frac") is not None:  # (constants of the committed PMC passes: that scene is not timed live here)
                 config[key] = {k: r_[k] for k in ("frac", "valu_insts_per_launch", "mean_issue_cycles_per_valu", "cycles_per_launch",
@@ -657,17 +702,19 @@ def main():
             time.sleep(3.0)   # (rank 0 prints first)
         os._exit(0)
 
+    # the side measurements below run with --full only: a plain run prints the line as it stands
+    extras_on = args.full and not args.no_extras
     deadline = float(os.environ.get("CUTRACE_BENCH_EXTRAS_DEADLINE_S", "900" if world == 1 else "420"))
     watchdog = threading.Timer(deadline, emit_and_leave, args=(f"abandoned after {deadline:.0f} s (a side measurement did not return)",))
     watchdog.daemon = True
-    if not args.no_extras:
+    if extras_on:
         watchdog.start()
 
     try:
         # BASELINE config 5 next to the metric's workload, at every N the driver runs: the 4x4 bunny grid @4096x4096, ONE frame
         # per step row-tiled over all ranks and gathered to rank 0 (strong scaling), untimed for `value`
         c4_leg = None
-        if not args.no_extras and args.workload != "c4" and not sim and os.path.basename(args.scene) == "bunny.json" and not (args.width or args.height):
+        if extras_on and args.workload != "c4" and not sim and os.path.basename(args.scene) == "bunny.json" and not (args.width or args.height):
             import tempfile
             from cutrace_amd import scenes
             c4_hs = ca.HostScene.load(scenes.make_bunny_grid(tempfile.mkdtemp(prefix=f"c4_r{rank}_")))
@@ -696,7 +743,7 @@ def main():
                 c4_leg["live_lanes"] = _live_summary(ca.DeviceScene.lane_stats(reset=True))
                 c4_ds.close()
             del c4_tiler
-        if not args.no_extras and args.in_flight == 1 and not sim:
+        if extras_on and args.in_flight == 1 and not sim:
             # the timed workload once more with two steps in flight (--in-flight 2), untimed for `value`
             _, t2_tiler, _, t2_dt, t2_rays, _, _ = measure(hs, args.scaling, args.roots, args.steps, args.warmup, False, 2)
             if rank == 0:
@@ -706,9 +753,9 @@ def main():
                             "slots the tail of step k leaves empty; `value` above is measured with one launch after the other"}
             del t2_tiler
         if rank == 0:
-            if world == 1 and not args.no_extras:
+            if world == 1 and extras_on:
                 out["config"].update(extras(ca, hs, args, ds))
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(ca, hs, args.bounces, args.cpu_sample_div)
     except Exception as e:  # noqa: BLE001 — whatever goes wrong in a side measurement must not cost the timed result
         import traceback
