@@ -28,6 +28,12 @@ VAR_IMAGE_ORDER_FIRST = 2048
 VAR_MERGE = 4096
 VAR_IGNORE_TRANSPARENT = 8192
 
+# ctr_cast_rays flags (include/cutrace_rays.h)
+RAY_IGNORE_TRANSPARENT = 1
+RAY_LINEAR = 2
+RAY_SHADOW = 4
+RAY_OUTPUTS = ("t", "object", "prim", "point", "normal", "uv")
+
 
 @contextlib.contextmanager
 def _cwd(path):
@@ -273,6 +279,100 @@ class DeviceScene:
                     kinds[label] = {"lanes": c[base + d], "trips": c[32 + base + d],
                                     "lanes_per_trip": c[base + d] / c[32 + base + d]}
         out["by_kind"] = kinds
+        return out
+
+    # ---- ray queries (ctr_cast_rays, include/cutrace_rays.h) ----
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self.device)
+
+    def _rays_arg(self, x, what, cols):
+        """(n, cols) float32 (cols 0: (n,)) on the scene's device: a tensor already there is used in place (made contiguous),
+        a CPU tensor or a numpy array is copied over; another GPU, another shape or dtype raise."""
+        import torch
+        dev = self._torch_device()
+        if isinstance(x, torch.Tensor):
+            if x.device.type != "cpu" and x.device != dev:
+                raise ValueError(f"{what}: tensor on {x.device}, the scene lives on {dev}")
+        elif isinstance(x, np.ndarray):
+            x = torch.from_numpy(x)
+        else:
+            raise TypeError(f"{what}: expected a torch tensor or a numpy array, got {type(x).__name__}")
+        shape_ok = x.dim() == 1 if cols == 0 else (x.dim() == 2 and x.shape[1] == cols)
+        if x.dtype != torch.float32 or not shape_ok:
+            raise ValueError(f"{what}: expected float32 of shape {'(n,)' if cols == 0 else f'(n, {cols})'}, "
+                             f"got {x.dtype} {tuple(x.shape)}")
+        return x.to(dev, non_blocking=False).contiguous()
+
+    def _cast(self, q, keep, stream):
+        """Fill the query's ray pointers from `keep` and launch on the stream (torch's current one of the scene's device)."""
+        import torch
+        q.n_rays = keep[0].shape[0]
+        q.d_origin, q.d_dir = keep[0].data_ptr() or None, keep[1].data_ptr() or None
+        st = _lib.hip_lib().ctr_cast_rays(self._h, C.byref(q), C.c_void_p(stream.cuda_stream))
+        if st:
+            raise RuntimeError(f"ctr_cast_rays failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
+
+    def _per_ray(self, x, n, what):
+        """A scalar, or (n,) float32 per-ray values: (scalar, tensor or None)."""
+        if isinstance(x, (int, float, np.integer, np.floating)):
+            return float(x), None
+        v = self._rays_arg(x, what, 0)
+        if v.shape[0] != n:
+            raise ValueError(f"{what}: {v.shape[0]} values for {n} rays")
+        return 0.0, v
+
+    def cast_rays(self, origins, dirs, min_t=1e-3, ignore_transparent=False, linear=False, outputs=None, stream=None):
+        """ray_cast (inc/ray_cast.hpp:29-55) of every ray (origins[k], dirs[k]): a dict of tensors on the scene's device,
+        `t` (n,) (+inf: miss), `object` (n,) int32 (-1: miss), `prim` (n,) int32 (file-order triangle of a mesh hit, else -1),
+        `point` (n, 3), `normal` (n, 3), `uv` (n, 2) — or the subset named in `outputs`.  origins, dirs: (n, 3) float32;
+        min_t: a scalar or (n,) float32.  Directions need not be normalised (a sphere measures t along dir/|dir|).
+        linear=True: meshes walked linearly — bit-identical to the reference also for rays in a triangle's plane.
+        Asynchronous on `stream` (a torch.cuda.Stream; default: torch's current stream of the scene's device)."""
+        import torch
+        outputs = RAY_OUTPUTS if outputs is None else tuple(outputs)
+        bad = [k for k in outputs if k not in RAY_OUTPUTS]
+        if bad or not outputs:
+            raise ValueError(f"outputs: a non-empty subset of {RAY_OUTPUTS}, got {outputs}")
+        dev = self._torch_device()
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            o = self._rays_arg(origins, "origins", 3)
+            d = self._rays_arg(dirs, "dirs", 3)
+            n = o.shape[0]
+            if d.shape[0] != n:
+                raise ValueError(f"dirs: {d.shape[0]} rays for {n} origins")
+            q = _lib.RayQuery()
+            q.flags = (RAY_IGNORE_TRANSPARENT if ignore_transparent else 0) | (RAY_LINEAR if linear else 0)
+            q.min_t, mt = self._per_ray(min_t, n, "min_t")
+            q.d_min_t = mt.data_ptr() if mt is not None and n else None
+            shapes = {"t": ((n,), torch.float32), "object": ((n,), torch.int32), "prim": ((n,), torch.int32),
+                      "point": ((n, 3), torch.float32), "normal": ((n, 3), torch.float32), "uv": ((n, 2), torch.float32)}
+            out = {k: torch.empty(*shapes[k][0], dtype=shapes[k][1], device=dev) for k in outputs}
+            for k, v in out.items():
+                setattr(q, "d_" + k, v.data_ptr() if n else None)
+            if n:
+                self._cast(q, (o, d, mt), torch.cuda.current_stream(dev))
+        return out
+
+    def shadow(self, origins, dirs, max_t, linear=False, stream=None):
+        """shadow_intensity (inc/shading.hpp:22-45) of every ray: (n,) float32 on the scene's device, 1 = fully blocked.
+        max_t: a scalar or (n,) float32.  The loop's first cast starts at (float)(0.0 + 1e-3), as the reference's does."""
+        import torch
+        dev = self._torch_device()
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            o = self._rays_arg(origins, "origins", 3)
+            d = self._rays_arg(dirs, "dirs", 3)
+            n = o.shape[0]
+            if d.shape[0] != n:
+                raise ValueError(f"dirs: {d.shape[0]} rays for {n} origins")
+            q = _lib.RayQuery()
+            q.flags = RAY_SHADOW | (RAY_LINEAR if linear else 0)
+            q.max_t, mx = self._per_ray(max_t, n, "max_t")
+            q.d_max_t = mx.data_ptr() if mx is not None and n else None
+            out = torch.empty(n, dtype=torch.float32, device=dev)
+            q.d_shadow = out.data_ptr() if n else None
+            if n:
+                self._cast(q, (o, d, mx), torch.cuda.current_stream(dev))
         return out
 
     def tile_costs(self):

@@ -65,6 +65,14 @@ class RenderStats(C.Structure):
                 ("rows", C.c_uint64), ("max_depth", C.c_float), ("reserved", C.c_uint32)]
 
 
+class RayQuery(C.Structure):
+    """ctr_ray_query (include/cutrace_rays.h)"""
+    _fields_ = [("n_rays", C.c_uint64), ("flags", C.c_uint32), ("min_t", C.c_float), ("max_t", C.c_float),
+                ("reserved", C.c_uint32), ("d_origin", C.c_void_p), ("d_dir", C.c_void_p), ("d_min_t", C.c_void_p),
+                ("d_max_t", C.c_void_p), ("d_t", C.c_void_p), ("d_object", C.c_void_p), ("d_prim", C.c_void_p),
+                ("d_point", C.c_void_p), ("d_normal", C.c_void_p), ("d_uv", C.c_void_p), ("d_shadow", C.c_void_p)]
+
+
 HOST_SYMBOLS = [
     "ctr_host_scene_load", "ctr_host_scene_parse", "ctr_host_scene_free", "ctr_host_scene_desc",
     "ctr_host_scene_set_size", "ctr_host_scene_set_material", "ctr_stl_read", "ctr_stl_write",
@@ -82,6 +90,9 @@ HIP_SYMBOLS = [
     "ctr_multi_set_variant", "ctr_render_multi", "ctr_multi_kernel_ms", "ctr_reinterleave_device",
     "ctr_multi_submit", "ctr_multi_wait",
 ]
+
+# include/cutrace_rays.h (kept apart from HIP_SYMBOLS, which mirrors cutrace_amd.h)
+RAY_SYMBOLS = ["ctr_cast_rays"]
 
 _host = None
 _hip = None
@@ -171,6 +182,7 @@ def hip_lib():
             "ctr_render_uv": ([C.c_void_p, C.c_float, C.c_int, C.POINTER(Rows), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(RenderStats)], C.c_int),
             "ctr_tile_costs": ([C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
+            "ctr_cast_rays": ([C.c_void_p, C.POINTER(RayQuery), C.c_void_p], C.c_int),
         }
         for name, (argt, rest) in opt.items():
             if hasattr(L, name):

@@ -23,6 +23,8 @@
 
 #include "bvh.h"
 #include "cutrace_amd.h"
+#include "cutrace_rays.h"
+#include "ray_query.h"
 #include "scene_device.h"
 
 namespace {
@@ -195,6 +197,9 @@ struct ctr_scene {
   bool order_valid = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::mutex mtx;
+  // ctr_cast_rays: LDS stack entries per lane of the deepest mesh tree (ray_stack_slots), computed at the first call
+  std::once_flag ray_once;
+  uint32_t ray_slots = 0;
 
   uint32_t kernel_variant(bool count) const {
     uint32_t kv = 0;
@@ -1436,3 +1441,92 @@ int ctr_algorithmic_bytes(ctr_scene *s, float fudge, int bounces, const ctr_rows
 }
 
 }  // extern "C"
+
+// LDS stack entries per lane that the ray-query walk (ray_query.hip) can need: a node pushes at most three of its
+// children (the fourth is visited next), so the stack holds at most three entries per level above the current node.
+// The depth counts the inner nodes of the longest path of any mesh tree, plus the spare node in front of a guarded
+// root (refresh_linear_meshes).  The trees' SHAPES never change after ctr_scene_create (only boxes and guard leaves do).
+static uint32_t ray_stack_slots(const ctr_scene *s) {
+  uint32_t deepest = 0;
+  std::vector<std::pair<uint32_t, uint32_t>> todo;  // (node relative to the mesh's first, its level)
+  for (const ctr_scene::MeshGuard &g : s->guards) {
+    if (g.mesh_pos < 0 || g.node_count == 0) continue;
+    todo.assign(1, {0u, 1u});
+    while (!todo.empty()) {
+      const auto [n, lvl] = todo.back();
+      todo.pop_back();
+      deepest = std::max(deepest, lvl);
+      const DNode4 &N = s->h_nodes4[g.node_begin + n];
+      for (int c = 0; c < 4; c++)
+        if (!(N.child[c] & BVH_LEAF_FLAG) && N.child[c] < g.node_count) todo.push_back({N.child[c], lvl + 1});
+    }
+  }
+  return 3u * (deepest + 1u);
+}
+
+extern "C" int ctr_cast_rays(ctr_scene *s, const ctr_ray_query *q, void *hip_stream) {
+  if (!q) return fail(CTR_E_INVALID, "ctr_cast_rays: null query");
+  constexpr uint32_t KNOWN = CTR_RAY_IGNORE_TRANSPARENT | CTR_RAY_LINEAR | CTR_RAY_SHADOW;
+  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, "ctr_cast_rays: unknown flag bits " + std::to_string(q->flags & ~KNOWN));
+  const bool shadow = (q->flags & CTR_RAY_SHADOW) != 0;
+  const bool any_nearest = q->d_t || q->d_object || q->d_prim || q->d_point || q->d_normal || q->d_uv;
+  if (shadow && (q->flags & CTR_RAY_IGNORE_TRANSPARENT))
+    return fail(CTR_E_INVALID, "ctr_cast_rays: CTR_RAY_SHADOW and CTR_RAY_IGNORE_TRANSPARENT exclude each other");
+  if (shadow && (any_nearest || !q->d_shadow))
+    return fail(CTR_E_INVALID, "ctr_cast_rays: CTR_RAY_SHADOW writes d_shadow only, and needs it");
+  if (!shadow && (!any_nearest || q->d_shadow))
+    return fail(CTR_E_INVALID, "ctr_cast_rays: a nearest-hit query needs at least one of its outputs and no d_shadow");
+  if (!s) return fail(CTR_E_INVALID, "ctr_cast_rays: null scene");
+  if (q->n_rays >= 0x80000000ull) return fail(CTR_E_INVALID, "ctr_cast_rays: n_rays must be below 2^31");
+  if (q->n_rays == 0) return CTR_OK;
+  if (!q->d_origin || !q->d_dir) return fail(CTR_E_INVALID, "ctr_cast_rays: null rays");
+  // every pointer the kernel touches must be device memory of the scene's device (no size check is possible here)
+  const void *ptrs[] = {q->d_origin, q->d_dir, q->d_min_t, q->d_max_t, q->d_t, q->d_object, q->d_prim, q->d_point,
+                        q->d_normal, q->d_uv, q->d_shadow};
+  const char *names[] = {"d_origin", "d_dir", "d_min_t", "d_max_t", "d_t", "d_object", "d_prim", "d_point",
+                         "d_normal", "d_uv", "d_shadow"};
+  for (size_t k = 0; k < sizeof(ptrs) / sizeof(ptrs[0]); k++) {
+    if (!ptrs[k]) continue;
+    hipPointerAttribute_t at{};
+    const bool ok = hipPointerGetAttributes(&at, ptrs[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == s->device;
+    if (!ok) {
+      (void)hipGetLastError();  // plain host memory: "invalid value", not an error of the stream
+      return fail(CTR_E_INVALID, std::string("ctr_cast_rays: ") + names[k] + " is not device memory of the scene's device");
+    }
+  }
+  int cur = -1;
+  if (hipGetDevice(&cur) == hipSuccess && cur != s->device) HIP_TRY(hipSetDevice(s->device));
+  std::call_once(s->ray_once, [s] { s->ray_slots = ray_stack_slots(s); });
+  RayLaunch L{};
+  L.objs = s->d_objs;
+  L.oloop = s->d_oloop;
+  L.meshes = s->d_meshes;
+  L.planes = s->d_planes;
+  L.tris = s->d_tris;
+  L.nodes4 = s->d_nodes4;
+  L.gnorm = s->d_gnorm;
+  L.mats = s->d_mats;
+  L.n_oloop = s->n_oloop;
+  L.n_plane_recs = s->n_plane_recs;
+  L.n_mesh = s->n_mesh;
+  L.stack_slots = s->ray_slots;
+  L.n_rays = (uint32_t)q->n_rays;
+  L.flags = q->flags;
+  L.anyhit = shadow && s->all_opaque;
+  L.min_t = q->min_t;
+  L.max_t = q->max_t;
+  L.origin = q->d_origin;
+  L.dir = q->d_dir;
+  L.min_t_arr = q->d_min_t;
+  L.max_t_arr = q->d_max_t;
+  L.t = q->d_t;
+  L.object = q->d_object;
+  L.prim = q->d_prim;
+  L.point = q->d_point;
+  L.normal = q->d_normal;
+  L.uv = q->d_uv;
+  L.shadow = q->d_shadow;
+  const int e = ctr_launch_rays(L, hip_stream);
+  if (e) return hip_fail((hipError_t)e, "ray query kernel launch");
+  return CTR_OK;
+}

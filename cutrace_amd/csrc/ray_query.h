@@ -1,0 +1,33 @@
+// ray_query.h — what ctr_cast_rays (ctr_api.cpp) hands the ray-query kernel (ray_query.hip).
+#ifndef CUTRACE_AMD_RAY_QUERY_H
+#define CUTRACE_AMD_RAY_QUERY_H
+
+#include <stdint.h>
+
+#include "scene_device.h"
+
+struct RayLaunch {
+  // the scene's device arrays, as the render kernel reads them (scene_device.h, bvh.h)
+  const DObj *objs;          // every object, scene order (hit records)
+  const DObj *oloop;         // spheres and stand-alone triangles, scene order
+  const DObj *meshes;        // non-empty meshes (the first n_mesh records: the regular ones, never the merged tree)
+  const DPlanePair *planes;
+  const DTri *tris;
+  const void *nodes4;        // DNode4[]: per-mesh trees
+  const float *gnorm;
+  const DMat *mats;
+  uint32_t n_oloop, n_plane_recs, n_mesh;
+  uint32_t stack_slots;      // LDS stack entries per lane the deepest mesh tree needs (ctr_api.cpp ray_stack_slots)
+  // the query (include/cutrace_rays.h)
+  uint32_t n_rays, flags;
+  bool anyhit;               // SHADOW on a scene whose materials are all opaque: stop at the first occluder
+  float min_t, max_t;
+  const float *origin, *dir, *min_t_arr, *max_t_arr;
+  float *t, *point, *normal, *uv, *shadow;
+  int32_t *object, *prim;
+};
+
+// host-callable launcher implemented in ray_query.hip; returns a hipError_t as int
+int ctr_launch_rays(const RayLaunch &L, void *stream);
+
+#endif
