@@ -17,7 +17,7 @@ struct RayLaunch {
   const float *gnorm;
   const DMat *mats;
   uint32_t n_oloop, n_plane_recs, n_mesh;
-  uint32_t stack_slots;      // LDS stack entries per lane the deepest mesh tree needs (ctr_api.cpp ray_stack_slots)
+  uint32_t stack_slots;      // LDS stack entries per lane the deepest mesh tree needs (scene_flatten.h FlatScene::ray_slots)
   // the query (include/cutrace_rays.h)
   uint32_t n_rays, flags;
   bool anyhit;               // SHADOW on a scene whose materials are all opaque: stop at the first occluder

@@ -10,7 +10,7 @@
 // trade turns: here ONE LANE = ONE RAY, each lane walking its own.  Records arrive through vector loads (16-byte
 // aligned: every record is 64 or 128 bytes, every array a hipMalloc), each mesh's four-wide BVH (bvh.h) is walked with
 // a per-lane stack in LDS laid out [entry][lane] (conflict-free whatever depth each lane is at), sized from the
-// scene's deepest mesh tree (ctr_api.cpp ray_stack_slots).  No scratch memory.
+// scene's deepest mesh tree (scene_flatten.h FlatScene::ray_slots).  No scratch memory.
 //
 // Exactness — what each step may and may not shortcut:
 //  * planes, spheres, stand-alone triangles: the reference's arithmetic, operation for operation (-ffp-contract=off,

@@ -1,0 +1,449 @@
+// scene_flatten.cpp — a scene description becomes the dense arrays of scene_device.h.  Pure host arithmetic, no HIP.
+// Compile with -ffp-contract=off: the ray-independent triangle quantities computed here (a, b, geometric normal) must
+// have the reference's bits.
+#include "scene_flatten.h"
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+
+namespace {
+
+constexpr float KAPPA = 1.0f / 16384.0f;  // prefilter slack factor 2^-14 (≈1000 ulp), see DESIGN.md
+
+struct f3 { float x, y, z; };
+inline f3 sub(ctr_vec3 a, ctr_vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+inline f3 cross(f3 a, f3 o) { return {a.y * o.z - a.z * o.y, a.z * o.x - a.x * o.z, a.x * o.y - a.y * o.x}; }
+
+void make_tri(const ctr_vec3 &p1, const ctr_vec3 &p2, const ctr_vec3 &p3, uint32_t orig, DTri &T, float *gn) {
+  f3 a = sub(p2, p1), b = sub(p2, p3);  // default_schema.hpp:58
+  T.ab[0][0] = a.x; T.ab[1][0] = a.y; T.ab[2][0] = a.z;
+  T.ab[0][1] = b.x; T.ab[1][1] = b.y; T.ab[2][1] = b.z;
+  T.px = p2.x; T.py = p2.y; T.pz = p2.z;
+  f3 n = cross(a, b);
+  T.nx = n.x; T.ny = n.y; T.nz = n.z;
+  float emax = 0.f;
+  for (float v : {a.x, a.y, a.z, b.x, b.y, b.z}) emax = fmaxf(emax, fabsf(v));
+  T.ke = KAPPA * emax;
+  T.ke2 = KAPPA * emax * emax;
+  T.orig = orig;
+  T.pad1 = 0.f;
+  // default_schema.hpp:72: -1.0f * (p2 - p3).cross(p1 - p3).normalized()
+  f3 c = cross(sub(p2, p3), sub(p1, p3));
+  float nrm = sqrtf(c.x * c.x + c.y * c.y + c.z * c.z);
+  float f = 1.0f / nrm;
+  gn[0] = -1.0f * (f * c.x);
+  gn[1] = -1.0f * (f * c.y);
+  gn[2] = -1.0f * (f * c.z);
+  gn[3] = 0.f;
+}
+
+// what the BVH builders want to know of each triangle: its box and the box's centre
+std::vector<BvhInput> tri_boxes(const ctr_triangle *src, size_t n) {
+  std::vector<BvhInput> prims(n);
+  for (size_t q = 0; q < n; q++) {
+    const ctr_vec3 *v[3] = {&src[q].p1, &src[q].p2, &src[q].p3};
+    BvhInput &b = prims[q];
+    for (int a = 0; a < 3; a++) {
+      const float c0 = (&v[0]->x)[a], c1 = (&v[1]->x)[a], c2 = (&v[2]->x)[a];
+      b.mn[a] = fminf(c0, fminf(c1, c2));
+      b.mx[a] = fmaxf(c0, fmaxf(c1, c2));
+      b.c[a] = 0.5f * (b.mn[a] + b.mx[a]);
+    }
+  }
+  return prims;
+}
+
+struct MeshTree { std::vector<DNode4> nodes; std::vector<uint32_t> order; };
+
+// The meshes' trees, several meshes at a time (a scene of 16 meshes of 1000 triangles: 2.5 -> 0.5 ms of ctr_scene_create; a
+// mesh large enough to matter is built on several threads by the builder itself).  One entry per object, empty for what is
+// not a mesh (or is one with too many triangles: mesh_record rejects it).
+std::vector<MeshTree> mesh_trees(const ctr_scene_desc &d) {
+  std::vector<MeshTree> trees(d.n_objects);
+  std::vector<uint64_t> mesh_ids;
+  for (uint64_t i = 0; i < d.n_objects; i++)
+    if (d.objects[i].type == CTR_OBJ_MESH && d.objects[i].tri_count <= 0xFFFFFFull) mesh_ids.push_back(i);
+  std::atomic<size_t> next{0};
+  auto work = [&] {
+    for (size_t k; (k = next.fetch_add(1)) < mesh_ids.size();) {
+      const ctr_object &o = d.objects[mesh_ids[k]];
+      bvh4_build(tri_boxes(d.triangles + o.tri_begin, (uint32_t)o.tri_count), BVH_LEAF, trees[mesh_ids[k]].nodes, trees[mesh_ids[k]].order);
+    }
+  };
+  const size_t n_thr = std::min<size_t>(mesh_ids.size() > 1 ? mesh_ids.size() : 1, std::max(1u, std::min(8u, std::thread::hardware_concurrency())));
+  std::vector<std::thread> pool;
+  for (size_t t = 1; t < n_thr; t++) pool.emplace_back(work);
+  work();
+  for (std::thread &t : pool) t.join();
+  return trees;
+}
+
+// What the guard (guard.h) checks eyes and lights against: per triangle, in leaf order like the DTri records, its plane
+// in double precision
+std::vector<double> guard_planes(const ctr_triangle *src, const std::vector<uint32_t> &order) {
+  std::vector<double> planes(7 * order.size());
+  for (size_t k = 0; k < order.size(); k++) {
+    const ctr_triangle &t = src[order[k]];
+    const double ax = (double)t.p2.x - t.p1.x, ay = (double)t.p2.y - t.p1.y, az = (double)t.p2.z - t.p1.z;
+    const double bx = (double)t.p2.x - t.p3.x, by = (double)t.p2.y - t.p3.y, bz = (double)t.p2.z - t.p3.z;
+    double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+    const double len = sqrt(nx * nx + ny * ny + nz * nz);
+    double *q = &planes[7 * k];
+    if (len > 0.0) { q[0] = nx / len; q[1] = ny / len; q[2] = nz / len; } else { q[0] = q[1] = q[2] = 0.0; }
+    q[3] = t.p2.x; q[4] = t.p2.y; q[5] = t.p2.z;
+    q[6] = fmax(fmax(fmax(fabs(ax), fabs(ay)), fabs(az)), fmax(fmax(fabs(bx), fabs(by)), fabs(bz)));
+  }
+  return planes;
+}
+
+// One mesh: its tree's nodes + a spare node, its triangles in leaf order (each keeps its file index for tie-breaks) + the
+// guard records, its normals, its MeshGuard
+void mesh_record(const ctr_object &o, const ctr_triangle *src, const MeshTree &tree, DObj &O, FlatScene &F) {
+  const uint32_t n = (uint32_t)o.tri_count;
+  const std::vector<uint32_t> &order = tree.order;
+  O.tri_begin = (uint32_t)F.tris.size();
+  O.tri_count = n;
+  O.node_begin = (uint32_t)F.nodes4.size();
+  O.node_count = (uint32_t)tree.nodes.size();
+  O.bvh_root = 0;  // node 0 of the mesh; child descriptors stay relative to the mesh's first node / first triangle
+  F.nodes4.insert(F.nodes4.end(), tree.nodes.begin(), tree.nodes.end());
+  F.nodes4.emplace_back();  // the mesh's spare node (guard records, apply_guards); unused = all zero
+  memset(&F.nodes4.back(), 0, sizeof(DNode4));
+  MeshGuard g;
+  g.node_begin = O.node_begin;
+  g.node_count = O.node_count;
+  g.tri_begin = O.tri_begin;
+  g.tri_count = n;
+  g.obj_index = O.index;
+  g.planes = guard_planes(src, order);
+  F.guards.push_back(std::move(g));
+  F.tris.resize(F.tris.size() + n + (n ? CTR_GUARD_SLOTS : 0u));  // + the mesh's guard records (apply_guards)
+  F.gn.resize(4 * F.tris.size());
+  for (uint32_t k = 0; k < n; k++) {
+    const ctr_triangle &t = src[order[k]];
+    make_tri(t.p1, t.p2, t.p3, order[k], F.tris[O.tri_begin + k], &F.gn[4 * (O.tri_begin + order[k])]);  // normals in FILE order: the kernel keeps only the winner's original index
+  }
+  for (uint32_t k = 0; n && k < CTR_GUARD_SLOTS; k++) {  // unused guard records: copies of the first triangle
+    F.tris[O.tri_begin + n + k] = F.tris[O.tri_begin];
+    for (int q = 0; q < 4; q++) F.gn[4 * (O.tri_begin + n + k) + q] = F.gn[4 * O.tri_begin + q];
+  }
+}
+
+// objs: one record per object, scene order; meshes and stand-alone triangles add their DTri records as they come
+int object_records(const ctr_scene_desc &d, const std::vector<MeshTree> &trees, FlatScene &F, std::string &err) {
+  F.objs.resize(d.n_objects);
+  F.tris.reserve(d.n_triangles + d.n_objects);
+  for (uint64_t i = 0; i < d.n_objects; i++) {
+    const ctr_object &o = d.objects[i];
+    DObj &O = F.objs[i];
+    memset(&O, 0, sizeof(O));
+    O.type = o.type;
+    O.mat = (uint32_t)o.mat_idx;
+    O.index = (uint32_t)i;
+    {  // material::is_transparent (default_schema.hpp:334: `transparency >= 1e-6`, a double comparison): ray_cast's ignore_transparent
+      const uint32_t tr = ((double)d.materials[o.mat_idx].transparency >= 1e-6) ? 1u : 0u;
+      memcpy(&O.f[7], &tr, sizeof(tr));
+    }
+    switch (o.type) {
+      case CTR_OBJ_TRIANGLE: {
+        O.tri_begin = (uint32_t)F.tris.size();
+        O.tri_count = 1;
+        F.tris.emplace_back();
+        F.gn.resize(4 * F.tris.size());
+        make_tri(o.v0, o.v1, o.v2, 0, F.tris.back(), &F.gn[4 * (F.tris.size() - 1)]);
+        O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;  // p1, p3: triangle::uv_for (KV_UV)
+        O.f[3] = o.v2.x; O.f[4] = o.v2.y; O.f[5] = o.v2.z;
+        break;
+      }
+      case CTR_OBJ_MESH:
+        F.has_mesh = true;
+        if (o.tri_count > 0xFFFFFFull) {
+          err = "object #" + std::to_string(i) + ": mesh has more than 2^24 triangles";
+          return CTR_E_INVALID;
+        }
+        mesh_record(o, d.triangles + o.tri_begin, trees[i], O, F);
+        [[fallthrough]];
+      case CTR_OBJ_PLANE:  // (a plane's point and normal, a mesh's box)
+        O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;
+        O.f[3] = o.v1.x; O.f[4] = o.v1.y; O.f[5] = o.v1.z;
+        break;
+      default:
+        O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;
+        O.f[3] = o.f0;
+        O.f[4] = o.f0 * o.f0;
+        break;
+    }
+  }
+  return CTR_OK;
+}
+
+// planes: two per record, the axis-aligned ones first and in whole triples (scene_device.h DPlanePair); oloop: what is
+// neither a plane nor a mesh
+void plane_records(FlatScene &F) {
+  std::vector<const DObj *> axis_planes[3], general_planes;
+  for (const DObj &O : F.objs) {
+    if (O.type == CTR_OBJ_PLANE) {
+      // axis-aligned: exactly one normal component is not zero (+0 and -0 both count as zero), everything finite
+      int nz = 0, axis = -1;
+      bool finite = true;
+      for (int a = 0; a < 3; a++) {
+        if (!std::isfinite(O.f[a]) || !std::isfinite(O.f[3 + a])) finite = false;
+        if (O.f[3 + a] != 0.0f) { nz++; axis = a; }
+      }
+      // (and the point within 1e37: with the kernel's |origin| < 8.5e37 gate no component of point - origin overflows to
+      //  inf, which the reference would multiply by the normal's zero into a NaN — ADVICE r03)
+      for (int a = 0; a < 3; a++)
+        if (!(fabsf(O.f[a]) <= 1e37f)) finite = false;
+      if (finite && nz == 1) axis_planes[axis].push_back(&O);
+      else general_planes.push_back(&O);
+    } else if (O.type != CTR_OBJ_MESH) F.oloop.push_back(O);
+  }
+  auto empty_pair = [] {
+    DPlanePair pr;
+    for (int a = 0; a < 3; a++) { pr.p[a][0] = pr.p[a][1] = 0.0f; pr.n[a][0] = pr.n[a][1] = 1.0f; }
+    pr.index[0] = pr.index[1] = CTR_PLANE_PAD;
+    pr.transparent[0] = pr.transparent[1] = 0;
+    return pr;
+  };
+  auto put = [](DPlanePair &pr, int slot, const DObj &O) {
+    for (int a = 0; a < 3; a++) { pr.p[a][slot] = O.f[a]; pr.n[a][slot] = O.f[3 + a]; }
+    pr.index[slot] = O.index;
+    uint32_t tr;
+    memcpy(&tr, &O.f[7], sizeof(tr));
+    pr.transparent[slot] = tr;
+  };
+  // fewer than three axis-aligned planes (a lone floor): one general record is less to fetch than a triple
+  if (axis_planes[0].size() + axis_planes[1].size() + axis_planes[2].size() < 3) {
+    general_planes.clear();
+    for (int a = 0; a < 3; a++) axis_planes[a].clear();
+    for (const DObj &O : F.objs)
+      if (O.type == CTR_OBJ_PLANE) general_planes.push_back(&O);
+  }
+  // axis triples: as many as the busiest axis needs (a box room: one)
+  size_t triples = 0;
+  for (int a = 0; a < 3; a++) triples = std::max(triples, (axis_planes[a].size() + 1) / 2);
+  for (size_t t = 0; t < triples; t++)
+    for (int a = 0; a < 3; a++) {
+      DPlanePair pr = empty_pair();
+      for (int slot = 0; slot < 2; slot++)
+        if (2 * t + slot < axis_planes[a].size()) put(pr, slot, *axis_planes[a][2 * t + slot]);
+      // an empty slot copies its neighbour (same numbers, never tested)
+      if (pr.index[0] != CTR_PLANE_PAD && pr.index[1] == CTR_PLANE_PAD)
+        for (int q = 0; q < 3; q++) { pr.p[q][1] = pr.p[q][0]; pr.n[q][1] = pr.n[q][0]; }
+      F.planes.push_back(pr);
+    }
+  F.n_axis_recs = (uint32_t)F.planes.size();
+  for (size_t k = 0; k < general_planes.size(); k++) {
+    if (k % 2 == 0) {
+      DPlanePair pr = empty_pair();
+      put(pr, 0, *general_planes[k]);
+      for (int q = 0; q < 3; q++) { pr.p[q][1] = pr.p[q][0]; pr.n[q][1] = pr.n[q][0]; }
+      F.planes.push_back(pr);
+    } else {
+      put(F.planes.back(), 1, *general_planes[k]);
+    }
+  }
+}
+
+// the meshes a ray can hit (an empty mesh is never hit), scene order
+std::vector<DObj> nonempty_meshes(const FlatScene &F) {
+  std::vector<DObj> m;
+  for (const DObj &O : F.objs)
+    if (O.type == CTR_OBJ_MESH && O.tri_count) m.push_back(O);
+  return m;
+}
+
+// top-level BVH over the mesh boxes, one mesh per leaf (same node layout as the per-mesh trees)
+void top_level(const std::vector<DObj> &meshes_in, FlatScene &F) {
+  F.n_mesh = (uint32_t)meshes_in.size();  // (meshes[] may continue with the merged pseudo mesh and the meshes in scene order)
+  F.tlas_begin = (uint32_t)F.nodes.size();
+  if (meshes_in.empty()) return;
+  std::vector<BvhInput> prims(meshes_in.size());
+  for (int a = 0; a < 3; a++) { F.tl_mn[a] = INFINITY; F.tl_mx[a] = -INFINITY; }
+  for (size_t k = 0; k < meshes_in.size(); k++) {
+    for (int a = 0; a < 3; a++) {
+      prims[k].mn[a] = meshes_in[k].f[a];
+      prims[k].mx[a] = meshes_in[k].f[3 + a];
+      prims[k].c[a] = 0.5f * (prims[k].mn[a] + prims[k].mx[a]);
+      F.tl_mn[a] = fminf(F.tl_mn[a], prims[k].mn[a]);
+      F.tl_mx[a] = fmaxf(F.tl_mx[a], prims[k].mx[a]);
+    }
+  }
+  std::vector<DNode> tnodes;
+  std::vector<uint32_t> order;
+  bvh_build(prims, 1, tnodes, order, F.tlas_root);
+  F.nodes.insert(F.nodes.end(), tnodes.begin(), tnodes.end());
+  for (uint32_t k : order) F.meshes.push_back(meshes_in[k]);
+  for (size_t pos = 0; pos < F.meshes.size(); pos++)
+    for (MeshGuard &g : F.guards)
+      if (g.obj_index == F.meshes[pos].index) g.mesh_pos = (int)pos;
+}
+
+// the merged tree (scene_flatten.h Merged): its room in the arrays is set aside and the triangles are kept
+void reserve_merged(const ctr_scene_desc &d, const std::vector<DObj> &by_rank, FlatScene &F) {
+  Merged &M = F.merged;
+  uint64_t total = 0;
+  for (const DObj &O : by_rank) total += O.tri_count;
+  if (by_rank.size() < 2 || by_rank.size() > CTR_MERGE_MAX_MESHES || total > 0xFFFFFFull) return;
+  M.reserved = true;
+  M.src.reserve(total);
+  for (uint32_t r = 0; r < by_rank.size(); r++) {
+    M.slot_of.push_back((uint32_t)M.src.size());
+    const ctr_object &o = d.objects[by_rank[r].index];
+    M.src.insert(M.src.end(), d.triangles + o.tri_begin, d.triangles + o.tri_begin + o.tri_count);
+  }
+  M.slot_of.push_back((uint32_t)total);
+  M.tri_begin = (uint32_t)F.tris.size();
+  M.tri_count = (uint32_t)total;
+  M.node_begin = (uint32_t)F.nodes4.size();
+  M.node_cap = (uint32_t)(total / 2 + 64);  // (a four-wide node has at least two children: far fewer in practice)
+  DNode4 zero4;
+  memset(&zero4, 0, sizeof(zero4));
+  F.nodes4.resize(F.nodes4.size() + M.node_cap + CTR_MERGED_SPARE_NODES, zero4);
+  DTri zero_t;
+  memset(&zero_t, 0, sizeof(zero_t));
+  F.tris.resize(F.tris.size() + total + CTR_GUARD_SLOTS, zero_t);
+  F.gn.resize(4 * F.tris.size());  // (unused for the merged records: normals are looked up in the mesh's own range)
+  // the pseudo mesh record: the kernel's mesh code walks it like a mesh whose AABB every lane passes
+  DObj P;
+  memset(&P, 0, sizeof(P));
+  P.type = CTR_OBJ_MERGED;
+  P.tri_begin = M.tri_begin;
+  P.tri_count = M.tri_count;
+  P.node_begin = M.node_begin;
+  P.node_count = 0;
+  P.bvh_root = 0;
+  P.index = 0xFFFFFFFFu;
+  for (int a = 0; a < 3; a++) { P.f[a] = F.tl_mn[a]; P.f[3 + a] = F.tl_mx[a]; }  // (margin of the box tests: the box of all meshes)
+  F.meshes.push_back(P);
+  for (const DObj &O : by_rank) F.meshes.push_back(O);
+}
+
+void lights_and_materials(const ctr_scene_desc &d, FlatScene &F) {
+  F.lights.resize(d.n_lights);
+  for (uint64_t i = 0; i < d.n_lights; i++) {
+    const ctr_light &l = d.lights[i];
+    F.lights[i] = DLight{l.type, l.v.x, l.v.y, l.v.z, l.color.x, l.color.y, l.color.z, 0.f};
+  }
+  F.mats.resize(d.n_materials);
+  for (uint64_t i = 0; i < d.n_materials; i++) {
+    const ctr_material &m = d.materials[i];
+    F.mats[i] = DMat{m.color.x, m.color.y, m.color.z, m.specular, m.reflexivity, m.phong_exp, m.transparency, 0.f};
+    if (!(m.transparency == 0.0f)) F.all_opaque = false;
+    if ((double)m.transparency >= 1e-6 && (double)m.reflexivity >= 1e-6) F.need_cold = true;
+    if ((double)m.transparency >= 1e-6 || (double)m.reflexivity >= 1e-6) F.any_bounce = true;
+  }
+}
+
+// FlatScene::ray_slots
+uint32_t ray_stack_slots(const FlatScene &F) {
+  uint32_t deepest = 0;
+  std::vector<std::pair<uint32_t, uint32_t>> todo;  // (node relative to the mesh's first, its level)
+  for (const MeshGuard &g : F.guards) {
+    if (g.mesh_pos < 0 || g.node_count == 0) continue;
+    todo.assign(1, {0u, 1u});
+    while (!todo.empty()) {
+      const auto [n, lvl] = todo.back();
+      todo.pop_back();
+      deepest = std::max(deepest, lvl);
+      const DNode4 &N = F.nodes4[g.node_begin + n];
+      for (int c = 0; c < 4; c++)
+        if (!(N.child[c] & BVH_LEAF_FLAG) && N.child[c] < g.node_count) todo.push_back({N.child[c], lvl + 1});
+    }
+  }
+  return 3u * (deepest + 1u);
+}
+
+}  // namespace
+
+DNode4 empty_node4() {
+  DNode4 N;
+  memset(&N, 0, sizeof(N));
+  for (int c = 0; c < 4; c++) {
+    for (int a = 0; a < 3; a++) { N.lo[a][c] = 3.4028235e38f; N.hi[a][c] = 3.4028235e38f; }
+    N.child[c] = BVH_LEAF_FLAG;
+  }
+  return N;
+}
+
+void create_stamp(const char *what) {
+  thread_local std::chrono::high_resolution_clock::time_point t0;
+  const auto now = std::chrono::high_resolution_clock::now();
+  if (what && getenv("CUTRACE_DEBUG_CREATE"))
+    fprintf(stderr, "cutrace_amd scene_create: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t0).count());
+  t0 = now;
+}
+
+int validate_desc(const ctr_scene_desc &d, std::string &err) {
+  auto bad = [&](const std::string &msg) { err = msg; return CTR_E_INVALID; };
+  if (d.n_objects > 0xFFFFFFFFull || d.n_triangles > 0x7FFFFFFFull || d.cam.w > 0x7FFFFFFFull ||
+      d.cam.h > 0x7FFFFFFFull)
+    return bad("scene too large for 32-bit device indices");
+  if (d.cam.w * d.cam.h > 0x7FFFFFFFull * 2) return bad("image too large");
+  for (uint64_t i = 0; i < d.n_objects; i++) {
+    const ctr_object &o = d.objects[i];
+    if (o.type > CTR_OBJ_SPHERE) return bad("object #" + std::to_string(i) + ": bad type");
+    if (o.mat_idx >= d.n_materials) return bad("object #" + std::to_string(i) + ": material index out of range");
+    if (o.type == CTR_OBJ_MESH && (o.tri_begin > d.n_triangles || o.tri_count > d.n_triangles - o.tri_begin))
+      return bad("object #" + std::to_string(i) + ": triangle range out of bounds");
+  }
+  for (uint64_t i = 0; i < d.n_lights; i++)
+    if (d.lights[i].type > CTR_LIGHT_POINT) return bad("light #" + std::to_string(i) + ": bad type");
+  for (uint64_t i = 0; i < d.n_materials; i++)
+    if (d.materials[i].type != CTR_MAT_PHONG) return bad("material #" + std::to_string(i) + ": bad type");
+  return CTR_OK;
+}
+
+int flatten_scene(const ctr_scene_desc &d, FlatScene &F, std::string &err) {
+  F = FlatScene();
+  if (int st = object_records(d, mesh_trees(d), F, err)) return st;
+  create_stamp("meshes: BVH + records");
+  plane_records(F);
+  const std::vector<DObj> in_scene_order = nonempty_meshes(F);
+  top_level(in_scene_order, F);
+  reserve_merged(d, in_scene_order, F);
+  lights_and_materials(d, F);
+  for (const MeshGuard &g : F.guards) F.mesh_tris += g.tri_count;
+  F.mesh_bytes = F.tris.size() * sizeof(DTri) + F.nodes.size() * sizeof(DNode) + F.nodes4.size() * sizeof(DNode4);
+  F.ray_slots = ray_stack_slots(F);
+  create_stamp("planes, top level, materials");
+  return CTR_OK;
+}
+
+std::vector<DirtyRange> build_merged_tree(FlatScene &F) {
+  Merged &M = F.merged;
+  if (!M.reserved || M.built) return {};
+  const uint32_t total = M.tri_count, n_rank = (uint32_t)M.slot_of.size() - 1;
+  std::vector<uint32_t> rank_of(total);
+  for (uint32_t r = 0; r < n_rank; r++)
+    for (uint32_t k = M.slot_of[r]; k < M.slot_of[r + 1]; k++) rank_of[k] = r;
+  std::vector<DNode4> mnodes;
+  std::vector<uint32_t> order;
+  bvh4_build(tri_boxes(M.src.data(), total), BVH_LEAF, mnodes, order);
+  if (mnodes.size() > M.node_cap) return {};  // (cannot happen for leaves of up to four triangles; then simply never used)
+  M.node_count = (uint32_t)mnodes.size();
+  std::copy(mnodes.begin(), mnodes.end(), F.nodes4.begin() + M.node_begin);
+  M.where.assign(total, 0u);
+  float dummy_gn[4];
+  for (uint32_t k = 0; k < total; k++) {
+    const uint32_t g = order[k], r = rank_of[g], f = g - M.slot_of[r];
+    const ctr_triangle &t = M.src[g];
+    make_tri(t.p1, t.p2, t.p3, (r << 24) | f, F.tris[M.tri_begin + k], dummy_gn);
+    M.where[g] = k;
+  }
+  for (uint32_t k = 0; k < CTR_GUARD_SLOTS; k++) F.tris[M.tri_begin + total + k] = F.tris[M.tri_begin];
+  DObj &P = F.meshes[F.n_mesh];
+  P.node_count = M.node_count;
+  P.bvh_root = 0;
+  M.built = true;
+  M.guarded.assign(1, 0xFFFFFFFFu);  // (no key: the first apply_guards writes the guard state, empty or not)
+  return {{DirtyRange::TRIS, M.tri_begin, (size_t)total + CTR_GUARD_SLOTS, {}},
+          {DirtyRange::NODES4, M.node_begin, M.node_count, {}},
+          {DirtyRange::MESHES, F.n_mesh, 1, {}}};
+}

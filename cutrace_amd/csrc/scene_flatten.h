@@ -1,0 +1,113 @@
+// scene_flatten.h — a ctr_scene_desc flattened into the arrays of scene_device.h, on the host, without a device.
+//
+// Everything ctr_scene_create (ctr_api.cpp) uploads is built here, and stays here as the host copy that the guard of
+// the BVH culling (guard.h) and the ray queries read and edit.  No HIP: scripts/flatten_check.cpp and
+// tests/test_scene_flatten.py run this code on any CPU.
+#ifndef CUTRACE_AMD_SCENE_FLATTEN_H
+#define CUTRACE_AMD_SCENE_FLATTEN_H
+
+#include <stdint.h>
+#include <string>
+#include <vector>
+
+#include "bvh.h"
+#include "cutrace_amd.h"
+#include "scene_device.h"
+
+#ifndef CTR_BVH_LEAF
+#define CTR_BVH_LEAF 4
+#endif
+constexpr uint32_t BVH_LEAF = CTR_BVH_LEAF;  // triangles per BVH leaf
+
+#define CTR_GUARD_SLOTS 64u  // spare DTri records per mesh (guard.h)
+#define CTR_MERGED_SPARE_NODES ((CTR_GUARD_SLOTS + 2u) / 3u)  // the merged tree: three meshes' guard leaves per spare node
+
+// Guard of the BVH culling (guard.h): what it needs to know of one mesh, and what it currently has on the device
+struct MeshGuard {
+  uint32_t node_begin = 0, node_count = 0;
+  uint32_t tri_begin = 0, tri_count = 0;  // the mesh's DTri range (leaf order); CTR_GUARD_SLOTS spare records follow it
+  uint32_t obj_index = 0;                 // position in objs
+  int mesh_pos = -1;                      // position in meshes (-1: an empty mesh, never walked)
+  std::vector<double> planes;  // per triangle (leaf order): unit normal (3), a point of the plane (3), extent
+  std::vector<uint32_t> guarded;          // triangles currently copied into the spare records
+  bool linear = false;         // its nodes currently carry unbounded boxes
+};
+
+// ONE four-wide tree over the triangles of ALL meshes (scenes with 2..255 non-empty meshes; render_kernel.hip "merged
+// walk"): its records are appended to tris / nodes4, a pseudo mesh record at meshes[n_mesh] leads to them, and
+// meshes[n_mesh + 1 + r] is mesh r in SCENE order (a merged triangle's key names r in its upper 8 bits).
+// With several meshes a cast otherwise walks the top-level tree, runs the reference's AABB test per mesh it reaches and
+// sets up a walk per mesh it enters (a fifth of the vector and the densest scalar code of the 16-mesh frame).  The merged
+// tree's records carry (mesh rank << 24 | file index) as their tie-break key — the reference's (object, triangle) order
+// as one integer — and the mesh's own AABB test (default_schema.hpp:99-114: a ray that fails it misses the mesh whatever
+// its triangles say) is applied afterwards, to the lanes the walk found something for.
+// Built on demand (build_merged_tree, at the first ctr_set_variant with CTR_VAR_MERGE): flatten_scene only sets its room in
+// the arrays aside and keeps the triangles.
+struct Merged {
+  bool reserved = false;   // the scene qualifies (2..255 non-empty meshes) and the arrays have room for the tree
+  bool built = false;      // the structures exist (build_merged_tree: at the first ctr_set_variant with CTR_VAR_MERGE)
+  uint32_t node_cap = 0;   // room for the tree's nodes in nodes4 (the spare nodes follow)
+  std::vector<ctr_triangle> src;  // the meshes' triangles, scene order then file order (kept for the build)
+  bool usable = false;     // ... and may be walked (apply_guards: no mesh went linear, the guard records fit)
+  uint32_t tri_begin = 0, tri_count = 0, node_begin = 0, node_count = 0;
+  std::vector<uint32_t> slot_of;  // per mesh rank: first index of its triangles in a (rank, file index) numbering (+ one past the last)
+  std::vector<uint32_t> where;    // merged position of triangle (rank, file index) -> tri_begin-relative record index
+  std::vector<uint32_t> guarded;  // keys currently in the guard records
+};
+
+// Records of a FlatScene array that a host-side edit changed: what the device copy has to receive, in this order.
+struct DirtyRange {
+  enum Array { OBJS, MESHES, TRIS, GNORM, NODES4 } array;
+  size_t begin, count;          // in records (GNORM: four floats per record)
+  std::vector<DNode4> payload;  // not empty: the device gets THESE nodes, FlatScene::nodes4 keeps the real boxes (a linear mesh)
+};
+
+struct FlatScene {
+  std::vector<DObj> objs;      // every object, scene order
+  std::vector<DObj> oloop;     // spheres and stand-alone triangles
+  std::vector<DObj> meshes;    // non-empty meshes in top-level leaf order (+ the merged pseudo mesh and the meshes in scene order)
+  std::vector<DPlanePair> planes;
+  std::vector<DTri> tris;
+  std::vector<DNode> nodes;    // top-level tree
+  std::vector<DNode4> nodes4;  // per-mesh trees (the real boxes), each followed by its spare node; the merged tree's room
+  std::vector<float> gn;
+  std::vector<DLight> lights;
+  std::vector<DMat> mats;
+  uint32_t n_mesh = 0, tlas_root = BVH_LEAF_FLAG, tlas_begin = 0;
+  float tl_mn[3] = {0, 0, 0}, tl_mx[3] = {0, 0, 0};
+  uint32_t n_axis_recs = 0;
+  bool has_mesh = false;
+  bool all_opaque = true;
+  bool need_cold = false;   // some material both reflects and transmits (>= 1e-6 each)
+  bool any_bounce = false;  // some material reflects or transmits (>= 1e-6): the recursion can go below depth 0
+  uint64_t mesh_tris = 0;   // triangles in meshes
+  size_t mesh_bytes = 0;    // triangles + BVH nodes
+  std::vector<MeshGuard> guards;  // one per mesh object, scene order
+  Merged merged;
+  // LDS stack entries per lane that the ray-query walk (ray_query.hip) can need: a node pushes at most three of its
+  // children (the fourth is visited next), so the stack holds at most three entries per level above the current node.
+  // The depth counts the inner nodes of the longest path of any mesh tree, plus the spare node in front of a guarded
+  // root.  The trees' SHAPES never change after flatten_scene (only boxes and guard leaves do).
+  uint32_t ray_slots = 0;
+};
+
+// The checks the kernel relies on (it trusts these indices).  CTR_OK, or CTR_E_INVALID and the message in `err`.
+int validate_desc(const ctr_scene_desc &d, std::string &err);
+// Flattens a description that passed validate_desc.  CTR_OK, or CTR_E_INVALID and the message in `err`.
+int flatten_scene(const ctr_scene_desc &d, FlatScene &F, std::string &err);
+// The merged tree of a scene that has room for it (Merged::reserved), built into the reserved ranges.  Returns the
+// ranges it filled; none when there is nothing to build (not reserved, built already, or the tree outgrew its room).
+std::vector<DirtyRange> build_merged_tree(FlatScene &F);
+
+// a node whose four slots are empty: a far-away point box and a leaf of no triangles each
+DNode4 empty_node4();
+// slot `c` of `N` gets a box that every ray passes
+inline void unbounded_box(DNode4 &N, int c) {
+  for (int a = 0; a < 3; a++) { N.lo[a][c] = -3.0e38f; N.hi[a][c] = 3.0e38f; }
+}
+
+// CUTRACE_DEBUG_CREATE=1: where ctr_scene_create spends its time (stderr): the time since the previous stamp of this
+// thread.  what == nullptr only restarts the clock.
+void create_stamp(const char *what);
+
+#endif

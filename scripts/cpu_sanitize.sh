@@ -1,6 +1,6 @@
 # usage: bash scripts/cpu_sanitize.sh   (build container, CPU only) — the host-side code (scene loader / JSON / STL / JPEG writers,
 # libcutrace_host.so) and the C oracle under AddressSanitizer + UndefinedBehaviorSanitizer, driven by the CPU tests that
-# exercise them.  (The GPU library cannot be sanitised on this pool; its host half — ctr_api.cpp, bvh.cpp — needs a device.)
+# exercise them.  (The GPU library cannot be sanitised on this pool; of its host half scene_flatten.cpp, guard.cpp and bvh.cpp need no device: scripts/flatten_check.cpp, scripts/bvh_check.cpp.)
 set -e
 OUT=${TMPDIR:-/tmp}/ctr_san
 mkdir -p $OUT

@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import cutrace_amd as ca
 import oracle
-from tests.test_gpu_parity import _random_scene
+from tests.util import _random_scene
 from tests.util import assert_parity, same_bits
 
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 1000

@@ -9,8 +9,8 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import cutrace_amd as ca
 import oracle
-from tests.test_gpu_parity import _random_scene
-from tests.test_gpu_merged import _multi_mesh_scene
+from tests.util import _random_scene
+from tests.util import _multi_mesh_scene
 from tests.util import assert_parity, same_bits
 
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 5000

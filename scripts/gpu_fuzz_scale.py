@@ -9,7 +9,7 @@ import numpy as np
 import cutrace_amd as ca
 import oracle
 from cutrace_amd import scenes
-from tests.test_gpu_parity import _random_scene
+from tests.util import _random_scene
 from tests.util import assert_parity, same_bits
 
 first = int(sys.argv[1]) if len(sys.argv) > 1 else 0

@@ -120,7 +120,7 @@ def main():
                "a_grays_s": n / ta[0] / 1e6, "b_grays_s": n / tb[0] / 1e6, "c_grays_s": nh / tc[0] / 1e6,
                "min_max_ms": {"a": ta[1:], "b": tb[1:], "c": tc[1:], "d": td[1:]},
                "permuted_same_bits": bool(same), "a_depth_equals_render_depth": bool(same_depth),
-               "stack_slots_note": "per lane, from the deepest mesh tree (ctr_api.cpp ray_stack_slots)"}
+               "stack_slots_note": "per lane, from the deepest mesh tree (scene_flatten.cpp ray_stack_slots)"}
         result["scenes"][name] = rec
         print(name, json.dumps(rec), flush=True)
         ds.close()

@@ -1,6 +1,6 @@
 """The merged walk (round 4, CTR_VAR_MERGE — opt-in: measured slower than the two-level walk on every shipped config,
 profiles/r04/exp_merged_tree_ab.txt): scenes with several meshes are walked through ONE four-wide tree over the triangles of all
-meshes (render_kernel.hip "merged walk", ctr_api.cpp ctr_scene::Merged) instead of a tree over the meshes' boxes and
+meshes (render_kernel.hip "merged walk", scene_flatten.h Merged) instead of a tree over the meshes' boxes and
 then each mesh's own tree.  What the reference does per mesh — its AABB test before any triangle
 (inc/default_schema.hpp:99-114,126), "first mesh in scene order wins ties" and "a mesh whose nearest valid t equals
 min_t is rejected whole" (inc/ray_cast.hpp:43) — must survive that: every case against the oracle, and bit for bit
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle
-from tests.util import assert_parity, same_bits
+from tests.util import assert_parity, same_bits, _multi_mesh_scene
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,39 +45,6 @@ def _all_ways(ca, s, what, bounces=3, fudge=1e-3, expect_merged=True):
     assert (walks > 0) == expect_merged, (what, walks)
     ds.close()
     return o, r, walks, redone
-
-
-def _multi_mesh_scene(tmp_path, seed, w=96, h=64, opaque=False, n_mesh=4):
-    """n_mesh meshes cut out of scene/bunny.stl and scene/skull.stl, translated so that their boxes overlap, at random
-    places of the object list, mixed with planes, a sphere and a stand-alone triangle."""
-    from cutrace_amd import scenes
-    rng = np.random.RandomState(seed)
-    src = [scenes.read_stl(os.path.join(ROOT, "scene", f)) for f in ("bunny.stl", "skull.stl")]
-    mats = [{"type": "solid", "color": [float(x) for x in rng.uniform(0.1, 1, 3)], "specular": float(rng.uniform(0, 1)),
-             "reflect": float(rng.choice([0.0, 0.3, 0.8])), "phong": float(rng.choice([1.0, 20.0, 200.0])),
-             "transparency": 0.0 if opaque else float(rng.choice([0.0, 0.0, 0.4]))} for _ in range(4)]
-    objs = [{"type": "plane", "point": [0, -1.3, 0], "normal": [0, 1, 0], "material": 0},
-            {"type": "plane", "point": [0, 0, -4], "normal": [0, 0, 1], "material": 1},
-            {"type": "sphere", "center": [1.2, 0.4, -0.5], "radius": 0.5, "material": 2},
-            {"type": "triangle", "p1": [-2, -1, -1], "p2": [-1, 1.5, -1.5], "p3": [-2.5, 1, 0], "material": 3}]
-    for m in range(n_mesh):
-        t = src[int(rng.randint(2))]
-        t = t[rng.rand(len(t)) < rng.uniform(0.2, 0.7)]           # a random part of the mesh (open surface)
-        c = t.reshape(-1, 3).mean(0)
-        scale = np.float32(1.2 / np.abs(t.reshape(-1, 3) - c).max())
-        t = ((t - c) * scale + np.float32(rng.uniform(-0.7, 0.7, 3))).astype(np.float32)
-        path = str(tmp_path / f"mm_{seed}_{m}.stl")
-        scenes.write_stl(path, t)
-        objs.insert(int(rng.randint(len(objs) + 1)), {"type": "mesh", "file": path, "material": int(rng.randint(4))})
-    if rng.rand() < 0.5:   # the same mesh twice: exact ties on t between two MESHES (the first in scene order wins)
-        first = next(o for o in objs if o["type"] == "mesh")
-        objs.append(dict(first, material=int(rng.randint(4))))
-    lights = [{"type": "sun", "direction": [float(x) for x in rng.uniform(-1, 1, 3)], "color": [0.7, 0.7, 0.7]},
-              {"type": "point", "point": [float(x) for x in rng.uniform(-3, 3, 3)], "color": [0.6, 0.5, 0.4]}]
-    cam = {"eye": [float(rng.uniform(-1, 1)), float(rng.uniform(-0.3, 1.0)), 4.0], "up": [0, 1, 0],
-           "look": [float(rng.uniform(-0.2, 0.2)), float(rng.uniform(-0.2, 0.1)), -1.0], "near_plane": 0.1, "far_plane": 100.0,
-           "width": w, "height": h, "ambient": 0.15}
-    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
 
 
 @pytest.mark.parametrize("seed", list(range(6)))
@@ -151,8 +118,8 @@ def test_more_meshes_than_the_key_has_room_for(ca, tmp_path):
 @pytest.mark.parametrize("seed", [1, 2])
 def test_rays_coplanar_with_triangles_of_two_meshes(ca, tmp_path, seed):
     """The guard records of the merged tree: triangles lying in the plane that contains every primary ray of one image
-    row (tests/test_gpu_parity.py::_coplanar_scene), split over two meshes."""
-    from tests.test_gpu_parity import _coplanar_scene
+    row (tests/util.py::_coplanar_scene), split over two meshes."""
+    from tests.util import _coplanar_scene
     from cutrace_amd import scenes
     w, h, row = 384, 32, 9
     one = _coplanar_scene(ca, tmp_path, w, h, row, 48, seed)

@@ -156,7 +156,7 @@ def _random_rays(rng, n, rs, lo, hi):
 
 @pytest.mark.parametrize("which", ["bunny", "random0", "random5"])
 def test_random_rays_against_ray_ref(ca, which):
-    from tests.test_gpu_parity import _random_scene
+    from tests.util import _random_scene
     s = load_scene(ca, "bunny", 32, 32) if which == "bunny" else ca.HostScene.parse(_random_scene(int(which[6:]), w=32, h=32))
     assert s.ok
     rs = ray_ref.RefScene(s)
@@ -248,7 +248,7 @@ def test_mesh_whose_box_test_fails_is_missed_whatever_its_triangles_say(ca, tmp_
 
 # ---- 5. ignore_transparent ----
 def test_ignore_transparent_against_ray_ref_and_the_render(ca):
-    from tests.test_gpu_parity import _random_scene
+    from tests.util import _random_scene
     for seed in (2, 4, 9):
         s = ca.HostScene.parse(_random_scene(seed + 40, w=64, h=40))
         assert s.ok
@@ -272,7 +272,7 @@ def test_ignore_transparent_against_ray_ref_and_the_render(ca):
 @pytest.mark.parametrize("seed,opaque", [(1, False), (7, False), (2, True), (5, True)])
 def test_shadow_against_ray_ref_and_a_loop_of_casts(ca, seed, opaque):
     import torch
-    from tests.test_gpu_parity import _random_scene
+    from tests.util import _random_scene
     s = ca.HostScene.parse(_random_scene(seed, w=32, h=32, opaque_mesh=opaque))
     assert s.ok
     rs = ray_ref.RefScene(s)

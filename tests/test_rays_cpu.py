@@ -100,7 +100,7 @@ def test_ray_ref_reproduces_the_oracle_primary_cast(ca, name, w, h):
 
 @pytest.mark.parametrize("seed", [0, 3, 7])
 def test_ray_ref_reproduces_the_oracle_on_random_scenes(ca, seed):
-    from tests.test_gpu_parity import _random_scene
+    from tests.util import _random_scene
     s = ca.HostScene.parse(_random_scene(seed, w=40, h=28))
     assert s.ok
     _check_primary(s, f"random scene {seed}")

@@ -1,5 +1,10 @@
-"""Shared comparison helpers for the parity tests."""
+"""Shared comparison helpers and scene builders for the parity tests."""
+import json
+import os
+
 import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TOL = 1e-4  # per-channel float tolerance stated by BASELINE.json:north_star
 
@@ -70,3 +75,183 @@ def corner_meshes():
            for a in np.arange(0, 6.28, 0.7)]
     far = (np.asarray(quad, np.float32) * 500.0 + np.float32([3000, 0, -9000])).tolist()
     return quad, dup, degenerate, fan, far
+
+
+def _random_scene(seed, w=72, h=48, opaque_mesh=False, extra_planes=False):
+    """Seeded random scene mixing every primitive, light and material feature (incl. reflect +
+    transparency on the same material, coincident planes, a mesh and stand-alone triangles)."""
+    import json
+    rng = np.random.RandomState(seed)
+
+    def v(lo, hi):
+        return [float(x) for x in rng.uniform(lo, hi, 3)]
+
+    mats = []
+    for _ in range(int(rng.randint(2, 6))):
+        mats.append({"type": "solid", "color": v(0.05, 1.0), "specular": float(rng.uniform(0, 1)),
+                     "reflect": float(rng.choice([0.0, 0.0, 0.3, 0.9])), "phong": float(rng.choice([0.0, 1.0, 20.0, 300.0])),
+                     "transparency": 0.0 if opaque_mesh else float(rng.choice([0.0, 0.0, 0.0, 0.5]))})
+    nm = len(mats)
+    objs = []
+    for _ in range(int(rng.randint(1, 5))):
+        objs.append({"type": "sphere", "center": v(-1.5, 1.5), "radius": float(rng.uniform(0.2, 0.8)), "material": int(rng.randint(nm))})
+    for _ in range(int(rng.randint(1, 4))):
+        objs.append({"type": "triangle", "p1": v(-2, 2), "p2": v(-2, 2), "p3": v(-2, 2), "material": int(rng.randint(nm))})
+    floor = {"type": "plane", "point": [0, -1.2, 0], "normal": [0, 1, 0], "material": int(rng.randint(nm))}
+    objs.append(floor)
+    if rng.rand() < 0.5:
+        objs.append(dict(floor, material=int(rng.randint(nm))))  # coincident plane: exact tie on t
+    objs.append({"type": "plane", "point": [0, 0, -3], "normal": [0, 0, 1], "material": int(rng.randint(nm))})
+    if extra_planes:
+        # more walls, axis-aligned (zeros of either sign, any length of normal) and not, anywhere in the object list
+        rng2 = np.random.RandomState(seed + 7919)
+        for _ in range(int(rng2.randint(1, 7))):
+            if rng2.rand() < 0.7:
+                a = int(rng2.randint(3))
+                n = [float(rng2.choice([0.0, -0.0])) for _ in range(3)]
+                n[a] = float(rng2.choice([-1.0, 1.0]) * rng2.choice([1.0, 0.25, 3.0, 1e-3]))
+                pt = [float(x) for x in rng2.uniform(-1, 1, 3)]
+                pt[a] = float(-np.sign(n[a]) * rng2.uniform(2.0, 6.0))
+            else:
+                n = [float(x) for x in rng2.uniform(-1, 1, 3)]
+                pt = [float(-4.0 * x) for x in n]
+            objs.insert(int(rng2.randint(len(objs) + 1)), {"type": "plane", "point": pt, "normal": n, "material": int(rng2.randint(nm))})
+    if opaque_mesh or rng.rand() < 0.7:
+        objs.insert(int(rng.randint(len(objs) + 1)), {"type": "mesh", "file": "scene/skull.stl", "material": int(rng.randint(nm))})
+    lights = [{"type": "sun", "direction": v(-1, 1), "color": v(0.2, 1)}]
+    for _ in range(int(rng.randint(0, 3))):
+        lights.append({"type": "point", "point": v(-3, 3), "color": v(0.2, 1)})
+    cam = {"eye": [float(rng.uniform(-1, 3)), float(rng.uniform(-0.5, 2)), 4.0], "up": [0, 1, 0], "look": v(-0.5, 0.5),
+           "near_plane": 0.1, "far_plane": 100.0, "width": w, "height": h, "ambient": float(rng.uniform(0, 0.3))}
+    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
+
+
+def _coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed):
+    """A mesh whose triangles all lie (to float rounding) in the plane that contains EVERY primary ray of image row
+    `row`: for those rays alpha = det[a b c] of default_schema.hpp:59 is pure rounding noise, and so are beta, gamma
+    and t — the regime in which the reference's float test can report a hit for a ray that passes far from the
+    triangle (BVH caveat)."""
+    import ctypes as C
+    import json
+    from cutrace_amd import _lib, scenes
+    rng = np.random.default_rng(seed)
+    eye, up, look = (0.3, 0.8, 4.0), (0.0, 1.0, 0.0), (-0.05, -0.15, -1.0)
+    cam = _lib.Camera()
+    _lib.host_lib().ctr_camera_look_at(C.byref(cam), _lib.Vec3(*eye), _lib.Vec3(*up), _lib.Vec3(*look))
+    f32 = np.float32
+    E, R, U, F = (np.array(v.tup(), f32) for v in (cam.pos, cam.right, cam.up, cam.forward))
+    v = (f32(0.5) - f32(row) / f32(h)) * U + F           # the row's rays: E + s*right*k + t*v
+    tris = []
+    for _ in range(n_tris):
+        s0, t0 = f32(rng.uniform(-1.2, 1.2)), f32(rng.uniform(2.0, 5.0))
+        pts = []
+        for _ in range(3):
+            s, t = s0 + f32(rng.uniform(-0.25, 0.25)), t0 + f32(rng.uniform(-0.4, 0.4))
+            pts.append((E + s * R + t * v).astype(f32))
+        tris.append(pts)
+    stl = str(tmp_path / f"coplanar_{seed}.stl")
+    scenes.write_stl(stl, np.asarray(tris, f32))
+    sc = {"camera": {"eye": list(eye), "up": list(up), "look": list(look), "near_plane": 0.1, "far_plane": 100.0,
+                     "width": w, "height": h, "ambient": 0.1},
+          "lights": [{"type": "point", "point": [1.5, 2.5, 2.0], "color": [0.8, 0.8, 0.8]},
+                     {"type": "point", "point": [float(E[0] + 0.5 * R[0] + 1.0 * v[0]), float(E[1] + 0.5 * R[1] + 1.0 * v[1]),
+                                                  float(E[2] + 0.5 * R[2] + 1.0 * v[2])]}],   # a light IN the plane too
+          "materials": [{"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.3, "phong": 40},
+                        {"type": "solid", "color": [0.3, 0.5, 0.9], "specular": 0.2, "reflect": 0.2, "phong": 10}],
+          "objects": [{"type": "mesh", "file": stl, "material": 0},
+                      {"type": "plane", "point": [0, -1.0, 0], "normal": [0, 1, 0], "material": 1},
+                      {"type": "plane", "point": [0, 0, -6.0], "normal": [0, 0, 1], "material": 1}]}
+    s = ca.HostScene.parse(json.dumps(sc))
+    assert s.ok
+    return s
+
+
+def _mirror_coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed, transparent, two_mirrors=False):
+    """The same regime for SECONDARY rays, which no upload-time guard can see (guard.cpp plan_guards checks eyes
+    and lights): a tilted mirror reflects every primary ray of image row `row` into ONE plane — the mirror image of the
+    row's plane, through the mirror image of the eye — and the mesh's triangles lie in that plane to float rounding, some
+    on the reflected rays' way, some far to the side of it.  For those reflected rays (and, with `transparent`, for the
+    pass-through rays that continue from an in-plane hit in the same plane) alpha and all three numerators of
+    default_schema.hpp:57-78 are rounding noise.  Neither the eye nor any light lies in that plane."""
+    import ctypes as C
+    import json
+    from cutrace_amd import _lib, scenes
+    rng = np.random.default_rng(seed)
+    eye, up, look = (0.2, 0.9, 3.5), (0.0, 1.0, 0.0), (0.02, -0.1, -1.0)
+    cam = _lib.Camera()
+    _lib.host_lib().ctr_camera_look_at(C.byref(cam), _lib.Vec3(*eye), _lib.Vec3(*up), _lib.Vec3(*look))
+    f32, f64 = np.float32, np.float64
+    E, R, U, F = (np.array(v.tup(), f64) for v in (cam.pos, cam.right, cam.up, cam.forward))
+    v = (0.5 - row / h) * U + F                           # the row's rays: E + s*R + t*v
+    pm = np.array([0.0, 0.0, -2.0])                       # the mirror: a plane through pm, tilted towards the ceiling
+    nm = np.array([0.0, 0.35, 1.0])
+    mirrors = [(pm, nm)]
+    if two_mirrors:                                       # ... and a second one above that sends the rays down again
+        mirrors.append((np.array([0.0, 3.0, 0.0]), np.array([0.0, -1.0, 0.25])))
+    E2, R2, v2, t_mirror = E, R, v, 0.0
+    for (p_, n_) in mirrors:                              # images of the eye and of the row's plane, mirror after mirror
+        nh = n_ / np.linalg.norm(n_)
+        t_mirror = np.dot(p_ - E2, nh) / np.dot(v2, nh)   # where the row's central ray meets this mirror
+        assert t_mirror > 0
+        E2 = E2 - 2.0 * np.dot(E2 - p_, nh) * nh
+        R2, v2 = R2 - 2.0 * np.dot(R2, nh) * nh, v2 - 2.0 * np.dot(v2, nh) * nh
+    tris = []
+    for _ in range(n_tris):
+        s0, t0 = rng.uniform(-1.5, 1.5), t_mirror + rng.uniform(0.4, 3.5)   # beyond the mirror point = on the reflected side
+        pts = []
+        for _ in range(3):
+            s_, t_ = s0 + rng.uniform(-0.3, 0.3), t0 + rng.uniform(-0.35, 0.35)
+            pts.append((E2 + s_ * R2 + t_ * v2).astype(f32))
+        tris.append(pts)
+    stl = str(tmp_path / f"mirror_coplanar_{seed}_{int(transparent)}.stl")
+    scenes.write_stl(stl, np.asarray(tris, f32))
+    mesh_mat = {"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.3, "phong": 40}
+    if transparent:
+        mesh_mat["transparency"] = 0.4
+    sc = {"camera": {"eye": list(eye), "up": list(up), "look": list(look), "near_plane": 0.1, "far_plane": 100.0,
+                     "width": w, "height": h, "ambient": 0.1},
+          "lights": [{"type": "point", "point": [1.5, 2.5, 2.0], "color": [0.8, 0.8, 0.8]},
+                     {"type": "sun", "direction": [0.3, -1.0, -0.2], "color": [0.4, 0.4, 0.4]}],
+          "materials": [mesh_mat,
+                        {"type": "solid", "color": [0.3, 0.5, 0.9], "specular": 0.2, "reflect": 0.0, "phong": 10},
+                        {"type": "solid", "color": [0.9, 0.9, 0.9], "specular": 0.1, "reflect": 0.9, "phong": 20}],
+          "objects": [{"type": "mesh", "file": stl, "material": 0},
+                      {"type": "plane", "point": [0, -1.5, 0], "normal": [0, 1, 0], "material": 1}] +
+                     [{"type": "plane", "point": [float(x) for x in p_], "normal": [float(x) for x in n_], "material": 2}
+                      for (p_, n_) in mirrors]}
+    s = ca.HostScene.parse(json.dumps(sc))
+    assert s.ok
+    return s
+
+
+def _multi_mesh_scene(tmp_path, seed, w=96, h=64, opaque=False, n_mesh=4):
+    """n_mesh meshes cut out of scene/bunny.stl and scene/skull.stl, translated so that their boxes overlap, at random
+    places of the object list, mixed with planes, a sphere and a stand-alone triangle."""
+    from cutrace_amd import scenes
+    rng = np.random.RandomState(seed)
+    src = [scenes.read_stl(os.path.join(ROOT, "scene", f)) for f in ("bunny.stl", "skull.stl")]
+    mats = [{"type": "solid", "color": [float(x) for x in rng.uniform(0.1, 1, 3)], "specular": float(rng.uniform(0, 1)),
+             "reflect": float(rng.choice([0.0, 0.3, 0.8])), "phong": float(rng.choice([1.0, 20.0, 200.0])),
+             "transparency": 0.0 if opaque else float(rng.choice([0.0, 0.0, 0.4]))} for _ in range(4)]
+    objs = [{"type": "plane", "point": [0, -1.3, 0], "normal": [0, 1, 0], "material": 0},
+            {"type": "plane", "point": [0, 0, -4], "normal": [0, 0, 1], "material": 1},
+            {"type": "sphere", "center": [1.2, 0.4, -0.5], "radius": 0.5, "material": 2},
+            {"type": "triangle", "p1": [-2, -1, -1], "p2": [-1, 1.5, -1.5], "p3": [-2.5, 1, 0], "material": 3}]
+    for m in range(n_mesh):
+        t = src[int(rng.randint(2))]
+        t = t[rng.rand(len(t)) < rng.uniform(0.2, 0.7)]           # a random part of the mesh (open surface)
+        c = t.reshape(-1, 3).mean(0)
+        scale = np.float32(1.2 / np.abs(t.reshape(-1, 3) - c).max())
+        t = ((t - c) * scale + np.float32(rng.uniform(-0.7, 0.7, 3))).astype(np.float32)
+        path = str(tmp_path / f"mm_{seed}_{m}.stl")
+        scenes.write_stl(path, t)
+        objs.insert(int(rng.randint(len(objs) + 1)), {"type": "mesh", "file": path, "material": int(rng.randint(4))})
+    if rng.rand() < 0.5:   # the same mesh twice: exact ties on t between two MESHES (the first in scene order wins)
+        first = next(o for o in objs if o["type"] == "mesh")
+        objs.append(dict(first, material=int(rng.randint(4))))
+    lights = [{"type": "sun", "direction": [float(x) for x in rng.uniform(-1, 1, 3)], "color": [0.7, 0.7, 0.7]},
+              {"type": "point", "point": [float(x) for x in rng.uniform(-3, 3, 3)], "color": [0.6, 0.5, 0.4]}]
+    cam = {"eye": [float(rng.uniform(-1, 1)), float(rng.uniform(-0.3, 1.0)), 4.0], "up": [0, 1, 0],
+           "look": [float(rng.uniform(-0.2, 0.2)), float(rng.uniform(-0.2, 0.1)), -1.0], "near_plane": 0.1, "far_plane": 100.0,
+           "width": w, "height": h, "ambient": 0.15}
+    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
