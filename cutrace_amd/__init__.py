@@ -33,6 +33,10 @@ RAY_IGNORE_TRANSPARENT = 1
 RAY_LINEAR = 2
 RAY_SHADOW = 4
 RAY_OUTPUTS = ("t", "object", "prim", "point", "normal", "uv")
+# ctr_shade_rays flags and outputs (include/cutrace_rays.h)
+SHADE_LINEAR = 1
+SHADE_EXACT_POW = 2
+SHADE_OUTPUTS = ("color", "t", "object", "normal")
 
 
 @contextlib.contextmanager
@@ -139,6 +143,7 @@ class DeviceScene:
         self._h = h
         self.device = device
         self.w, self.h = host_scene.size
+        self._ambient = float(host_scene.desc.contents.cam.ambient)  # shade_rays' default
 
     def set_variant(self, bits):
         st = _lib.hip_lib().ctr_set_variant(self._h, bits)
@@ -373,6 +378,49 @@ class DeviceScene:
             q.d_shadow = out.data_ptr() if n else None
             if n:
                 self._cast(q, (o, d, mx), torch.cuda.current_stream(dev))
+        return out
+
+    def shade_rays(self, origins, dirs, bounces=5, min_t=1e-3, ambient=None, exact_pow=False, linear=False, outputs=None,
+                   stream=None):
+        """ray_color<S, bounces> (inc/shading.hpp:116-154) of every ray (origins[k], dirs[k]): Phong shading over every
+        light, reflection and transparency recursed to `bounces` (0 .. 15), with the render's numerics.  A dict of tensors
+        on the scene's device: `color` (n, 3) always ((0, 0, 0) on a miss), and of the FIRST cast's hit what `outputs`
+        names among `t` (n,) (+inf: miss), `object` (n,) int32 (-1: miss), `normal` (n, 3).  origins, dirs: (n, 3) float32;
+        directions need not be normalised.  min_t: ray_color's min_t (the render's fudge).  ambient: phong's ambient
+        factor; None: that of the camera the scene was created with.  exact_pow=True: the specular term as under
+        VAR_EXACT_POW (bitwise the reference's); linear=True: meshes walked linearly, exact also for rays in a triangle's
+        plane.  Asynchronous on `stream` (a torch.cuda.Stream; default: torch's current stream of the scene's device)."""
+        import torch
+        outputs = ("color",) if outputs is None else tuple(outputs)
+        bad = [k for k in outputs if k not in SHADE_OUTPUTS]
+        if bad:
+            raise ValueError(f"outputs: a subset of {SHADE_OUTPUTS}, got {outputs}")
+        outputs = ("color",) + tuple(k for k in outputs if k != "color")
+        if not 0 <= int(bounces) <= 15:
+            raise ValueError(f"bounces: 0 .. 15, got {bounces}")
+        dev = self._torch_device()
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            o = self._rays_arg(origins, "origins", 3)
+            d = self._rays_arg(dirs, "dirs", 3)
+            n = o.shape[0]
+            if d.shape[0] != n:
+                raise ValueError(f"dirs: {d.shape[0]} rays for {n} origins")
+            q = _lib.ShadeQuery()
+            q.n_rays = n
+            q.flags = (SHADE_LINEAR if linear else 0) | (SHADE_EXACT_POW if exact_pow else 0)
+            q.bounces = int(bounces)
+            q.min_t = float(min_t)
+            q.ambient = float(self._ambient if ambient is None else ambient)
+            shapes = {"color": ((n, 3), torch.float32), "t": ((n,), torch.float32), "object": ((n,), torch.int32),
+                      "normal": ((n, 3), torch.float32)}
+            out = {k: torch.empty(*shapes[k][0], dtype=shapes[k][1], device=dev) for k in outputs}
+            if n:
+                q.d_origin, q.d_dir = o.data_ptr(), d.data_ptr()
+                for k, v in out.items():
+                    setattr(q, "d_" + k, v.data_ptr())
+                st = _lib.hip_lib().ctr_shade_rays(self._h, C.byref(q), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                if st:
+                    raise RuntimeError(f"ctr_shade_rays failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
         return out
 
     def tile_costs(self):

@@ -73,6 +73,13 @@ class RayQuery(C.Structure):
                 ("d_point", C.c_void_p), ("d_normal", C.c_void_p), ("d_uv", C.c_void_p), ("d_shadow", C.c_void_p)]
 
 
+class ShadeQuery(C.Structure):
+    """ctr_shade_query (include/cutrace_rays.h)"""
+    _fields_ = [("n_rays", C.c_uint64), ("flags", C.c_uint32), ("bounces", C.c_int32), ("min_t", C.c_float),
+                ("ambient", C.c_float), ("d_origin", C.c_void_p), ("d_dir", C.c_void_p), ("d_color", C.c_void_p),
+                ("d_t", C.c_void_p), ("d_object", C.c_void_p), ("d_normal", C.c_void_p)]
+
+
 HOST_SYMBOLS = [
     "ctr_host_scene_load", "ctr_host_scene_parse", "ctr_host_scene_free", "ctr_host_scene_desc",
     "ctr_host_scene_set_size", "ctr_host_scene_set_material", "ctr_stl_read", "ctr_stl_write",
@@ -92,7 +99,7 @@ HIP_SYMBOLS = [
 ]
 
 # include/cutrace_rays.h (kept apart from HIP_SYMBOLS, which mirrors cutrace_amd.h)
-RAY_SYMBOLS = ["ctr_cast_rays"]
+RAY_SYMBOLS = ["ctr_cast_rays", "ctr_shade_rays"]
 
 _host = None
 _hip = None
@@ -183,6 +190,7 @@ def hip_lib():
                                C.POINTER(RenderStats)], C.c_int),
             "ctr_tile_costs": ([C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
             "ctr_cast_rays": ([C.c_void_p, C.POINTER(RayQuery), C.c_void_p], C.c_int),
+            "ctr_shade_rays": ([C.c_void_p, C.POINTER(ShadeQuery), C.c_void_p], C.c_int),
         }
         for name, (argt, rest) in opt.items():
             if hasattr(L, name):

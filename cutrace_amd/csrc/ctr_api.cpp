@@ -19,6 +19,7 @@
 #include "cutrace_rays.h"
 #include "guard.h"
 #include "ray_query.h"
+#include "ray_shade.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
 
@@ -853,5 +854,69 @@ extern "C" int ctr_cast_rays(ctr_scene *s, const ctr_ray_query *q, void *hip_str
   L.shadow = q->d_shadow;
   const int e = ctr_launch_rays(L, hip_stream);
   if (e) return hip_fail((hipError_t)e, "ray query kernel launch");
+  return CTR_OK;
+}
+
+extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_stream) {
+  if (!q) return fail(CTR_E_INVALID, "ctr_shade_rays: null query");
+  constexpr uint32_t KNOWN = CTR_SHADE_LINEAR | CTR_SHADE_EXACT_POW;
+  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, "ctr_shade_rays: unknown flag bits " + std::to_string(q->flags & ~KNOWN));
+  if (q->bounces < 0 || q->bounces > CTR_MAX_BOUNCES)
+    return fail(CTR_E_INVALID, "ctr_shade_rays: bounces " + std::to_string(q->bounces) + " outside [0, " + std::to_string(CTR_MAX_BOUNCES) + "]");
+  if (!q->d_color) return fail(CTR_E_INVALID, "ctr_shade_rays: d_color is required");
+  if (!s) return fail(CTR_E_INVALID, "ctr_shade_rays: null scene");
+  if (q->n_rays >= 0x80000000ull) return fail(CTR_E_INVALID, "ctr_shade_rays: n_rays must be below 2^31");
+  if (q->n_rays == 0) return CTR_OK;
+  if (!q->d_origin || !q->d_dir) return fail(CTR_E_INVALID, "ctr_shade_rays: null rays");
+  // every pointer the kernel touches must be device memory of the scene's device (no size check is possible here)
+  const void *ptrs[] = {q->d_origin, q->d_dir, q->d_color, q->d_t, q->d_object, q->d_normal};
+  const char *names[] = {"d_origin", "d_dir", "d_color", "d_t", "d_object", "d_normal"};
+  for (size_t k = 0; k < sizeof(ptrs) / sizeof(ptrs[0]); k++) {
+    if (!ptrs[k]) continue;
+    hipPointerAttribute_t at{};
+    const bool ok = hipPointerGetAttributes(&at, ptrs[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == s->device;
+    if (!ok) {
+      (void)hipGetLastError();  // plain host memory: "invalid value", not an error of the stream
+      return fail(CTR_E_INVALID, std::string("ctr_shade_rays: ") + names[k] + " is not device memory of the scene's device");
+    }
+  }
+  ShadeLaunch L{};
+  L.objs = s->d_objs;
+  L.oloop = s->d_oloop;
+  L.meshes = s->d_meshes;
+  L.planes = s->d_planes;
+  L.tris = s->d_tris;
+  L.nodes4 = s->d_nodes4;
+  L.gnorm = s->d_gnorm;
+  L.mats = s->d_mats;
+  L.lights = s->d_lights;
+  L.n_oloop = (uint32_t)s->flat.oloop.size();
+  L.n_plane_recs = (uint32_t)s->flat.planes.size();
+  L.n_mesh = s->flat.n_mesh;
+  L.n_light = (uint32_t)s->flat.lights.size();
+  L.stack_slots = s->flat.ray_slots;
+  L.frames = ctr_shade_frames(q->bounces, s->flat.any_bounce);
+  L.frame_dwords = s->flat.need_cold ? 10u : 4u;
+  L.all_opaque = s->flat.all_opaque ? 1u : 0u;
+  L.n_rays = (uint32_t)q->n_rays;
+  L.flags = q->flags;
+  L.bounces = q->bounces;
+  L.min_t = q->min_t;
+  L.ambient = q->ambient;
+  L.origin = q->d_origin;
+  L.dir = q->d_dir;
+  L.color = q->d_color;
+  L.t = q->d_t;
+  L.object = q->d_object;
+  L.normal = q->d_normal;
+  if (ctr_shade_lds_bytes(L) > CTR_SHADE_LDS_MAX)
+    return fail(CTR_E_INVALID, "ctr_shade_rays: the walk stack of this scene's mesh trees and " + std::to_string(L.frames) +
+                                   " recursion frames need " + std::to_string(ctr_shade_lds_bytes(L)) +
+                                   " bytes of LDS per workgroup, more than " + std::to_string(CTR_SHADE_LDS_MAX) +
+                                   " (fewer bounces or CTR_SHADE_LINEAR fit)");
+  int cur = -1;
+  if (hipGetDevice(&cur) == hipSuccess && cur != s->device) HIP_TRY(hipSetDevice(s->device));
+  const int e = ctr_launch_shade(L, hip_stream);
+  if (e) return hip_fail((hipError_t)e, "radiance query kernel launch");
   return CTR_OK;
 }

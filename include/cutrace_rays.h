@@ -1,7 +1,7 @@
 /*
- * cutrace_rays.h — cast caller-supplied rays against a scene uploaded with ctr_scene_create.
+ * cutrace_rays.h — cast and shade caller-supplied rays against a scene uploaded with ctr_scene_create.
  *
- * One entry point, ctr_cast_rays, answers per ray what the reference answers for its own rays:
+ * ctr_cast_rays answers per ray what the reference answers for its own rays:
  *
  *   nearest-hit mode (default)  ray_cast(scene, ray, min_t, ..., ignore_transparent)   inc/ray_cast.hpp:29-55
  *   CTR_RAY_SHADOW              shadow_intensity(scene, ray, max_t)                     inc/shading.hpp:22-45
@@ -66,6 +66,51 @@ typedef struct ctr_ray_query {
  * with IGNORE_TRANSPARENT; SHADOW with a nearest-hit output or without d_shadow; nearest-hit mode without any output
  * or with d_shadow; a pointer that is not device memory of the scene's device; n_rays >= 2^31. */
 int ctr_cast_rays(ctr_scene *scene, const ctr_ray_query *q, void *hip_stream);
+
+/*
+ * Radiance queries: ctr_shade_rays answers per ray the reference's third per-ray function,
+ *
+ *   ray_color<S, bounces>(scene, ray, min_t, ambient)                                   inc/shading.hpp:116-154
+ *
+ * Phong shading over every light (phong, shading.hpp:64-99, with shadow_intensity per light), reflection and
+ * transparency recursed to `bounces`, with the render kernel's numerics: for a camera's rays the colours are the
+ * render's.  By default the specular term is the render's fast one (within 1e-4 of the reference);
+ * CTR_SHADE_EXACT_POW is the render's CTR_VAR_EXACT_POW (IEEE half vector, f64 pow rounded once).  The reference's
+ * unit mix is kept: a sphere's distance is measured along dir / |dir| while the child rays of a hit start at
+ * start + distance * dir.
+ *
+ * Exactness is that of ctr_cast_rays, for every cast of the activation tree: the default walk culls each mesh with its
+ * BVH, exact except for rays lying in a triangle's plane; eyes, lights and mirror images of the scene's uploaded
+ * cameras are guarded, arbitrary origins are not.  CTR_SHADE_LINEAR walks meshes linearly and is
+ * exact for every ray, secondary rays included.
+ *
+ * The contract is ctr_cast_rays': asynchronous on `hip_stream`, no allocation, no synchronisation (capturable into a
+ * graph), no per-handle scratch (later renders, their counters and the tile scheduler are undisturbed).
+ */
+#define CTR_SHADE_LINEAR 1u    /* walk meshes linearly (exact for every ray), as CTR_RAY_LINEAR                   */
+#define CTR_SHADE_EXACT_POW 2u /* the specular term and half vector as under CTR_VAR_EXACT_POW                    */
+
+typedef struct ctr_shade_query {
+  uint64_t n_rays;        /* < 2^31; 0: nothing is launched                                                       */
+  uint32_t flags;         /* CTR_SHADE_*                                                                          */
+  int32_t bounces;        /* 0 .. 15 (CTR_MAX_BOUNCES), ray_color's template argument                             */
+  float min_t;            /* ray_color's min_t: what the render passes as fudge                                   */
+  float ambient;          /* phong's ambient factor (the render passes the camera's)                              */
+  const float *d_origin;  /* n x 3, device memory of the scene's device (as every pointer below)                 */
+  const float *d_dir;     /* n x 3, need not be normalised                                                        */
+  float *d_color;         /* n x 3, required; (0, 0, 0) on a miss (shading.hpp:119)                               */
+  /* optional (NULL = not written), the hit of ray_color's FIRST cast (shading.hpp:123):                          */
+  float *d_t;             /* n: distance, +inf on a miss                                                          */
+  int32_t *d_object;      /* n: index into ctr_scene_desc.objects, -1 on a miss                                   */
+  float *d_normal;        /* n x 3: the reference's normal (0, 0, 0 on a miss)                                    */
+} ctr_shade_query;
+
+/* Shades q->n_rays rays on `hip_stream` (NULL: the null stream of the scene's device).  CTR_E_INVALID, with a
+ * ctr_last_error message, before the GPU is touched, for: a NULL scene or query; NULL rays when n_rays > 0; unknown
+ * flag bits; bounces outside [0, 15]; a missing d_color; a pointer that is not device memory of the scene's device;
+ * n_rays >= 2^31; a scene whose mesh trees are so deep that the walk's stack and `bounces` frames do not fit one
+ * workgroup's 64 KiB of LDS (CTR_SHADE_LINEAR needs no walk stack). */
+int ctr_shade_rays(ctr_scene *scene, const ctr_shade_query *q, void *hip_stream);
 
 #ifdef __cplusplus
 }
