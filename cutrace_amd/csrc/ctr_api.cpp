@@ -11,22 +11,22 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "ctr_internal.h"
 #include "cutrace_amd.h"
-#include "cutrace_rays.h"
 #include "guard.h"
-#include "ray_query.h"
-#include "ray_shade.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
 
 namespace {
-
 thread_local std::string g_err;
+}
 
+// ---- what ctr_internal.h declares for every host translation unit ----
 int fail(int code, const std::string &msg) {
   g_err = msg;
   fprintf(stderr, "cutrace_amd: %s\n", msg.c_str());  // print-and-continue, like cudaCheck (inc/cuda.hpp:12-22)
@@ -35,11 +35,33 @@ int fail(int code, const std::string &msg) {
 int hip_fail(hipError_t e, const char *what) {
   return fail(CTR_E_HIP_BASE + (int)e, std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
 }
-#define HIP_TRY(expr)                                     \
-  do {                                                    \
-    hipError_t _e = (expr);                               \
-    if (_e != hipSuccess) return hip_fail(_e, #expr);     \
-  } while (0)
+
+bool is_pinned(const void *p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();  // plain malloc'ed memory: "invalid value", not an error of ours
+    return false;
+  }
+  return at.type == hipMemoryTypeHost;
+}
+
+bool device_view(float *host, float **dev) {
+  void *d = nullptr;
+  if (hipHostGetDevicePointer(&d, host, 0) != hipSuccess || !d) {
+    (void)hipGetLastError();
+    return false;
+  }
+  *dev = (float *)d;
+  return true;
+}
+
+int use_device(const ctr_scene *s) {
+  int cur = -1;
+  if (hipGetDevice(&cur) == hipSuccess && cur != s->device) HIP_TRY(hipSetDevice(s->device));
+  return CTR_OK;
+}
+
+void ctr_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
 
 #ifndef CTR_OCC6_MIN_TRIS
 #define CTR_OCC6_MIN_TRIS 1000  // scenes with at least this many mesh triangles use the 6-waves-per-SIMD build
@@ -50,6 +72,28 @@ int hip_fail(hipError_t e, const char *what) {
 #ifndef CTR_ORDER_PERIOD
 #define CTR_ORDER_PERIOD 8  // launches between rebuilds of the tile order
 #endif
+
+uint64_t ctr_scene::occ6_min_tris() {
+  static const uint64_t v = [] { const char *e = getenv("CUTRACE_OCC6_MIN_TRIS"); return e ? (uint64_t)atoll(e) : (uint64_t)CTR_OCC6_MIN_TRIS; }();
+  return v;
+}
+
+uint32_t ctr_scene::kernel_variant(bool count) const {
+  uint32_t kv = 0;
+  if (!(user_variant & CTR_VAR_NO_PREFILTER)) kv |= KV_PREFILTER;
+  // shadow any-hit is result-identical only when every material is exactly opaque
+  // (SURVEY §8(a) row a9); with any transparency the ordered nearest-hit loop is kept
+  if (flat.all_opaque && !(user_variant & CTR_VAR_NO_ANYHIT) && !count) kv |= KV_ANYHIT;
+  if (!(user_variant & CTR_VAR_NO_CLUSTER) && !count) kv |= KV_BVH;
+  if (!(user_variant & CTR_VAR_EXACT_POW)) kv |= KV_FASTPOW;
+  // meshes of CTR_OCC6_MIN_TRIS triangles and more: the build for 6 waves per SIMD (render_kernel.hip KV_OCC6)
+  if (flat.mesh_tris >= occ6_min_tris() && !(user_variant & CTR_VAR_NO_OCC6)) kv |= KV_OCC6;
+  if (user_variant & CTR_VAR_STATS) kv = KV_STATS | (flat.all_opaque && !(user_variant & CTR_VAR_NO_ANYHIT) ? KV_ANYHIT : 0u);
+  if (count) kv = KV_PREFILTER | KV_COUNT;  // the counting launch walks like the reference (and wins over STATS)
+  return kv;
+}
+
+namespace {
 
 DCam to_dcam(const ctr_camera &c) {
   DCam cam{};
@@ -63,74 +107,36 @@ DCam to_dcam(const ctr_camera &c) {
   return cam;
 }
 
-}  // namespace
+// The scene's ten device arrays, each ONCE: its pointer in the handle, its host copy (scene_flatten.h FlatScene), the bytes
+// of the whole array and of one record, and the key under which a DirtyRange names it (-1: never edited after the
+// upload).  ctr_scene_create uploads, upload_dirty re-uploads and ctr_scene_destroy frees by this table.
+// F: s->flat, or what ctr_scene_create is about to move there.
+struct SceneArray { void **dev; const void *host; size_t bytes, rec; int dirty; };
+std::vector<SceneArray> scene_arrays(ctr_scene *s, const FlatScene &F) {
+  auto row = [](auto &dev, const auto &v, int dirty = -1, size_t rec = 0) {
+    return SceneArray{(void **)&dev, v.data(), v.size() * sizeof(v[0]), rec ? rec : sizeof(v[0]), dirty};
+  };
+  return {row(s->d_objs, F.objs, DirtyRange::OBJS), row(s->d_oloop, F.oloop), row(s->d_meshes, F.meshes, DirtyRange::MESHES),
+          row(s->d_planes, F.planes), row(s->d_tris, F.tris, DirtyRange::TRIS), row(s->d_nodes, F.nodes),
+          row(s->d_nodes4, F.nodes4, DirtyRange::NODES4), row(s->d_gnorm, F.gn, DirtyRange::GNORM, 4 * sizeof(float)),
+          row(s->d_lights, F.lights), row(s->d_mats, F.mats)};
+}
 
-void ctr_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
-
-struct ctr_scene {
-  int device = 0;
-  FlatScene flat;             // the host copy of every scene array below, and what the guard knows of it (scene_flatten.h)
-  DObj *d_objs = nullptr;
-  DObj *d_oloop = nullptr;
-  DObj *d_meshes = nullptr;
-  DPlanePair *d_planes = nullptr;
-  DTri *d_tris = nullptr;
-  DNode *d_nodes = nullptr;
-  DNode4 *d_nodes4 = nullptr;
-  float *d_gnorm = nullptr;
-  DLight *d_lights = nullptr;
-  DMat *d_mats = nullptr;
-  static uint64_t occ6_min_tris() {
-    static const uint64_t v = [] { const char *e = getenv("CUTRACE_OCC6_MIN_TRIS"); return e ? (uint64_t)atoll(e) : (uint64_t)CTR_OCC6_MIN_TRIS; }();
-    return v;
+// Buffers that only grow: when `need` elements exceed `cap`, every buffer of the list is freed and allocated anew for
+// `need` elements of its size (`host`: page-locked host memory).  An allocation that fails leaves cap == 0 — and, of
+// the buffers, some null — so that the next call comes back here whatever its size.
+struct GrowBuf { void **p; size_t elem; bool host; };
+int grow(size_t need, size_t &cap, std::initializer_list<GrowBuf> bufs) {
+  if (need <= cap) return CTR_OK;
+  cap = 0;
+  for (const GrowBuf &b : bufs) {
+    if (*b.p) (void)(b.host ? hipHostFree(*b.p) : hipFree(*b.p));
+    *b.p = nullptr;
   }
-  DCam cam{};                 // camera 0 (image size of every camera)
-  DCam *d_cams = nullptr;     // device camera array (>= 1 entry)
-  uint32_t n_cams = 0;
-  uint32_t user_variant = CTR_VAR_AUTO;
-  // cached device outputs for the host-buffer form: ONE allocation, a call's buffers are its consecutive
-  // parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
-  float *d_out = nullptr;
-  float *d_uv = nullptr;      // ctr_render_uv: 2 floats per pixel, allocated on first use
-  size_t uv_px = 0;
-  std::vector<DCam> h_cams;     // host copy of d_cams: the eyes the guard checks (refresh_linear_meshes)
-  unsigned long long *h_counters = nullptr;  // pinned landing zone of the 16 counter words
-  unsigned long long last_cnt[16] = {0};     // the counter words of the last host-form render
-  unsigned long long *d_counters = nullptr;
-  unsigned long long *d_shards = nullptr;  // CTR_SHARDS x CTR_SHARD_WORDS, zero between launches
-  size_t out_px = 0;
-  uint32_t *d_groups = nullptr;  // host delivery: one completion counter per group of tiles (render_kernel.hip)
-  uint32_t *h_groups = nullptr;  // page-locked landing zone of the counters (checked after every direct launch)
-  size_t groups_cap = 0;
-  bool poison_next_order = false;  // test hook (ctr_debug_poison_next_order)
-  // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling")
-  uint32_t *d_cost = nullptr, *d_order = nullptr;
-  uint32_t order_age = 0;  // launches of the current shape
-  uint64_t order_view = 0; // camera set + first frame of the previous launch
-  uint32_t cams_epoch = 0; // bumped by ctr_scene_set_cameras / ctr_scene_set_size
-  uint64_t order_cap = 0;
-  uint64_t order_key[6] = {0, 0, 0, 0, 0, 0};
-  bool order_valid = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  std::mutex mtx;
-
-  uint32_t kernel_variant(bool count) const {
-    uint32_t kv = 0;
-    if (!(user_variant & CTR_VAR_NO_PREFILTER)) kv |= KV_PREFILTER;
-    // shadow any-hit is result-identical only when every material is exactly opaque
-    // (SURVEY §8(a) row a9); with any transparency the ordered nearest-hit loop is kept
-    if (flat.all_opaque && !(user_variant & CTR_VAR_NO_ANYHIT) && !count) kv |= KV_ANYHIT;
-    if (!(user_variant & CTR_VAR_NO_CLUSTER) && !count) kv |= KV_BVH;
-    if (!(user_variant & CTR_VAR_EXACT_POW)) kv |= KV_FASTPOW;
-    // meshes of CTR_OCC6_MIN_TRIS triangles and more: the build for 6 waves per SIMD (render_kernel.hip KV_OCC6)
-    if (flat.mesh_tris >= occ6_min_tris() && !(user_variant & CTR_VAR_NO_OCC6)) kv |= KV_OCC6;
-    if (user_variant & CTR_VAR_STATS) kv = KV_STATS | (flat.all_opaque && !(user_variant & CTR_VAR_NO_ANYHIT) ? KV_ANYHIT : 0u);
-    if (count) kv = KV_PREFILTER | KV_COUNT;  // the counting launch walks like the reference (and wins over STATS)
-    return kv;
-  }
-};
-
-namespace {
+  for (const GrowBuf &b : bufs) HIP_TRY(b.host ? hipHostMalloc(b.p, need * b.elem, hipHostMallocDefault) : hipMalloc(b.p, need * b.elem));
+  cap = need;
+  return CTR_OK;
+}
 
 int make_rows(const ctr_scene *s, const ctr_rows *rin, DRows &R) {
   const uint64_t h = s->cam.h;
@@ -226,16 +232,8 @@ int attach_order(ctr_scene *s, RenderLaunch &L, bool count) {
   if ((s->user_variant & (CTR_VAR_NO_REORDER | CTR_VAR_STATS)) || count) return CTR_OK;
   const uint64_t n = ctr_launch_waves(L);
   if (n == 0 || n > 0x7FFFFFFFull) return CTR_OK;
-  if (n > s->order_cap) {
-    if (s->d_cost) (void)hipFree(s->d_cost);
-    if (s->d_order) (void)hipFree(s->d_order);
-    s->d_cost = s->d_order = nullptr;
-    s->order_cap = 0;
-    s->order_valid = false;
-    HIP_TRY(hipMalloc((void **)&s->d_cost, n * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&s->d_order, n * sizeof(uint32_t)));
-    s->order_cap = n;
-  }
+  if (n > s->order_cap) s->order_valid = false;  // new buffers hold no order
+  if (int st = grow(n, s->order_cap, {{(void **)&s->d_cost, sizeof(uint32_t), false}, {(void **)&s->d_order, sizeof(uint32_t), false}})) return st;
   const uint64_t key[6] = {n, ((uint64_t)L.w << 32) | L.h, ((uint64_t)L.rows.row_begin << 32) | L.rows.row_end,
                            ((uint64_t)L.rows.block_rows << 32) | L.rows.n_parts,
                            ((uint64_t)L.rows.part << 32) | L.rows.part_stride,
@@ -286,15 +284,13 @@ int attach_order(ctr_scene *s, RenderLaunch &L, bool count) {
 
 // the device receives the records a host-side edit changed (scene_flatten.h DirtyRange), in the order of the list
 int upload_dirty(ctr_scene *s, const std::vector<DirtyRange> &dirty) {
-  const FlatScene &F = s->flat;
-  const struct { void *dev; const void *host; size_t rec; } arrays[] = {  // indexed by DirtyRange::Array; rec: bytes per record
-      {s->d_objs, F.objs.data(), sizeof(DObj)}, {s->d_meshes, F.meshes.data(), sizeof(DObj)}, {s->d_tris, F.tris.data(), sizeof(DTri)},
-      {s->d_gnorm, F.gn.data(), 4 * sizeof(float)}, {s->d_nodes4, F.nodes4.data(), sizeof(DNode4)}};
-  for (const DirtyRange &r : dirty) {
-    const auto &a = arrays[r.array];
-    const void *src = r.payload.empty() ? (const char *)a.host + r.begin * a.rec : (const char *)r.payload.data();
-    if (r.count) HIP_TRY(hipMemcpy((char *)a.dev + r.begin * a.rec, src, r.count * a.rec, hipMemcpyHostToDevice));
-  }
+  const std::vector<SceneArray> arrays = scene_arrays(s, s->flat);
+  for (const DirtyRange &r : dirty)
+    for (const SceneArray &a : arrays) {
+      if (a.dirty != (int)r.array || !r.count) continue;
+      const void *src = r.payload.empty() ? (const char *)a.host + r.begin * a.rec : (const char *)r.payload.data();
+      HIP_TRY(hipMemcpy((char *)*a.dev + r.begin * a.rec, src, r.count * a.rec, hipMemcpyHostToDevice));
+    }
   return CTR_OK;
 }
 
@@ -331,36 +327,130 @@ int check_args(const ctr_scene *s, int bounces) {
   return CTR_OK;
 }
 
-int ensure_outputs(ctr_scene *s, size_t px) {
+// the caller's buffers of a host-form render; direct_delivery: the same buffers as the device sees them
+struct HostFrame { float *depth, *color3, *normal3, *uv2; };
+
+// Page-locked destinations (ctr_frame_alloc, hipHostMalloc, mapped hipHostRegister) are visible to the device:
+// the kernel then delivers the frame ITSELF, group of tiles by group of tiles while it renders (render_kernel.hip
+// "Host delivery"), so the 28 bytes per pixel cross PCIe underneath the rendering instead of in a DMA after it.
+// Any other destination: device buffers + copies (copy_out).
+bool direct_delivery(const ctr_scene *s, const HostFrame &o, size_t px, bool count, HostFrame &z) {
+  const bool merge_wanted = (s->user_variant & CTR_VAR_MERGE) && s->flat.merged.built && s->flat.merged.usable;  // (no delivering build of it)
+  return px && o.depth && o.color3 && o.normal3 && !count && !o.uv2 && !(s->user_variant & (CTR_VAR_NO_DIRECT | CTR_VAR_STATS | CTR_VAR_IGNORE_TRANSPARENT)) && !merge_wanted &&
+         ctr_host_delivery_available(s->kernel_variant(false)) &&
+         is_pinned(o.depth) && is_pinned(o.depth + px - 1) && is_pinned(o.color3) && is_pinned(o.color3 + 3 * px - 1) &&
+         is_pinned(o.normal3) && is_pinned(o.normal3 + 3 * px - 1) && device_view(o.depth, &z.depth) &&
+         device_view(o.color3, &z.color3) && device_view(o.normal3, &z.normal3);
+}
+
+// What the launch writes on the device: `spx` pixels per output buffer in d_out; for a direct launch (z: the caller's
+// buffers as the device sees them, else null) also the groups' completion counters.
+int prepare_outputs(ctr_scene *s, RenderLaunch &L, size_t spx, const HostFrame *z) {
   if (!s->h_counters) HIP_TRY(hipHostMalloc((void **)&s->h_counters, 16 * sizeof(unsigned long long), hipHostMallocDefault));
-  if (px <= s->out_px && s->d_out) return CTR_OK;
-  if (s->d_out) (void)hipFree(s->d_out);
-  s->d_out = nullptr;
-  s->out_px = 0;
-  HIP_TRY(hipMalloc((void **)&s->d_out, sizeof(float) * 7 * px));
-  s->out_px = px;
+  if (int st = grow(spx, s->out_px, {{(void **)&s->d_out, 7 * sizeof(float), false}})) return st;
+  L.depth = s->d_out;
+  L.color = s->d_out + spx;
+  L.normal = s->d_out + 4 * spx;
+  if (!z) return CTR_OK;
+  const size_t groups = (size_t)ctr_staging_groups(L);
+  if (int st = grow(groups, s->groups_cap, {{(void **)&s->d_groups, sizeof(uint32_t), false}, {(void **)&s->h_groups, sizeof(uint32_t), true}})) return st;
+  // cleared at the head of EVERY direct launch (a few microseconds): whatever an earlier launch left behind — one
+  // that faulted or was cut short included — this one starts from zero
+  HIP_TRY(hipMemsetAsync(s->d_groups, 0, groups * sizeof(uint32_t), nullptr));
+  L.host_depth = z->depth;
+  L.host_color = z->color3;
+  L.host_normal = z->normal3;
+  L.group_done = s->d_groups;
   return CTR_OK;
 }
 
-// is `p` page-locked host memory (hipHostMalloc / hipHostRegister)?  Then a D2H copy is one direct DMA.
-bool is_pinned(const void *p) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();  // plain malloc'ed memory: "invalid value", not an error of ours
-    return false;
+// Copy-out (the reference does 3·h row-wise copies, kernel.hpp:110-114).  Page-locked destinations
+// (ctr_frame_alloc, hipHostMalloc, hipHostRegister) are written by direct DMA queued behind the kernel:
+// ONE transfer when the three buffers are the consecutive parts of one block, else one per buffer.
+// Pageable destinations go through the runtime's staged copy, one call per buffer.
+int copy_out(ctr_scene *s, const RenderLaunch &L, const HostFrame &o, size_t px) {
+  const bool packed = o.depth && o.color3 == o.depth + px && o.normal3 == o.color3 + 3 * px;
+  if (packed && is_pinned(o.depth) && is_pinned(o.normal3 + 3 * px - 1)) {
+    HIP_TRY(hipMemcpyAsync(o.depth, s->d_out, sizeof(float) * 7 * px, hipMemcpyDeviceToHost, nullptr));
+  } else {
+    auto out = [&](float *dst, const float *src, size_t n) -> hipError_t {
+      if (!dst) return hipSuccess;
+      if (is_pinned(dst) && is_pinned(dst + n - 1)) return hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost, nullptr);
+      return hipMemcpy(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost);
+    };
+    HIP_TRY(out(o.depth, L.depth, px));
+    HIP_TRY(out(o.color3, L.color, 3 * px));
+    HIP_TRY(out(o.normal3, L.normal, 3 * px));
   }
-  return at.type == hipMemoryTypeHost;
+  if (o.uv2) HIP_TRY(hipMemcpy(o.uv2, s->d_uv, sizeof(float) * 2 * px, hipMemcpyDeviceToHost));
+  return CTR_OK;
 }
 
-// the device's address of page-locked host memory (false: not mapped for this device)
-bool device_view(float *host, float **dev) {
-  void *d = nullptr;
-  if (hipHostGetDevicePointer(&d, host, 0) != hipSuccess || !d) {
-    (void)hipGetLastError();
-    return false;
+// A direct launch is over and h_groups holds its counters: did the whole frame reach the caller's buffers?
+int check_delivery(ctr_scene *s, const RenderLaunch &L, const HostFrame &o, size_t spx, size_t n_groups) {
+  // every group of tiles must have counted all its tiles, or its pixels never left for the caller's buffers
+  // (how many tiles a group has is the kernel's business — its tile shape is a build option: ctr_group_tile_count)
+  size_t missing = 0;
+  for (size_t g = 0; g < n_groups; g++)
+    if (s->h_groups[g] != ctr_group_tile_count(L, g)) missing++;
+  if (missing) {
+    s->order_valid = false;  // whatever order that launch ran in is not to be trusted
+    return fail(CTR_E_DELIVERY, std::to_string(missing) + " of " + std::to_string(n_groups) +
+                " tile groups were not delivered to the caller's buffers (incomplete launch); render again");
   }
-  *dev = (float *)d;
-  return true;
+  if (!getenv("CUTRACE_VERIFY_DELIVERY")) return CTR_OK;
+  // Debug aid for the kernel's own delivery (render_kernel.hip "Host delivery" relies on write-through stores and
+  // scoped loads instead of fences): the tile-major staging copy of the frame is still on the device — fetch it
+  // and compare every pixel with what arrived in the caller's buffers.
+  std::vector<float> stg(7 * spx);
+  HIP_TRY(hipMemcpy(stg.data(), s->d_out, sizeof(float) * 7 * spx, hipMemcpyDeviceToHost));
+  const uint32_t w = s->cam.w;
+  uint64_t bad = 0;
+  for (uint32_t y = 0; y < L.rows.n_rows; y++)
+    for (uint32_t x = 0; x < w; x++) {
+      const size_t at = (size_t)y * w + x, sp = (size_t)ctr_staging_index(L, x, y);
+      bool ok = memcmp(&o.depth[at], &stg[sp], 4) == 0;
+      ok = ok && memcmp(&o.color3[3 * at], &stg[spx + 3 * sp], 12) == 0 && memcmp(&o.normal3[3 * at], &stg[4 * spx + 3 * sp], 12) == 0;
+      bad += ok ? 0 : 1;
+    }
+  if (bad) return fail(CTR_E_INVALID, "CUTRACE_VERIFY_DELIVERY: " + std::to_string(bad) + " delivered pixels differ from the staged frame");
+  return CTR_OK;
+}
+
+// What the launch counted and how long it took: kept for ctr_last_counters, printed by the statistics / timing builds,
+// returned in `stats` and `aabb_tris`.
+int report(ctr_scene *s, const RenderLaunch &L, std::chrono::high_resolution_clock::time_point t0, ctr_render_stats *stats,
+           unsigned long long *aabb_tris) {
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+  unsigned long long cnt[16];
+  memcpy(cnt, s->h_counters, sizeof(cnt));
+  memcpy(s->last_cnt, cnt, sizeof(cnt));
+  if (s->user_variant & CTR_VAR_STATS)
+    fprintf(stderr, "cutrace_amd stats: wave_casts=%llu nodes=%llu tri_prefilter=%llu tri_exact=%llu mesh_entries=%llu "
+                    "active_lanes=%llu node_lanes=%llu prefilter_lanes=%llu exact_lanes=%llu lane_max_nodes=%llu "
+                    "lane_max_tris=%llu kernel_ms=%.3f\n", cnt[4], cnt[5],
+            cnt[6], cnt[7], cnt[8], cnt[9], cnt[10], cnt[11], cnt[12], cnt[13], cnt[14], ms);
+  if (aabb_tris) *aabb_tris = cnt[2];
+  if (cnt[13] && !(s->user_variant & CTR_VAR_STATS))  // CTR_TIMING diagnostic build: share of the waves' lifetime
+    fprintf(stderr, "cutrace_amd timing (%% of wave cycles): cast_setup=%.1f planes=%.1f object_loop=%.1f tlas+aabb=%.1f "
+                    "mesh_setup=%.1f bvh_nodes=%.1f leaves=%.1f cont_mode=%.1f cont_rest=%.1f | wave_total=%llu kernel_ms=%.3f\n",
+            100.0 * cnt[4] / cnt[13], 100.0 * cnt[5] / cnt[13], 100.0 * cnt[6] / cnt[13], 100.0 * cnt[7] / cnt[13],
+            100.0 * cnt[8] / cnt[13], 100.0 * cnt[9] / cnt[13], 100.0 * cnt[10] / cnt[13], 100.0 * cnt[11] / cnt[13],
+            100.0 * cnt[12] / cnt[13], cnt[13], ms);
+  auto t1 = std::chrono::high_resolution_clock::now();
+  if (stats) {
+    stats->kernel_ms = ms;
+    stats->total_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    stats->ray_count = cnt[0];
+    stats->rows = L.rows.n_rows;
+    uint32_t bits = (uint32_t)cnt[1];
+    float md;
+    memcpy(&md, &bits, 4);
+    stats->max_depth = md;  // largest finite depth, 0 if none (kernel.hpp:120-125)
+    stats->reserved = 0;
+  }
+  return CTR_OK;
 }
 
 }  // namespace
@@ -397,30 +487,19 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   s->device = device;
   s->cam = to_dcam(d->cam);
 
-  auto upload = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
+  hipError_t er = hipSuccess;
+  for (const SceneArray &a : scene_arrays(s, F)) {
     // never hand the kernel a null base pointer: allocate at least one element's worth
     // (and 256 bytes beyond the end: the leaf loop requests the three cache lines after a leaf's first triangle ahead
     //  of their use, whether the leaf has that many triangles or not — render_kernel.hip, "touch")
-    hipError_t er = hipMalloc(dst, (bytes ? bytes : 64) + 256);
-    if (er != hipSuccess) return er;
-    if (bytes) er = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    return er;
-  };
-  hipError_t er;
-  if ((er = upload((void **)&s->d_objs, F.objs.data(), F.objs.size() * sizeof(DObj))) != hipSuccess ||
-      (er = upload((void **)&s->d_oloop, F.oloop.data(), F.oloop.size() * sizeof(DObj))) != hipSuccess ||
-      (er = upload((void **)&s->d_meshes, F.meshes.data(), F.meshes.size() * sizeof(DObj))) != hipSuccess ||
-      (er = upload((void **)&s->d_planes, F.planes.data(), F.planes.size() * sizeof(DPlanePair))) != hipSuccess ||
-      (er = upload((void **)&s->d_tris, F.tris.data(), F.tris.size() * sizeof(DTri))) != hipSuccess ||
-      (er = upload((void **)&s->d_nodes, F.nodes.data(), F.nodes.size() * sizeof(DNode))) != hipSuccess ||
-      (er = upload((void **)&s->d_nodes4, F.nodes4.data(), F.nodes4.size() * sizeof(DNode4))) != hipSuccess ||
-      (er = upload((void **)&s->d_gnorm, F.gn.data(), F.gn.size() * sizeof(float))) != hipSuccess ||
-      (er = upload((void **)&s->d_lights, F.lights.data(), F.lights.size() * sizeof(DLight))) != hipSuccess ||
-      (er = upload((void **)&s->d_mats, F.mats.data(), F.mats.size() * sizeof(DMat))) != hipSuccess ||
-      (er = upload((void **)&s->d_cams, &s->cam, sizeof(DCam))) != hipSuccess ||
+    if (er == hipSuccess) er = hipMalloc(a.dev, (a.bytes ? a.bytes : 64) + 256);
+    if (er == hipSuccess && a.bytes) er = hipMemcpy(*a.dev, a.host, a.bytes, hipMemcpyHostToDevice);
+  }
+  const size_t shard_bytes = (size_t)CTR_SHARDS * CTR_SHARD_WORDS * sizeof(unsigned long long);
+  if (er != hipSuccess || (er = hipMalloc((void **)&s->d_cams, sizeof(DCam))) != hipSuccess ||
+      (er = hipMemcpy(s->d_cams, &s->cam, sizeof(DCam), hipMemcpyHostToDevice)) != hipSuccess ||
       (er = hipMalloc((void **)&s->d_counters, 16 * sizeof(unsigned long long))) != hipSuccess ||
-      (er = hipMalloc((void **)&s->d_shards, (size_t)CTR_SHARDS * CTR_SHARD_WORDS * sizeof(unsigned long long))) != hipSuccess ||
-      (er = hipMemset(s->d_shards, 0, (size_t)CTR_SHARDS * CTR_SHARD_WORDS * sizeof(unsigned long long))) != hipSuccess ||
+      (er = hipMalloc((void **)&s->d_shards, shard_bytes)) != hipSuccess || (er = hipMemset(s->d_shards, 0, shard_bytes)) != hipSuccess ||
       (er = hipEventCreate(&s->ev0)) != hipSuccess || (er = hipEventCreate(&s->ev1)) != hipSuccess) {
     ctr_scene_destroy(s);
     return hip_fail(er, "scene upload");
@@ -467,8 +546,10 @@ int ctr_scene_set_cameras(ctr_scene *s, const ctr_camera *cams, uint32_t n) {
 void ctr_scene_destroy(ctr_scene *s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  for (void *p : {(void *)s->d_objs, (void *)s->d_oloop, (void *)s->d_meshes, (void *)s->d_planes, (void *)s->d_tris, (void *)s->d_nodes, (void *)s->d_nodes4, (void *)s->d_gnorm, (void *)s->d_lights, (void *)s->d_mats, (void *)s->d_cams,
-                  (void *)s->d_out, (void *)s->d_uv, (void *)s->d_groups, (void *)s->d_counters, (void *)s->d_shards, (void *)s->d_cost, (void *)s->d_order})
+  for (const SceneArray &a : scene_arrays(s, s->flat))
+    if (*a.dev) (void)hipFree(*a.dev);
+  for (void *p : {(void *)s->d_cams, (void *)s->d_out, (void *)s->d_uv, (void *)s->d_groups, (void *)s->d_counters, (void *)s->d_shards,
+                  (void *)s->d_cost, (void *)s->d_order})
     if (p) (void)hipFree(p);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
   if (s->h_groups) (void)hipHostFree(s->h_groups);
@@ -523,8 +604,7 @@ int ctr_render_device_batch(ctr_scene *s, float fudge, int bounces, const ctr_ro
   if (s->user_variant & CTR_VAR_IGNORE_TRANSPARENT) return fail(CTR_E_INVALID, "CTR_VAR_IGNORE_TRANSPARENT: host-buffer calls only (ctr_render, ctr_render_uv)");
   if (n_frames == 0 || first_frame >= s->n_cams || n_frames > s->n_cams - first_frame)
     return fail(CTR_E_INVALID, "frame range exceeds the cameras set with ctr_scene_set_cameras");
-  int cur = -1;
-  if (hipGetDevice(&cur) == hipSuccess && cur != s->device) HIP_TRY(hipSetDevice(s->device));
+  if ((st = use_device(s))) return st;
   RenderLaunch L{};
   fill_launch(s, L);
   if ((st = make_rows(s, rows, L.rows))) return st;
@@ -568,8 +648,8 @@ int ctr_render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows *ro
   return ctr_render_device_batch(s, fudge, bounces, rows, 0, 1, 0, 0, d_depth, d_color3, d_normal3, d_counters, hip_stream);
 }
 
-static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, float *depth, float *color3,
-                       float *normal3, ctr_render_stats *stats, bool count, unsigned long long *aabb_tris, float *uv2 = nullptr) {
+static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, const HostFrame &out, ctr_render_stats *stats,
+                       bool count, unsigned long long *aabb_tris) {
   auto t0 = std::chrono::high_resolution_clock::now();
   int st = check_args(s, bounces);
   if (st) return st;
@@ -579,56 +659,18 @@ static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *r
   fill_launch(s, L);
   if ((st = make_rows(s, rows, L.rows))) return st;
   const size_t px = (size_t)L.rows.n_rows * s->cam.w;
-  // Page-locked destinations (ctr_frame_alloc, hipHostMalloc, mapped hipHostRegister) are visible to the device:
-  // the kernel then delivers the frame ITSELF, group of tiles by group of tiles while it renders (render_kernel.hip
-  // "Host delivery"), so the 28 bytes per pixel cross PCIe underneath the rendering instead of in a DMA after it.
-  // Any other destination: device buffers + copies, below.
-  float *zd = nullptr, *zc = nullptr, *zn = nullptr;
-  const bool merge_wanted = (s->user_variant & CTR_VAR_MERGE) && s->flat.merged.built && s->flat.merged.usable;  // (no delivering build of it)
-  const bool direct = px && depth && color3 && normal3 && !count && !uv2 && !(s->user_variant & (CTR_VAR_NO_DIRECT | CTR_VAR_STATS | CTR_VAR_IGNORE_TRANSPARENT)) && !merge_wanted &&
-                      ctr_host_delivery_available(s->kernel_variant(false)) &&
-                      is_pinned(depth) && is_pinned(depth + px - 1) && is_pinned(color3) && is_pinned(color3 + 3 * px - 1) &&
-                      is_pinned(normal3) && is_pinned(normal3 + 3 * px - 1) && device_view(depth, &zd) &&
-                      device_view(color3, &zc) && device_view(normal3, &zn);
+  HostFrame z{};
+  const bool direct = direct_delivery(s, out, px, count, z);
   const size_t spx = direct ? (size_t)ctr_staging_pixels(L) : (px ? px : 1);  // pixels per output buffer on the device
-  if ((st = ensure_outputs(s, spx))) return st;
   L.fudge = fudge;
   L.bounces = bounces;
-  L.depth = s->d_out;
-  L.color = s->d_out + spx;
-  L.normal = s->d_out + 4 * spx;
-  if (direct) {
-    const size_t groups = (size_t)ctr_staging_groups(L);
-    if (groups > s->groups_cap) {
-      if (s->d_groups) (void)hipFree(s->d_groups);
-      s->d_groups = nullptr;
-      s->groups_cap = 0;
-      if (s->h_groups) (void)hipHostFree(s->h_groups);
-      s->h_groups = nullptr;
-      HIP_TRY(hipMalloc((void **)&s->d_groups, groups * sizeof(uint32_t)));
-      HIP_TRY(hipHostMalloc((void **)&s->h_groups, groups * sizeof(uint32_t), hipHostMallocDefault));
-      s->groups_cap = groups;
-    }
-    // cleared at the head of EVERY direct launch (a few microseconds): whatever an earlier launch left behind — one
-    // that faulted or was cut short included — this one starts from zero
-    HIP_TRY(hipMemsetAsync(s->d_groups, 0, groups * sizeof(uint32_t), nullptr));
-    L.host_depth = zd;
-    L.host_color = zc;
-    L.host_normal = zn;
-    L.group_done = s->d_groups;
-  }
+  if ((st = prepare_outputs(s, L, spx, direct ? &z : nullptr))) return st;
   L.counters = s->d_counters;
   L.variant = s->kernel_variant(count);
   const bool igntr = (s->user_variant & CTR_VAR_IGNORE_TRANSPARENT) != 0 && !count;
-  if ((uv2 || igntr) && px) {
+  if ((out.uv2 || igntr) && px) {
     if (count || (s->user_variant & CTR_VAR_STATS)) return fail(CTR_E_INVALID, "ctr_render_uv / CTR_VAR_IGNORE_TRANSPARENT: not with the counting / statistics variants");
-    if (px > s->uv_px) {
-      if (s->d_uv) (void)hipFree(s->d_uv);
-      s->d_uv = nullptr;
-      s->uv_px = 0;
-      HIP_TRY(hipMalloc((void **)&s->d_uv, sizeof(float) * 2 * px));
-      s->uv_px = px;
-    }
+    if ((st = grow(px, s->uv_px, {{(void **)&s->d_uv, 2 * sizeof(float), false}}))) return st;
     L.uv = s->d_uv;
     L.variant = (L.variant & (KV_ANYHIT | KV_FASTPOW)) | KV_PREFILTER | KV_BVH | KV_UV | (igntr ? KV_IGNTR : 0u);
   }
@@ -639,100 +681,24 @@ static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *r
   int e = ctr_launch_render(L, nullptr);
   if (e) return hip_fail((hipError_t)e, "render kernel launch");
   HIP_TRY(hipEventRecord(s->ev1, nullptr));
-  // Copy-out (the reference does 3·h row-wise copies, kernel.hpp:110-114).  Page-locked destinations
-  // (ctr_frame_alloc, hipHostMalloc, hipHostRegister) are written by direct DMA queued behind the kernel:
-  // ONE transfer when the three buffers are the consecutive parts of one block, else one per buffer.
-  // Pageable destinations go through the runtime's staged copy, one call per buffer.
-  if (px && !direct) {
-    const bool packed = depth && color3 == depth + px && normal3 == color3 + 3 * px;
-    if (packed && is_pinned(depth) && is_pinned(normal3 + 3 * px - 1)) {
-      HIP_TRY(hipMemcpyAsync(depth, s->d_out, sizeof(float) * 7 * px, hipMemcpyDeviceToHost, nullptr));
-    } else {
-      auto out = [&](float *dst, const float *src, size_t n) -> hipError_t {
-        if (!dst) return hipSuccess;
-        if (is_pinned(dst) && is_pinned(dst + n - 1)) return hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost, nullptr);
-        return hipMemcpy(dst, src, sizeof(float) * n, hipMemcpyDeviceToHost);
-      };
-      HIP_TRY(out(depth, L.depth, px));
-      HIP_TRY(out(color3, L.color, 3 * px));
-      HIP_TRY(out(normal3, L.normal, 3 * px));
-    }
-    if (uv2) HIP_TRY(hipMemcpy(uv2, s->d_uv, sizeof(float) * 2 * px, hipMemcpyDeviceToHost));
-  }
+  if (px && !direct && (st = copy_out(s, L, out, px))) return st;
   HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
   const size_t n_groups = direct ? (size_t)ctr_staging_groups(L) : 0;
   if (direct) HIP_TRY(hipMemcpyAsync(s->h_groups, s->d_groups, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));
-  if (direct) {
-    // every group of tiles must have counted all its tiles, or its pixels never left for the caller's buffers
-    // (how many tiles a group has is the kernel's business — its tile shape is a build option: ctr_group_tile_count)
-    size_t missing = 0;
-    for (size_t g = 0; g < n_groups; g++)
-      if (s->h_groups[g] != ctr_group_tile_count(L, g)) missing++;
-    if (missing) {
-      s->order_valid = false;  // whatever order that launch ran in is not to be trusted
-      return fail(CTR_E_DELIVERY, std::to_string(missing) + " of " + std::to_string(n_groups) +
-                  " tile groups were not delivered to the caller's buffers (incomplete launch); render again");
-    }
-  }
-  if (direct && getenv("CUTRACE_VERIFY_DELIVERY")) {
-    // Debug aid for the kernel's own delivery (render_kernel.hip "Host delivery" relies on write-through stores and
-    // scoped loads instead of fences): the tile-major staging copy of the frame is still on the device — fetch it
-    // and compare every pixel with what arrived in the caller's buffers.
-    std::vector<float> stg(7 * spx);
-    HIP_TRY(hipMemcpy(stg.data(), s->d_out, sizeof(float) * 7 * spx, hipMemcpyDeviceToHost));
-    const uint32_t w = s->cam.w;
-    uint64_t bad = 0;
-    for (uint32_t y = 0; y < L.rows.n_rows; y++)
-      for (uint32_t x = 0; x < w; x++) {
-        const size_t at = (size_t)y * w + x, sp = (size_t)ctr_staging_index(L, x, y);
-        bool ok = memcmp(&depth[at], &stg[sp], 4) == 0;
-        ok = ok && memcmp(&color3[3 * at], &stg[spx + 3 * sp], 12) == 0 && memcmp(&normal3[3 * at], &stg[4 * spx + 3 * sp], 12) == 0;
-        bad += ok ? 0 : 1;
-      }
-    if (bad) return fail(CTR_E_INVALID, "CUTRACE_VERIFY_DELIVERY: " + std::to_string(bad) + " delivered pixels differ from the staged frame");
-  }
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-  unsigned long long cnt[16];
-  memcpy(cnt, s->h_counters, sizeof(cnt));
-  memcpy(s->last_cnt, cnt, sizeof(cnt));
-  if (s->user_variant & CTR_VAR_STATS)
-    fprintf(stderr, "cutrace_amd stats: wave_casts=%llu nodes=%llu tri_prefilter=%llu tri_exact=%llu mesh_entries=%llu "
-                    "active_lanes=%llu node_lanes=%llu prefilter_lanes=%llu exact_lanes=%llu lane_max_nodes=%llu "
-                    "lane_max_tris=%llu kernel_ms=%.3f\n", cnt[4], cnt[5],
-            cnt[6], cnt[7], cnt[8], cnt[9], cnt[10], cnt[11], cnt[12], cnt[13], cnt[14], ms);
-  if (aabb_tris) *aabb_tris = cnt[2];
-  if (cnt[13] && !(s->user_variant & CTR_VAR_STATS))  // CTR_TIMING diagnostic build: share of the waves' lifetime
-    fprintf(stderr, "cutrace_amd timing (%% of wave cycles): cast_setup=%.1f planes=%.1f object_loop=%.1f tlas+aabb=%.1f "
-                    "mesh_setup=%.1f bvh_nodes=%.1f leaves=%.1f cont_mode=%.1f cont_rest=%.1f | wave_total=%llu kernel_ms=%.3f\n",
-            100.0 * cnt[4] / cnt[13], 100.0 * cnt[5] / cnt[13], 100.0 * cnt[6] / cnt[13], 100.0 * cnt[7] / cnt[13],
-            100.0 * cnt[8] / cnt[13], 100.0 * cnt[9] / cnt[13], 100.0 * cnt[10] / cnt[13], 100.0 * cnt[11] / cnt[13],
-            100.0 * cnt[12] / cnt[13], cnt[13], ms);
-  auto t1 = std::chrono::high_resolution_clock::now();
-  if (stats) {
-    stats->kernel_ms = ms;
-    stats->total_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    stats->ray_count = cnt[0];
-    stats->rows = L.rows.n_rows;
-    uint32_t bits = (uint32_t)cnt[1];
-    float md;
-    memcpy(&md, &bits, 4);
-    stats->max_depth = md;  // largest finite depth, 0 if none (kernel.hpp:120-125)
-    stats->reserved = 0;
-  }
-  return CTR_OK;
+  if (direct && (st = check_delivery(s, L, out, spx, n_groups))) return st;
+  return report(s, L, t0, stats, aabb_tris);
 }
 
 int ctr_render(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, float *depth, float *color3,
                float *normal3, ctr_render_stats *stats) {
-  return render_host(s, fudge, bounces, rows, depth, color3, normal3, stats, false, nullptr);
+  return render_host(s, fudge, bounces, rows, {depth, color3, normal3, nullptr}, stats, false, nullptr);
 }
 
 int ctr_render_uv(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, float *depth, float *color3,
                   float *normal3, float *uv2, ctr_render_stats *stats) {
   if (!uv2) return fail(CTR_E_INVALID, "ctr_render_uv: null uv buffer");
-  return render_host(s, fudge, bounces, rows, depth, color3, normal3, stats, false, nullptr, uv2);
+  return render_host(s, fudge, bounces, rows, {depth, color3, normal3, uv2}, stats, false, nullptr);
 }
 
 int ctr_debug_poison_next_order(ctr_scene *s) {
@@ -781,7 +747,7 @@ int ctr_algorithmic_bytes(ctr_scene *s, float fudge, int bounces, const ctr_rows
                           uint64_t *ray_count) {
   ctr_render_stats stt{};
   unsigned long long aabb = 0;
-  int st = render_host(s, fudge, bounces, rows, nullptr, nullptr, nullptr, &stt, true, &aabb);
+  int st = render_host(s, fudge, bounces, rows, {}, &stt, true, &aabb);
   if (st) return st;
   // 56·N_obj per ray_cast + 48·N_tri per AABB-hit mesh + 28 B per pixel written
   if (bytes) *bytes = 56ull * s->flat.objs.size() * stt.ray_count + 48ull * aabb + 28ull * stt.rows * s->cam.w;
@@ -790,133 +756,3 @@ int ctr_algorithmic_bytes(ctr_scene *s, float fudge, int bounces, const ctr_rows
 }
 
 }  // extern "C"
-
-extern "C" int ctr_cast_rays(ctr_scene *s, const ctr_ray_query *q, void *hip_stream) {
-  if (!q) return fail(CTR_E_INVALID, "ctr_cast_rays: null query");
-  constexpr uint32_t KNOWN = CTR_RAY_IGNORE_TRANSPARENT | CTR_RAY_LINEAR | CTR_RAY_SHADOW;
-  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, "ctr_cast_rays: unknown flag bits " + std::to_string(q->flags & ~KNOWN));
-  const bool shadow = (q->flags & CTR_RAY_SHADOW) != 0;
-  const bool any_nearest = q->d_t || q->d_object || q->d_prim || q->d_point || q->d_normal || q->d_uv;
-  if (shadow && (q->flags & CTR_RAY_IGNORE_TRANSPARENT))
-    return fail(CTR_E_INVALID, "ctr_cast_rays: CTR_RAY_SHADOW and CTR_RAY_IGNORE_TRANSPARENT exclude each other");
-  if (shadow && (any_nearest || !q->d_shadow))
-    return fail(CTR_E_INVALID, "ctr_cast_rays: CTR_RAY_SHADOW writes d_shadow only, and needs it");
-  if (!shadow && (!any_nearest || q->d_shadow))
-    return fail(CTR_E_INVALID, "ctr_cast_rays: a nearest-hit query needs at least one of its outputs and no d_shadow");
-  if (!s) return fail(CTR_E_INVALID, "ctr_cast_rays: null scene");
-  if (q->n_rays >= 0x80000000ull) return fail(CTR_E_INVALID, "ctr_cast_rays: n_rays must be below 2^31");
-  if (q->n_rays == 0) return CTR_OK;
-  if (!q->d_origin || !q->d_dir) return fail(CTR_E_INVALID, "ctr_cast_rays: null rays");
-  // every pointer the kernel touches must be device memory of the scene's device (no size check is possible here)
-  const void *ptrs[] = {q->d_origin, q->d_dir, q->d_min_t, q->d_max_t, q->d_t, q->d_object, q->d_prim, q->d_point,
-                        q->d_normal, q->d_uv, q->d_shadow};
-  const char *names[] = {"d_origin", "d_dir", "d_min_t", "d_max_t", "d_t", "d_object", "d_prim", "d_point",
-                         "d_normal", "d_uv", "d_shadow"};
-  for (size_t k = 0; k < sizeof(ptrs) / sizeof(ptrs[0]); k++) {
-    if (!ptrs[k]) continue;
-    hipPointerAttribute_t at{};
-    const bool ok = hipPointerGetAttributes(&at, ptrs[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == s->device;
-    if (!ok) {
-      (void)hipGetLastError();  // plain host memory: "invalid value", not an error of the stream
-      return fail(CTR_E_INVALID, std::string("ctr_cast_rays: ") + names[k] + " is not device memory of the scene's device");
-    }
-  }
-  int cur = -1;
-  if (hipGetDevice(&cur) == hipSuccess && cur != s->device) HIP_TRY(hipSetDevice(s->device));
-  RayLaunch L{};
-  L.objs = s->d_objs;
-  L.oloop = s->d_oloop;
-  L.meshes = s->d_meshes;
-  L.planes = s->d_planes;
-  L.tris = s->d_tris;
-  L.nodes4 = s->d_nodes4;
-  L.gnorm = s->d_gnorm;
-  L.mats = s->d_mats;
-  L.n_oloop = (uint32_t)s->flat.oloop.size();
-  L.n_plane_recs = (uint32_t)s->flat.planes.size();
-  L.n_mesh = s->flat.n_mesh;
-  L.stack_slots = s->flat.ray_slots;
-  L.n_rays = (uint32_t)q->n_rays;
-  L.flags = q->flags;
-  L.anyhit = shadow && s->flat.all_opaque;
-  L.min_t = q->min_t;
-  L.max_t = q->max_t;
-  L.origin = q->d_origin;
-  L.dir = q->d_dir;
-  L.min_t_arr = q->d_min_t;
-  L.max_t_arr = q->d_max_t;
-  L.t = q->d_t;
-  L.object = q->d_object;
-  L.prim = q->d_prim;
-  L.point = q->d_point;
-  L.normal = q->d_normal;
-  L.uv = q->d_uv;
-  L.shadow = q->d_shadow;
-  const int e = ctr_launch_rays(L, hip_stream);
-  if (e) return hip_fail((hipError_t)e, "ray query kernel launch");
-  return CTR_OK;
-}
-
-extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_stream) {
-  if (!q) return fail(CTR_E_INVALID, "ctr_shade_rays: null query");
-  constexpr uint32_t KNOWN = CTR_SHADE_LINEAR | CTR_SHADE_EXACT_POW;
-  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, "ctr_shade_rays: unknown flag bits " + std::to_string(q->flags & ~KNOWN));
-  if (q->bounces < 0 || q->bounces > CTR_MAX_BOUNCES)
-    return fail(CTR_E_INVALID, "ctr_shade_rays: bounces " + std::to_string(q->bounces) + " outside [0, " + std::to_string(CTR_MAX_BOUNCES) + "]");
-  if (!q->d_color) return fail(CTR_E_INVALID, "ctr_shade_rays: d_color is required");
-  if (!s) return fail(CTR_E_INVALID, "ctr_shade_rays: null scene");
-  if (q->n_rays >= 0x80000000ull) return fail(CTR_E_INVALID, "ctr_shade_rays: n_rays must be below 2^31");
-  if (q->n_rays == 0) return CTR_OK;
-  if (!q->d_origin || !q->d_dir) return fail(CTR_E_INVALID, "ctr_shade_rays: null rays");
-  // every pointer the kernel touches must be device memory of the scene's device (no size check is possible here)
-  const void *ptrs[] = {q->d_origin, q->d_dir, q->d_color, q->d_t, q->d_object, q->d_normal};
-  const char *names[] = {"d_origin", "d_dir", "d_color", "d_t", "d_object", "d_normal"};
-  for (size_t k = 0; k < sizeof(ptrs) / sizeof(ptrs[0]); k++) {
-    if (!ptrs[k]) continue;
-    hipPointerAttribute_t at{};
-    const bool ok = hipPointerGetAttributes(&at, ptrs[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == s->device;
-    if (!ok) {
-      (void)hipGetLastError();  // plain host memory: "invalid value", not an error of the stream
-      return fail(CTR_E_INVALID, std::string("ctr_shade_rays: ") + names[k] + " is not device memory of the scene's device");
-    }
-  }
-  ShadeLaunch L{};
-  L.objs = s->d_objs;
-  L.oloop = s->d_oloop;
-  L.meshes = s->d_meshes;
-  L.planes = s->d_planes;
-  L.tris = s->d_tris;
-  L.nodes4 = s->d_nodes4;
-  L.gnorm = s->d_gnorm;
-  L.mats = s->d_mats;
-  L.lights = s->d_lights;
-  L.n_oloop = (uint32_t)s->flat.oloop.size();
-  L.n_plane_recs = (uint32_t)s->flat.planes.size();
-  L.n_mesh = s->flat.n_mesh;
-  L.n_light = (uint32_t)s->flat.lights.size();
-  L.stack_slots = s->flat.ray_slots;
-  L.frames = ctr_shade_frames(q->bounces, s->flat.any_bounce);
-  L.frame_dwords = s->flat.need_cold ? 10u : 4u;
-  L.all_opaque = s->flat.all_opaque ? 1u : 0u;
-  L.n_rays = (uint32_t)q->n_rays;
-  L.flags = q->flags;
-  L.bounces = q->bounces;
-  L.min_t = q->min_t;
-  L.ambient = q->ambient;
-  L.origin = q->d_origin;
-  L.dir = q->d_dir;
-  L.color = q->d_color;
-  L.t = q->d_t;
-  L.object = q->d_object;
-  L.normal = q->d_normal;
-  if (ctr_shade_lds_bytes(L) > CTR_SHADE_LDS_MAX)
-    return fail(CTR_E_INVALID, "ctr_shade_rays: the walk stack of this scene's mesh trees and " + std::to_string(L.frames) +
-                                   " recursion frames need " + std::to_string(ctr_shade_lds_bytes(L)) +
-                                   " bytes of LDS per workgroup, more than " + std::to_string(CTR_SHADE_LDS_MAX) +
-                                   " (fewer bounces or CTR_SHADE_LINEAR fit)");
-  int cur = -1;
-  if (hipGetDevice(&cur) == hipSuccess && cur != s->device) HIP_TRY(hipSetDevice(s->device));
-  const int e = ctr_launch_shade(L, hip_stream);
-  if (e) return hip_fail((hipError_t)e, "radiance query kernel launch");
-  return CTR_OK;
-}

@@ -24,21 +24,11 @@
 #include <string>
 #include <vector>
 
+#include "ctr_internal.h"
 #include "cutrace_amd.h"
 #include "scene_device.h"
 
 namespace {
-
-int mfail(int code, const std::string &msg) {
-  ctr_internal_set_error(msg.c_str());
-  fprintf(stderr, "cutrace_amd: %s\n", msg.c_str());  // print-and-continue, like cudaCheck (inc/cuda.hpp:12-22)
-  return code;
-}
-#define MHIP(expr)                                                                                          \
-  do {                                                                                                      \
-    hipError_t e_ = (expr);                                                                                 \
-    if (e_ != hipSuccess) return mfail(CTR_E_HIP_BASE + (int)e_, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
 // ---- RCCL, bound at run time ----
 struct Rccl {
@@ -129,24 +119,10 @@ uint64_t part_rows(uint64_t h, uint64_t block_rows, uint32_t part, uint32_t n_pa
   return n;
 }
 
-bool pinned(const void *p) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return at.type == hipMemoryTypeHost;
-}
-
 // the device's address of a page-locked host range (nullptr: not page-locked, or not mapped for the current device)
 float *device_view(float *host, size_t n) {
-  if (!host || !n || !pinned(host) || !pinned(host + n - 1)) return nullptr;
-  void *d = nullptr;
-  if (hipHostGetDevicePointer(&d, host, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
-  return (float *)d;
+  float *d = nullptr;
+  return host && n && is_pinned(host) && is_pinned(host + n - 1) && ::device_view(host, &d) ? d : nullptr;
 }
 
 }  // namespace
@@ -200,33 +176,33 @@ int ensure_buffers(ctr_multi *m, uint64_t block_rows) {
   }
   if (cap == 0) cap = 1;
   if (cap > m->cap_px) {
-    if (m->inflight) return mfail(CTR_E_INVALID, "ctr_multi: the frame grew while frames are in flight (ctr_multi_wait first)");
+    if (m->inflight) return fail(CTR_E_INVALID, "ctr_multi: the frame grew while frames are in flight (ctr_multi_wait first)");
     m->cap_px = 0;  // (an allocation that fails below leaves null buffers: the next call must come back here whatever its size)
     for (uint32_t p = 0; p < n; p++) {
       Part &P = m->parts[p];
       for (int q = 0; q < SLOTS; q++) {
-        MHIP(hipSetDevice(P.device));
+        HIP_TRY(hipSetDevice(P.device));
         if (P.buf[q]) (void)hipFree(P.buf[q]);
         P.buf[q] = nullptr;
-        MHIP(hipMalloc((void **)&P.buf[q], sizeof(float) * 7 * cap));
+        HIP_TRY(hipMalloc((void **)&P.buf[q], sizeof(float) * 7 * cap));
         // (part 0 has a gathered copy only under "rccl-self"; it is sized like everybody's and regrown with them —
         //  round 2 grew only the others', and a larger frame then overran it)
-        MHIP(hipSetDevice(m->parts[0].device));
+        HIP_TRY(hipSetDevice(m->parts[0].device));
         if (P.gathered[q]) (void)hipFree(P.gathered[q]);
         P.gathered[q] = nullptr;
-        if (p > 0 || (n == 1 && m->use_rccl)) MHIP(hipMalloc((void **)&P.gathered[q], sizeof(float) * 7 * cap));
+        if (p > 0 || (n == 1 && m->use_rccl)) HIP_TRY(hipMalloc((void **)&P.gathered[q], sizeof(float) * 7 * cap));
       }
     }
     m->cap_px = cap;
   }
   if (m->w * m->h > m->frame_px && n > 1) {
-    if (m->inflight) return mfail(CTR_E_INVALID, "ctr_multi: the frame grew while frames are in flight (ctr_multi_wait first)");
-    MHIP(hipSetDevice(m->parts[0].device));
+    if (m->inflight) return fail(CTR_E_INVALID, "ctr_multi: the frame grew while frames are in flight (ctr_multi_wait first)");
+    HIP_TRY(hipSetDevice(m->parts[0].device));
     m->frame_px = 0;
     for (int q = 0; q < SLOTS; q++) {
       if (m->frame[q]) (void)hipFree(m->frame[q]);
       m->frame[q] = nullptr;
-      MHIP(hipMalloc((void **)&m->frame[q], sizeof(float) * 7 * m->w * m->h));
+      HIP_TRY(hipMalloc((void **)&m->frame[q], sizeof(float) * 7 * m->w * m->h));
     }
     m->frame_px = m->w * m->h;
   }
@@ -239,7 +215,7 @@ extern "C" {
 
 int ctr_multi_create(const ctr_scene_desc *desc, const int *devices, int n_devices, ctr_multi **out) {
   if (!desc || !devices || !out || n_devices < 1 || n_devices > CTR_MULTI_MAX_DEVICES)
-    return mfail(CTR_E_INVALID, "ctr_multi_create: bad argument (1.." + std::to_string(CTR_MULTI_MAX_DEVICES) + " devices)");
+    return fail(CTR_E_INVALID, "ctr_multi_create: bad argument (1.." + std::to_string(CTR_MULTI_MAX_DEVICES) + " devices)");
   *out = nullptr;
   auto *m = new ctr_multi();
   m->w = desc->cam.w;
@@ -267,12 +243,12 @@ int ctr_multi_create(const ctr_scene_desc *desc, const int *devices, int n_devic
       if (e == hipSuccess) e = hipSetDevice(devices[i]);
       if (e == hipSuccess) e = hipMalloc((void **)&P.counters[q], 16 * sizeof(unsigned long long));
     }
-    if (e != hipSuccess) { ctr_multi_destroy(m); return mfail(CTR_E_HIP_BASE + (int)e, std::string("ctr_multi_create: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) { ctr_multi_destroy(m); return hip_fail(e, "ctr_multi_create"); }
   }
   hipError_t e = hipHostMalloc((void **)&m->h_counters, sizeof(unsigned long long) * 16 * n_devices * SLOTS, hipHostMallocDefault);
   if (e == hipSuccess) e = hipSetDevice(devices[0]);
   for (int q = 0; q < SLOTS && e == hipSuccess; q++) e = hipEventCreateWithFlags(&m->frames[q].ev_done, hipEventDisableTiming);
-  if (e != hipSuccess) { ctr_multi_destroy(m); return mfail(CTR_E_HIP_BASE + (int)e, "ctr_multi_create: hipHostMalloc / events"); }
+  if (e != hipSuccess) { ctr_multi_destroy(m); return hip_fail(e, "ctr_multi_create: hipHostMalloc / events"); }
   const char *force = getenv("CUTRACE_MULTI_TRANSPORT");  // "peer" forces hipMemcpyPeerAsync; "rccl-self" see below
   if (n_devices == 1 && force && !strcmp(force, "rccl-self") && g_rccl.load()) {
     // Self-test of the RCCL plumbing on a one-GPU box: a one-rank communicator, and the frame travels through one
@@ -284,7 +260,7 @@ int ctr_multi_create(const ctr_scene_desc *desc, const int *devices, int n_devic
       m->use_rccl = true;
       m->transport = "rccl-self";
     } else {
-      mfail(CTR_E_HIP_BASE, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r));
+      fail(CTR_E_HIP_BASE, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r));
     }
   }
   if (n_devices > 1) {
@@ -296,7 +272,7 @@ int ctr_multi_create(const ctr_scene_desc *desc, const int *devices, int n_devic
         m->use_rccl = true;
         m->transport = "rccl";
       } else {
-        mfail(CTR_E_HIP_BASE, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r) + " — falling back to peer copies");
+        fail(CTR_E_HIP_BASE, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r) + " — falling back to peer copies");
       }
     }
     if (!m->use_rccl) {
@@ -357,15 +333,15 @@ int ctr_multi_devices(const ctr_multi *m) { return m ? (int)m->parts.size() : 0;
 const char *ctr_multi_transport(const ctr_multi *m) { return m ? m->transport.c_str() : ""; }
 
 int ctr_multi_size(const ctr_multi *m, uint64_t *w, uint64_t *h) {
-  if (!m) return mfail(CTR_E_INVALID, "null group");
+  if (!m) return fail(CTR_E_INVALID, "null group");
   if (w) *w = m->w;
   if (h) *h = m->h;
   return CTR_OK;
 }
 
 int ctr_multi_set_size(ctr_multi *m, uint64_t w, uint64_t h) {
-  if (!m) return mfail(CTR_E_INVALID, "null group");
-  if (m->inflight) return mfail(CTR_E_INVALID, "ctr_multi_set_size: frames in flight (ctr_multi_wait first)");
+  if (!m) return fail(CTR_E_INVALID, "null group");
+  if (m->inflight) return fail(CTR_E_INVALID, "ctr_multi_set_size: frames in flight (ctr_multi_wait first)");
   for (Part &P : m->parts) {
     int st = ctr_scene_set_size(P.scene, w, h);
     if (st) return st;
@@ -376,7 +352,7 @@ int ctr_multi_set_size(ctr_multi *m, uint64_t w, uint64_t h) {
 }
 
 int ctr_multi_set_variant(ctr_multi *m, uint32_t bits) {
-  if (!m) return mfail(CTR_E_INVALID, "null group");
+  if (!m) return fail(CTR_E_INVALID, "null group");
   for (Part &P : m->parts) {
     int st = ctr_set_variant(P.scene, bits);
     if (st) return st;
@@ -396,8 +372,8 @@ int ctr_multi_set_variant(ctr_multi *m, uint32_t bits) {
 // ctr_render_multi = submit + wait.  One device with a page-locked or pageable destination goes through ctr_render
 // (host delivery / its own copies) and is synchronous; "page-locked" is what makes the final D2H asynchronous at all.
 int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows, float *depth, float *color3, float *normal3) {
-  if (!m) return mfail(CTR_E_INVALID, "null group");
-  if (m->inflight >= SLOTS) return mfail(CTR_E_INVALID, "ctr_multi_submit: two frames are in flight already (ctr_multi_wait first)");
+  if (!m) return fail(CTR_E_INVALID, "null group");
+  if (m->inflight >= SLOTS) return fail(CTR_E_INVALID, "ctr_multi_submit: two frames are in flight already (ctr_multi_wait first)");
   if (block_rows == 0) block_rows = 8;
   const uint32_t n = (uint32_t)m->parts.size();
   int st = ensure_buffers(m, block_rows);
@@ -412,12 +388,12 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
   Part &P0 = m->parts[0];
   // Page-locked destinations are written by device 0 itself: through ctr_render's host delivery when there is one
   // device, by the re-interleave kernel (whole rows, 16 bytes per lane) otherwise — no frame-sized D2H after it.
-  MHIP(hipSetDevice(P0.device));
+  HIP_TRY(hipSetDevice(P0.device));
   float *zd = nullptr, *zc = nullptr, *zn = nullptr;
   const bool direct = fpx && !(m->variant & CTR_VAR_NO_DIRECT) && (zd = device_view(depth, fpx)) &&
                       (zc = device_view(color3, 3 * fpx)) && (zn = device_view(normal3, 3 * fpx));
-  const bool dest_pinned = fpx && depth && color3 && normal3 && pinned(depth) && pinned(depth + fpx - 1) && pinned(color3) &&
-                           pinned(color3 + 3 * fpx - 1) && pinned(normal3) && pinned(normal3 + 3 * fpx - 1);
+  const bool dest_pinned = fpx && depth && color3 && normal3 && is_pinned(depth) && is_pinned(depth + fpx - 1) && is_pinned(color3) &&
+                           is_pinned(color3 + 3 * fpx - 1) && is_pinned(normal3) && is_pinned(normal3 + 3 * fpx - 1);
   if (n == 1 && !m->use_rccl && (direct || !dest_pinned)) {
     // one device: ctr_render is the better path both for page-locked destinations (delivered by the kernel) and for
     // pageable ones (its three plain copies: 2.2 ms per 1080p frame where queuing them on a side stream took 4.8)
@@ -428,7 +404,7 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
     if (m->inflight) {
       hipError_t e = hipStreamSynchronize(P0.stream);
       if (e == hipSuccess) e = hipStreamSynchronize(P0.cstream);
-      if (e != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)e, std::string("ctr_multi_submit: ") + hipGetErrorString(e)));
+      if (e != hipSuccess) return fail_sync(m, hip_fail(e, "ctr_multi_submit"));
     }
     if ((st = ctr_render(P0.scene, fudge, bounces, nullptr, depth, color3, normal3, &F.one))) return fail_sync(m, st);
     F.sync_done = true;
@@ -440,12 +416,12 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
   // ---- 1. every device renders its interleaved row blocks into its compact buffer of this slot ----
   for (uint32_t p = 0; p < n; p++) {
     Part &P = m->parts[p];
-    if ((st = (int)hipSetDevice(P.device))) return fail_sync(m, mfail(CTR_E_HIP_BASE + st, "hipSetDevice"));
+    if ((st = (int)hipSetDevice(P.device))) return fail_sync(m, hip_fail((hipError_t)st, "hipSetDevice"));
     hipError_t e = hipStreamWaitEvent(P.stream, P.ev_moved[q], 0);  // (never recorded yet: no wait)
     if (e == hipSuccess) e = hipStreamWaitEvent(P.stream, P.ev_moved0[q], 0);
     if (e == hipSuccess) e = hipMemsetAsync(P.counters[q], 0, 16 * sizeof(unsigned long long), P.stream);
     if (e == hipSuccess) e = hipEventRecord(P.ev0[q], P.stream);
-    if (e != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)e, std::string("ctr_multi_submit: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return fail_sync(m, hip_fail(e, "ctr_multi_submit"));
     const uint64_t px = P.rows * w;
     if (px) {
       ctr_rows r{0, h, block_rows, p, n};
@@ -455,7 +431,7 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
     e = hipEventRecord(P.ev1[q], P.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(hc + 16 * p, P.counters[q], 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, P.stream);
     if (e == hipSuccess) e = hipEventRecord(P.ev_cnt[q], P.stream);
-    if (e != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)e, std::string("ctr_multi_submit: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return fail_sync(m, hip_fail(e, "ctr_multi_submit"));
   }
   // ---- 2. one gather to device 0, on the transfer streams ----
   hipError_t he = hipSuccess;
@@ -465,7 +441,7 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
         he = hipSetDevice(m->parts[p].device);
         if (he == hipSuccess) he = hipStreamWaitEvent(m->parts[p].cstream, m->parts[p].ev1[q], 0);
       }
-      if (he != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)he, std::string("RCCL gather: ") + hipGetErrorString(he)));
+      if (he != hipSuccess) return fail_sync(m, hip_fail(he, "RCCL gather"));
       // (no early return between GroupStart and GroupEnd: an open group would poison every later call)
       ncclResult_t r = g_rccl.GroupStart();
       for (uint32_t p = 1; p < n && r == ncclSuccess && he == hipSuccess; p++) {
@@ -482,8 +458,8 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
       }
       const ncclResult_t r2 = g_rccl.GroupEnd();
       if (r == ncclSuccess) r = r2;
-      if (he != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)he, std::string("RCCL gather: ") + hipGetErrorString(he)));
-      if (r != ncclSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE, std::string("RCCL gather: ") + g_rccl.GetErrorString(r)));
+      if (he != hipSuccess) return fail_sync(m, hip_fail(he, "RCCL gather"));
+      if (r != ncclSuccess) return fail_sync(m, fail(CTR_E_HIP_BASE, std::string("RCCL gather: ") + g_rccl.GetErrorString(r)));
       for (uint32_t p = 1; p < n && he == hipSuccess; p++) {  // sent: the compact buffer may be rendered into again
         he = hipSetDevice(m->parts[p].device);
         if (he == hipSuccess) he = hipEventRecord(m->parts[p].ev_moved[q], m->parts[p].cstream);
@@ -501,12 +477,12 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
         if (he == hipSuccess) he = hipEventRecord(P.ev_moved0[q], P0.cstream);
       }
     }
-    if (he != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)he, std::string("gather: ") + hipGetErrorString(he)));
+    if (he != hipSuccess) return fail_sync(m, hip_fail(he, "gather"));
   }
   // device 0's transfer stream also needs device 0's own part
   he = hipSetDevice(P0.device);
   if (he == hipSuccess) he = hipStreamWaitEvent(P0.cstream, P0.ev1[q], 0);
-  if (he != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)he, std::string("ctr_multi_submit: ") + hipGetErrorString(he)));
+  if (he != hipSuccess) return fail_sync(m, hip_fail(he, "ctr_multi_submit"));
   const float *self_result = nullptr;
   if (n == 1 && m->use_rccl && fpx) {  // "rccl-self": the frame goes through RCCL once, rank 0 -> rank 0
     ncclResult_t r = g_rccl.GroupStart();
@@ -514,7 +490,7 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
     if (r == ncclSuccess) r = g_rccl.Recv(P0.gathered[q], (size_t)(7 * fpx), ncclFloat, 0, P0.comm, P0.cstream);
     const ncclResult_t r2 = g_rccl.GroupEnd();
     if (r == ncclSuccess) r = r2;
-    if (r != ncclSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE, std::string("RCCL self send/recv: ") + g_rccl.GetErrorString(r)));
+    if (r != ncclSuccess) return fail_sync(m, fail(CTR_E_HIP_BASE, std::string("RCCL self send/recv: ") + g_rccl.GetErrorString(r)));
     self_result = P0.gathered[q];
   }
   // ---- 3. re-interleave on device 0, 4. one D2H ----
@@ -536,7 +512,7 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
     if (direct) hipLaunchKernelGGL(reinterleave_rows, dim3((uint32_t)h), dim3(256), 0, P0.cstream, R, zd, zc, zn);
     else hipLaunchKernelGGL(reinterleave_rows, dim3((uint32_t)h), dim3(256), 0, P0.cstream, R, fr, fr + fpx, fr + 4 * fpx);
     he = hipGetLastError();
-    if (he != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)he, std::string("reinterleave_rows: ") + hipGetErrorString(he)));
+    if (he != hipSuccess) return fail_sync(m, hip_fail(he, "reinterleave_rows"));
     result = fr;
   }
   if (fpx && !(direct && n > 1)) {
@@ -549,20 +525,20 @@ int ctr_multi_submit(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
       if (color3 && he == hipSuccess) he = hipMemcpyAsync(color3, result + fpx, sizeof(float) * 3 * fpx, hipMemcpyDeviceToHost, P0.cstream);
       if (normal3 && he == hipSuccess) he = hipMemcpyAsync(normal3, result + 4 * fpx, sizeof(float) * 3 * fpx, hipMemcpyDeviceToHost, P0.cstream);
     }
-    if (he != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)he, std::string("frame copy-out: ") + hipGetErrorString(he)));
+    if (he != hipSuccess) return fail_sync(m, hip_fail(he, "frame copy-out"));
   }
   // device 0's compact buffer has been read once the assembly (or, n == 1, the copy-out) is through
   he = hipEventRecord(P0.ev_moved[q], P0.cstream);
   if (he == hipSuccess) he = hipEventRecord(F.ev_done, P0.cstream);
-  if (he != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)he, std::string("ctr_multi_submit: ") + hipGetErrorString(he)));
+  if (he != hipSuccess) return fail_sync(m, hip_fail(he, "ctr_multi_submit"));
   F.busy = true;
   m->inflight++;
   return CTR_OK;
 }
 
 int ctr_multi_wait(ctr_multi *m, ctr_render_stats *stats) {
-  if (!m) return mfail(CTR_E_INVALID, "null group");
-  if (m->inflight == 0) return mfail(CTR_E_INVALID, "ctr_multi_wait: no frame in flight");
+  if (!m) return fail(CTR_E_INVALID, "null group");
+  if (m->inflight == 0) return fail(CTR_E_INVALID, "ctr_multi_wait: no frame in flight");
   const int q = m->head;
   Frame &F = m->frames[q];
   const uint32_t n = (uint32_t)m->parts.size();
@@ -582,7 +558,7 @@ int ctr_multi_wait(ctr_multi *m, ctr_render_stats *stats) {
       if (e == hipSuccess) e = hipEventSynchronize(m->parts[p].ev_moved[q]);
       if (e == hipSuccess) e = hipEventSynchronize(m->parts[p].ev_moved0[q]);
     }
-    if (e != hipSuccess) return fail_sync(m, mfail(CTR_E_HIP_BASE + (int)e, std::string("ctr_multi_wait: ") + hipGetErrorString(e)));
+    if (e != hipSuccess) return fail_sync(m, hip_fail(e, "ctr_multi_wait"));
     auto t1 = std::chrono::high_resolution_clock::now();
     if (stats) {
       memset(stats, 0, sizeof(*stats));
@@ -590,8 +566,8 @@ int ctr_multi_wait(ctr_multi *m, ctr_render_stats *stats) {
       uint32_t bits = 0;
       for (uint32_t p = 0; p < n; p++) {
         float ms = 0.f;
-        MHIP(hipSetDevice(m->parts[p].device));
-        MHIP(hipEventElapsedTime(&ms, m->parts[p].ev0[q], m->parts[p].ev1[q]));
+        HIP_TRY(hipSetDevice(m->parts[p].device));
+        HIP_TRY(hipEventElapsedTime(&ms, m->parts[p].ev0[q], m->parts[p].ev1[q]));
         stats->kernel_ms = stats->kernel_ms > ms ? stats->kernel_ms : ms;  // the slowest device's kernel
         stats->ray_count += hc[16 * p + 0];
         const uint32_t b = (uint32_t)hc[16 * p + 1];
@@ -611,8 +587,8 @@ int ctr_multi_wait(ctr_multi *m, ctr_render_stats *stats) {
 
 int ctr_render_multi(ctr_multi *m, float fudge, int bounces, uint64_t block_rows, float *depth, float *color3,
                      float *normal3, ctr_render_stats *stats) {
-  if (!m) return mfail(CTR_E_INVALID, "null group");
-  if (m->inflight) return mfail(CTR_E_INVALID, "ctr_render_multi: frames are in flight (ctr_multi_wait first)");
+  if (!m) return fail(CTR_E_INVALID, "null group");
+  if (m->inflight) return fail(CTR_E_INVALID, "ctr_render_multi: frames are in flight (ctr_multi_wait first)");
   int st = ctr_multi_submit(m, fudge, bounces, block_rows, depth, color3, normal3);
   if (st) return st;
   return ctr_multi_wait(m, stats);
@@ -621,9 +597,9 @@ int ctr_render_multi(ctr_multi *m, float fudge, int bounces, uint64_t block_rows
 int ctr_reinterleave_device(const ctr_reint_part *parts, uint32_t n_parts, uint64_t block_rows, uint64_t w, uint64_t h,
                             void *d_depth, void *d_color3, void *d_normal3, void *hip_stream) {
   if (!parts || n_parts == 0 || n_parts > CTR_MULTI_MAX_DEVICES || block_rows == 0 || !d_depth || !d_color3 || !d_normal3)
-    return mfail(CTR_E_INVALID, "ctr_reinterleave_device: bad argument");
+    return fail(CTR_E_INVALID, "ctr_reinterleave_device: bad argument");
   if (w == 0 || h == 0) return CTR_OK;
-  if (w > 0x7FFFFFFFull || h > 0x7FFFFFFFull) return mfail(CTR_E_INVALID, "ctr_reinterleave_device: image too large");
+  if (w > 0x7FFFFFFFull || h > 0x7FFFFFFFull) return fail(CTR_E_INVALID, "ctr_reinterleave_device: image too large");
   Reint R{};
   for (uint32_t p = 0; p < n_parts; p++) {
     R.depth[p] = (const float *)parts[p].d_depth;
@@ -636,20 +612,20 @@ int ctr_reinterleave_device(const ctr_reint_part *parts, uint32_t n_parts, uint6
   R.h = (uint32_t)h;
   hipLaunchKernelGGL(reinterleave_rows, dim3((uint32_t)h), dim3(256), 0, (hipStream_t)hip_stream, R, (float *)d_depth,
                      (float *)d_color3, (float *)d_normal3);
-  MHIP(hipGetLastError());
+  HIP_TRY(hipGetLastError());
   return CTR_OK;
 }
 
 int ctr_multi_kernel_ms(ctr_multi *m, double *ms_per_device, int capacity) {
-  if (!m || !ms_per_device) return mfail(CTR_E_INVALID, "ctr_multi_kernel_ms: null argument");
+  if (!m || !ms_per_device) return fail(CTR_E_INVALID, "ctr_multi_kernel_ms: null argument");
   if (m->single_ms >= 0.0 && capacity > 0) {
     ms_per_device[0] = m->single_ms;
     return CTR_OK;
   }
   for (int p = 0; p < (int)m->parts.size() && p < capacity; p++) {
     float ms = 0.f;
-    MHIP(hipSetDevice(m->parts[p].device));
-    MHIP(hipEventElapsedTime(&ms, m->parts[p].ev0[m->last], m->parts[p].ev1[m->last]));
+    HIP_TRY(hipSetDevice(m->parts[p].device));
+    HIP_TRY(hipEventElapsedTime(&ms, m->parts[p].ev0[m->last], m->parts[p].ev1[m->last]));
     ms_per_device[p] = ms;
   }
   return CTR_OK;

@@ -1,4 +1,5 @@
-// ray_query.h — what ctr_cast_rays (ctr_api.cpp) hands the ray-query kernel (ray_query.hip).
+// ray_query.h — what ctr_cast_rays (ctr_rays.cpp) hands the ray-query kernel (ray_query.hip), and the description of the
+// scene (RayScene) that it shares with the radiance queries (ray_shade.h).
 #ifndef CUTRACE_AMD_RAY_QUERY_H
 #define CUTRACE_AMD_RAY_QUERY_H
 
@@ -6,8 +7,8 @@
 
 #include "scene_device.h"
 
-struct RayLaunch {
-  // the scene's device arrays, as the render kernel reads them (scene_device.h, bvh.h)
+// the scene's device arrays, as the render kernel reads them (scene_device.h, bvh.h): what the walk of ray_walk.h needs
+struct RayScene {
   const DObj *objs;          // every object, scene order (hit records)
   const DObj *oloop;         // spheres and stand-alone triangles, scene order
   const DObj *meshes;        // non-empty meshes (the first n_mesh records: the regular ones, never the merged tree)
@@ -18,6 +19,10 @@ struct RayLaunch {
   const DMat *mats;
   uint32_t n_oloop, n_plane_recs, n_mesh;
   uint32_t stack_slots;      // LDS stack entries per lane the deepest mesh tree needs (scene_flatten.h FlatScene::ray_slots)
+};
+
+struct RayLaunch {
+  RayScene scene;
   // the query (include/cutrace_rays.h)
   uint32_t n_rays, flags;
   bool anyhit;               // SHADOW on a scene whose materials are all opaque: stop at the first occluder

@@ -46,20 +46,7 @@ __global__ __launch_bounds__(RQ_THREADS) void ray_query_kernel(RayLaunch L) {
   extern __shared__ uint32_t rq_stack[];
   const uint32_t i = blockIdx.x * (uint32_t)RQ_THREADS + threadIdx.x;
   if (i >= L.n_rays) return;
-  Scene S;
-  S.objs = (const float4 *)L.objs;
-  S.oloop = (const float4 *)L.oloop;
-  S.meshes = (const float4 *)L.meshes;
-  S.planes = (const float4 *)L.planes;
-  S.tris = (const float4 *)L.tris;
-  S.nodes4 = (const float4 *)L.nodes4;
-  S.gnorm = L.gnorm;
-  S.mats = L.mats;
-  S.n_oloop = L.n_oloop;
-  S.n_plane_recs = L.n_plane_recs;
-  S.n_mesh = L.n_mesh;
-  S.slots = L.stack_slots;
-  S.ign = (L.flags & CTR_RAY_IGNORE_TRANSPARENT) != 0u;
+  const Scene S = make_scene(L.scene, L.flags & CTR_RAY_IGNORE_TRANSPARENT);
   uint32_t *stk = rq_stack + threadIdx.x;
   const size_t i3 = (size_t)i * 3;
   const V3 ro = mk(L.origin[i3], L.origin[i3 + 1], L.origin[i3 + 2]);
@@ -77,7 +64,7 @@ __global__ __launch_bounds__(RQ_THREADS) void ray_query_kernel(RayLaunch L) {
         break;
       }
       const uint32_t mat = bits(S.objs[(size_t)h.obj * 4].y);
-      intensity += (1.0f - L.mats[mat].transparency);  // get_bounce_params, default_schema.hpp:337-340
+      intensity += (1.0f - L.scene.mats[mat].transparency);  // get_bounce_params, default_schema.hpp:337-340
       if (intensity >= 1.0f) {
         intensity = 1.0f;
         break;
@@ -143,7 +130,7 @@ __global__ __launch_bounds__(RQ_THREADS) void ray_query_kernel(RayLaunch L) {
 
 template <uint32_t V>
 int launch(const RayLaunch &L, hipStream_t stream) {
-  const size_t lds = (V & RQ_LINEAR) ? 0 : (size_t)L.stack_slots * RQ_THREADS * sizeof(uint32_t);
+  const size_t lds = (V & RQ_LINEAR) ? 0 : (size_t)L.scene.stack_slots * RQ_THREADS * sizeof(uint32_t);
   const uint32_t grid = (L.n_rays + RQ_THREADS - 1) / RQ_THREADS;
   hipLaunchKernelGGL(ray_query_kernel<V>, dim3(grid), dim3(RQ_THREADS), lds, stream, L);
   return (int)hipGetLastError();

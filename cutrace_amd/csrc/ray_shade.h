@@ -1,25 +1,17 @@
-// ray_shade.h — what ctr_shade_rays (ctr_api.cpp) hands the radiance-query kernel (ray_shade.hip).
+// ray_shade.h — what ctr_shade_rays (ctr_rays.cpp) hands the radiance-query kernel (ray_shade.hip).
 #ifndef CUTRACE_AMD_RAY_SHADE_H
 #define CUTRACE_AMD_RAY_SHADE_H
 
 #include <stddef.h>
 #include <stdint.h>
 
+#include "ray_query.h"
 #include "scene_device.h"
 
 struct ShadeLaunch {
-  // the scene's device arrays, as the render kernel reads them (scene_device.h, bvh.h)
-  const DObj *objs;          // every object, scene order (hit records)
-  const DObj *oloop;         // spheres and stand-alone triangles, scene order
-  const DObj *meshes;        // non-empty meshes (the first n_mesh records: the regular ones, never the merged tree)
-  const DPlanePair *planes;
-  const DTri *tris;
-  const void *nodes4;        // DNode4[]: per-mesh trees
-  const float *gnorm;
-  const DMat *mats;
+  RayScene scene;           // (ray_query.h)
   const DLight *lights;
-  uint32_t n_oloop, n_plane_recs, n_mesh, n_light;
-  uint32_t stack_slots;      // LDS walk-stack entries per lane (scene_flatten.h FlatScene::ray_slots)
+  uint32_t n_light;
   uint32_t frames;           // LDS recursion frames per lane (ctr_shade_frames)
   uint32_t frame_dwords;     // 4, or 10 when some material both reflects and transmits (FlatScene::need_cold)
   uint32_t all_opaque;       // no material transmits: a shadow cast stops at the first occluder

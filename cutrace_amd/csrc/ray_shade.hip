@@ -48,25 +48,12 @@ __global__ __launch_bounds__(RS_THREADS) void ray_shade_kernel(ShadeLaunch L) {
   extern __shared__ uint32_t rs_lds[];
   const uint32_t i = blockIdx.x * (uint32_t)RS_THREADS + threadIdx.x;
   if (i >= L.n_rays) return;
-  Scene S;
-  S.objs = (const float4 *)L.objs;
-  S.oloop = (const float4 *)L.oloop;
-  S.meshes = (const float4 *)L.meshes;
-  S.planes = (const float4 *)L.planes;
-  S.tris = (const float4 *)L.tris;
-  S.nodes4 = (const float4 *)L.nodes4;
-  S.gnorm = L.gnorm;
-  S.mats = L.mats;
-  S.n_oloop = L.n_oloop;
-  S.n_plane_recs = L.n_plane_recs;
-  S.n_mesh = L.n_mesh;
-  S.slots = L.stack_slots;
-  S.ign = false;  // every cast of ray_color, phong and shadow_intensity passes ignore_transparent = false
+  const Scene S = make_scene(L.scene, 0u);  // every cast of ray_color, phong and shadow_intensity passes ignore_transparent = false
   uint32_t *const stk = rs_lds + threadIdx.x;
-  float *const frm = (float *)(rs_lds + ((V & RQ_LINEAR) ? 0u : L.stack_slots * (uint32_t)RS_THREADS)) + threadIdx.x;
+  float *const frm = (float *)(rs_lds + ((V & RQ_LINEAR) ? 0u : L.scene.stack_slots * (uint32_t)RS_THREADS)) + threadIdx.x;
   const uint32_t fd = L.frame_dwords;
 #define FRM(sp, f) frm[((uint32_t)(sp) * fd + (uint32_t)(f)) * (uint32_t)RS_THREADS]
-  const DMat *const mats = L.mats;
+  const DMat *const mats = L.scene.mats;
   const DLight *const lights = L.lights;
   const uint32_t n_light = L.n_light;
   const bool opaque = L.all_opaque != 0u;
@@ -279,7 +266,7 @@ int launch(const ShadeLaunch &L, hipStream_t stream) {
 }  // namespace
 
 size_t ctr_shade_lds_bytes(const ShadeLaunch &L) {
-  const size_t stack = (L.flags & CTR_SHADE_LINEAR) ? 0 : L.stack_slots;
+  const size_t stack = (L.flags & CTR_SHADE_LINEAR) ? 0 : L.scene.stack_slots;
   return (stack + (size_t)L.frames * L.frame_dwords) * RS_THREADS * sizeof(uint32_t);
 }
 

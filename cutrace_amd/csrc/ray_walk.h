@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "bvh.h"
+#include "ray_query.h"
 #include "scene_device.h"
 
 namespace {
@@ -94,6 +95,24 @@ struct Scene {
   uint32_t n_oloop, n_plane_recs, n_mesh, slots;
   bool ign;
 };
+// `ign` != 0: ray_cast's ignore_transparent
+__device__ __forceinline__ Scene make_scene(const RayScene &R, uint32_t ign) {
+  Scene S;
+  S.objs = (const float4 *)R.objs;
+  S.oloop = (const float4 *)R.oloop;
+  S.meshes = (const float4 *)R.meshes;
+  S.planes = (const float4 *)R.planes;
+  S.tris = (const float4 *)R.tris;
+  S.nodes4 = (const float4 *)R.nodes4;
+  S.gnorm = R.gnorm;
+  S.mats = R.mats;
+  S.n_oloop = R.n_oloop;
+  S.n_plane_recs = R.n_plane_recs;
+  S.n_mesh = R.n_mesh;
+  S.slots = R.stack_slots;
+  S.ign = ign != 0u;
+  return S;
+}
 
 // One mesh (a DObj record that passed the reference's AABB test): its nearest valid triangle, ties to the lower file
 // index (default_schema.hpp:133-134, strict < in file order), then ray_cast.hpp:43's strict test against min_t.
