@@ -18,7 +18,8 @@
 //    IEEE division and square root);
 //  * a mesh: first the reference's AABB test (bound_intersects: IEEE reciprocals, tmin from 0, std::min/max selects);
 //    then its triangles in order (CTR_RAY_LINEAR), or its BVH.  The BVH's box test is the render kernel's: a world-space
-//    margin of 2^-14 x the distance from the origin to the mesh box, 1-ulp reciprocals clamped to +-1e30, the same FMAs,
+//    margin of 2^-14 x the distance from the origin to the mesh box, 1-ulp reciprocals clamped to +-1e30 (of the direction
+//    scaled by a power of two to unit size, so that a direction of any length gets that direction's test), the same FMAs,
 //    a NaN dropping its axis' constraint; a child is entered unless max(entry, min_t) > min(exit, limit) — so a box
 //    that only ties the nearest hit so far is still entered.  Culling is exact except for rays in a triangle's plane
 //    (the header says which); LINEAR is exact for every ray;

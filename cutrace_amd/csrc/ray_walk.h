@@ -116,8 +116,40 @@ __device__ __forceinline__ Scene make_scene(const RayScene &R, uint32_t ign) {
 
 // One mesh (a DObj record that passed the reference's AABB test): its nearest valid triangle, ties to the lower file
 // index (default_schema.hpp:133-134, strict < in file order), then ray_cast.hpp:43's strict test against min_t.
+//
+// The BVH's box test runs on the direction scaled by a power of two to a largest component in [1, 2) (BoxRay, made once
+// per cast): its distances are t * tk, and so are the two bounds it compares them with, min_t and the limit.  Scaling
+// by a power of two is exact, so for a direction of any length the test decides what it decides for that direction at
+// unit length; a bound that leaves the normal range on the way is moved outwards (floor_tk, ceil_tk).
+struct BoxRay {
+  V3 ria;    // 1-ulp reciprocals of the scaled direction, clamped to +-1e30
+  float tk;  // a power of two: box distance = t * tk
+};
+__device__ __forceinline__ BoxRay box_ray(V3 rd) {
+  const float am = fmaxf(fmaxf(fabsf(rd.x), fabsf(rd.y)), fabsf(rd.z));  // (fmaxf skips a NaN component)
+  int e = 1;                                                              // am = m * 2^e, m in [0.5, 1)
+  if (am > 0.0f && am < INFINITY) (void)frexpf(am, &e);                   // no finite non-zero component: unscaled
+  const V3 rs = mk(ldexpf(rd.x, 1 - e), ldexpf(rd.y, 1 - e), ldexpf(rd.z, 1 - e));
+  BoxRay B;
+  B.ria = mk(fminf(fmaxf(__builtin_amdgcn_rcpf(rs.x), -1e30f), 1e30f), fminf(fmaxf(__builtin_amdgcn_rcpf(rs.y), -1e30f), 1e30f),
+             fminf(fmaxf(__builtin_amdgcn_rcpf(rs.z), -1e30f), 1e30f));
+  B.tk = ldexpf(1.0f, e - 1);  // 2^-149 .. 2^127: always representable
+  return B;
+}
+// t * tk as a lower / an upper bound of box distances: exact unless the product is denormal, then rounded outwards.  A
+// lower bound that overflows stays finite (the largest float is still below it): no box distance, which the clamped
+// reciprocals keep finite, is then culled by an infinity the linear walk never sees.
+__device__ __forceinline__ float floor_tk(float t, float tk) {
+  const float p = fminf(t * tk, 3.4028235e38f);
+  return fabsf(p) < 0x1p-126f ? (p > 0.0f ? 0.0f : -0x1p-126f) : p;
+}
+__device__ __forceinline__ float ceil_tk(float t, float tk) {
+  const float p = t * tk;
+  return fabsf(p) < 0x1p-126f ? (p < 0.0f ? 0.0f : 0x1p-126f) : p;
+}
+
 template <uint32_t V, int STRIDE = RQ_THREADS>
-__device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro, V3 rd, V3 ria, float min_t, float t_lim,
+__device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro, V3 rd, const BoxRay &B, float min_t, float t_lim,
                                           Best &best, uint32_t *stk) {
   const float4 o0 = O[0], o1 = O[1], o2 = O[2], o3 = O[3];
   const uint32_t tri_begin = bits(o0.z), tri_count = bits(o0.w), node_begin = bits(o1.x), bvh_root = bits(o1.z),
@@ -125,6 +157,7 @@ __device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro
   float mt = INFINITY;
   uint32_t morig = RQ_NONE;
   float lim = fminf(best.t, t_lim);  // no triangle beyond it can win or tie
+  float blim = (V & RQ_LINEAR) ? 0.0f : ceil_tk(lim, B.tk);  // `lim` as a box distance
   auto test = [&](uint32_t k) {
     float t0;
     uint32_t orig;
@@ -132,12 +165,15 @@ __device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro
       mt = t0;
       morig = orig;
       lim = fminf(lim, mt);
+      if (!(V & RQ_LINEAR)) blim = ceil_tk(lim, B.tk);
     }
   };
   if (V & RQ_LINEAR) {
     for (uint32_t k = 0; k < tri_count; ++k) test(tri_begin + k);
   } else {
     // box constants of render_kernel.hip's per-mesh walk: the boxes widened by mw in world space
+    const V3 ria = B.ria;
+    const float bmin = floor_tk(min_t, B.tk);  // min_t as a box distance
     const float gx = fmaxf(fabsf(o2.x - ro.x), fabsf(o2.w - ro.x));
     const float gy = fmaxf(fabsf(o2.y - ro.y), fabsf(o3.x - ro.y));
     const float gz = fmaxf(fabsf(o2.z - ro.z), fabsf(o3.y - ro.z));
@@ -158,7 +194,7 @@ __device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro
     const float t1x = __builtin_fmaf(q0.F, ria.x, -ka.x), t2x = __builtin_fmaf(q3.F, ria.x, -kb.x);      \
     const float t1y = __builtin_fmaf(q1.F, ria.y, -ka.y), t2y = __builtin_fmaf(q4.F, ria.y, -kb.y);      \
     const float t1z = __builtin_fmaf(q2.F, ria.z, -ka.z), t2z = __builtin_fmaf(q5.F, ria.z, -kb.z);      \
-    en[c] = fmaxf(fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z)), min_t);              \
+    en[c] = fmaxf(fmaxf(fmaxf(fminf(t1x, t2x), fminf(t1y, t2y)), fminf(t1z, t2z)), bmin);               \
     ex[c] = fminf(fminf(fmaxf(t1x, t2x), fmaxf(t1y, t2y)), fmaxf(t1z, t2z));                            \
   }
       RQ_BOX(0, x) RQ_BOX(1, y) RQ_BOX(2, z) RQ_BOX(3, w)
@@ -175,7 +211,7 @@ __device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro
       // the others wait on the stack
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        if ((ch[c] & BVH_LEAF_FLAG) && !(en[c] > fminf(ex[c], lim))) {
+        if ((ch[c] & BVH_LEAF_FLAG) && !(en[c] > fminf(ex[c], blim))) {
           const uint32_t first = tri_begin + (ch[c] & 0xFFFFFFu), n = (ch[c] >> 24) & 0x7Fu;
           for (uint32_t j = 0; j < n; ++j) test(first + j);
         }
@@ -183,7 +219,7 @@ __device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro
       uint32_t next = RQ_NONE;
 #pragma unroll
       for (int c = 3; c >= 0; --c) {
-        if (!(ch[c] & BVH_LEAF_FLAG) && !(en[c] > fminf(ex[c], lim))) {
+        if (!(ch[c] & BVH_LEAF_FLAG) && !(en[c] > fminf(ex[c], blim))) {
           if (next != RQ_NONE && sp < S.slots) stk[(sp++) * STRIDE] = next;
           next = ch[c];
         }
@@ -277,11 +313,12 @@ __device__ Best cast(const Scene &S, V3 ro, V3 rd, float min_t, float t_lim, uin
   // ---- meshes ----
   if (S.n_mesh != 0u) {
     const V3 rinv = mk(1.0f / rd.x, 1.0f / rd.y, 1.0f / rd.z);  // default_schema.hpp:103
-    // the BVH's box test: 1-ulp reciprocals clamped to +-1e30 (an axis-parallel ray gets huge finite slab distances)
-    V3 ria = mk(0, 0, 0);
-    if (!(V & RQ_LINEAR))
-      ria = mk(fminf(fmaxf(__builtin_amdgcn_rcpf(rd.x), -1e30f), 1e30f), fminf(fmaxf(__builtin_amdgcn_rcpf(rd.y), -1e30f), 1e30f),
-               fminf(fmaxf(__builtin_amdgcn_rcpf(rd.z), -1e30f), 1e30f));
+    // the BVH's box test: 1-ulp reciprocals of the direction at unit scale, clamped to +-1e30 (an axis-parallel ray gets
+    // huge finite slab distances)
+    BoxRay B;
+    B.ria = mk(0, 0, 0);
+    B.tk = 1.0f;
+    if (!(V & RQ_LINEAR)) B = box_ray(rd);
     for (uint32_t m = 0; m < S.n_mesh; ++m) {
       const float4 *O = S.meshes + (size_t)m * 4;
       const float4 o2 = O[2], o3 = O[3];
@@ -298,7 +335,7 @@ __device__ Best cast(const Scene &S, V3 ro, V3 rd, float min_t, float t_lim, uin
       tmin = smin(smax(t1, tmin), smax(t2, tmin));
       tmax = smax(smin(t1, tmax), smin(t2, tmax));
       if (!(tmin <= tmax)) continue;
-      cast_mesh<V, STRIDE>(S, O, ro, rd, ria, min_t, t_lim, best, stk);
+      cast_mesh<V, STRIDE>(S, O, ro, rd, B, min_t, t_lim, best, stk);
       if (ANYHIT && best.t < t_lim) return best;
     }
   }

@@ -18,6 +18,16 @@
  * scene's cameras are guarded; arbitrary query origins are not.  CTR_RAY_LINEAR walks every
  * mesh's triangles linearly after the AABB test and is bit-identical to the reference for every ray.
  *
+ * Directions of any length: the BVH's box test runs on the direction scaled by a power of two to unit size (and min_t
+ * and the distance limit with it), so the default walk decides for dir * 2^j what it decides for dir.  Checked bit for
+ * bit from 2^-104 to 2^100 and for scenes scaled by 2^-20 to 2^24 (tests/test_gpu_query_ranges.py).  What remains is
+ * the reference's own float range: where its products overflow or go denormal (a direction with components below
+ * about 2^-110 against triangles a hundredth of a unit across, say) both walks still restate its arithmetic operation
+ * for operation, but no test pins them there.  The same holds where min_t * 2^e, e the exponent of the direction's
+ * largest component, leaves the float range (a direction of length 2^100 with min_t 2^30, say): the default walk keeps
+ * its scaled min_t finite and conservative there, untested.  Rays with NaN, infinite or all-zero components get the reference's
+ * answer (as a rule a miss) and do not disturb the other rays of their batch.
+ *
  * Calls are asynchronous on `hip_stream`, allocate nothing and never synchronise (a call can be captured into a
  * graph), and use no per-handle scratch (later renders and their counters are undisturbed).  Like renders, calls on
  * one handle must be ordered by the caller against ctr_scene_set_cameras and ctr_set_variant(CTR_VAR_MERGE), which

@@ -11,46 +11,13 @@ import pytest
 import oracle
 from tests import ray_ref
 from tests.conftest import load_scene
+from tests.util import (assert_same as _assert_same, f32_bits as _bits, random_rays as _random_rays, ref_dict as _ref_dict,
+                        to_np as _np)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 THREADS = os.cpu_count() or 4
-
-
-def _np(r):
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, f32).view(np.uint32)
-
-
-def _sphere_mask(rs, obj):
-    return np.isin(obj, [i for i, o in enumerate(rs.objects) if o["type"] == ray_ref.OBJ_SPHERE])
-
-
-def _assert_same(rs, got, want, what):
-    """every output of `want` present in `got` with the same bits (sphere uv: 1e-4); returns the number of hits"""
-    obj = np.asarray(want["object"])
-    assert np.array_equal(got["object"], obj), f"{what}: object differs in {int((got['object'] != obj).sum())} rays"
-    if "prim" in want:
-        assert np.array_equal(got["prim"], want["prim"]), f"{what}: prim"
-    for k in ("t", "point", "normal"):
-        if k in want:
-            assert np.array_equal(_bits(got[k]), _bits(want[k])), f"{what}: {k} differs in {int((_bits(got[k]) != _bits(want[k])).any(-1).sum() if got[k].ndim > 1 else (_bits(got[k]) != _bits(want[k])).sum())} rays"
-    if "uv" in want:
-        sph = _sphere_mask(rs, obj)
-        g, w = got["uv"], np.asarray(want["uv"], f32)
-        assert np.array_equal(np.isnan(g), np.isnan(w)), f"{what}: uv NaNs"
-        assert np.array_equal(_bits(np.nan_to_num(g[~sph])), _bits(np.nan_to_num(w[~sph]))), f"{what}: uv"
-        if sph.any():
-            assert np.abs(g[sph].astype(np.float64) - w[sph]).max() <= 1e-4, f"{what}: sphere uv"
-    return int((obj >= 0).sum())
-
-
-def _ref_dict(r):
-    return {k: (v.astype(np.int32) if k in ("object", "prim") else v) for k, v in r.items()}
 
 
 # ---- 1. camera rays in image order ----
@@ -135,25 +102,6 @@ def test_incoherent_batch_of_many_cameras(ca):
 
 
 # ---- 3. random rays against ray_ref ----
-def _random_rays(rng, n, rs, lo, hi):
-    o = rng.uniform(lo, hi, (n, 3)).astype(f32)
-    d = rng.normal(size=(n, 3)).astype(f32) * rng.choice([0.01, 1.0, 30.0], (n, 1)).astype(f32)
-    z = rng.rand(n) < 0.1                                      # a direction component exactly zero (either sign)
-    d[z, rng.randint(0, 3, int(z.sum()))] = rng.choice([0.0, -0.0], int(z.sum())).astype(f32)
-    k = 0
-    for ob in rs.objects:                                      # origins inside spheres and inside mesh boxes
-        if ob["type"] == ray_ref.OBJ_SPHERE:
-            m = n // 20
-            o[k:k + m] = ob["v0"] + rng.uniform(-0.3, 0.3, (m, 3)).astype(f32) * ob["f0"]
-            k += m
-        elif ob["type"] == ray_ref.OBJ_MESH:
-            m = n // 10
-            o[k:k + m] = rng.uniform(ob["v0"], ob["v1"], (m, 3)).astype(f32)
-            k += m
-    mt = rng.choice([1e-3, 0.0, -0.5, 0.25], n).astype(f32)  # per-ray min_t, zero and negative included
-    return o, d, mt
-
-
 @pytest.mark.parametrize("which", ["bunny", "random0", "random5"])
 def test_random_rays_against_ray_ref(ca, which):
     from tests.util import _random_scene

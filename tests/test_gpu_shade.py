@@ -11,43 +11,14 @@ import pytest
 import oracle
 from tests import ray_ref, shade_ref
 from tests.conftest import load_scene
-from tests.util import TOL
+from tests.util import (TOL, assert_bitwise as _bitwise, f32_bits as _bits, first_hit_same as _first_hit_same,
+                        max_diff as _max_diff, random_rays, to_np as _np)
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 THREADS = os.cpu_count() or 4
 FIRST = ("t", "object", "normal")
 ALL = ("color",) + FIRST
-
-
-def _np(r):
-    return {k: v.cpu().numpy() for k, v in r.items()}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, f32).view(np.uint32)
-
-
-def _bitwise(got, want, what):
-    g, w = _bits(got), _bits(np.asarray(want, f32).reshape(np.shape(got)))
-    bad = g != w
-    assert not bad.any(), f"{what}: {int(bad.reshape(len(g), -1).any(-1).sum())} of {len(g)} rays differ"
-
-
-def _max_diff(got, want, what):
-    """largest per-channel difference; NaN positions must agree"""
-    want = np.asarray(want, f32).reshape(got.shape)
-    assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
-    d = np.abs(np.nan_to_num(got).astype(np.float64) - np.nan_to_num(want).astype(np.float64))
-    m = float(d.max()) if d.size else 0.0
-    print(f"{what}: colour max|diff| {m:.3e}")
-    return m
-
-
-def _first_hit_same(got, want, what):
-    assert np.array_equal(got["object"], np.asarray(want["object"]).astype(np.int32)), f"{what}: object"
-    _bitwise(got["t"], want["t"], f"{what}: t")
-    _bitwise(got["normal"], want["normal"], f"{what}: normal")
 
 
 # ---- 5. camera rays in image order ----
@@ -124,25 +95,6 @@ def test_incoherent_batch_of_many_cameras(ca, name):
 
 
 # ---- 7. random rays against shade_ref ----
-def _random_rays(rng, n, rs, lo, hi):
-    """(the generator of test_gpu_rays.py, without the per-ray min_t)"""
-    o = rng.uniform(lo, hi, (n, 3)).astype(f32)
-    d = rng.normal(size=(n, 3)).astype(f32) * rng.choice([0.01, 1.0, 30.0], (n, 1)).astype(f32)
-    z = rng.rand(n) < 0.1                                      # a direction component exactly zero (either sign)
-    d[z, rng.randint(0, 3, int(z.sum()))] = rng.choice([0.0, -0.0], int(z.sum())).astype(f32)
-    k = 0
-    for ob in rs.objects:                                      # origins inside spheres and inside mesh boxes
-        if ob["type"] == ray_ref.OBJ_SPHERE:
-            m = n // 20
-            o[k:k + m] = ob["v0"] + rng.uniform(-0.3, 0.3, (m, 3)).astype(f32) * ob["f0"]
-            k += m
-        elif ob["type"] == ray_ref.OBJ_MESH:
-            m = n // 10
-            o[k:k + m] = rng.uniform(ob["v0"], ob["v1"], (m, 3)).astype(f32)
-            k += m
-    return o, d
-
-
 @pytest.mark.parametrize("which", ["bunny", "random0", "random1", "random5"])
 def test_random_rays_against_shade_ref(ca, which):
     from tests.util import _random_scene
@@ -153,7 +105,7 @@ def test_random_rays_against_shade_ref(ca, which):
     rng = np.random.RandomState(3)
     n = 4000 if which == "bunny" else 3000
     bounces = 3
-    o, d = _random_rays(rng, n, sc, -3.0, 3.0)
+    o, d, _ = random_rays(rng, n, sc, -3.0, 3.0)
     want = shade_ref.ray_color(sc, o, d, min_t=1e-3, bounces=bounces)
     assert int((want["object"] >= 0).sum()) > n // 10
     for exact in (False, True):
@@ -171,19 +123,8 @@ def test_random_rays_against_shade_ref(ca, which):
 # ---- 8. deep recursion ----
 def _hall_of_mirrors(ca, w, h):
     """two facing mirror walls, a floor, and a sphere that both reflects and transmits: every level to bounces 15 is live"""
-    import json
-    mats = [{"type": "solid", "color": [0.9, 0.9, 0.95], "specular": 0.3, "reflect": 0.8, "phong": 60},
-            {"type": "solid", "color": [0.7, 0.5, 0.3], "specular": 0.1, "reflect": 0.0, "phong": 5},
-            {"type": "solid", "color": [0.3, 0.8, 0.5], "specular": 0.6, "reflect": 0.3, "phong": 30, "transparency": 0.5}]
-    objs = [{"type": "plane", "point": [-2, 0, 0], "normal": [1, 0, 0], "material": 0},
-            {"type": "plane", "point": [2, 0, 0], "normal": [-1, 0, 0], "material": 0},
-            {"type": "plane", "point": [0, -1, 0], "normal": [0, 1, 0], "material": 1},
-            {"type": "sphere", "center": [0.2, -0.3, 0.0], "radius": 0.6, "material": 2}]
-    lights = [{"type": "point", "point": [0.5, 2.5, 2.0], "color": [0.8, 0.8, 0.8]},
-              {"type": "sun", "direction": [-0.3, -1.0, -0.2], "color": [0.4, 0.4, 0.4]}]
-    cam = {"eye": [0.9, 0.4, 4.0], "up": [0, 1, 0], "look": [-0.6, -0.2, -1.0], "near_plane": 0.1, "far_plane": 100.0,
-           "width": w, "height": h, "ambient": 0.1}
-    s = ca.HostScene.parse(json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs}))
+    from tests.util import hall_of_mirrors_json
+    s = ca.HostScene.parse(hall_of_mirrors_json(w, h))
     assert s.ok
     return s
 
@@ -238,7 +179,7 @@ def test_streams_graph_capture_sizes_and_output_subsets(ca):
     sc = shade_ref.ShadeScene(s)
     ds = ca.DeviceScene(s)
     rng = np.random.RandomState(9)
-    o, d = _random_rays(rng, 1000, sc, -3.0, 3.0)
+    o, d, _ = random_rays(rng, 1000, sc, -3.0, 3.0)
     full = _np(ds.shade_rays(o, d, outputs=ALL))
     assert list(ds.shade_rays(o, d)) == ["color"]
     empty = ds.shade_rays(o[:0], d[:0], outputs=ALL)
@@ -332,7 +273,7 @@ def test_renders_before_and_after_a_radiance_query_are_identical(ca):
     a = ds.render(bounces=5)
     ca_ = ds.last_counters()
     rng = np.random.RandomState(10)
-    o, d = _random_rays(rng, 50000, sc, -3.0, 3.0)
+    o, d, _ = random_rays(rng, 50000, sc, -3.0, 3.0)
     ds.shade_rays(o, d, bounces=5)
     ds.shade_rays(o, d, bounces=2, linear=True, exact_pow=True, outputs=ALL)
     b = ds.render(bounces=5)

@@ -186,6 +186,33 @@ def check_flat(flat, desc):
         assert objs["f"][i, 7:8].view("u4")[0] == int(tr[objs["mat"][i]] >= 1e-6)
 
 
+def worst_stack(child, root):
+    """The highest the walk of ray_walk.h can stack on a tree: a visited node pushes all of its entered inner children but
+    the one it goes to next, so no lane holds more than the maximum over root-to-node paths of the sum of
+    (inner children - 1) along the path.  `child`: the (n, 4) child descriptors of one mesh, spare node included."""
+    worst, todo = 0, [(int(root), 0)]
+    while todo:
+        n, above = todo.pop()
+        inner = [int(c) for c in child[n] if not c & LEAF]
+        here = above + max(len(inner) - 1, 0)
+        worst = max(worst, here)
+        todo += [(c, here) for c in inner]
+    return worst
+
+
+def check_ray_slots(flat, stages):
+    """FlatScene::ray_slots is what every mesh's tree can stack, in every stage, from the record's own bvh_root (the spare
+    node where the mesh is guarded).  Returns the worst height met."""
+    slots, n_mesh, worst = flat["scalars"]["ray_slots"], flat["scalars"]["n_mesh"], 0
+    for st in [flat] + list(stages):
+        for M in st["meshes"][:n_mesh]:
+            nb, nc = int(M["node_begin"]), int(M["node_count"])
+            h = worst_stack(st["nodes4"]["child"][nb:nb + nc + 1], M["bvh_root"])
+            assert h <= slots, f"stage {st['what']}: mesh {int(M['index'])} can stack {h} entries, ray_slots is {slots}: the walk would drop a subtree"
+            worst = max(worst, h)
+    return worst
+
+
 def check_planes(flat):
     objs, planes, n_axis = flat["objs"], flat["planes"], flat["scalars"]["n_axis_recs"]
     assert n_axis % 3 == 0 and n_axis <= len(planes)
@@ -225,9 +252,11 @@ def test_shipped_scenes_flatten_by_the_rules(harness, tmp_path, ca):
         assert s.ok
         flat, stages = run(harness, tmp_path, s)
         check_flat(flat, s.desc.contents)
+        check_ray_slots(flat, stages)
     grid = ca.HostScene.load(scenes.make_bunny_grid(str(tmp_path), 4, width=64, height=64))
     flat, stages = run(harness, tmp_path, grid)
     check_flat(flat, grid.desc.contents)
+    check_ray_slots(flat, stages)
     assert flat["scalars"]["n_mesh"] == 16 and flat["scalars"]["merged_reserved"] == 1
 
 
@@ -236,9 +265,11 @@ def test_random_scenes_flatten_by_the_rules(harness, tmp_path, seed):
     s = _parse(_random_scene(seed, extra_planes=seed % 2 == 1))
     flat, stages = run(harness, tmp_path, s)
     check_flat(flat, s.desc.contents)
+    check_ray_slots(flat, stages)
     s = _parse(_multi_mesh_scene(tmp_path, seed, opaque=seed % 2 == 0, n_mesh=2 + seed % 4))
     flat, stages = run(harness, tmp_path, s, merge=True)
     check_flat(flat, s.desc.contents)
+    check_ray_slots(flat, stages)
     # the merged tree, built: its keys are (rank << 24 | file index), every triangle of every mesh once
     last = stages[-1]
     sc, n_mesh = flat["scalars"], flat["scalars"]["n_mesh"]
@@ -246,6 +277,59 @@ def test_random_scenes_flatten_by_the_rules(harness, tmp_path, seed):
     counts = [int(c) for c in last["meshes"]["tri_count"][n_mesh + 1:]]
     assert sorted(keys) == [(r << 24) | k for r, c in enumerate(counts) for k in range(c)]
     assert last["merged"][0] == 1 and 0 < last["meshes"]["node_count"][n_mesh] <= sc["merged_node_cap"]
+
+
+def test_ray_slots_hold_the_deepest_walk(harness, tmp_path, ca):
+    """the trees this project builds deepest: the 64 000-triangle bunny, a mesh whose triangles span 24 octaves of size, and
+    guarded meshes, whose walk starts at the spare node"""
+    dense = ca.HostScene.load(scenes.make_dense_bunny(str(tmp_path), rounds=3, width=32, height=32))
+    assert dense.ok
+    flat, stages = run(harness, tmp_path, dense)
+    worst = check_ray_slots(flat, stages)
+    print(f"dense bunny: worst stack {worst}, ray_slots {flat['scalars']['ray_slots']}")
+    # the deepest this project builds: tests/test_gpu_query_ranges.py makes the largest LDS launch with this mesh
+    assert worst >= 26 and flat["scalars"]["ray_slots"] >= 33
+    rng = np.random.RandomState(4)
+    tris = []
+    for i in range(6000):
+        c, r = rng.uniform(-1, 1, 3), 2.0 ** -(i % 24)
+        tris.append([c + r * rng.uniform(-0.3, 0.3, 3) for _ in range(3)])
+    scenes.write_stl(str(tmp_path / "cluster.stl"), np.asarray(tris, np.float32))
+    flat, stages = run(harness, tmp_path, _scene([{"type": "mesh", "file": str(tmp_path / "cluster.stl"), "material": 0}]))
+    worst = check_ray_slots(flat, stages)
+    print(f"geometric cluster: worst stack {worst}, ray_slots {flat['scalars']['ray_slots']}")
+    for k in (7, GUARD_SLOTS):
+        flat, stages = run(harness, tmp_path, _scene([_guard_mesh(tmp_path, k, n_other=400)]), eyes=[[IN_PLANE], [OFF_PLANE]])
+        assert _selected(flat, stages[0]) == list(range(k)) and stages[0]["meshes"]["bvh_root"][0] != 0   # walked from the spare node
+        check_ray_slots(flat, stages)
+
+
+def test_the_shade_kernels_lds_cap_is_unreachable():
+    """ctr_shade_rays refuses a launch whose walk stack and recursion frames exceed CTR_SHADE_LDS_MAX.  From the headers'
+    own constants no scene can get there today, so that CTR_E_INVALID branch has no test.  If this fails, the branch has
+    become reachable: it now needs a test of its own (a scene that deep, bounces that high, the message checked)."""
+    import re
+
+    def const(header, name):
+        m = re.search(r"#define\s+%s\s+(\d+)" % name, open(os.path.join(CSRC, header)).read())
+        assert m, f"{name} is no longer a #define of {header}"
+        return int(m.group(1))
+    depth, bounces, cap = const("bvh.h", "BVH4_MAX_DEPTH"), const("scene_device.h", "CTR_MAX_BOUNCES"), const("ray_shade.h", "CTR_SHADE_LDS_MAX")
+    rs_threads = int(re.search(r"constexpr int RS_THREADS = (\d+);", open(os.path.join(CSRC, "ray_shade.hip")).read()).group(1))
+    # scene_flatten.cpp ray_stack_slots: slots = 3 * (deepest level + 1), levels counted from 1 at the root
+    m = re.search(r"return (\d+)u \* \(deepest \+ (\d+)u\);", open(os.path.join(CSRC, "scene_flatten.cpp")).read())
+    assert m, "ray_stack_slots no longer returns a * (deepest + b): restate its formula here"
+    per_level, extra = int(m.group(1)), int(m.group(2))
+    levels = depth + 1 + 1                      # node depths 0 .. BVH4_MAX_DEPTH and, generously, the spare node above the root
+    slots = per_level * (levels + extra)
+    # ctr_rays.cpp: frame_dwords = need_cold ? 10 : 4 — the larger of the two
+    m = re.search(r"frame_dwords = s->flat\.need_cold \? (\d+)u : (\d+)u;", open(os.path.join(CSRC, "ctr_rays.cpp")).read())
+    assert m, "ctr_rays.cpp no longer sets frame_dwords from need_cold: restate it here"
+    frame_dwords = max(int(m.group(1)), int(m.group(2)))
+    worst = (slots + bounces * frame_dwords) * rs_threads * 4
+    print(f"largest request: ({slots} + {bounces * frame_dwords}) dwords x {rs_threads} lanes = {worst} bytes of {cap}")
+    assert worst <= cap, (f"a scene can now ask ctr_shade_rays for {worst} bytes of LDS, more than CTR_SHADE_LDS_MAX = {cap}: the "
+                          "CTR_E_INVALID path of ctr_rays.cpp is reachable and needs a test of its own")
 
 
 MATS = [{"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.0, "phong": 40}]

@@ -255,3 +255,188 @@ def _multi_mesh_scene(tmp_path, seed, w=96, h=64, opaque=False, n_mesh=4):
            "look": [float(rng.uniform(-0.2, 0.2)), float(rng.uniform(-0.2, 0.1)), -1.0], "near_plane": 0.1, "far_plane": 100.0,
            "width": w, "height": h, "ambient": 0.15}
     return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
+
+
+# ---- ray and radiance queries: the generator and the comparers of tests/test_gpu_rays.py, test_gpu_shade.py and
+# test_gpu_query_ranges.py ----
+f32 = np.float32
+
+
+def to_np(r):
+    return {k: v.cpu().numpy() for k, v in r.items()}
+
+
+def f32_bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def sphere_mask(rs, obj):
+    from tests import ray_ref
+    return np.isin(obj, [i for i, o in enumerate(rs.objects) if o["type"] == ray_ref.OBJ_SPHERE])
+
+
+def assert_same(rs, got, want, what):
+    """every output of `want` present in `got` with the same bits (sphere uv: 1e-4); returns the number of hits"""
+    _bits = f32_bits
+    obj = np.asarray(want["object"])
+    assert np.array_equal(got["object"], obj), f"{what}: object differs in {int((got['object'] != obj).sum())} rays"
+    if "prim" in want:
+        assert np.array_equal(got["prim"], want["prim"]), f"{what}: prim"
+    for k in ("t", "point", "normal"):
+        if k in want:
+            assert np.array_equal(_bits(got[k]), _bits(want[k])), f"{what}: {k} differs in {int((_bits(got[k]) != _bits(want[k])).any(-1).sum() if got[k].ndim > 1 else (_bits(got[k]) != _bits(want[k])).sum())} rays"
+    if "uv" in want:
+        sph = sphere_mask(rs, obj)
+        g, w = got["uv"], np.asarray(want["uv"], f32)
+        assert np.array_equal(np.isnan(g), np.isnan(w)), f"{what}: uv NaNs"
+        assert np.array_equal(_bits(np.nan_to_num(g[~sph])), _bits(np.nan_to_num(w[~sph]))), f"{what}: uv"
+        if sph.any():
+            assert np.abs(g[sph].astype(np.float64) - w[sph]).max() <= 1e-4, f"{what}: sphere uv"
+    return int((obj >= 0).sum())
+
+
+def ref_dict(r):
+    return {k: (v.astype(np.int32) if k in ("object", "prim") else v) for k, v in r.items()}
+
+
+def assert_bitwise(got, want, what):
+    g, w = f32_bits(got), f32_bits(np.asarray(want, f32).reshape(np.shape(got)))
+    bad = g != w
+    assert not bad.any(), f"{what}: {int(bad.reshape(len(g), -1).any(-1).sum())} of {len(g)} rays differ"
+
+
+def max_diff(got, want, what):
+    """largest per-channel difference; NaN positions must agree"""
+    want = np.asarray(want, f32).reshape(got.shape)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN positions differ"
+    d = np.abs(np.nan_to_num(got).astype(np.float64) - np.nan_to_num(want).astype(np.float64))
+    m = float(d.max()) if d.size else 0.0
+    print(f"{what}: colour max|diff| {m:.3e}")
+    return m
+
+
+def first_hit_same(got, want, what):
+    assert np.array_equal(got["object"], np.asarray(want["object"]).astype(np.int32)), f"{what}: object"
+    assert_bitwise(got["t"], want["t"], f"{what}: t")
+    assert_bitwise(got["normal"], want["normal"], f"{what}: normal")
+
+
+def random_rays(rng, n, rs, lo, hi, lengths=(0.01, 1.0, 30.0)):
+    """(origins, directions, per-ray min_t): origins uniform in [lo, hi]^3 and inside spheres and mesh boxes, Gaussian
+    directions times one of `lengths`, a component exactly zero (either sign) in 10 % of them"""
+    from tests import ray_ref
+    o = rng.uniform(lo, hi, (n, 3)).astype(f32)
+    d = rng.normal(size=(n, 3)).astype(f32) * rng.choice(list(lengths), (n, 1)).astype(f32)
+    z = rng.rand(n) < 0.1                                      # a direction component exactly zero (either sign)
+    d[z, rng.randint(0, 3, int(z.sum()))] = rng.choice([0.0, -0.0], int(z.sum())).astype(f32)
+    k = 0
+    for ob in rs.objects:                                      # origins inside spheres and inside mesh boxes
+        if ob["type"] == ray_ref.OBJ_SPHERE:
+            m = n // 20
+            o[k:k + m] = ob["v0"] + rng.uniform(-0.3, 0.3, (m, 3)).astype(f32) * ob["f0"]
+            k += m
+        elif ob["type"] == ray_ref.OBJ_MESH:
+            m = n // 10
+            o[k:k + m] = rng.uniform(ob["v0"], ob["v1"], (m, 3)).astype(f32)
+            k += m
+    mt = rng.choice([1e-3, 0.0, -0.5, 0.25], n).astype(f32)  # per-ray min_t, zero and negative included
+    return o, d, mt
+
+# ---- the range sweeps of tests/test_gpu_query_ranges.py.  tests/test_query_ranges_cpu.py proves, exponent by exponent,
+# that tests/ray_ref.py neither overflows nor goes denormal on these inputs: an exponent that fails there leaves both
+# lists, it is not tolerated ----
+DIR_EXPONENTS = (-104, -100, -96, -64, -24, 24, 64, 100)   # directions are multiplied by 2^j
+SCALE_EXPONENTS = (-20, -12, 0, 12, 24)   # every position by 2^k (at -30 and 30 the checker's own normals go denormal / overflow)
+
+
+def pow2(j):
+    return f32(np.ldexp(1.0, int(j)))
+
+
+def sweep_rays(seed, n, rs, min_ratio=2.0 ** -6, aim=0.5):
+    """The sweeps' base rays on scene `rs`: random_rays with directions of length about 1.  The fraction `aim` of the rays
+    (none with a zero component) then points at a vertex of one of the scene's meshes, and a direction whose smallest
+    non-zero component is below min_ratio x its largest is drawn again, so that no product of the reference goes denormal
+    when the direction is scaled.  `sel` in {0, 1, 2} picks each ray's min_t and max_t."""
+    from tests import ray_ref
+
+    def narrow(v):
+        a = np.abs(v)
+        return np.where(a > 0, a, np.inf).min(-1) < f32(min_ratio) * a.max(-1)
+
+    rng = np.random.RandomState(seed)
+    o, d, _ = random_rays(rng, n, rs, -3.0, 3.0, lengths=(1.0,))
+    zero = d == 0
+    meshes = [ob for ob in rs.objects if ob["type"] == ray_ref.OBJ_MESH and ob["tri_count"]]
+    if meshes:
+        verts = np.concatenate([rs.tris[ob["tri_begin"]:ob["tri_begin"] + ob["tri_count"]].reshape(-1, 3) for ob in meshes])
+        todo = np.nonzero((rng.rand(n) < aim) & ~zero.any(-1))[0]
+        while len(todo):
+            v = verts[rng.randint(0, len(verts), len(todo))] - o[todo]
+            v = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(f32)
+            ok = np.isfinite(v).all(-1) & ~narrow(v)
+            d[todo[ok]] = v[ok]
+            todo = todo[~ok]
+    todo = np.nonzero(narrow(d))[0]
+    while len(todo):
+        v = rng.normal(size=(len(todo), 3)).astype(f32)
+        # a draw that changes nothing: it keeps the stream, and so the rays, those on which the counts of
+        # profiles/rays/direction_length_before_fix.txt were measured — do not remove it without measuring them again
+        rng.choice([1.0], (len(todo), 1))
+        d[todo] = np.where(zero[todo], d[todo], v)
+        todo = todo[narrow(d[todo])]
+    return o, d, rng.randint(0, 3, n)
+
+
+def sweep_min_t(sel, j):
+    """per-ray min_t from {0, 1e-3, 1e-3 * 2^-j}; j may be per ray"""
+    return np.where(sel == 0, f32(0.0), np.where(sel == 1, f32(1e-3), f32(1e-3) * np.ldexp(f32(1.0), -np.asarray(j)).astype(f32))).astype(f32)
+
+
+def sweep_max_t(sel, j):
+    """per-ray max_t from {inf, 2 * 2^-j, 100 * 2^-j}"""
+    s = np.ldexp(f32(1.0), -np.asarray(j)).astype(f32)
+    return np.where(sel == 0, f32(np.inf), np.where(sel == 1, f32(2.0) * s, f32(100.0) * s)).astype(f32)
+
+
+def scaled_scene_json(tmp_path, k, w=32, h=32):
+    """One scene of every primitive, light and material kind, every position and the radius multiplied by 2^k: half of
+    scene/bunny.stl, a plane, a stand-alone triangle, a sphere; a point light and a sun; an opaque, a reflecting and a
+    transmitting material."""
+    from cutrace_amd import scenes
+    s = float(pow2(k))
+    tris = scenes.read_stl(os.path.join(ROOT, "scene", "bunny.stl"))[::2]
+    stl = str(tmp_path / f"scaled_{k}.stl")
+    scenes.write_stl(stl, (tris * pow2(k)).astype(np.float32))
+
+    def p(*v):
+        return [float(np.float32(x)) * s for x in v]
+    mats = [{"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.0, "phong": 40},
+            {"type": "solid", "color": [0.9, 0.9, 0.95], "specular": 0.3, "reflect": 0.7, "phong": 60},
+            {"type": "solid", "color": [0.3, 0.8, 0.5], "specular": 0.6, "reflect": 0.0, "phong": 30, "transparency": 0.5}]
+    objs = [{"type": "mesh", "file": stl, "material": 0},
+            {"type": "plane", "point": p(0, -1.25, 0), "normal": [0.0, 1.0, 0.0], "material": 1},
+            {"type": "triangle", "p1": p(-2.5, -1, -1.5), "p2": p(2.5, -1, -1.5), "p3": p(0.25, 2.5, -1.75), "material": 2},
+            {"type": "sphere", "center": p(1.5, 0.25, 0.5), "radius": p(0.5)[0], "material": 2}]
+    lights = [{"type": "point", "point": p(0.5, 2.5, 2.0), "color": [0.8, 0.8, 0.8]},
+              {"type": "sun", "direction": [-0.3, -1.0, -0.2], "color": [0.4, 0.4, 0.4]}]
+    cam = {"eye": p(0.5, 0.75, 4.0), "up": [0, 1, 0], "look": [-0.05, -0.15, -1.0], "near_plane": 0.1, "far_plane": 100.0,
+           "width": w, "height": h, "ambient": 0.1}
+    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
+
+
+def hall_of_mirrors_json(w, h, middle=None):
+    """two facing mirror walls, a floor, and between them a sphere that both reflects and transmits (or the object `middle`,
+    which gets that material): every level to bounces 15 is live"""
+    mats = [{"type": "solid", "color": [0.9, 0.9, 0.95], "specular": 0.3, "reflect": 0.8, "phong": 60},
+            {"type": "solid", "color": [0.7, 0.5, 0.3], "specular": 0.1, "reflect": 0.0, "phong": 5},
+            {"type": "solid", "color": [0.3, 0.8, 0.5], "specular": 0.6, "reflect": 0.3, "phong": 30, "transparency": 0.5}]
+    objs = [{"type": "plane", "point": [-2, 0, 0], "normal": [1, 0, 0], "material": 0},
+            {"type": "plane", "point": [2, 0, 0], "normal": [-1, 0, 0], "material": 0},
+            {"type": "plane", "point": [0, -1, 0], "normal": [0, 1, 0], "material": 1},
+            dict(middle, material=2) if middle else {"type": "sphere", "center": [0.2, -0.3, 0.0], "radius": 0.6, "material": 2}]
+    lights = [{"type": "point", "point": [0.5, 2.5, 2.0], "color": [0.8, 0.8, 0.8]},
+              {"type": "sun", "direction": [-0.3, -1.0, -0.2], "color": [0.4, 0.4, 0.4]}]
+    cam = {"eye": [0.9, 0.4, 4.0], "up": [0, 1, 0], "look": [-0.6, -0.2, -1.0], "near_plane": 0.1, "far_plane": 100.0,
+           "width": w, "height": h, "ambient": 0.1}
+    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
