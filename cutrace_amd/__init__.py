@@ -172,10 +172,19 @@ class DeviceScene:
             _lib.hip_lib().ctr_frame_free(self._pin)
             self._pin_px = 0
 
-    def render(self, fudge=1e-3, bounces=5, rows=None, pinned=False, into=None):
+    @staticmethod
+    def _samples(samples):
+        if isinstance(samples, bool) or not isinstance(samples, (int, np.integer)) or int(samples) not in (1, 2, 4, 8):
+            raise ValueError(f"samples: 1, 2, 4 or 8 per axis, got {samples!r}")
+        return int(samples)
+
+    def render(self, fudge=1e-3, bounces=5, rows=None, pinned=False, into=None, samples=1):
         """Host-buffer form (ctr_render): returns numpy buffers + stats.  pinned=True: the buffers are views of
         the scene handle's page-locked frame block (valid until the next pinned render / close).  into: a dict
-        returned by an earlier call of the same shape, whose buffers are written again."""
+        returned by an earlier call of the same shape, whose buffers are written again.  samples = 2, 4 or 8: the
+        supersampled frame (ctr_render_aa, include/cutrace_aa.h): samples x samples rays per pixel, averaged in the
+        kernel; the buffers, `rows` and stats['rows'] stay those of the w x h frame."""
+        samples = self._samples(samples)
         L = _lib.hip_lib()
         r = make_rows(self.h, rows)
         n = rows_count(self.h, rows)
@@ -193,10 +202,16 @@ class DeviceScene:
             color = np.empty((n, self.w, 3), np.float32)
             normal = np.empty((n, self.w, 3), np.float32)
         stats = RenderStats()
-        st = L.ctr_render(self._h, C.c_float(fudge), bounces, C.byref(r), depth.ctypes.data, color.ctypes.data,
-                          normal.ctypes.data, C.byref(stats))
-        if st:
-            raise RuntimeError(f"ctr_render failed ({st}): {L.ctr_last_error().decode()}")
+        if samples != 1:
+            st = L.ctr_render_aa(self._h, C.c_float(fudge), bounces, samples, C.byref(r), depth.ctypes.data, color.ctypes.data,
+                                 normal.ctypes.data, C.byref(stats))
+            if st:
+                raise RuntimeError(f"ctr_render_aa failed ({st}): {L.ctr_last_error().decode()}")
+        else:
+            st = L.ctr_render(self._h, C.c_float(fudge), bounces, C.byref(r), depth.ctypes.data, color.ctypes.data,
+                              normal.ctypes.data, C.byref(stats))
+            if st:
+                raise RuntimeError(f"ctr_render failed ({st}): {L.ctr_last_error().decode()}")
         return dict(depth=depth, color=color, normal=normal, ray_count=int(stats.ray_count),
                     kernel_ms=stats.kernel_ms, total_ms=stats.total_ms, max_depth=float(stats.max_depth),
                     rows=int(stats.rows))
@@ -218,10 +233,18 @@ class DeviceScene:
         return dict(depth=depth, color=color, normal=normal, uv=uv, ray_count=int(stats.ray_count),
                     kernel_ms=stats.kernel_ms, total_ms=stats.total_ms, max_depth=float(stats.max_depth), rows=int(stats.rows))
 
-    def render_device(self, d_depth, d_color, d_normal, d_counters=0, stream=0, fudge=1e-3, bounces=5, rows=None):
-        """Device-buffer form (ctr_render_device): raw device pointers, async on `stream`."""
+    def render_device(self, d_depth, d_color, d_normal, d_counters=0, stream=0, fudge=1e-3, bounces=5, rows=None, samples=1):
+        """Device-buffer form (ctr_render_device): raw device pointers, async on `stream`.  samples = 2, 4 or 8:
+        ctr_render_device_aa, the supersampled frame into the same w x h buffers."""
+        samples = self._samples(samples)
         L = _lib.hip_lib()
         r = make_rows(self.h, rows)
+        if samples != 1:
+            st = L.ctr_render_device_aa(self._h, C.c_float(fudge), bounces, samples, C.byref(r), d_depth, d_color, d_normal,
+                                        d_counters, stream)
+            if st:
+                raise RuntimeError(f"ctr_render_device_aa failed ({st}): {L.ctr_last_error().decode()}")
+            return
         st = L.ctr_render_device(self._h, C.c_float(fudge), bounces, C.byref(r), d_depth, d_color, d_normal,
                                  d_counters, stream)
         if st:

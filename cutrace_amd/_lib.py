@@ -100,6 +100,8 @@ HIP_SYMBOLS = [
 
 # include/cutrace_rays.h (kept apart from HIP_SYMBOLS, which mirrors cutrace_amd.h)
 RAY_SYMBOLS = ["ctr_cast_rays", "ctr_shade_rays"]
+# include/cutrace_aa.h
+AA_SYMBOLS = ["ctr_render_aa", "ctr_render_device_aa"]
 
 _host = None
 _hip = None
@@ -191,6 +193,10 @@ def hip_lib():
             "ctr_tile_costs": ([C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
             "ctr_cast_rays": ([C.c_void_p, C.POINTER(RayQuery), C.c_void_p], C.c_int),
             "ctr_shade_rays": ([C.c_void_p, C.POINTER(ShadeQuery), C.c_void_p], C.c_int),
+            "ctr_render_aa": ([C.c_void_p, C.c_float, C.c_int, C.c_uint32, C.POINTER(Rows), C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.POINTER(RenderStats)], C.c_int),
+            "ctr_render_device_aa": ([C.c_void_p, C.c_float, C.c_int, C.c_uint32, C.POINTER(Rows), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
         }
         for name, (argt, rest) in opt.items():
             if hasattr(L, name):

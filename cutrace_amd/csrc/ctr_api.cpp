@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ctr_internal.h"
+#include "cutrace_aa.h"
 #include "cutrace_amd.h"
 #include "guard.h"
 #include "scene_device.h"
@@ -215,7 +216,7 @@ void fill_launch(const ctr_scene *s, RenderLaunch &L) {
 // the shipped kind, frame leaving through device buffers.  The top-level tree over the meshes stays the fallback the kernel
 // itself takes for a cast the merged walk cannot decide (render_kernel.hip "merged walk").
 void use_merged_tree(const ctr_scene *s, RenderLaunch &L) {
-  const bool bvh_walk = (L.variant & (KV_BVH | KV_STATS)) && !(L.variant & (KV_COUNT | KV_UV));
+  const bool bvh_walk = (L.variant & (KV_BVH | KV_STATS)) && !(L.variant & (KV_COUNT | KV_UV | KV_SS));
   if ((s->user_variant & CTR_VAR_MERGE) && s->flat.merged.built && s->flat.merged.usable && bvh_walk && !L.group_done &&
       (L.variant & KV_PREFILTER || (L.variant & KV_STATS))) {
     L.variant |= KV_MERGE;
@@ -325,6 +326,40 @@ int check_args(const ctr_scene *s, int bounces) {
     return fail(CTR_E_INVALID, "bounces must be in [0," + std::to_string(CTR_MAX_BOUNCES) + "]");
   if (s->cam.w == 0 || s->cam.h == 0) return fail(CTR_E_INVALID, "camera has zero width or height");
   return CTR_OK;
+}
+
+// ---- supersampling (include/cutrace_aa.h) ----
+// `samples` as log2, or why the handle cannot make the call; nothing here touches the GPU
+int aa_check(const ctr_scene *s, uint32_t samples, uint32_t &ls) {
+  if (samples != 1 && samples != 2 && samples != 4 && samples != 8)
+    return fail(CTR_E_INVALID, "samples must be 1, 2, 4 or 8 per axis, got " + std::to_string(samples));
+  ls = samples == 8 ? 3u : samples == 4 ? 2u : samples == 2 ? 1u : 0u;
+  if (!ls) return CTR_OK;
+  if (s->user_variant & (CTR_VAR_STATS | CTR_VAR_IGNORE_TRANSPARENT | CTR_VAR_NO_PREFILTER | CTR_VAR_NO_CLUSTER))
+    return fail(CTR_E_INVALID, "supersampling: no build for CTR_VAR_STATS, CTR_VAR_IGNORE_TRANSPARENT, CTR_VAR_NO_PREFILTER or CTR_VAR_NO_CLUSTER");
+  if (((uint64_t)s->cam.w << ls) > 0xFFFFFFFFull || ((uint64_t)s->cam.h << ls) > 0xFFFFFFFFull)
+    return fail(CTR_E_INVALID, "supersampling: samples x width or samples x height exceeds 32 bits");
+  return CTR_OK;
+}
+// The launch of the w x h output pixels (fill_launch, make_rows) becomes the launch of the s*w x s*h samples.  The part rule
+// ((y / block_rows) % n_parts) == part is invariant under the scaling; first_block counts blocks and stays.
+int aa_scale(RenderLaunch &L, uint32_t ls) {
+  DRows &R = L.rows;
+  if (R.block_rows > L.h) R.block_rows = L.h;  // (rows end at h: a taller block selects what a block of h rows selects)
+  L.w <<= ls; L.h <<= ls;
+  R.row_begin <<= ls; R.row_end <<= ls; R.n_rows <<= ls; R.block_rows <<= ls;
+  L.ss_log2 = ls;
+  if (ctr_launch_waves(L) > 0x7FFFFFFFull) return fail(CTR_E_INVALID, "supersampling: the sample frame has more than 0x7FFFFFFF tiles");
+  return CTR_OK;
+}
+// the checks of both entry points, in the order the header lists them
+int aa_precheck(ctr_scene *s, int bounces, uint32_t samples, const ctr_rows *rows, uint32_t &ls) {
+  int st = check_args(s, bounces);
+  if (st || (st = aa_check(s, samples, ls)) || !ls) return st;
+  RenderLaunch L{};
+  L.w = s->cam.w; L.h = s->cam.h; L.n_frames = 1;
+  if ((st = make_rows(s, rows, L.rows))) return st;
+  return aa_scale(L, ls);
 }
 
 // the caller's buffers of a host-form render; direct_delivery: the same buffers as the device sees them
@@ -443,7 +478,7 @@ int report(ctr_scene *s, const RenderLaunch &L, std::chrono::high_resolution_clo
     stats->kernel_ms = ms;
     stats->total_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     stats->ray_count = cnt[0];
-    stats->rows = L.rows.n_rows;
+    stats->rows = L.rows.n_rows >> L.ss_log2;  // (output rows)
     uint32_t bits = (uint32_t)cnt[1];
     float md;
     memcpy(&md, &bits, 4);
@@ -595,9 +630,10 @@ int ctr_set_variant(ctr_scene *s, uint32_t bits) {
   return CTR_OK;
 }
 
-int ctr_render_device_batch(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, uint32_t first_frame,
-                            uint32_t n_frames, uint64_t frame_stride_px, uint32_t part_stride, void *d_depth,
-                            void *d_color3, void *d_normal3, void *d_counters, void *hip_stream) {
+// ss_log2 != 0: one supersampled frame (ctr_render_device_aa, whose checks have passed)
+static int render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, uint32_t first_frame,
+                         uint32_t n_frames, uint64_t frame_stride_px, uint32_t part_stride, void *d_depth,
+                         void *d_color3, void *d_normal3, void *d_counters, void *hip_stream, uint32_t ss_log2) {
   int st = check_args(s, bounces);
   if (st) return st;
   if (!d_depth || !d_color3 || !d_normal3) return fail(CTR_E_INVALID, "null output buffer");
@@ -633,6 +669,10 @@ int ctr_render_device_batch(ctr_scene *s, float fudge, int bounces, const ctr_ro
   L.normal = (float *)d_normal3;
   L.counters = (unsigned long long *)d_counters;
   L.variant = s->kernel_variant(false);
+  if (ss_log2) {
+    if ((st = aa_scale(L, ss_log2))) return st;
+    L.variant = (L.variant & (KV_ANYHIT | KV_FASTPOW | KV_OCC6)) | KV_PREFILTER | KV_BVH | KV_SS;
+  }
   use_merged_tree(s, L);
   {
     std::lock_guard<std::mutex> lk(s->mtx);
@@ -643,13 +683,28 @@ int ctr_render_device_batch(ctr_scene *s, float fudge, int bounces, const ctr_ro
   return CTR_OK;
 }
 
+int ctr_render_device_batch(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, uint32_t first_frame,
+                            uint32_t n_frames, uint64_t frame_stride_px, uint32_t part_stride, void *d_depth,
+                            void *d_color3, void *d_normal3, void *d_counters, void *hip_stream) {
+  return render_device(s, fudge, bounces, rows, first_frame, n_frames, frame_stride_px, part_stride, d_depth, d_color3, d_normal3,
+                       d_counters, hip_stream, 0);
+}
+
+int ctr_render_device_aa(ctr_scene *s, float fudge, int bounces, uint32_t samples, const ctr_rows *rows, void *d_depth,
+                         void *d_color3, void *d_normal3, void *d_counters, void *hip_stream) {
+  uint32_t ls = 0;
+  if (int st = aa_precheck(s, bounces, samples, rows, ls)) return st;
+  return render_device(s, fudge, bounces, rows, 0, 1, 0, 0, d_depth, d_color3, d_normal3, d_counters, hip_stream, ls);
+}
+
 int ctr_render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, void *d_depth, void *d_color3,
                       void *d_normal3, void *d_counters, void *hip_stream) {
   return ctr_render_device_batch(s, fudge, bounces, rows, 0, 1, 0, 0, d_depth, d_color3, d_normal3, d_counters, hip_stream);
 }
 
+// ss_log2 != 0: a supersampled frame (ctr_render_aa, whose checks have passed): rows, px and the buffers are the output's
 static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, const HostFrame &out, ctr_render_stats *stats,
-                       bool count, unsigned long long *aabb_tris) {
+                       bool count, unsigned long long *aabb_tris, uint32_t ss_log2 = 0) {
   auto t0 = std::chrono::high_resolution_clock::now();
   int st = check_args(s, bounces);
   if (st) return st;
@@ -660,13 +715,15 @@ static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *r
   if ((st = make_rows(s, rows, L.rows))) return st;
   const size_t px = (size_t)L.rows.n_rows * s->cam.w;
   HostFrame z{};
-  const bool direct = direct_delivery(s, out, px, count, z);
+  if (ss_log2 && (st = aa_scale(L, ss_log2))) return st;
+  const bool direct = !ss_log2 && direct_delivery(s, out, px, count, z);  // (no delivering build of the supersampled kernel)
   const size_t spx = direct ? (size_t)ctr_staging_pixels(L) : (px ? px : 1);  // pixels per output buffer on the device
   L.fudge = fudge;
   L.bounces = bounces;
   if ((st = prepare_outputs(s, L, spx, direct ? &z : nullptr))) return st;
   L.counters = s->d_counters;
   L.variant = s->kernel_variant(count);
+  if (ss_log2) L.variant = (L.variant & (KV_ANYHIT | KV_FASTPOW | KV_OCC6)) | KV_PREFILTER | KV_BVH | KV_SS;
   const bool igntr = (s->user_variant & CTR_VAR_IGNORE_TRANSPARENT) != 0 && !count;
   if ((out.uv2 || igntr) && px) {
     if (count || (s->user_variant & CTR_VAR_STATS)) return fail(CTR_E_INVALID, "ctr_render_uv / CTR_VAR_IGNORE_TRANSPARENT: not with the counting / statistics variants");
@@ -693,6 +750,13 @@ static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *r
 int ctr_render(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, float *depth, float *color3,
                float *normal3, ctr_render_stats *stats) {
   return render_host(s, fudge, bounces, rows, {depth, color3, normal3, nullptr}, stats, false, nullptr);
+}
+
+int ctr_render_aa(ctr_scene *s, float fudge, int bounces, uint32_t samples, const ctr_rows *rows, float *depth, float *color3,
+                  float *normal3, ctr_render_stats *stats) {
+  uint32_t ls = 0;
+  if (int st = aa_precheck(s, bounces, samples, rows, ls)) return st;
+  return render_host(s, fudge, bounces, rows, {depth, color3, normal3, nullptr}, stats, false, nullptr, ls);
 }
 
 int ctr_render_uv(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, float *depth, float *color3,

@@ -322,6 +322,7 @@ struct KArgs {
   float *host_depth, *host_color, *host_normal;
   uint32_t *group_done;
   float *uv_out;      // KV_UV: texture coordinates of the primary hit, 2 floats per pixel
+  uint32_t ss_log2;   // KV_SS: log2 of the samples per axis (1, 2 or 3); w, h and rows are those of the s*w x s*h sample frame
 };
 
 static_assert(offsetof(KArgs, planes) == 0 && offsetof(KArgs, has_mesh) == 28, "KArgs: the hot block is the first eight dwords");
@@ -377,6 +378,11 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   constexpr bool FASTPOW = (KV & KV_FASTPOW) != 0;
   constexpr bool HOSTOUT = (KV & KV_HOSTOUT) != 0;  // "Host delivery"
   constexpr bool UV = (KV & KV_UV) != 0;            // ray_cast's tex_coords of the primary cast as a fourth output
+  // "Supersampling": the launch renders the s*w x s*h sample frame (s = 1 << ss_log2 divides TW and TH, so an s x s block
+  // of samples lies inside one wave); depth and normal of a pixel are those of its sample (0, 0), its colour the mean of
+  // the block, reduced across the lanes at the end of the wave (include/cutrace_aa.h has the definition and the order)
+  constexpr bool SS = (KV & KV_SS) != 0;
+  static_assert(!SS || !((KV & (KV_HOSTOUT | KV_STATS | KV_UV)) != 0), "the supersampled frame leaves through device buffers, three outputs");
   // ray_cast's ninth argument (ray_cast.hpp:30,39-40: `if (ignore_transparent && is_transparent(mat)) continue;`).  Every caller
   // of the reference passes false; with IGNTR the cast of kernel.hpp:52 — the one depth, normal and tex_coords come from — is
   // made with true, as a trip of its own before ray_color's first cast (shading.hpp:123, false), which it otherwise shares
@@ -447,7 +453,8 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   const bool in_image = x_id < w && k_row < A.rows.n_rows && y_id < A.rows.row_end;
   // kernel.hpp:54 (compact buffer).  Recomputed from the lane id at its three uses rather than kept
   // in two VGPRs for the whole wave: registers, not instructions, are what this kernel is short of.
-  const uint32_t tile_px0 = ty * TH * w + tx * TW;  // wave-uniform
+  // (SS: the tile's first OUTPUT pixel, in the w/s-wide frame)
+  const uint32_t tile_px0 = SS ? ((ty * TH) >> A.ss_log2) * (w >> A.ss_log2) + ((tx * TW) >> A.ss_log2) : ty * TH * w + tx * TW;  // wave-uniform
   // a pixel's three floats: in place, or — staged — written THROUGH to memory (agent scope), because the wave that
   // copies the group to the host usually runs on another XCD, whose L2 is not coherent with this one
   auto store3 = [&](float *__restrict__ out, size_t px_id, V3 v) {
@@ -467,7 +474,18 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   auto px_index = [&]() -> size_t {
     const uint32_t l = lane_now();  // recomputed here: hoisted out of the loop the addresses would be spilled to scratch
     if (HOSTOUT) return (size_t)wave * 64u + l;  // tile-major staging ("Host delivery")
+    if constexpr (SS) {  // the output pixel the lane's sample belongs to: (k_row / s) * (w / s) + x_id / s
+      const uint32_t ls = ((const CADDR KArgs *)__builtin_amdgcn_kernarg_segment_ptr())->ss_log2;
+      return (size_t)frame * A.frame_stride_px + (size_t)(tile_px0 + ((l / TW) >> ls) * (w >> ls) + ((l % TW) >> ls));
+    }
     return (size_t)frame * A.frame_stride_px + (size_t)(tile_px0 + (l / TW) * w + (l % TW));
+  };
+
+  // SS: the lane that holds sample (0, 0) of its block — x_id % s == 0 && k_row % s == 0 — is the one that stores the pixel
+  auto ss_kept = [&]() -> bool {
+    const uint32_t l = lane_now();
+    const uint32_t m = (1u << ((const CADDR KArgs *)__builtin_amdgcn_kernarg_segment_ptr())->ss_log2) - 1u;
+    return (((l % TW) | (l / TW)) & m) == 0u;
   };
 
   // ---- cam::get_ray, default_schema.hpp:376-386 ----
@@ -1543,9 +1561,16 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         CTR_MARK(40);
         const size_t px_id = px_index();
         float *const k_depth_out = ((const CADDR KParams *)AK)->depth_out, *const k_normal_out = ((const CADDR KParams *)AK)->normal_out;
-        if (HOSTOUT) __hip_atomic_store(k_depth_out + px_id, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else k_depth_out[px_id] = best;
-        store3(k_normal_out, px_id, normal);
+        if constexpr (SS) {
+          if (ss_kept()) {
+            k_depth_out[px_id] = best;
+            store3(k_normal_out, px_id, normal);
+          }
+        } else {
+          if (HOSTOUT) __hip_atomic_store(k_depth_out + px_id, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          else k_depth_out[px_id] = best;
+          store3(k_normal_out, px_id, normal);
+        }
         if (UV) {
           float *const uvp = AK->uv_out;
           uvp[2 * px_id + 0] = tc_u;
@@ -1696,9 +1721,16 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
       for (;;) {
         CTR_MARK(52);  // unwind one level
         if (sp == 0) {
-          const size_t px_id = px_index();
-          store3(((const CADDR KParams *)AK)->color_out, px_id, out_rgb);
-          msp = MSP_DONE;
+          if constexpr (SS) {
+            // parked, not stored: the sample's colour waits in the lane's own frame 0 (free from here on; A.frames >= 1)
+            // for the reduction after the loop, where the wave has reconverged.  MSP_DONE | 1: "this lane has a sample"
+            STK(0, F_R) = out_rgb.x; STK(0, F_G) = out_rgb.y; STK(0, F_B) = out_rgb.z;
+            msp = MSP_DONE | 1u;
+          } else {
+            const size_t px_id = px_index();
+            store3(((const CADDR KParams *)AK)->color_out, px_id, out_rgb);
+            msp = MSP_DONE;
+          }
           break;
         }
         CTR_MARK(53);
@@ -1733,6 +1765,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
       // max finite depth of the tile, reduced once here instead of carrying the depth to the end
       CTR_MARK(54);
       uint32_t dbits = (__builtin_isfinite(first_depth) && first_depth > 0.f) ? __float_as_uint(first_depth) : 0u;
+      if constexpr (SS) dbits = ss_kept() ? dbits : 0u;  // the maximum of the depth buffer that is returned
       for (int off = 32; off > 0; off >>= 1) {
         const uint32_t o = (uint32_t)__shfl_xor((int)dbits, off);
         dbits = o > dbits ? o : dbits;
@@ -1743,6 +1776,25 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     TSTAMP(t_cont1);
     TACC(8, t_cont_mid, t_cont1);
     CTR_MARK(55);
+  }
+  if constexpr (SS) {
+    // ---- "Supersampling": the mean of each s x s block of parked sample colours, in float32 and in a fixed order ----
+    // along x by repeated halving (a[i] = a[2i] + a[2i+1]), then along y in the same way, then times 1 / (s*s).  A sum of
+    // two floats does not depend on the operands' order, so the xor butterfly gives every lane of a block the tree's value.
+    // The lanes of a block are inside or outside the image together (w, h and the rows are multiples of s); what lanes
+    // outside it read from their never-written frame is added only among themselves and never stored.
+    const uint32_t ls = AK->ss_log2;
+    V3 c = mk(STK(0, F_R), STK(0, F_G), STK(0, F_B));
+    for (uint32_t k = 0; k < ls; k++) {
+      const int off = 1 << k;
+      c = mk(c.x + __shfl_xor(c.x, off), c.y + __shfl_xor(c.y, off), c.z + __shfl_xor(c.z, off));
+    }
+    for (uint32_t k = 0; k < ls; k++) {
+      const int off = TW << k;
+      c = mk(c.x + __shfl_xor(c.x, off), c.y + __shfl_xor(c.y, off), c.z + __shfl_xor(c.z, off));
+    }
+    const float inv = 1.0f / (float)(1u << (2u * ls));
+    if (msp == (MSP_DONE | 1u) && ss_kept()) store3(((const CADDR KParams *)AK)->color_out, px_index(), vscale(c, inv));
   }
 #undef STK
 #undef PRK
@@ -2154,6 +2206,14 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
   A.group_done = L.group_done;
   A.uv_out = L.uv;
   if (((KV & KV_UV) != 0) != (L.uv != nullptr)) return (int)hipErrorInvalidValue;
+  // "Supersampling": s = 2, 4 or 8 must divide the tile (a block of samples inside one wave) and the sample frame; one frame
+  A.ss_log2 = (KV & KV_SS) ? L.ss_log2 : 0u;
+  if (((KV & KV_SS) != 0) != (L.ss_log2 != 0u)) return (int)hipErrorInvalidValue;
+  if (KV & KV_SS) {
+    const uint32_t m = (1u << L.ss_log2) - 1u;
+    if (L.ss_log2 > 3u || ((TW | TH) & m) || ((L.w | L.h | L.rows.n_rows | L.rows.row_begin | L.rows.row_end | L.rows.block_rows) & m) || L.n_frames != 1)
+      return (int)hipErrorInvalidValue;
+  }
   size_t lds_bytes = (size_t)WAVES_PER_WG * A.frames * A.nf * 64 * sizeof(float);
   if (KV & KV_OCC6) lds_bytes += (size_t)WAVES_PER_WG * 5 * 64 * sizeof(float);  // PARK
   // diagnostic only: extra dynamic LDS per workgroup caps the waves resident per CU (occupancy sweeps)
@@ -2304,6 +2364,14 @@ int ctr_launch_render(const RenderLaunch &L, void *stream) {
   }
   if (L.variant & KV_UV) {  // the fourth output: the shipped walk only (BVH + prefilter), any-hit and pow as the scene / caller say
     constexpr uint32_t U = KV_PREFILTER | KV_BVH | KV_UV;
+    if (L.variant & KV_FASTPOW) return (L.variant & KV_ANYHIT) ? launch<U | KV_FASTPOW | KV_ANYHIT>(L, s) : launch<U | KV_FASTPOW>(L, s);
+    return (L.variant & KV_ANYHIT) ? launch<U | KV_ANYHIT>(L, s) : launch<U>(L, s);
+  }
+  if (L.variant & KV_SS) {  // the supersampled frame: the shipped walk only, as KV_UV; the 6-wave build where the plain render picks it
+    constexpr uint32_t U = KV_PREFILTER | KV_BVH | KV_SS;
+    const size_t sb = (size_t)((L.bounces > 0 && L.any_bounce) ? L.bounces : 1) * (L.need_cold_frames ? 10u : 4u) * 64 * sizeof(float);
+    if ((L.variant & (KV_OCC6 | KV_ANYHIT | KV_FASTPOW)) == (KV_OCC6 | KV_ANYHIT | KV_FASTPOW) && occ6_fits(sb))
+      return launch<U | KV_FASTPOW | KV_ANYHIT | KV_OCC6>(L, s);
     if (L.variant & KV_FASTPOW) return (L.variant & KV_ANYHIT) ? launch<U | KV_FASTPOW | KV_ANYHIT>(L, s) : launch<U | KV_FASTPOW>(L, s);
     return (L.variant & KV_ANYHIT) ? launch<U | KV_ANYHIT>(L, s) : launch<U>(L, s);
   }

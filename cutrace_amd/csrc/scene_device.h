@@ -119,6 +119,7 @@ enum : uint32_t {
   KV_UV = 256u,        // also write the texture coordinates of the primary hit (ray_cast's tex_coords), RenderLaunch::uv
   KV_IGNTR = 1024u,    // the cast of kernel.hpp:52 (depth, normal, uv) is made with ray_cast's ignore_transparent = true (CTR_VAR_IGNORE_TRANSPARENT)
   KV_MERGE = 512u,     // the walk may meet the merged pseudo mesh: ONE tree over the triangles of all meshes (CTR_VAR_MERGE)
+  KV_SS = 2048u,       // supersampling: the launch renders s x s samples per pixel and reduces them in the wave (RenderLaunch::ss_log2)
 };
 
 struct DRows {
@@ -177,6 +178,10 @@ struct RenderLaunch {
   // the wave that completes each group of tiles.  group_done: ctr_staging_groups() zeroed words (left zeroed).
   float *host_depth, *host_color, *host_normal;
   uint32_t *group_done;
+  // Supersampling (KV_SS; render_kernel.hip "Supersampling", include/cutrace_aa.h): log2 of the samples per axis, 1..3.  w, h and
+  // rows above are then those of the s*w x s*h SAMPLE frame (every one a multiple of s); depth / color / normal hold the
+  // (rows.n_rows / s) x (w / s) output pixels.  0: a plain launch.
+  uint32_t ss_log2;
 };
 uint64_t ctr_staging_pixels(const RenderLaunch &L);
 uint64_t ctr_staging_groups(const RenderLaunch &L);

@@ -4,6 +4,7 @@
 //
 // Extras (ignored by anything that drives the reference): environment overrides
 //   CUTRACE_BOUNCES, CUTRACE_WIDTH, CUTRACE_HEIGHT, CUTRACE_DEVICE
+//   CUTRACE_SAMPLES=2|4|8   that many rays per axis through every pixel, averaged in the kernel (ctr_render_aa; one device only)
 // because the reference has no flags (main.cu:8-12) and benchmarking needs them, and
 //   CUTRACE_DEVICES=N   row-tile the frame over the first N GPUs of the node (ctr_render_multi: one RCCL
 //                       gather to GPU 0, same three files); CUTRACE_DEVICE_LIST=0,2,... names them instead
@@ -54,6 +55,12 @@ int main(int argc, const char **argv) {
     desc = ctr_host_scene_desc(hs);
   }
 
+  const long samples = env_long("CUTRACE_SAMPLES", 1);
+  if (samples != 1 && samples != 2 && samples != 4 && samples != 8) {
+    std::cerr << "CUTRACE_SAMPLES must be 1, 2, 4 or 8\n";
+    ctr_host_scene_free(hs);
+    return -4;
+  }
   long n_dev = env_long("CUTRACE_DEVICES", 1);
   std::vector<int> devs;
   if (const char *list = getenv("CUTRACE_DEVICE_LIST")) {  // explicit list, e.g. "0,2,4,6" (or "0,0": rehearsal on one GPU)
@@ -65,6 +72,11 @@ int main(int argc, const char **argv) {
     n_dev = (long)devs.size();
   } else {
     for (long i = 0; i < n_dev; i++) devs.push_back((int)i);
+  }
+  if (n_dev > 1 && samples != 1) {
+    std::cerr << "CUTRACE_SAMPLES applies to one device only (CUTRACE_DEVICES / CUTRACE_DEVICE_LIST name " << n_dev << ")\n";
+    ctr_host_scene_free(hs);
+    return -4;
   }
   if (n_dev > 1) {
     ctr_multi *group = nullptr;
@@ -103,7 +115,7 @@ int main(int argc, const char **argv) {
   cutrace::grid<cutrace::vector> normal_map;
   size_t render, total;
   cutrace::gpu::render(scene, (size_t)env_long("CUTRACE_BOUNCES", 5), 1e-3, max_d, depth_map, color_map, normal_map,
-                       render, total);
+                       render, total, (uint32_t)samples);
 
   std::cout << "Render time was " << render << " ms; kernel time with setup/teardown was " << total << " ms.\n";
 

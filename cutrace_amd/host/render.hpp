@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cstddef>
 
+#include "cutrace_aa.h"
 #include "cutrace_amd.h"
 #include "grid.hpp"
 
@@ -44,14 +45,16 @@ inline void adopt_frame(uint64_t w, uint64_t h, grid<float> &depth_map, grid<vec
   }
 }
 
+// samples: 1 (the reference's frame), or 2, 4, 8 rays per axis and pixel averaged in the kernel (ctr_render_aa, cutrace_aa.h)
 inline void render(ctr_scene *scene, size_t bounces, float fudge, float &max, grid<float> &depth_map,
-                   grid<vector> &color_map, grid<vector> &normal_map, size_t &render_ms, size_t &total_ms) {
+                   grid<vector> &color_map, grid<vector> &normal_map, size_t &render_ms, size_t &total_ms, uint32_t samples = 1) {
   auto start = std::chrono::high_resolution_clock::now();
   uint64_t w = 0, h = 0;
   ctr_scene_size(scene, &w, &h);
   adopt_frame(w, h, depth_map, color_map, normal_map);
   ctr_render_stats st{};
-  ctr_render(scene, fudge, (int)bounces, nullptr, depth_map.data(), &color_map.data()->x, &normal_map.data()->x, &st);
+  if (samples > 1) ctr_render_aa(scene, fudge, (int)bounces, samples, nullptr, depth_map.data(), &color_map.data()->x, &normal_map.data()->x, &st);
+  else ctr_render(scene, fudge, (int)bounces, nullptr, depth_map.data(), &color_map.data()->x, &normal_map.data()->x, &st);
   max = st.max_depth;       // kernel.hpp:120-125 (reduced on the GPU instead of a host scan)
   auto end = std::chrono::high_resolution_clock::now();
   render_ms = (size_t)st.kernel_ms;
