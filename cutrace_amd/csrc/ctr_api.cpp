@@ -222,6 +222,10 @@ void use_merged_tree(const ctr_scene *s, RenderLaunch &L) {
     L.variant |= KV_MERGE;
     L.tlas_root = BVH_LEAF_FLAG | s->flat.n_mesh;
   }
+  // the scene head of THIS launch (scene_device.h DSceneHead), from the host copy the device arrays mirror: made here, per
+  // launch, because the top-level root is final only now, and so that no edit of the arrays (guard selection, merged
+  // tree, cameras) can leave a stale one behind
+  if (!s->no_scene_head) fill_scene_head(s->flat, L.tlas_root, L.head);
 }
 
 // Attach the tile-order buffers to a launch: use the stored order when the launch has the shape the
@@ -521,6 +525,7 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   auto *s = new ctr_scene();
   s->device = device;
   s->cam = to_dcam(d->cam);
+  if (const char *e = getenv("CUTRACE_NO_SCENE_HEAD")) s->no_scene_head = atoi(e) != 0;  // A/B and tests: every record by pointer
 
   hipError_t er = hipSuccess;
   for (const SceneArray &a : scene_arrays(s, F)) {

@@ -52,6 +52,7 @@ struct ctr_scene {
   DCam *d_cams = nullptr;     // device camera array (>= 1 entry)
   uint32_t n_cams = 0;
   uint32_t user_variant = CTR_VAR_AUTO;
+  bool no_scene_head = false;  // CUTRACE_NO_SCENE_HEAD=1 when the handle was created: launches carry an empty scene head
   // cached device outputs for the host-buffer form: ONE allocation, a call's buffers are its consecutive
   // parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
   float *d_out = nullptr;

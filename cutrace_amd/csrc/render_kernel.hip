@@ -291,7 +291,8 @@ struct KArgs {
   // hot block, the first 32 bytes: what every cast needs before it reaches a mesh — fetched with ONE s_load_dwordx8 at
   // the head of the trip instead of five dependent scalar loads spread over it (each a round trip the wave waits for)
   const CADDR DPlanePair *planes;
-  uint32_t n_plane_recs, n_axis_recs, n_oloop, n_mesh, tlas_root, has_mesh;
+  uint32_t n_plane_recs, n_axis_recs, n_oloop, n_mesh, tlas_root, has_mesh;  // has_mesh: bit 0 = the scene has a mesh, bit 1 = `head` holds the axis triple;
+                                                                             // tlas_root: | CTR_TL_HEAD_FLAG when `head` holds that leaf's mesh record
   // cold block, the next 48 bytes: what the continuation needs, fetched together at its start
   const CADDR DObj *objs;      // every object in scene order (hit records)
   const CADDR float *gnorm;
@@ -323,6 +324,11 @@ struct KArgs {
   uint32_t *group_done;
   float *uv_out;      // KV_UV: texture coordinates of the primary hit, 2 floats per pixel
   uint32_t ss_log2;   // KV_SS: log2 of the samples per axis (1, 2 or 3); w, h and rows are those of the s*w x s*h sample frame
+  // "Scene head" (scene_device.h DSceneHead): the first plane triple and the first mesh record INSIDE the argument block.
+  // Their address is kernarg base + constant, so the planes are requested in the same burst as the hot block (one
+  // scalar round trip at the head of a cast, not two dependent ones) and the mesh record without fetching `meshes`
+  // first.  Only scalar loads read it, like the rest of the kernarg segment.
+  DSceneHead head;
 };
 
 static_assert(offsetof(KArgs, planes) == 0 && offsetof(KArgs, has_mesh) == 28, "KArgs: the hot block is the first eight dwords");
@@ -337,7 +343,7 @@ struct KParams {
   float *depth_out, *color_out, *normal_out;
   unsigned long long *counters;
 };
-static_assert(sizeof(KArgs) % 8 == 0 && offsetof(KParams, depth_out) == sizeof(KArgs), "KParams mirrors the kernel's parameter list");
+static_assert(sizeof(KArgs) % 64 == 0 && offsetof(KArgs, head) % 64 == 0 && offsetof(KParams, depth_out) == sizeof(KArgs), "KParams mirrors the kernel's parameter list; the scene head lies on 64-byte lines");
 
 // ---- Host delivery ----
 // ctr_render hands the kernel page-locked HOST buffers.  Storing the pixels there tile by tile works (the memory is
@@ -548,7 +554,13 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     const u32x8 hot = *(const CADDR u32x8 *)AK;  // KArgs' hot block
     const CADDR DPlanePair *const k_planes = (const CADDR DPlanePair *)(((uint64_t)hot[1] << 32) | hot[0]);
     const uint32_t k_plane_recs = hot[2], k_axis_recs = hot[3], k_n_oloop = hot[4], k_mesh = hot[5], k_tlas_root = hot[6];
-    const bool k_has_mesh = hot[7] != 0u;
+    const bool k_has_mesh = (hot[7] & 1u) != 0u;
+    // the scene head's axis triple, requested with the hot block whether it is filled or not (hot[7] says; constant addresses)
+    typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const u32x16 hd_ax = *(const CADDR u32x16 *)&AK->head.ax[0][0];  // ax[0..5], ax_index[0..3]
+    const u32x2 hd_ix = *(const CADDR u32x2 *)&AK->head.ax_index[4];
+    const bool k_head_axis = (hot[7] & 2u) != 0u;
     TSTAMP(t_trip0);
     CTR_MARK(1);  // trip head: cast set-up
     typedef unsigned long long mask_t;
@@ -687,13 +699,48 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         const float chk = __builtin_fmaf(ro.x, 4.0f, __builtin_fmaf(ro.y, 4.0f, __builtin_fmaf(ro.z, 4.0f, (rd.x + rd.y) + rd.z))) * 0.0f;
         axis_fast = (alive_m & ~FCMP(chk, 0.0f, FC_OEQ)) == 0ull;
       }
-      for (uint32_t p = 0; p < n_recs;) {
+      // the six slots of a triple, in scene order; false: every lane has retired (any-hit)
+      // (a slot without a plane: CTR_PLANE_PAD; IGNTR: tr.. != 0 = a plane whose material is transparent does not exist for this cast)
+      auto triple_tests = [&](uint32_t i00, uint32_t i01, uint32_t i10, uint32_t i11, uint32_t i20, uint32_t i21, float2_ num0, float2_ den0,
+                              float2_ num1, float2_ den1, float2_ num2, float2_ den2, uint32_t tr00, uint32_t tr01, uint32_t tr10,
+                              uint32_t tr11, uint32_t tr20, uint32_t tr21) -> bool {
+        if (i00 != CTR_PLANE_PAD && !(IGNTR && ign_now && tr00)) { if (!plane_test(i00, num0.x, den0.x, SITE(0))) return false; }
+        if (i01 != CTR_PLANE_PAD && !(IGNTR && ign_now && tr01)) { if (!plane_test(i01, num0.y, den0.y, SITE(1))) return false; }
+        if (i10 != CTR_PLANE_PAD && !(IGNTR && ign_now && tr10)) { if (!plane_test(i10, num1.x, den1.x, SITE(2))) return false; }
+        if (i11 != CTR_PLANE_PAD && !(IGNTR && ign_now && tr11)) { if (!plane_test(i11, num1.y, den1.y, SITE(3))) return false; }
+        if (i20 != CTR_PLANE_PAD && !(IGNTR && ign_now && tr20)) { if (!plane_test(i20, num2.x, den2.x, SITE(4))) return false; }
+        if (i21 != CTR_PLANE_PAD && !(IGNTR && ign_now && tr21)) { if (!plane_test(i21, num2.y, den2.y, SITE(5))) return false; }
+        return true;
+      };
+      uint32_t p = 0;
+      bool more = true;  // wave-uniform
+      // the scene head's axis triple first, as code of its own: inside the loop its values would be loop-invariant inputs of a
+      // merge with the pointer path's (register copies per cast, and 13 VGPRs more in the builds without a mesh walk)
+      if (k_head_axis && axis_fast) {
+        CTR_MARK(59);  // the axis triple of the scene head: the same twelve floats and six indices, already here
+        auto pr = [&](int k) -> float2_ { const float2_ v = {__uint_as_float(hd_ax[2 * k]), __uint_as_float(hd_ax[2 * k + 1])}; return v; };
+        const float2_ nx = pr(1), ny = pr(3), nz = pr(5);
+        uint32_t tr00 = 0u, tr01 = 0u, tr10 = 0u, tr11 = 0u, tr20 = 0u, tr21 = 0u;
+        if (IGNTR && ign_now) {
+          tr00 = AK->head.ax_transparent[0]; tr01 = AK->head.ax_transparent[1]; tr10 = AK->head.ax_transparent[2];
+          tr11 = AK->head.ax_transparent[3]; tr20 = AK->head.ax_transparent[4]; tr21 = AK->head.ax_transparent[5];
+        }
+        p = 3u;
+        more = triple_tests(hd_ax[12], hd_ax[13], hd_ax[14], hd_ax[15], hd_ix[0], hd_ix[1], (pr(0) - rox) * nx, rdx * nx, (pr(2) - roy) * ny,
+                            rdy * ny, (pr(4) - roz) * nz, rdz * nz, tr00, tr01, tr10, tr11, tr20, tr21);
+      }
+      while (more && p < n_recs) {
         if (n_recs - p >= 3u) {
-          const CADDR DPlanePair &P0 = k_planes[p], &P1 = k_planes[p + 1], &P2 = k_planes[p + 2];
           float2_ num0, den0, num1, den1, num2, den2;
+          uint32_t i00, i01, i10, i11, i20, i21;
+          uint32_t tr00 = 0u, tr01 = 0u, tr10 = 0u, tr11 = 0u, tr20 = 0u, tr21 = 0u;  // IGNTR: the slots' transparency words
+          const CADDR DPlanePair &P0 = k_planes[p], &P1 = k_planes[p + 1], &P2 = k_planes[p + 2];
           // (indices first: their loads then travel with the coordinates', one round trip for the triple)
-          const uint32_t i00 = P0.index[0], i01 = P0.index[1], i10 = P1.index[0], i11 = P1.index[1], i20 = P2.index[0],
-                         i21 = P2.index[1];
+          i00 = P0.index[0]; i01 = P0.index[1]; i10 = P1.index[0]; i11 = P1.index[1]; i20 = P2.index[0]; i21 = P2.index[1];
+          if (IGNTR && ign_now) {
+            tr00 = P0.transparent[0]; tr01 = P0.transparent[1]; tr10 = P1.transparent[0];
+            tr11 = P1.transparent[1]; tr20 = P2.transparent[0]; tr21 = P2.transparent[1];
+          }
           if (p < n_axis && axis_fast) {
             CTR_MARK(5);  // an axis triple
             const float2_ nx = ldpair(P0.n[0]), ny = ldpair(P1.n[1]), nz = ldpair(P2.n[2]);
@@ -707,14 +754,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
             num_den(P2, num2, den2);
           }
           p += 3;
-          // (a slot without a plane: CTR_PLANE_PAD)
-          // (a slot without a plane: CTR_PLANE_PAD; IGNTR: a plane whose material is transparent does not exist for this cast)
-          if (i00 != CTR_PLANE_PAD && !(IGNTR && ign_now && P0.transparent[0])) { if (!plane_test(i00, num0.x, den0.x, SITE(0))) break; }
-          if (i01 != CTR_PLANE_PAD && !(IGNTR && ign_now && P0.transparent[1])) { if (!plane_test(i01, num0.y, den0.y, SITE(1))) break; }
-          if (i10 != CTR_PLANE_PAD && !(IGNTR && ign_now && P1.transparent[0])) { if (!plane_test(i10, num1.x, den1.x, SITE(2))) break; }
-          if (i11 != CTR_PLANE_PAD && !(IGNTR && ign_now && P1.transparent[1])) { if (!plane_test(i11, num1.y, den1.y, SITE(3))) break; }
-          if (i20 != CTR_PLANE_PAD && !(IGNTR && ign_now && P2.transparent[0])) { if (!plane_test(i20, num2.x, den2.x, SITE(4))) break; }
-          if (i21 != CTR_PLANE_PAD && !(IGNTR && ign_now && P2.transparent[1])) { if (!plane_test(i21, num2.y, den2.y, SITE(5))) break; }
+          if (!triple_tests(i00, i01, i10, i11, i20, i21, num0, den0, num1, den1, num2, den2, tr00, tr01, tr10, tr11, tr20, tr21)) break;
         } else {
           const CADDR DPlanePair &P0 = k_planes[p];
           CTR_MARK(7);  // one plane record
@@ -929,7 +969,11 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         }
         CTR_MARK(16);
         if (t_pend == TL_NONE) break;
-        const CADDR DObj &O = AK->meshes[t_pend & 0xFFFFFFu];
+        // (the leaf the scene head holds: its record lies at a constant address of the argument block — no `meshes` to fetch first)
+        const CADDR DObj *o_rec;
+        if (t_pend & CTR_TL_HEAD_FLAG) o_rec = &AK->head.mesh;
+        else o_rec = &AK->meshes[t_pend & 0xFFFFFFu];
+        const CADDR DObj &O = *o_rec;
         // advance first, so that `continue` below moves on to the next mesh
         if (t_sp != 0u) {
           t_sp--;
@@ -2167,7 +2211,11 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
   A.oloop = (const CADDR DObj *)L.oloop;
   A.meshes = (const CADDR DObj *)L.meshes;
   A.n_mesh = L.n_mesh;
-  A.tlas_root = L.tlas_root;
+  // "Scene head": the flags ride in words of the hot block the trip head has anyway
+  A.head = L.head;
+  const bool head_mesh = L.head.n_mesh == 1u && (L.tlas_root & BVH_LEAF_FLAG) && L.n_mesh != 0u;
+  const bool head_axis = L.head.n_axis_recs == 3u && L.n_axis_recs >= 3u && L.n_plane_recs >= 3u;
+  A.tlas_root = L.tlas_root | (head_mesh ? CTR_TL_HEAD_FLAG : 0u);
   A.tlas_root2 = L.tlas_root_regular;
   A.tlas_begin = L.tlas_begin;
   for (int q = 0; q < 3; q++) { A.tl_mn[q] = L.tl_mn[q]; A.tl_mx[q] = L.tl_mx[q]; }
@@ -2192,7 +2240,7 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
   A.rows = L.rows;
   A.fudge = L.fudge;
   A.bounces = L.bounces;
-  A.has_mesh = L.has_mesh;
+  A.has_mesh = (L.has_mesh ? 1u : 0u) | (head_axis ? 2u : 0u);
   A.nf = L.need_cold_frames ? 10u : 4u;
   A.frames = (uint32_t)((L.bounces > 0 && L.any_bounce) ? L.bounces : 1);
   A.order = (const CADDR uint32_t *)L.order;

@@ -25,6 +25,7 @@
 #ifndef CUTRACE_AMD_SCENE_DEVICE_H
 #define CUTRACE_AMD_SCENE_DEVICE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 struct DTri {
@@ -132,6 +133,32 @@ struct DRows {
   uint32_t first_block; // index of the first selected block
 };
 
+// The scene head: a fixed-size copy of the records EVERY cast starts with, carried inside the kernel-argument block
+// (render_kernel.hip KArgs).  The kernel reads the scene arrays by pointer chasing — argument block -> array pointer -> record,
+// two dependent scalar round trips — although neither the addresses nor the records change during a launch; a record
+// in the argument block has a constant address (kernarg base + offset), so it is requested together with the
+// arguments themselves.  Filled on the host from the flat scene for every launch (scene_flatten.h fill_scene_head), so it
+// always mirrors the arrays the launch walks; beyond its capacity the kernel takes the pointer path, on the same
+// records, so nothing changes bit for bit.
+//   axis triple : of planes[0..2], when those are an axis triple (n_axis_recs >= 3), exactly what the axis fast path
+//                 reads — per record the one point / normal pair that is not multiplied by zero, in the pair order of
+//                 the packed instructions, then the six index words: one 16-dword request and one of 2 dwords where
+//                 the records themselves take nine.  The general (non-axis) evaluation keeps reading full records.
+//   mesh        : the record the top-level walk starts with when tlas_root is a leaf: the scene's only mesh, or the
+//                 merged pseudo mesh (CTR_VAR_MERGE).  Second and later meshes, and every mesh of a top-level tree
+//                 with inner nodes, are read from meshes[].
+struct alignas(64) DSceneHead {
+  float ax[6][2];              // planes[0].p[0], planes[0].n[0], planes[1].p[1], planes[1].n[1], planes[2].p[2], planes[2].n[2]
+  uint32_t ax_index[6];        // planes[0].index[0..1], planes[1].index[0..1], planes[2].index[0..1]
+  uint32_t ax_transparent[6];  // the same of .transparent (KV_IGNTR only)
+  uint32_t n_axis_recs;        // plane records the triple stands for: 3, or 0 = not filled
+  uint32_t n_mesh;             // 1: `mesh` is meshes[tlas_root & 0xFFFFFF], 0 = not filled
+  uint32_t pad[6];
+  DObj mesh;
+};
+static_assert(sizeof(DSceneHead) == 192 && offsetof(DSceneHead, mesh) == 128, "DSceneHead: two 64-byte lines of planes, one of mesh");
+#define CTR_TL_HEAD_FLAG 0x40000000u  /* kernel-side only: the top-level leaf whose record is DSceneHead::mesh */
+
 struct RenderLaunch {
   const DObj *objs;        // every object, scene order (hit records)
   const DObj *oloop;       // spheres and stand-alone triangles, scene order (sequential loop)
@@ -182,6 +209,7 @@ struct RenderLaunch {
   // rows above are then those of the s*w x s*h SAMPLE frame (every one a multiple of s); depth / color / normal hold the
   // (rows.n_rows / s) x (w / s) output pixels.  0: a plain launch.
   uint32_t ss_log2;
+  DSceneHead head;  // "scene head" above; all zero = every record by pointer
 };
 uint64_t ctr_staging_pixels(const RenderLaunch &L);
 uint64_t ctr_staging_groups(const RenderLaunch &L);

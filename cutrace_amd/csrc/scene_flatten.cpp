@@ -447,3 +447,22 @@ std::vector<DirtyRange> build_merged_tree(FlatScene &F) {
           {DirtyRange::NODES4, M.node_begin, M.node_count, {}},
           {DirtyRange::MESHES, F.n_mesh, 1, {}}};
 }
+
+void fill_scene_head(const FlatScene &F, uint32_t tlas_root, DSceneHead &H) {
+  H = DSceneHead{};
+  if (F.n_axis_recs >= 3u && F.planes.size() >= 3u) {
+    for (int r = 0; r < 3; r++)
+      for (int k = 0; k < 2; k++) {
+        H.ax[2 * r][k] = F.planes[r].p[r][k];
+        H.ax[2 * r + 1][k] = F.planes[r].n[r][k];
+        H.ax_index[2 * r + k] = F.planes[r].index[k];
+        H.ax_transparent[2 * r + k] = F.planes[r].transparent[k];
+      }
+    H.n_axis_recs = 3u;
+  }
+  const uint32_t leaf = tlas_root & 0xFFFFFFu;
+  if (F.n_mesh != 0u && (tlas_root & BVH_LEAF_FLAG) && leaf < F.meshes.size()) {
+    H.mesh = F.meshes[leaf];
+    H.n_mesh = 1u;
+  }
+}

@@ -99,6 +99,10 @@ int flatten_scene(const ctr_scene_desc &d, FlatScene &F, std::string &err);
 // ranges it filled; none when there is nothing to build (not reserved, built already, or the tree outgrew its room).
 std::vector<DirtyRange> build_merged_tree(FlatScene &F);
 
+// The scene head of a launch whose top-level walk starts at `tlas_root` (scene_device.h DSceneHead): copies of planes[0..2]
+// and of the mesh record behind a leaf root, as far as the scene has them; everything else zero.
+void fill_scene_head(const FlatScene &F, uint32_t tlas_root, DSceneHead &H);
+
 // a node whose four slots are empty: a far-away point box and a leaf of no triangles each
 DNode4 empty_node4();
 // slot `c` of `N` gets a box that every ray passes
