@@ -284,6 +284,13 @@ class DeviceScene:
         _lib.hip_lib().ctr_last_counters(self._h, out.ctypes.data)
         return out
 
+    def last_kernel(self):
+        """The build (KV_* bits) of the handle's most recent launch (ctr_debug_last_kernel)."""
+        kv = C.c_uint32()
+        if _lib.hip_lib().ctr_debug_last_kernel(self._h, C.byref(kv)):
+            raise RuntimeError("ctr_debug_last_kernel failed")
+        return int(kv.value)
+
     @staticmethod
     def lane_stats(reset=True):
         """Live-lane statistics of the VAR_STATS launches since the last reset (ctr_debug_lane_stats), decoded."""

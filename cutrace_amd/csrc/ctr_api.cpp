@@ -20,6 +20,7 @@
 #include "cutrace_aa.h"
 #include "cutrace_amd.h"
 #include "guard.h"
+#include "kernel_choice.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
 
@@ -77,21 +78,6 @@ void ctr_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
 uint64_t ctr_scene::occ6_min_tris() {
   static const uint64_t v = [] { const char *e = getenv("CUTRACE_OCC6_MIN_TRIS"); return e ? (uint64_t)atoll(e) : (uint64_t)CTR_OCC6_MIN_TRIS; }();
   return v;
-}
-
-uint32_t ctr_scene::kernel_variant(bool count) const {
-  uint32_t kv = 0;
-  if (!(user_variant & CTR_VAR_NO_PREFILTER)) kv |= KV_PREFILTER;
-  // shadow any-hit is result-identical only when every material is exactly opaque
-  // (SURVEY §8(a) row a9); with any transparency the ordered nearest-hit loop is kept
-  if (flat.all_opaque && !(user_variant & CTR_VAR_NO_ANYHIT) && !count) kv |= KV_ANYHIT;
-  if (!(user_variant & CTR_VAR_NO_CLUSTER) && !count) kv |= KV_BVH;
-  if (!(user_variant & CTR_VAR_EXACT_POW)) kv |= KV_FASTPOW;
-  // meshes of CTR_OCC6_MIN_TRIS triangles and more: the build for 6 waves per SIMD (render_kernel.hip KV_OCC6)
-  if (flat.mesh_tris >= occ6_min_tris() && !(user_variant & CTR_VAR_NO_OCC6)) kv |= KV_OCC6;
-  if (user_variant & CTR_VAR_STATS) kv = KV_STATS | (flat.all_opaque && !(user_variant & CTR_VAR_NO_ANYHIT) ? KV_ANYHIT : 0u);
-  if (count) kv = KV_PREFILTER | KV_COUNT;  // the counting launch walks like the reference (and wins over STATS)
-  return kv;
 }
 
 namespace {
@@ -183,7 +169,7 @@ void fill_launch(const ctr_scene *s, RenderLaunch &L) {
   L.oloop = s->d_oloop;
   L.meshes = s->d_meshes;
   L.n_mesh = F.n_mesh;
-  L.tlas_root = F.tlas_root;          // (use_merged_tree, once the launch's variant is known, may put the merged tree here)
+  L.tlas_root = F.tlas_root;          // (set_root_and_head, once the launch's build is known, may put the merged tree here)
   L.tlas_root_regular = F.tlas_root;
   L.tlas_begin = F.tlas_begin;
   for (int q = 0; q < 3; q++) { L.tl_mn[q] = F.tl_mn[q]; L.tl_mx[q] = F.tl_mx[q]; }
@@ -212,16 +198,18 @@ void fill_launch(const ctr_scene *s, RenderLaunch &L) {
   L.frame_stride_px = 0;
 }
 
-// The merged tree (CTR_VAR_MERGE) when the scene has one and nothing speaks against it (scene_flatten.h Merged): a BVH walk of
-// the shipped kind, frame leaving through device buffers.  The top-level tree over the meshes stays the fallback the kernel
-// itself takes for a cast the merged walk cannot decide (render_kernel.hip "merged walk").
-void use_merged_tree(const ctr_scene *s, RenderLaunch &L) {
-  const bool bvh_walk = (L.variant & (KV_BVH | KV_STATS)) && !(L.variant & (KV_COUNT | KV_UV | KV_SS));
-  if ((s->user_variant & CTR_VAR_MERGE) && s->flat.merged.built && s->flat.merged.usable && bvh_walk && !L.group_done &&
-      (L.variant & KV_PREFILTER || (L.variant & KV_STATS))) {
-    L.variant |= KV_MERGE;
-    L.tlas_root = BVH_LEAF_FLAG | s->flat.n_mesh;
-  }
+// What choose_kernel (kernel_choice.h) is told about this handle, the entry point and the call.
+KernelFacts kernel_facts(const ctr_scene *s, KernelEntry entry, int bounces, bool deliverable) {
+  const FlatScene &F = s->flat;
+  return {s->user_variant, F.all_opaque, F.mesh_tris >= ctr_scene::occ6_min_tris(), F.merged.built && F.merged.usable, entry, deliverable,
+          stack_shape(bounces, F.any_bounce, F.need_cold)};
+}
+
+// The launch's top-level root and scene head.  A build that walks the merged tree (scene_flatten.h Merged) starts at the merged
+// pseudo mesh; the top-level tree over the meshes stays the fallback the kernel itself takes for a cast the merged walk
+// cannot decide (render_kernel.hip "merged walk").
+void set_root_and_head(const ctr_scene *s, RenderLaunch &L, bool merged) {
+  if (merged) L.tlas_root = BVH_LEAF_FLAG | s->flat.n_mesh;
   // the scene head of THIS launch (scene_device.h DSceneHead), from the host copy the device arrays mirror: made here, per
   // launch, because the top-level root is final only now, and so that no edit of the arrays (guard selection, merged
   // tree, cameras) can leave a stale one behind
@@ -334,12 +322,12 @@ int check_args(const ctr_scene *s, int bounces) {
 
 // ---- supersampling (include/cutrace_aa.h) ----
 // `samples` as log2, or why the handle cannot make the call; nothing here touches the GPU
-int aa_check(const ctr_scene *s, uint32_t samples, uint32_t &ls) {
+int aa_check(const ctr_scene *s, KernelEntry entry, uint32_t samples, uint32_t &ls) {
   if (samples != 1 && samples != 2 && samples != 4 && samples != 8)
     return fail(CTR_E_INVALID, "samples must be 1, 2, 4 or 8 per axis, got " + std::to_string(samples));
   ls = samples == 8 ? 3u : samples == 4 ? 2u : samples == 2 ? 1u : 0u;
   if (!ls) return CTR_OK;
-  if (s->user_variant & (CTR_VAR_STATS | CTR_VAR_IGNORE_TRANSPARENT | CTR_VAR_NO_PREFILTER | CTR_VAR_NO_CLUSTER))
+  if (choose_kernel(kernel_facts(s, entry, 0, false)).reject == KR_SS)
     return fail(CTR_E_INVALID, "supersampling: no build for CTR_VAR_STATS, CTR_VAR_IGNORE_TRANSPARENT, CTR_VAR_NO_PREFILTER or CTR_VAR_NO_CLUSTER");
   if (((uint64_t)s->cam.w << ls) > 0xFFFFFFFFull || ((uint64_t)s->cam.h << ls) > 0xFFFFFFFFull)
     return fail(CTR_E_INVALID, "supersampling: samples x width or samples x height exceeds 32 bits");
@@ -357,26 +345,24 @@ int aa_scale(RenderLaunch &L, uint32_t ls) {
   return CTR_OK;
 }
 // the checks of both entry points, in the order the header lists them
-int aa_precheck(ctr_scene *s, int bounces, uint32_t samples, const ctr_rows *rows, uint32_t &ls) {
+int aa_precheck(ctr_scene *s, KernelEntry entry, int bounces, uint32_t samples, const ctr_rows *rows, uint32_t &ls) {
   int st = check_args(s, bounces);
-  if (st || (st = aa_check(s, samples, ls)) || !ls) return st;
+  if (st || (st = aa_check(s, entry, samples, ls)) || !ls) return st;
   RenderLaunch L{};
   L.w = s->cam.w; L.h = s->cam.h; L.n_frames = 1;
   if ((st = make_rows(s, rows, L.rows))) return st;
   return aa_scale(L, ls);
 }
 
-// the caller's buffers of a host-form render; direct_delivery: the same buffers as the device sees them
+// the caller's buffers of a host-form render; device_visible: the same buffers as the device sees them
 struct HostFrame { float *depth, *color3, *normal3, *uv2; };
 
 // Page-locked destinations (ctr_frame_alloc, hipHostMalloc, mapped hipHostRegister) are visible to the device:
 // the kernel then delivers the frame ITSELF, group of tiles by group of tiles while it renders (render_kernel.hip
 // "Host delivery"), so the 28 bytes per pixel cross PCIe underneath the rendering instead of in a DMA after it.
 // Any other destination: device buffers + copies (copy_out).
-bool direct_delivery(const ctr_scene *s, const HostFrame &o, size_t px, bool count, HostFrame &z) {
-  const bool merge_wanted = (s->user_variant & CTR_VAR_MERGE) && s->flat.merged.built && s->flat.merged.usable;  // (no delivering build of it)
-  return px && o.depth && o.color3 && o.normal3 && !count && !o.uv2 && !(s->user_variant & (CTR_VAR_NO_DIRECT | CTR_VAR_STATS | CTR_VAR_IGNORE_TRANSPARENT)) && !merge_wanted &&
-         ctr_host_delivery_available(s->kernel_variant(false)) &&
+bool device_visible(const HostFrame &o, size_t px, HostFrame &z) {
+  return px && o.depth && o.color3 && o.normal3 &&
          is_pinned(o.depth) && is_pinned(o.depth + px - 1) && is_pinned(o.color3) && is_pinned(o.color3 + 3 * px - 1) &&
          is_pinned(o.normal3) && is_pinned(o.normal3 + 3 * px - 1) && device_view(o.depth, &z.depth) &&
          device_view(o.color3, &z.color3) && device_view(o.normal3, &z.normal3);
@@ -642,7 +628,8 @@ static int render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows 
   int st = check_args(s, bounces);
   if (st) return st;
   if (!d_depth || !d_color3 || !d_normal3) return fail(CTR_E_INVALID, "null output buffer");
-  if (s->user_variant & CTR_VAR_IGNORE_TRANSPARENT) return fail(CTR_E_INVALID, "CTR_VAR_IGNORE_TRANSPARENT: host-buffer calls only (ctr_render, ctr_render_uv)");
+  const KernelChoice choice = choose_kernel(kernel_facts(s, ss_log2 ? KE_DEVICE_SS : KE_DEVICE, bounces, false));
+  if (choice.reject == KR_IGNTR_DEVICE) return fail(CTR_E_INVALID, "CTR_VAR_IGNORE_TRANSPARENT: host-buffer calls only (ctr_render, ctr_render_uv)");
   if (n_frames == 0 || first_frame >= s->n_cams || n_frames > s->n_cams - first_frame)
     return fail(CTR_E_INVALID, "frame range exceeds the cameras set with ctr_scene_set_cameras");
   if ((st = use_device(s))) return st;
@@ -673,15 +660,13 @@ static int render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows 
   L.color = (float *)d_color3;
   L.normal = (float *)d_normal3;
   L.counters = (unsigned long long *)d_counters;
-  L.variant = s->kernel_variant(false);
-  if (ss_log2) {
-    if ((st = aa_scale(L, ss_log2))) return st;
-    L.variant = (L.variant & (KV_ANYHIT | KV_FASTPOW | KV_OCC6)) | KV_PREFILTER | KV_BVH | KV_SS;
-  }
-  use_merged_tree(s, L);
+  L.variant = choice.kv;
+  if (ss_log2 && (st = aa_scale(L, ss_log2))) return st;
+  set_root_and_head(s, L, choice.merged);
   {
     std::lock_guard<std::mutex> lk(s->mtx);
     if ((st = attach_order(s, L, false))) return st;
+    s->last_kernel = L.variant;
   }
   int e = ctr_launch_render(L, hip_stream);
   if (e) return hip_fail((hipError_t)e, "render kernel launch");
@@ -698,7 +683,7 @@ int ctr_render_device_batch(ctr_scene *s, float fudge, int bounces, const ctr_ro
 int ctr_render_device_aa(ctr_scene *s, float fudge, int bounces, uint32_t samples, const ctr_rows *rows, void *d_depth,
                          void *d_color3, void *d_normal3, void *d_counters, void *hip_stream) {
   uint32_t ls = 0;
-  if (int st = aa_precheck(s, bounces, samples, rows, ls)) return st;
+  if (int st = aa_precheck(s, KE_DEVICE_SS, bounces, samples, rows, ls)) return st;
   return render_device(s, fudge, bounces, rows, 0, 1, 0, 0, d_depth, d_color3, d_normal3, d_counters, hip_stream, ls);
 }
 
@@ -721,22 +706,28 @@ static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *r
   const size_t px = (size_t)L.rows.n_rows * s->cam.w;
   HostFrame z{};
   if (ss_log2 && (st = aa_scale(L, ss_log2))) return st;
-  const bool direct = !ss_log2 && direct_delivery(s, out, px, count, z);  // (no delivering build of the supersampled kernel)
+  // an empty selection launches nothing and has no fourth output: it is chosen for as a plain render
+  KernelFacts facts = kernel_facts(s, count ? KE_COUNT : ss_log2 ? KE_HOST_SS : out.uv2 && px ? KE_UV : KE_HOST, bounces, true);
+  if (!px) facts.user &= ~CTR_VAR_IGNORE_TRANSPARENT;
+  KernelChoice choice = choose_kernel(facts);
+  // (the caller's buffers are looked at only where everything else allows delivery by the kernel)
+  if (choice.direct && !device_visible(out, px, z)) {
+    facts.deliverable = false;
+    choice = choose_kernel(facts);
+  }
+  const bool direct = choice.direct;
   const size_t spx = direct ? (size_t)ctr_staging_pixels(L) : (px ? px : 1);  // pixels per output buffer on the device
   L.fudge = fudge;
   L.bounces = bounces;
   if ((st = prepare_outputs(s, L, spx, direct ? &z : nullptr))) return st;
   L.counters = s->d_counters;
-  L.variant = s->kernel_variant(count);
-  if (ss_log2) L.variant = (L.variant & (KV_ANYHIT | KV_FASTPOW | KV_OCC6)) | KV_PREFILTER | KV_BVH | KV_SS;
-  const bool igntr = (s->user_variant & CTR_VAR_IGNORE_TRANSPARENT) != 0 && !count;
-  if ((out.uv2 || igntr) && px) {
-    if (count || (s->user_variant & CTR_VAR_STATS)) return fail(CTR_E_INVALID, "ctr_render_uv / CTR_VAR_IGNORE_TRANSPARENT: not with the counting / statistics variants");
+  if (choice.reject == KR_UV_STATS) return fail(CTR_E_INVALID, "ctr_render_uv / CTR_VAR_IGNORE_TRANSPARENT: not with the counting / statistics variants");
+  L.variant = s->last_kernel = choice.kv;
+  if (L.variant & KV_UV) {
     if ((st = grow(px, s->uv_px, {{(void **)&s->d_uv, 2 * sizeof(float), false}}))) return st;
     L.uv = s->d_uv;
-    L.variant = (L.variant & (KV_ANYHIT | KV_FASTPOW)) | KV_PREFILTER | KV_BVH | KV_UV | (igntr ? KV_IGNTR : 0u);
   }
-  use_merged_tree(s, L);
+  set_root_and_head(s, L, choice.merged);
   if ((st = attach_order(s, L, count))) return st;
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, 16 * sizeof(unsigned long long), nullptr));
   HIP_TRY(hipEventRecord(s->ev0, nullptr));
@@ -760,7 +751,7 @@ int ctr_render(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, flo
 int ctr_render_aa(ctr_scene *s, float fudge, int bounces, uint32_t samples, const ctr_rows *rows, float *depth, float *color3,
                   float *normal3, ctr_render_stats *stats) {
   uint32_t ls = 0;
-  if (int st = aa_precheck(s, bounces, samples, rows, ls)) return st;
+  if (int st = aa_precheck(s, KE_HOST_SS, bounces, samples, rows, ls)) return st;
   return render_host(s, fudge, bounces, rows, {depth, color3, normal3, nullptr}, stats, false, nullptr, ls);
 }
 
@@ -774,6 +765,13 @@ int ctr_debug_poison_next_order(ctr_scene *s) {
   if (!s) return fail(CTR_E_INVALID, "null scene");
   std::lock_guard<std::mutex> lk(s->mtx);
   s->poison_next_order = true;
+  return CTR_OK;
+}
+
+int ctr_debug_last_kernel(ctr_scene *s, uint32_t *kv) {
+  if (!s || !kv) return fail(CTR_E_INVALID, "ctr_debug_last_kernel: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  *kv = s->last_kernel;
   return CTR_OK;
 }
 

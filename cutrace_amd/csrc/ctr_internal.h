@@ -68,6 +68,7 @@ struct ctr_scene {
   uint32_t *h_groups = nullptr;  // page-locked landing zone of the counters (checked after every direct launch)
   size_t groups_cap = 0;
   bool poison_next_order = false;  // test hook (ctr_debug_poison_next_order)
+  uint32_t last_kernel = 0;        // the KV of the most recent launch (ctr_debug_last_kernel)
   // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling")
   uint32_t *d_cost = nullptr, *d_order = nullptr;
   uint32_t order_age = 0;  // launches of the current shape
@@ -79,8 +80,7 @@ struct ctr_scene {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::mutex mtx;
 
-  static uint64_t occ6_min_tris();            // CTR_OCC6_MIN_TRIS, or CUTRACE_OCC6_MIN_TRIS from the environment
-  uint32_t kernel_variant(bool count) const;  // the KV_* bits a launch of this scene gets (ctr_api.cpp)
+  static uint64_t occ6_min_tris();  // CTR_OCC6_MIN_TRIS, or CUTRACE_OCC6_MIN_TRIS from the environment
 };
 
 #endif

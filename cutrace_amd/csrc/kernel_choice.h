@@ -1,0 +1,92 @@
+// kernel_choice.h — which build of render_kernel<KV> a launch gets: the list of builds, the stack shape of a launch, and the
+// ONE function that knows which combination of caller's wishes, scene facts and entry point has a build.
+//
+// Host only, no HIP: ctr_api.cpp asks choose_kernel() and hands the answer to ctr_launch_render (render_kernel.hip), whose
+// switch is generated from the same list; scripts/kernel_choice_check.cpp prints the answer for the whole input space.
+#ifndef CUTRACE_AMD_KERNEL_CHOICE_H
+#define CUTRACE_AMD_KERNEL_CHOICE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "scene_device.h"
+
+// Every instantiation of render_kernel, once.  A family is a fixed set of bits plus the optional bits it honours; what a
+// family does not list it ignores (the shipped walk is KV_PREFILTER | KV_BVH).
+#define CTR_RENDER_KERNELS(X)                                                                                                  \
+  /* main walk: KV_PREFILTER, KV_ANYHIT, KV_BVH, KV_FASTPOW, each on or off */                                                 \
+  X(0u) X(KV_PREFILTER) X(KV_ANYHIT) X(KV_PREFILTER | KV_ANYHIT)                                                               \
+  X(KV_BVH) X(KV_BVH | KV_PREFILTER) X(KV_BVH | KV_ANYHIT) X(KV_BVH | KV_PREFILTER | KV_ANYHIT)                                \
+  X(KV_FASTPOW) X(KV_FASTPOW | KV_PREFILTER) X(KV_FASTPOW | KV_ANYHIT) X(KV_FASTPOW | KV_PREFILTER | KV_ANYHIT)                \
+  X(KV_FASTPOW | KV_BVH) X(KV_FASTPOW | KV_BVH | KV_PREFILTER) X(KV_FASTPOW | KV_BVH | KV_ANYHIT)                              \
+  X(KV_FASTPOW | KV_BVH | KV_PREFILTER | KV_ANYHIT)                                                                            \
+  /* 6-wave: the default variant only (shipped walk, any-hit, fast pow); no optional bit */                                    \
+  X(KV_OCC6 | KV_PREFILTER | KV_ANYHIT | KV_BVH | KV_FASTPOW)                                                                  \
+  /* host delivery: shipped walk, fast pow; honours KV_ANYHIT, and with it KV_OCC6 */                                          \
+  X(KV_PREFILTER | KV_BVH | KV_FASTPOW | KV_HOSTOUT) X(KV_PREFILTER | KV_BVH | KV_FASTPOW | KV_HOSTOUT | KV_ANYHIT)            \
+  X(KV_PREFILTER | KV_BVH | KV_FASTPOW | KV_HOSTOUT | KV_ANYHIT | KV_OCC6)                                                     \
+  /* STATS: shipped walk, fast pow; honours KV_ANYHIT */                                                                       \
+  X(KV_BVH | KV_PREFILTER | KV_FASTPOW | KV_STATS) X(KV_BVH | KV_PREFILTER | KV_ANYHIT | KV_FASTPOW | KV_STATS)                \
+  /* COUNT: the reference's walk with the prefilter; no optional bit */                                                        \
+  X(KV_PREFILTER | KV_COUNT)                                                                                                   \
+  /* UV: shipped walk; honours KV_ANYHIT, KV_FASTPOW */                                                                        \
+  X(KV_PREFILTER | KV_BVH | KV_UV) X(KV_PREFILTER | KV_BVH | KV_UV | KV_ANYHIT)                                                \
+  X(KV_PREFILTER | KV_BVH | KV_UV | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_UV | KV_FASTPOW | KV_ANYHIT)                      \
+  /* UV + IGNTR: as UV */                                                                                                      \
+  X(KV_PREFILTER | KV_BVH | KV_UV | KV_IGNTR) X(KV_PREFILTER | KV_BVH | KV_UV | KV_IGNTR | KV_ANYHIT)                          \
+  X(KV_PREFILTER | KV_BVH | KV_UV | KV_IGNTR | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_UV | KV_IGNTR | KV_FASTPOW | KV_ANYHIT) \
+  /* MERGE: shipped walk; honours KV_ANYHIT, KV_FASTPOW, with both KV_OCC6, and KV_STATS (then fast pow, no 6-wave) */         \
+  X(KV_PREFILTER | KV_BVH | KV_MERGE) X(KV_PREFILTER | KV_BVH | KV_MERGE | KV_ANYHIT)                                          \
+  X(KV_PREFILTER | KV_BVH | KV_MERGE | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_MERGE | KV_FASTPOW | KV_ANYHIT)                \
+  X(KV_PREFILTER | KV_BVH | KV_MERGE | KV_FASTPOW | KV_ANYHIT | KV_OCC6)                                                       \
+  X(KV_PREFILTER | KV_BVH | KV_MERGE | KV_FASTPOW | KV_STATS) X(KV_PREFILTER | KV_BVH | KV_MERGE | KV_ANYHIT | KV_FASTPOW | KV_STATS) \
+  /* SS: shipped walk; honours KV_ANYHIT, KV_FASTPOW, and with both KV_OCC6 */                                                 \
+  X(KV_PREFILTER | KV_BVH | KV_SS) X(KV_PREFILTER | KV_BVH | KV_SS | KV_ANYHIT)                                                \
+  X(KV_PREFILTER | KV_BVH | KV_SS | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_SS | KV_FASTPOW | KV_ANYHIT)                      \
+  X(KV_PREFILTER | KV_BVH | KV_SS | KV_FASTPOW | KV_ANYHIT | KV_OCC6)
+
+// The recursion stack of a launch: `frames` frames of `nf` floats per lane (render_kernel.hip KArgs::frames, ::nf).
+struct StackShape {
+  uint32_t frames, nf;
+  size_t bytes_per_wave() const { return (size_t)frames * nf * 64 * sizeof(float); }
+};
+// need_cold: some material both reflects and transmits; any_bounce: some material does either (only then does ray_color recurse)
+inline StackShape stack_shape(int bounces, bool any_bounce, bool need_cold) {
+  return {(uint32_t)((bounces > 0 && any_bounce) ? bounces : 1), need_cold ? 10u : 4u};
+}
+// The 6-waves-per-SIMD build parks 1280 bytes of shading state per wave in LDS (render_kernel PARK); LDS is handed out
+// in granules of 1280 bytes (160 KB / 128), and 24 waves per CU need at most 5 granules each: bounces <= 5 without cold frames
+inline bool occ6_fits(StackShape st) { return (st.bytes_per_wave() + 1280u + 1279u) / 1280u <= 5u; }
+
+enum KernelEntry {
+  KE_HOST,       // ctr_render
+  KE_COUNT,      // ctr_algorithmic_bytes
+  KE_UV,         // ctr_render_uv
+  KE_HOST_SS,    // ctr_render_aa
+  KE_DEVICE,     // ctr_render_device, ctr_render_device_batch
+  KE_DEVICE_SS,  // ctr_render_device_aa
+};
+enum KernelReject {
+  KR_NONE,
+  KR_SS,             // supersampling has no build for the caller's variant bits
+  KR_UV_STATS,       // the fourth output / ignore_transparent cast has no statistics build
+  KR_IGNTR_DEVICE,   // CTR_VAR_IGNORE_TRANSPARENT is for host-buffer calls
+};
+struct KernelFacts {
+  uint32_t user;        // CTR_VAR_* of the handle
+  bool all_opaque;      // every material exactly opaque: shadow any-hit is result-identical
+  bool big_mesh;        // mesh triangles >= ctr_scene::occ6_min_tris()
+  bool merged_usable;   // the merged tree is built and nothing speaks against walking it (scene_flatten.h Merged)
+  KernelEntry entry;
+  bool deliverable;     // KE_HOST: the caller's buffers are page-locked and visible to the device
+  StackShape stack;
+};
+struct KernelChoice {
+  uint32_t kv;          // the build, one of CTR_RENDER_KERNELS (reject == KR_NONE)
+  bool direct;          // the kernel delivers the frame to the caller's buffers itself (KV_HOSTOUT)
+  bool merged;          // the top-level root is the merged pseudo mesh (KV_MERGE)
+  KernelReject reject;
+};
+KernelChoice choose_kernel(const KernelFacts &f);
+
+#endif

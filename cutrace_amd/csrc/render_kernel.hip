@@ -67,6 +67,7 @@
 #include "cutrace_amd.h"
 #include "scene_device.h"
 #include "bvh.h"
+#include "kernel_choice.h"
 
 #define CADDR __attribute__((address_space(4)))
 #define BALLOT(p) __builtin_amdgcn_ballot_w64(p)
@@ -2241,8 +2242,9 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
   A.fudge = L.fudge;
   A.bounces = L.bounces;
   A.has_mesh = (L.has_mesh ? 1u : 0u) | (head_axis ? 2u : 0u);
-  A.nf = L.need_cold_frames ? 10u : 4u;
-  A.frames = (uint32_t)((L.bounces > 0 && L.any_bounce) ? L.bounces : 1);
+  const StackShape stack = stack_shape(L.bounces, L.any_bounce != 0, L.need_cold_frames != 0);
+  A.nf = stack.nf;
+  A.frames = stack.frames;
   A.order = (const CADDR uint32_t *)L.order;
   A.cost = L.cost;
   const bool host_delivery = (KV & KV_HOSTOUT) != 0;
@@ -2262,7 +2264,7 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
     if (L.ss_log2 > 3u || ((TW | TH) & m) || ((L.w | L.h | L.rows.n_rows | L.rows.row_begin | L.rows.row_end | L.rows.block_rows) & m) || L.n_frames != 1)
       return (int)hipErrorInvalidValue;
   }
-  size_t lds_bytes = (size_t)WAVES_PER_WG * A.frames * A.nf * 64 * sizeof(float);
+  size_t lds_bytes = (size_t)WAVES_PER_WG * stack.bytes_per_wave();
   if (KV & KV_OCC6) lds_bytes += (size_t)WAVES_PER_WG * 5 * 64 * sizeof(float);  // PARK
   // diagnostic only: extra dynamic LDS per workgroup caps the waves resident per CU (occupancy sweeps)
   if (const char *pad = getenv("CUTRACE_LDS_PAD")) lds_bytes += (size_t)atol(pad);
@@ -2285,20 +2287,6 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
                        reorder ? L.cost : nullptr, L.order_next, (uint32_t)waves,
                        host_delivery ? (L.w + TW - 1) / TW : 0u);
   return (int)hipGetLastError();
-}
-
-template <uint32_t BASE>
-int launch_main(const RenderLaunch &L, hipStream_t s) {
-  switch (L.variant & (KV_PREFILTER | KV_ANYHIT | KV_BVH)) {
-    case 0: return launch<BASE>(L, s);
-    case KV_PREFILTER: return launch<BASE | KV_PREFILTER>(L, s);
-    case KV_ANYHIT: return launch<BASE | KV_ANYHIT>(L, s);
-    case KV_PREFILTER | KV_ANYHIT: return launch<BASE | KV_PREFILTER | KV_ANYHIT>(L, s);
-    case KV_BVH: return launch<BASE | KV_BVH>(L, s);
-    case KV_BVH | KV_PREFILTER: return launch<BASE | KV_BVH | KV_PREFILTER>(L, s);
-    case KV_BVH | KV_ANYHIT: return launch<BASE | KV_BVH | KV_ANYHIT>(L, s);
-    default: return launch<BASE | KV_BVH | KV_PREFILTER | KV_ANYHIT>(L, s);
-  }
 }
 
 }  // namespace
@@ -2385,65 +2373,12 @@ uint64_t ctr_staging_index(const RenderLaunch &L, uint32_t x, uint32_t k_row) {
   return ((uint64_t)(k_row / TH) * tiles_x + x / TW) * 64u + (k_row % TH) * TW + x % TW;
 }
 
-// The 6-waves-per-SIMD build parks 1280 bytes of shading state per wave in LDS (render_kernel PARK); LDS is handed out
-// in granules of 1280 bytes (160 KB / 128), and 24 waves per CU need at most 5 granules each
-static bool occ6_fits(size_t stack_bytes) { return (stack_bytes + 1280u + 1279u) / 1280u <= 5u; }
-
-// Host delivery exists for the variants ctr_api.cpp picks by itself (not for the ablation / diagnostic builds)
-bool ctr_host_delivery_available(uint32_t variant) {
-  constexpr uint32_t DEF = KV_PREFILTER | KV_BVH | KV_FASTPOW;
-  return (variant & ~(KV_ANYHIT | KV_OCC6)) == DEF;
-}
-
+// L.variant is the build (kernel_choice.h choose_kernel decides; launch<KV> cross-checks the launch's buffers against it)
 int ctr_launch_render(const RenderLaunch &L, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (L.group_done) {
-    if (!ctr_host_delivery_available(L.variant)) return (int)hipErrorInvalidValue;
-    constexpr uint32_t DEF = KV_PREFILTER | KV_BVH | KV_FASTPOW | KV_HOSTOUT;
-    const size_t sb = (size_t)((L.bounces > 0 && L.any_bounce) ? L.bounces : 1) * (L.need_cold_frames ? 10u : 4u) * 64 * sizeof(float);
-    if (!(L.variant & KV_ANYHIT)) return launch<DEF>(L, s);
-    if ((L.variant & KV_OCC6) && occ6_fits(sb)) return launch<DEF | KV_ANYHIT | KV_OCC6>(L, s);
-    return launch<DEF | KV_ANYHIT>(L, s);
+  switch (L.variant) {
+#define X(kv) case (kv): return launch<(kv)>(L, (hipStream_t)stream);
+    CTR_RENDER_KERNELS(X)
+#undef X
+    default: return (int)hipErrorInvalidValue;
   }
-  if ((L.variant & (KV_UV | KV_IGNTR)) == (KV_UV | KV_IGNTR)) {  // ... with the kernel.hpp:52 cast ignoring transparent objects
-    constexpr uint32_t U = KV_PREFILTER | KV_BVH | KV_UV | KV_IGNTR;
-    if (L.variant & KV_FASTPOW) return (L.variant & KV_ANYHIT) ? launch<U | KV_FASTPOW | KV_ANYHIT>(L, s) : launch<U | KV_FASTPOW>(L, s);
-    return (L.variant & KV_ANYHIT) ? launch<U | KV_ANYHIT>(L, s) : launch<U>(L, s);
-  }
-  if (L.variant & KV_UV) {  // the fourth output: the shipped walk only (BVH + prefilter), any-hit and pow as the scene / caller say
-    constexpr uint32_t U = KV_PREFILTER | KV_BVH | KV_UV;
-    if (L.variant & KV_FASTPOW) return (L.variant & KV_ANYHIT) ? launch<U | KV_FASTPOW | KV_ANYHIT>(L, s) : launch<U | KV_FASTPOW>(L, s);
-    return (L.variant & KV_ANYHIT) ? launch<U | KV_ANYHIT>(L, s) : launch<U>(L, s);
-  }
-  if (L.variant & KV_SS) {  // the supersampled frame: the shipped walk only, as KV_UV; the 6-wave build where the plain render picks it
-    constexpr uint32_t U = KV_PREFILTER | KV_BVH | KV_SS;
-    const size_t sb = (size_t)((L.bounces > 0 && L.any_bounce) ? L.bounces : 1) * (L.need_cold_frames ? 10u : 4u) * 64 * sizeof(float);
-    if ((L.variant & (KV_OCC6 | KV_ANYHIT | KV_FASTPOW)) == (KV_OCC6 | KV_ANYHIT | KV_FASTPOW) && occ6_fits(sb))
-      return launch<U | KV_FASTPOW | KV_ANYHIT | KV_OCC6>(L, s);
-    if (L.variant & KV_FASTPOW) return (L.variant & KV_ANYHIT) ? launch<U | KV_FASTPOW | KV_ANYHIT>(L, s) : launch<U | KV_FASTPOW>(L, s);
-    return (L.variant & KV_ANYHIT) ? launch<U | KV_ANYHIT>(L, s) : launch<U>(L, s);
-  }
-  if (L.variant & KV_COUNT) return launch<KV_PREFILTER | KV_COUNT>(L, s);
-  if (L.variant & KV_MERGE) {
-    // the merged walk (CTR_VAR_MERGE, scenes with several meshes): the shipped walk's variants only
-    constexpr uint32_t M = KV_PREFILTER | KV_BVH | KV_MERGE;
-    const bool any = (L.variant & KV_ANYHIT) != 0;
-    if (L.variant & KV_STATS) return any ? launch<M | KV_ANYHIT | KV_FASTPOW | KV_STATS>(L, s) : launch<M | KV_FASTPOW | KV_STATS>(L, s);
-    if (!(L.variant & KV_FASTPOW)) return any ? launch<M | KV_ANYHIT>(L, s) : launch<M>(L, s);
-    const size_t sb = (size_t)((L.bounces > 0 && L.any_bounce) ? L.bounces : 1) * (L.need_cold_frames ? 10u : 4u) * 64 * sizeof(float);
-    if (any && (L.variant & KV_OCC6) && occ6_fits(sb)) return launch<M | KV_FASTPOW | KV_ANYHIT | KV_OCC6>(L, s);
-    return any ? launch<M | KV_FASTPOW | KV_ANYHIT>(L, s) : launch<M | KV_FASTPOW>(L, s);
-  }
-  if (L.variant & KV_STATS)
-    return (L.variant & KV_ANYHIT) ? launch<KV_BVH | KV_PREFILTER | KV_ANYHIT | KV_FASTPOW | KV_STATS>(L, s)
-                                   : launch<KV_BVH | KV_PREFILTER | KV_FASTPOW | KV_STATS>(L, s);
-  // KV_OCC6: the same kernel compiled for 6 waves per SIMD (80 VGPRs; five cold dwords parked in LDS, see PARK) instead
-  // of 5 (85): worth it where the mesh data exceed the scalar cache many times over and a wave mostly waits for L2
-  // (ctr_api.cpp picks it by triangle count); only the shipped default variant has it (and only when 24 waves' recursion
-  // stacks plus the parking granule fit the CU's 160 KB of LDS: bounces <= 5 without cold frames, occ6_fits)
-  const size_t stack_bytes = (size_t)((L.bounces > 0 && L.any_bounce) ? L.bounces : 1) * (L.need_cold_frames ? 10u : 4u) * 64 * sizeof(float);
-  if ((L.variant & KV_OCC6) && occ6_fits(stack_bytes) &&
-      (L.variant & (KV_PREFILTER | KV_ANYHIT | KV_BVH | KV_FASTPOW)) == (KV_PREFILTER | KV_ANYHIT | KV_BVH | KV_FASTPOW))
-    return launch<KV_OCC6 | KV_PREFILTER | KV_ANYHIT | KV_BVH | KV_FASTPOW>(L, s);
-  return (L.variant & KV_FASTPOW) ? launch_main<KV_FASTPOW>(L, s) : launch_main<0>(L, s);
 }

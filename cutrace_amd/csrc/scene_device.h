@@ -107,7 +107,7 @@ struct DCam {
   uint32_t w, h;
 };
 
-// kernel variant bits (internal; selected from CTR_VAR_* + scene properties)
+// kernel variant bits (internal; selected from CTR_VAR_* + scene properties: kernel_choice.h)
 enum : uint32_t {
   KV_PREFILTER = 1u,   // conservative FMA prefilter before the exact Cramer test
   KV_ANYHIT = 2u,      // shadow casts stop at the first occluder (all-opaque scenes only)
@@ -191,7 +191,7 @@ struct RenderLaunch {
   float *uv;                     // KV_UV: 2 floats per pixel (same indexing as depth), else null
   unsigned long long *shards;    // scene-owned CTR_SHARDS x CTR_SHARD_WORDS scratch the kernel adds into
   unsigned long long *counters;  // [0] ray_count, [1] max-depth bits, [2] AABB-hit triangle count (KV_COUNT), [4..9] KV_STATS
-  uint32_t variant;
+  uint32_t variant;               // the build: exactly one KV of kernel_choice.h CTR_RENDER_KERNELS, not a wish (choose_kernel)
   // tile scheduling (render_kernel.hip "Dispatch order"): all three may be null
   const uint32_t *order;  // dispatch slot -> wave index for THIS launch (a permutation of 0..waves-1)
   uint32_t *cost;         // out: per-wave cost of this launch
@@ -215,7 +215,6 @@ uint64_t ctr_staging_pixels(const RenderLaunch &L);
 uint64_t ctr_staging_groups(const RenderLaunch &L);
 uint32_t ctr_group_tile_count(const RenderLaunch &L, uint64_t group);          // tiles group `group` counts when it is complete
 uint64_t ctr_staging_index(const RenderLaunch &L, uint32_t x, uint32_t k_row); // staging pixel of compact pixel (x, k_row)
-bool ctr_host_delivery_available(uint32_t kernel_variant);
 
 // keeps `msg` for ctr_last_error() (ctr_api.cpp); used by the other translation units of the library
 void ctr_internal_set_error(const char *msg);

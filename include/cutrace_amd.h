@@ -316,6 +316,9 @@ int ctr_render_uv(ctr_scene *scene, float fudge, int bounces, const ctr_rows *ro
  * half the tiles and leaves the rest untouched.  A ctr_render that delivers the frame itself then fails with
  * CTR_E_DELIVERY; the handle stays usable (tests/test_gpu_parity.py). */
 int ctr_debug_poison_next_order(ctr_scene *scene);
+/* Diagnostic: which build of the render kernel the handle's most recent launch was (0 before the first) — the library's
+ * internal variant bits (KV_*, csrc/scene_device.h; the builds and who picks them: csrc/kernel_choice.h). */
+int ctr_debug_last_kernel(ctr_scene *scene, uint32_t *kv);
 /* Diagnostic: what each 8x8 tile of the last launch cost (shader-clock ticks / 64; tile index = frame-major,
  * then row-major over the launch's tile grid).  n_tiles receives the count; out may be NULL. */
 int ctr_tile_costs(ctr_scene *scene, uint32_t *out, uint64_t capacity, uint64_t *n_tiles);

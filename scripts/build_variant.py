@@ -14,6 +14,7 @@ if args and args[0] == "--rev":
     subprocess.check_call(["git", "-C", ROOT, "worktree", "add", "--detach", tmp, rev], stdout=subprocess.DEVNULL)
     try:
         srcs = [os.path.join(tmp, os.path.relpath(p, ROOT)) for p in build.HIP_SRCS]
+        srcs = [p for p in srcs if os.path.exists(p)]  # (a source file the revision did not have yet)
         flags = [f.replace(ROOT, tmp) if f.startswith("-I") else f for f in build.HIP_FLAGS]
         subprocess.check_call([build.hipcc(), *flags, "-shared", "-o", os.path.join(OUT, name + ".so"), *srcs, "-ldl"])
     finally:
