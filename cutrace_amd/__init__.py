@@ -453,6 +453,61 @@ class DeviceScene:
                     raise RuntimeError(f"ctr_shade_rays failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
         return out
 
+    # ---- the lens render (ctr_render_device_lens, include/cutrace_lens.h) ----
+    def render_lens(self, origins, dirs, fudge=1e-3, bounces=5, rows=None, samples=1, ambient=None, stream=None):
+        """The render kernel on caller-supplied primary rays: pixel (x, y) of the scene's current w x h frame holds what the
+        plain render holds for the ray (origins[y, x], dirs[y, x].normalized()) in place of the camera's.  origins, dirs:
+        float32 of shape (H, W, 3) or (H*W, 3), torch tensors on the scene's device or numpy arrays (uploaded), with
+        H, W = samples*h, samples*w — the whole frame also when `rows` selects a part.  samples = 2, 4 or 8: one ray per
+        sample, box-filtered in the kernel as render(samples=...) filters.  A ray with a non-finite origin, or a NaN,
+        infinite or zero direction, is masked: no cast, depth +inf, normal and colour 0 (`lenses.fisheye` masks what lies
+        outside its image circle).  ambient: phong's ambient factor; None: that of the camera the scene was created with.
+        Returns tensors on the scene's device — `depth` (n, w), `color` (n, w, 3), `normal` (n, w, 3) for the n selected
+        rows — plus `ray_count` and `max_depth`; reading those two waits for the launch, which is otherwise asynchronous on
+        `stream` (a torch.cuda.Stream; default: torch's current stream of the scene's device)."""
+        import torch
+        samples = self._samples(samples)
+        L = _lib.hip_lib()
+        r = make_rows(self.h, rows)
+        n = rows_count(self.h, rows)
+        dev = self._torch_device()
+        H, W = samples * self.h, samples * self.w
+
+        def flat(x, what):
+            if not isinstance(x, (np.ndarray, torch.Tensor)):
+                raise TypeError(f"{what}: expected a torch tensor or a numpy array, got {type(x).__name__}")
+            shape = tuple(x.shape)
+            if len(shape) == 3:
+                if shape != (H, W, 3):
+                    raise ValueError(f"{what}: expected shape ({H}, {W}, 3) or ({H * W}, 3), got {shape}")
+                x = x.reshape(H * W, 3)
+            x = self._rays_arg(x, what, 3)
+            if x.shape[0] != H * W:
+                raise ValueError(f"{what}: {x.shape[0]} rays for the {W} x {H} frame ({H * W})")
+            return x
+
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            o = flat(origins, "origins")
+            d = flat(dirs, "dirs")
+            depth = torch.empty(n, self.w, dtype=torch.float32, device=dev)
+            color = torch.empty(n, self.w, 3, dtype=torch.float32, device=dev)
+            normal = torch.empty(n, self.w, 3, dtype=torch.float32, device=dev)
+            counters = torch.zeros(16, dtype=torch.int64, device=dev)
+            q = _lib.Lens()
+            q.n_rays = H * W
+            q.samples = samples
+            q.ambient = float(self._ambient if ambient is None else ambient)
+            q.d_origin, q.d_dir = o.data_ptr() or None, d.data_ptr() or None
+            st = L.ctr_render_device_lens(self._h, C.c_float(fudge), int(bounces), C.byref(q), C.byref(r), depth.data_ptr() or None,
+                                          color.data_ptr() or None, normal.data_ptr() or None, counters.data_ptr(),
+                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if st:
+                raise RuntimeError(f"ctr_render_device_lens failed ({st}): {L.ctr_last_error().decode()}")
+            # (the rays must outlive the launch: tensors made here are kept until the counters have been read)
+            c = counters.cpu()
+        md = np.array([int(c[1]) & 0xFFFFFFFF], np.uint32).view(np.float32)[0]
+        return dict(depth=depth, color=color, normal=normal, ray_count=int(c[0]), max_depth=float(md), rows=n)
+
     def tile_costs(self):
         """Per-tile cost of the last launch (ctr_tile_costs), as a uint32 array."""
         L = _lib.hip_lib()

@@ -80,6 +80,12 @@ class ShadeQuery(C.Structure):
                 ("d_t", C.c_void_p), ("d_object", C.c_void_p), ("d_normal", C.c_void_p)]
 
 
+class Lens(C.Structure):
+    """ctr_lens (include/cutrace_lens.h)"""
+    _fields_ = [("n_rays", C.c_uint64), ("samples", C.c_uint32), ("ambient", C.c_float), ("d_origin", C.c_void_p),
+                ("d_dir", C.c_void_p)]
+
+
 HOST_SYMBOLS = [
     "ctr_host_scene_load", "ctr_host_scene_parse", "ctr_host_scene_free", "ctr_host_scene_desc",
     "ctr_host_scene_set_size", "ctr_host_scene_set_material", "ctr_stl_read", "ctr_stl_write",
@@ -102,6 +108,8 @@ HIP_SYMBOLS = [
 RAY_SYMBOLS = ["ctr_cast_rays", "ctr_shade_rays"]
 # include/cutrace_aa.h
 AA_SYMBOLS = ["ctr_render_aa", "ctr_render_device_aa"]
+# include/cutrace_lens.h
+LENS_SYMBOLS = ["ctr_render_device_lens"]
 
 _host = None
 _hip = None
@@ -198,6 +206,8 @@ def hip_lib():
                                C.POINTER(RenderStats)], C.c_int),
             "ctr_render_device_aa": ([C.c_void_p, C.c_float, C.c_int, C.c_uint32, C.POINTER(Rows), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "ctr_render_device_lens": ([C.c_void_p, C.c_float, C.c_int, C.POINTER(Lens), C.POINTER(Rows), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
         }
         for name, (argt, rest) in opt.items():
             if hasattr(L, name):

@@ -19,6 +19,7 @@
 #include "ctr_internal.h"
 #include "cutrace_aa.h"
 #include "cutrace_amd.h"
+#include "cutrace_lens.h"
 #include "guard.h"
 #include "kernel_choice.h"
 #include "scene_device.h"
@@ -622,13 +623,16 @@ int ctr_set_variant(ctr_scene *s, uint32_t bits) {
 }
 
 // ss_log2 != 0: one supersampled frame (ctr_render_device_aa, whose checks have passed)
+// lens: the primary rays are the caller's (ctr_render_device_lens, whose checks have passed), with ss_log2 one per sample
 static int render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, uint32_t first_frame,
                          uint32_t n_frames, uint64_t frame_stride_px, uint32_t part_stride, void *d_depth,
-                         void *d_color3, void *d_normal3, void *d_counters, void *hip_stream, uint32_t ss_log2) {
+                         void *d_color3, void *d_normal3, void *d_counters, void *hip_stream, uint32_t ss_log2,
+                         const ctr_lens *lens = nullptr) {
   int st = check_args(s, bounces);
   if (st) return st;
   if (!d_depth || !d_color3 || !d_normal3) return fail(CTR_E_INVALID, "null output buffer");
-  const KernelChoice choice = choose_kernel(kernel_facts(s, ss_log2 ? KE_DEVICE_SS : KE_DEVICE, bounces, false));
+  const KernelEntry entry = lens ? (ss_log2 ? KE_DEVICE_LENS_SS : KE_DEVICE_LENS) : (ss_log2 ? KE_DEVICE_SS : KE_DEVICE);
+  const KernelChoice choice = choose_kernel(kernel_facts(s, entry, bounces, false));
   if (choice.reject == KR_IGNTR_DEVICE) return fail(CTR_E_INVALID, "CTR_VAR_IGNORE_TRANSPARENT: host-buffer calls only (ctr_render, ctr_render_uv)");
   if (n_frames == 0 || first_frame >= s->n_cams || n_frames > s->n_cams - first_frame)
     return fail(CTR_E_INVALID, "frame range exceeds the cameras set with ctr_scene_set_cameras");
@@ -661,6 +665,11 @@ static int render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows 
   L.normal = (float *)d_normal3;
   L.counters = (unsigned long long *)d_counters;
   L.variant = choice.kv;
+  if (lens) {
+    L.ray_origin = lens->d_origin;
+    L.ray_dir = lens->d_dir;
+    L.ray_ambient = lens->ambient;
+  }
   if (ss_log2 && (st = aa_scale(L, ss_log2))) return st;
   set_root_and_head(s, L, choice.merged);
   {
@@ -685,6 +694,33 @@ int ctr_render_device_aa(ctr_scene *s, float fudge, int bounces, uint32_t sample
   uint32_t ls = 0;
   if (int st = aa_precheck(s, KE_DEVICE_SS, bounces, samples, rows, ls)) return st;
   return render_device(s, fudge, bounces, rows, 0, 1, 0, 0, d_depth, d_color3, d_normal3, d_counters, hip_stream, ls);
+}
+
+// include/cutrace_lens.h.  Every check comes before the GPU is touched (hipPointerGetAttributes asks the runtime, no device work)
+int ctr_render_device_lens(ctr_scene *s, float fudge, int bounces, const ctr_lens *lens, const ctr_rows *rows, void *d_depth,
+                           void *d_color3, void *d_normal3, void *d_counters, void *hip_stream) {
+  const std::string who = "ctr_render_device_lens: ";
+  int st = check_args(s, bounces);
+  if (st) return st;
+  if (!lens) return fail(CTR_E_INVALID, who + "null lens");
+  if (!lens->d_origin || !lens->d_dir) return fail(CTR_E_INVALID, who + "null rays");
+  if (!d_depth || !d_color3 || !d_normal3) return fail(CTR_E_INVALID, who + "null output buffer");
+  const uint32_t samples = lens->samples;
+  if (samples != 1 && samples != 2 && samples != 4 && samples != 8)
+    return fail(CTR_E_INVALID, who + "samples must be 1, 2, 4 or 8 per axis, got " + std::to_string(samples));
+  if (choose_kernel(kernel_facts(s, samples > 1 ? KE_DEVICE_LENS_SS : KE_DEVICE_LENS, bounces, false)).reject == KR_LENS)
+    return fail(CTR_E_INVALID, who + "no build for CTR_VAR_STATS, CTR_VAR_IGNORE_TRANSPARENT, CTR_VAR_NO_PREFILTER or CTR_VAR_NO_CLUSTER");
+  uint32_t ls = 0;
+  if ((st = aa_precheck(s, KE_DEVICE_SS, bounces, samples, rows, ls))) return st;  // (the size limits of the sample frame)
+  // (w, h <= 2^32 / s each, s*s <= 64: the product fits 64 bits)
+  const uint64_t want = ((uint64_t)s->cam.w << ls) * ((uint64_t)s->cam.h << ls);
+  if (lens->n_rays != want)
+    return fail(CTR_E_INVALID, who + "n_rays is " + std::to_string(lens->n_rays) + ", the " + std::to_string(samples) + " x " + std::to_string(samples) +
+                                   " samples of the " + std::to_string(s->cam.w) + " x " + std::to_string(s->cam.h) + " frame are " + std::to_string(want));
+  const void *const ptrs[] = {lens->d_origin, lens->d_dir};
+  const char *const names[] = {"d_origin", "d_dir"};
+  if ((st = check_device_pointers(s, who, ptrs, names, 2))) return st;
+  return render_device(s, fudge, bounces, rows, 0, 1, 0, 0, d_depth, d_color3, d_normal3, d_counters, hip_stream, ls, lens);
 }
 
 int ctr_render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, void *d_depth, void *d_color3,

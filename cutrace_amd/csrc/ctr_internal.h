@@ -32,6 +32,8 @@ bool is_pinned(const void *p);
 bool device_view(float *host, float **dev);
 // the scene's device becomes the calling thread's current one, unless it is already
 int use_device(const ctr_scene *s);
+// CTR_E_INVALID "<who><name> is not device memory of the scene's device" for the first non-null pointer that is not (ctr_rays.cpp)
+int check_device_pointers(const ctr_scene *s, const std::string &who, const void *const *ptrs, const char *const *names, size_t n);
 #pragma GCC visibility pop
 
 struct ctr_scene {

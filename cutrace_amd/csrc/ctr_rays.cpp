@@ -19,7 +19,10 @@ int check_rays(const ctr_scene *s, const std::string &who, uint64_t n_rays, cons
   return CTR_OK;
 }
 
+}  // namespace
+
 // every pointer the kernel touches must be device memory of the scene's device (no size check is possible here)
+// (ctr_internal.h: the lens render checks its ray arrays with it)
 int check_device_pointers(const ctr_scene *s, const std::string &who, const void *const *ptrs, const char *const *names, size_t n) {
   for (size_t k = 0; k < n; k++) {
     if (!ptrs[k]) continue;
@@ -32,6 +35,8 @@ int check_device_pointers(const ctr_scene *s, const std::string &who, const void
   }
   return CTR_OK;
 }
+
+namespace {
 
 RayScene ray_scene(const ctr_scene *s) {
   RayScene R{};

@@ -1,11 +1,13 @@
 // kernel_choice.cpp — choose_kernel: from the caller's CTR_VAR_* bits, the scene's facts and the entry point to the one build
-// of CTR_RENDER_KERNELS the launch gets, or to the reason why there is none (kernel_choice.h).
+// of CTR_RENDER_KERNELS (CTR_LENS_KERNELS for the lens entries) the launch gets, or to the reason why there is none (kernel_choice.h).
 #include "kernel_choice.h"
 
 #include "cutrace_amd.h"
 
 KernelChoice choose_kernel(const KernelFacts &f) {
   const uint32_t u = f.user;
+  const bool lens = f.entry == KE_DEVICE_LENS || f.entry == KE_DEVICE_LENS_SS;
+  if (lens && (u & (CTR_VAR_STATS | CTR_VAR_IGNORE_TRANSPARENT | CTR_VAR_NO_PREFILTER | CTR_VAR_NO_CLUSTER))) return {0, false, false, KR_LENS};
   const bool ss = f.entry == KE_HOST_SS || f.entry == KE_DEVICE_SS;
   if (ss && (u & (CTR_VAR_STATS | CTR_VAR_IGNORE_TRANSPARENT | CTR_VAR_NO_PREFILTER | CTR_VAR_NO_CLUSTER))) return {0, false, false, KR_SS};
   if (f.entry == KE_DEVICE && (u & CTR_VAR_IGNORE_TRANSPARENT)) return {0, false, false, KR_IGNTR_DEVICE};
@@ -28,6 +30,8 @@ KernelChoice choose_kernel(const KernelFacts &f) {
   // the fourth output and the supersampled frame: the shipped walk only, through device buffers
   if (uv) return {SHIPPED | KV_UV | (igntr ? KV_IGNTR : 0u) | anyhit | pow, false, false, KR_NONE};
   if (ss) return {SHIPPED | KV_SS | anyhit | pow | occ6, false, false, KR_NONE};
+  // the caller's primary rays: the same, with or without the in-kernel reduction
+  if (lens) return {SHIPPED | KV_RAYS | (f.entry == KE_DEVICE_LENS_SS ? KV_SS : 0u) | anyhit | pow | occ6, false, false, KR_NONE};
   // KE_HOST, KE_DEVICE.  The merged tree (CTR_VAR_MERGE): a walk of the shipped kind, frame leaving through device buffers
   const bool merged = (u & CTR_VAR_MERGE) && f.merged_usable && (stats || walk == SHIPPED);
   const uint32_t merge = merged ? KV_MERGE : 0u;

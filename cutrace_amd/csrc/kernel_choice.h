@@ -45,6 +45,18 @@
   X(KV_PREFILTER | KV_BVH | KV_SS | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_SS | KV_FASTPOW | KV_ANYHIT)                      \
   X(KV_PREFILTER | KV_BVH | KV_SS | KV_FASTPOW | KV_ANYHIT | KV_OCC6)
 
+// The builds of the lens render (caller-supplied primary rays, KV_RAYS), a list of their own beside the first: ctr_launch_render's
+// switch is generated from both, and choose_kernel returns one of THESE for KE_DEVICE_LENS / KE_DEVICE_LENS_SS only.
+#define CTR_LENS_KERNELS(X)                                                                                                    \
+  /* RAYS: shipped walk; honours KV_ANYHIT, KV_FASTPOW, and with both KV_OCC6 */                                               \
+  X(KV_PREFILTER | KV_BVH | KV_RAYS) X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_ANYHIT)                                            \
+  X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_FASTPOW | KV_ANYHIT)                  \
+  X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_FASTPOW | KV_ANYHIT | KV_OCC6)                                                        \
+  /* RAYS + SS: as RAYS */                                                                                                     \
+  X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS) X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS | KV_ANYHIT)                            \
+  X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS | KV_FASTPOW | KV_ANYHIT)  \
+  X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS | KV_FASTPOW | KV_ANYHIT | KV_OCC6)
+
 // The recursion stack of a launch: `frames` frames of `nf` floats per lane (render_kernel.hip KArgs::frames, ::nf).
 struct StackShape {
   uint32_t frames, nf;
@@ -65,12 +77,15 @@ enum KernelEntry {
   KE_HOST_SS,    // ctr_render_aa
   KE_DEVICE,     // ctr_render_device, ctr_render_device_batch
   KE_DEVICE_SS,  // ctr_render_device_aa
+  KE_DEVICE_LENS,     // ctr_render_device_lens, samples == 1
+  KE_DEVICE_LENS_SS,  // ctr_render_device_lens, samples > 1
 };
 enum KernelReject {
   KR_NONE,
   KR_SS,             // supersampling has no build for the caller's variant bits
   KR_UV_STATS,       // the fourth output / ignore_transparent cast has no statistics build
   KR_IGNTR_DEVICE,   // CTR_VAR_IGNORE_TRANSPARENT is for host-buffer calls
+  KR_LENS,           // the lens render has no build for the caller's variant bits
 };
 struct KernelFacts {
   uint32_t user;        // CTR_VAR_* of the handle
@@ -82,7 +97,7 @@ struct KernelFacts {
   StackShape stack;
 };
 struct KernelChoice {
-  uint32_t kv;          // the build, one of CTR_RENDER_KERNELS (reject == KR_NONE)
+  uint32_t kv;          // the build, one of CTR_RENDER_KERNELS — of CTR_LENS_KERNELS for the lens entries — (reject == KR_NONE)
   bool direct;          // the kernel delivers the frame to the caller's buffers itself (KV_HOSTOUT)
   bool merged;          // the top-level root is the merged pseudo mesh (KV_MERGE)
   KernelReject reject;

@@ -325,6 +325,11 @@ struct KArgs {
   uint32_t *group_done;
   float *uv_out;      // KV_UV: texture coordinates of the primary hit, 2 floats per pixel
   uint32_t ss_log2;   // KV_SS: log2 of the samples per axis (1, 2 or 3); w, h and rows are those of the s*w x s*h sample frame
+  // "Lens render" (KV_RAYS): the primary rays, 3 floats per pixel (sample) of the whole w x h frame, row-major by GLOBAL row,
+  // and phong's ambient factor (the plain render takes the camera's).  They fill the gap in front of the 64-byte aligned
+  // scene head, so nothing else in the argument block moves.
+  const float *ray_origin, *ray_dir;
+  float ray_ambient;
   // "Scene head" (scene_device.h DSceneHead): the first plane triple and the first mesh record INSIDE the argument block.
   // Their address is kernarg base + constant, so the planes are requested in the same burst as the hot block (one
   // scalar round trip at the head of a cast, not two dependent ones) and the mesh record without fetching `meshes`
@@ -344,6 +349,7 @@ struct KParams {
   float *depth_out, *color_out, *normal_out;
   unsigned long long *counters;
 };
+static_assert(offsetof(KArgs, ss_log2) == 288 && offsetof(KArgs, ray_origin) == 296 && offsetof(KArgs, head) == 320, "KArgs: the lens arguments lie in the padding behind ss_log2");
 static_assert(sizeof(KArgs) % 64 == 0 && offsetof(KArgs, head) % 64 == 0 && offsetof(KParams, depth_out) == sizeof(KArgs), "KParams mirrors the kernel's parameter list; the scene head lies on 64-byte lines");
 
 // ---- Host delivery ----
@@ -396,6 +402,12 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   constexpr bool IGNTR = (KV & KV_IGNTR) != 0;
   constexpr bool MERGE = (KV & KV_MERGE) != 0;      // "merged walk": the top-level item may be the pseudo mesh over all meshes' triangles
   static_assert(!MERGE || BVH, "the merged tree is a BVH walk");
+  // "Lens render": the primary ray of a pixel (sample) is the caller's (origin, direction) instead of cam::get_ray's; a ray
+  // with a non-finite origin, or whose normalised direction is not finite or is (0, 0, 0), is MASKED: no cast, the miss values
+  // (include/cutrace_lens.h has the definition).  Only the prologue differs: origin and direction are per-lane VGPRs in the
+  // cast loops anyway.
+  constexpr bool RAYS = (KV & KV_RAYS) != 0;
+  static_assert(!RAYS || !((KV & (KV_HOSTOUT | KV_STATS | KV_UV | KV_COUNT | KV_IGNTR | KV_MERGE)) != 0), "the lens render leaves through device buffers, three outputs, two-level walk");
   // wave-level work counters (STATS build only): [0] casts, [1] BVH nodes visited, [2] triangle
   // prefilters, [3] exact tests, [4] mesh entries (AABB ballot != 0), [5] sum of active lanes per cast,
   // and how many of the 64 lanes had a use for the wave-level work: [6] lanes whose ray meets one of the
@@ -483,8 +495,12 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     if (HOSTOUT) return (size_t)wave * 64u + l;  // tile-major staging ("Host delivery")
     if constexpr (SS) {  // the output pixel the lane's sample belongs to: (k_row / s) * (w / s) + x_id / s
       const uint32_t ls = ((const CADDR KArgs *)__builtin_amdgcn_kernarg_segment_ptr())->ss_log2;
+      if constexpr (RAYS) return (size_t)(tile_px0 + ((l / TW) >> ls) * (w >> ls) + ((l % TW) >> ls));  // (one frame: launch<KV>)
       return (size_t)frame * A.frame_stride_px + (size_t)(tile_px0 + ((l / TW) >> ls) * (w >> ls) + ((l % TW) >> ls));
     }
+    // (RAYS: one frame, launch<KV> checks; the frame offset, computed before the loop for a masked pixel, would be kept for the
+    //  stores inside it — in scratch, in the 6-wave build)
+    if constexpr (RAYS) return (size_t)(tile_px0 + (l / TW) * w + (l % TW));
     return (size_t)frame * A.frame_stride_px + (size_t)(tile_px0 + (l / TW) * w + (l % TW));
   };
 
@@ -497,7 +513,23 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
 
   // ---- cam::get_ray, default_schema.hpp:376-386 ----
   V3 ro, rd;
-  {
+  bool masked = false;  // RAYS: an in-image lane without a ray
+  if constexpr (RAYS) {
+    const CADDR KArgs *AR = (const CADDR KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+    const float *const po = AR->ray_origin, *const pd = AR->ray_dir;
+    ro = mk(0.f, 0.f, 0.f);
+    rd = mk(0.f, 0.f, 1.f);
+    if (in_image) {  // (in_image: x_id < w and y_id < h, so the index is inside the caller's w*h rays)
+      const size_t i = ((size_t)y_id * (size_t)w + (size_t)x_id) * 3u;
+      ro = mk(po[i + 0], po[i + 1], po[i + 2]);
+      rd = mk(pd[i + 0], pd[i + 1], pd[i + 2]);
+    }
+    rd = vnormalized(rd);
+    const bool o_fin = __builtin_isfinite(ro.x) && __builtin_isfinite(ro.y) && __builtin_isfinite(ro.z);
+    const bool d_fin = __builtin_isfinite(rd.x) && __builtin_isfinite(rd.y) && __builtin_isfinite(rd.z);
+    const bool d_zero = rd.x == 0.f && rd.y == 0.f && rd.z == 0.f;
+    masked = in_image && !(o_fin && d_fin && !d_zero);
+  } else {
     const float fw = (float)w, fh = (float)h;
     const float aspect = fw / fh;
     const V3 right = mk(cam.right[0], cam.right[1], cam.right[2]);
@@ -508,10 +540,10 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     ro = mk(cam.pos[0], cam.pos[1], cam.pos[2]);
     rd = vnormalized(vadd(vadd(x_v, y_v), fwd));
   }
-  const float ambient = cam.ambient;
+  const float ambient = RAYS ? 0.f : cam.ambient;  // (RAYS: the launch's, read where phong starts)
 
   // ---- per-lane state machine ----
-  uint32_t msp = in_image ? 0u : MSP_DONE;  // mode | stack depth (MSP_*); bounces left for the current activation = bounces - depth
+  uint32_t msp = (in_image && !masked) ? 0u : MSP_DONE;  // mode | stack depth (MSP_*); bounces left for the current activation = bounces - depth
   bool first_trip = true;   // wave-uniform: every in-image lane shades its primary hit in the first trip
   uint32_t wave_dbits = 0u; // wave-uniform: max finite depth bits of the tile (kernel.hpp:120-125)
   float min_t = A.fudge;
@@ -540,7 +572,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   bool recv_mesh = false;   // STATS only: the surface this lane's shadow rays start on is a mesh / triangle
   // casts of the whole wave, counted on the scalar unit; the duplicated primary cast (kernel.hpp:52) counts too
   // (IGNTR: the kernel.hpp:52 cast is a trip of its own and is counted there)
-  unsigned long long n_casts = IGNTR ? 0ull : (unsigned long long)__builtin_popcountll(BALLOT(in_image));
+  unsigned long long n_casts = IGNTR ? 0ull : (unsigned long long)__builtin_popcountll(BALLOT(in_image && !masked));
   unsigned long long n_aabb_tris = 0;
 
   // Cold kernel arguments — what only the continuation needs (hit records, lights, materials) — are read from
@@ -549,6 +581,28 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   // back by v_readlane (a half-rate VALU instruction per dword, every trip); an s_load from the scalar cache costs
   // no VALU slot.  The pointer is made opaque once per trip so that the loads stay inside the trip.
   const CADDR KArgs *AK = (const CADDR KArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+  if constexpr (RAYS) {
+    // a masked pixel is finished before the first cast: kernel.hpp:55-56's miss values, colour (0, 0, 0); it is not counted
+    // and, its depth being infinite, does not enter max_depth.  SS: depth and normal from the lane that holds sample (0, 0);
+    // the colour is parked as zeros in the lane's frame 0, where the reduction after the loop finds it
+    if (masked) {
+      const V3 zero = mk(0.f, 0.f, 0.f);
+      if constexpr (SS) {
+        if (ss_kept()) {
+          const size_t px_id = px_index();
+          ((const CADDR KParams *)AK)->depth_out[px_id] = INFINITY;
+          store3(((const CADDR KParams *)AK)->normal_out, px_id, zero);
+        }
+        STK(0, F_R) = 0.f; STK(0, F_G) = 0.f; STK(0, F_B) = 0.f;
+        msp = MSP_DONE | 1u;
+      } else {
+        const size_t px_id = px_index();
+        ((const CADDR KParams *)AK)->depth_out[px_id] = INFINITY;
+        store3(((const CADDR KParams *)AK)->normal_out, px_id, zero);
+        store3(((const CADDR KParams *)AK)->color_out, px_id, zero);
+      }
+    }
+  }
   while (BALLOT(MSP_ACTIVE(msp)) != 0ull) {
     asm volatile("" : "+s"(AK));
     typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
@@ -1635,7 +1689,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         // phong prologue, shading.hpp:66-76
         CTR_MARK(42);
         const CADDR DMat &M = k_mats[mat_i];
-        fin = vscale(mk(M.cx, M.cy, M.cz), ambient);
+        fin = vscale(mk(M.cx, M.cy, M.cz), RAYS ? AK->ray_ambient : ambient);
         { float unused_n; const V3 nrm_ = vnormalized_n(normal, unused_n); CTR_MARK(93); set_nn(nrm_); }
         li = 0;
         act = ACT_LIGHT;
@@ -2258,6 +2312,12 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
   if (((KV & KV_UV) != 0) != (L.uv != nullptr)) return (int)hipErrorInvalidValue;
   // "Supersampling": s = 2, 4 or 8 must divide the tile (a block of samples inside one wave) and the sample frame; one frame
   A.ss_log2 = (KV & KV_SS) ? L.ss_log2 : 0u;
+  // "Lens render": the caller's rays, one pair per pixel (sample) of the one frame
+  A.ray_origin = (KV & KV_RAYS) ? L.ray_origin : nullptr;
+  A.ray_dir = (KV & KV_RAYS) ? L.ray_dir : nullptr;
+  A.ray_ambient = (KV & KV_RAYS) ? L.ray_ambient : 0.f;
+  if (((KV & KV_RAYS) != 0) != (L.ray_origin != nullptr) || ((KV & KV_RAYS) != 0) != (L.ray_dir != nullptr)) return (int)hipErrorInvalidValue;
+  if ((KV & KV_RAYS) && L.n_frames != 1) return (int)hipErrorInvalidValue;
   if (((KV & KV_SS) != 0) != (L.ss_log2 != 0u)) return (int)hipErrorInvalidValue;
   if (KV & KV_SS) {
     const uint32_t m = (1u << L.ss_log2) - 1u;
@@ -2378,6 +2438,7 @@ int ctr_launch_render(const RenderLaunch &L, void *stream) {
   switch (L.variant) {
 #define X(kv) case (kv): return launch<(kv)>(L, (hipStream_t)stream);
     CTR_RENDER_KERNELS(X)
+    CTR_LENS_KERNELS(X)
 #undef X
     default: return (int)hipErrorInvalidValue;
   }

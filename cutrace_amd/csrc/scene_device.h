@@ -121,6 +121,7 @@ enum : uint32_t {
   KV_IGNTR = 1024u,    // the cast of kernel.hpp:52 (depth, normal, uv) is made with ray_cast's ignore_transparent = true (CTR_VAR_IGNORE_TRANSPARENT)
   KV_MERGE = 512u,     // the walk may meet the merged pseudo mesh: ONE tree over the triangles of all meshes (CTR_VAR_MERGE)
   KV_SS = 2048u,       // supersampling: the launch renders s x s samples per pixel and reduces them in the wave (RenderLaunch::ss_log2)
+  KV_RAYS = 4096u,     // lens render: the primary rays are the caller's, one (origin, direction) per pixel or sample (RenderLaunch::ray_origin)
 };
 
 struct DRows {
@@ -210,6 +211,11 @@ struct RenderLaunch {
   // (rows.n_rows / s) x (w / s) output pixels.  0: a plain launch.
   uint32_t ss_log2;
   DSceneHead head;  // "scene head" above; all zero = every record by pointer
+  // Lens render (KV_RAYS; render_kernel.hip "Lens render", include/cutrace_lens.h): the primary rays of the ONE frame, 3 floats
+  // per pixel — with KV_SS per sample of the s*w x s*h frame — row-major over the whole frame (indexed by the global row, whatever
+  // `rows` selects), and phong's ambient factor.  Null: a launch that makes its rays from the camera.
+  const float *ray_origin, *ray_dir;
+  float ray_ambient;
 };
 uint64_t ctr_staging_pixels(const RenderLaunch &L);
 uint64_t ctr_staging_groups(const RenderLaunch &L);
