@@ -177,7 +177,9 @@ __device__ __forceinline__ void cast_mesh(const Scene &S, const float4 *O, V3 ro
     const float gx = fmaxf(fabsf(o2.x - ro.x), fabsf(o2.w - ro.x));
     const float gy = fmaxf(fabsf(o2.y - ro.y), fabsf(o3.x - ro.y));
     const float gz = fmaxf(fabsf(o2.z - ro.z), fabsf(o3.y - ro.z));
-    const float mw = fmaxf(fmaxf(gx, gy), gz) * 0x1p-14f;
+    // (+ 2^-21 x the origin's largest |coordinate|: (ro + mw) and its product are rounded to 2^-24 of |ro|, which for a scene far off
+    //  the origin exceeds 2^-14 x the distance to the box — the walk then missed triangles; as in render_kernel.hip)
+    const float mw = __builtin_fmaf(fmaxf(fmaxf(fabsf(ro.x), fabsf(ro.y)), fabsf(ro.z)), 0x1p-21f, fmaxf(fmaxf(gx, gy), gz) * 0x1p-14f);
     const V3 ka = mk((ro.x + mw) * ria.x, (ro.y + mw) * ria.y, (ro.z + mw) * ria.z);  // for box minima
     const V3 kb = mk((ro.x - mw) * ria.x, (ro.y - mw) * ria.y, (ro.z - mw) * ria.z);  // for box maxima
     const float4 *nodes = S.nodes4 + (size_t)node_begin * 8;

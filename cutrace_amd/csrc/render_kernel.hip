@@ -55,8 +55,9 @@
 // is the parity target; profiles/r02/cuda_minmax_gap.txt counts what the difference touches.
 // The specular term — the half vector's normalisation and pow() — uses
 // v_rsq_f32 and exp2(e*log2(x)) in f32 by default (colour within 3e-6 of the reference) or IEEE
-// sqrt/division and f64 pow rounded once (CTR_VAR_EXACT_POW, bit-identical to glibc powf on every
-// tested pixel); it only feeds the colour.  Texture coordinates (atan2/asin, uv_for)
+// sqrt/division and f64 pow rounded once (CTR_VAR_EXACT_POW: the correctly rounded power, which glibc's powf is for all
+// but about one argument in a thousand — there the reference's colour is the neighbouring float); it only
+// feeds the colour.  Texture coordinates (atan2/asin, uv_for)
 // are never produced: the only material type ignores them (default_schema.hpp:326-340).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -971,7 +972,8 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
           const float gx = fmaxf(fabsf(AK->tl_mn[0] - ro.x), fabsf(AK->tl_mx[0] - ro.x));
           const float gy = fmaxf(fabsf(AK->tl_mn[1] - ro.y), fabsf(AK->tl_mx[1] - ro.y));
           const float gz = fmaxf(fabsf(AK->tl_mn[2] - ro.z), fabsf(AK->tl_mx[2] - ro.z));
-          const float mw = fmaxf(fmaxf(gx, gy), gz) * 0x1p-14f;
+          // (+ 2^-21 x the origin's largest |coordinate|: what rounding ro + mw and its product takes back, see the per-mesh walk)
+          const float mw = __builtin_fmaf(fmaxf(fmaxf(fabsf(ro.x), fabsf(ro.y)), fabsf(ro.z)), 0x1p-21f, fmaxf(fmaxf(gx, gy), gz) * 0x1p-14f);
           const V3 t_ka = mk((ro.x + mw) * ria.x, (ro.y + mw) * ria.y, (ro.z + mw) * ria.z);
           const V3 t_kb = mk((ro.x - mw) * ria.x, (ro.y - mw) * ria.y, (ro.z - mw) * ria.z);
           const uint32_t t_lead = (uint32_t)__builtin_ctzll(lv_m);
@@ -1281,13 +1283,18 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
             // and a wave whose lead ray points the other way takes them in reverse.
             // The box test is conservative: every box is widened in WORLD space by
             //   m = 2^-14 x (largest |coordinate difference| between the ray origin and the mesh box)
+            //       + 2^-21 x (largest |coordinate| of the ray origin)
             // per axis ((mn - m - o)/d and (mx + m - o)/d, folded into the two FMA constants below), far
             // above the rounding of either this test or the reference's triangle test (DESIGN.md
             // §bvh); a NaN (0 x inf for an axis-parallel ray) drops that axis' constraint.
             const float gx = fmaxf(fabsf(O.f[0] - ro.x), fabsf(O.f[3] - ro.x));
             const float gy = fmaxf(fabsf(O.f[1] - ro.y), fabsf(O.f[4] - ro.y));
             const float gz = fmaxf(fabsf(O.f[2] - ro.z), fabsf(O.f[5] - ro.z));
-            const float mw = fmaxf(fmaxf(gx, gy), gz) * 0x1p-14f;
+            // The margin is folded into the ORIGIN's term: (ro + mw) and its product with 1/d are each rounded to 2^-24 of
+            // |ro|, not of the distance to the box.  For a scene far off the origin that rounding exceeds 2^-14 x the distance
+            // (from |ro| = 2^10 distances on) and the walk missed triangles the reference hits; so the margin also carries
+            // 2^-21 x the origin's largest |coordinate|, four times what the two roundings can take back.
+            const float mw = __builtin_fmaf(fmaxf(fmaxf(fabsf(ro.x), fabsf(ro.y)), fabsf(ro.z)), 0x1p-21f, fmaxf(fmaxf(gx, gy), gz) * 0x1p-14f);
             const V3 ka = mk((ro.x + mw) * ria.x, (ro.y + mw) * ria.y, (ro.z + mw) * ria.z);  // for box minima
             const V3 kb = mk((ro.x - mw) * ria.x, (ro.y - mw) * ria.y, (ro.z - mw) * ria.z);  // for box maxima
             const CADDR DNode4 *nodes4 = A.nodes4 + o_node_begin;

@@ -32,6 +32,8 @@ def oracle_lib():
         L.orc_quantise_depth.argtypes = [C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]
         L.orc_quantise_normal.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
         L.orc_quantise_color.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        _render_sig(L.orc_render_pow, ex=True)
+        L.orc_render_pow.argtypes = L.orc_render_pow.argtypes + [C.c_int]
         L.orc_trace_pixel.argtypes = [C.POINTER(_lib.SceneDesc), C.c_uint64, C.c_uint64, C.c_float, C.c_int]
         _oracle = L
     return _oracle
@@ -103,7 +105,7 @@ def ref_fmad_render(scene, fudge=1e-3, bounces=5, rows=None, threads=1, hit_ids=
     return _cpu_render(L.ref_render, scene, fudge, bounces, rows, threads, hit_ids)
 
 
-def _cpu_render(fn, scene, fudge, bounces, rows, threads, want_hit_ids, want_uv=False, ignore_transparent=None):
+def _cpu_render(fn, scene, fudge, bounces, rows, threads, want_hit_ids, want_uv=False, ignore_transparent=None, pow_rounded_once=None):
     w, h = scene.size
     r = make_rows(h, rows)
     n = rows_count(h, rows)
@@ -119,6 +121,8 @@ def _cpu_render(fn, scene, fudge, bounces, rows, threads, want_hit_ids, want_uv=
         args.append(uv.ctypes.data if uv is not None else None)
     if ignore_transparent is not None:   # the *_render_ex entry points
         args.append(1 if ignore_transparent else 0)
+    if pow_rounded_once is not None:   # orc_render_pow
+        args.append(1 if pow_rounded_once else 0)
     st = fn(*args)
     if st:
         raise RuntimeError(f"cpu render failed: {st}")
@@ -126,10 +130,15 @@ def _cpu_render(fn, scene, fudge, bounces, rows, threads, want_hit_ids, want_uv=
                 alg_bytes=int(counters[1]), uv=uv)
 
 
-def oracle_render(scene, fudge=1e-3, bounces=5, rows=None, threads=1, hit_ids=True, uv=False, ignore_transparent_primary=False):
+def oracle_render(scene, fudge=1e-3, bounces=5, rows=None, threads=1, hit_ids=True, uv=False, ignore_transparent_primary=False,
+                  pow_rounded_once=False):
     """CPU restatement (oracle/ctr_oracle.c).  uv=True: also the texture coordinates of the primary hit.
-    ignore_transparent_primary: the kernel.hpp:52 cast with ray_cast's ignore_transparent = true (ray_cast.hpp:39-40)."""
+    ignore_transparent_primary: the kernel.hpp:52 cast with ray_cast's ignore_transparent = true (ray_cast.hpp:39-40).
+    pow_rounded_once: NOT the reference — the specular term as (float)pow((double)x, (double)e) in place of glibc's powf,
+    for tests that ask whether a frame depends on the difference (orc_render_pow)."""
     L = oracle_lib()
+    if pow_rounded_once:
+        return _cpu_render(L.orc_render_pow, scene, fudge, bounces, rows, threads, hit_ids, uv, bool(ignore_transparent_primary), True)
     if ignore_transparent_primary:
         return _cpu_render(L.orc_render_ex, scene, fudge, bounces, rows, threads, hit_ids, uv, True)
     return _cpu_render(L.orc_render_uv if uv else L.orc_render, scene, fudge, bounces, rows, threads, hit_ids, uv)

@@ -76,6 +76,7 @@ typedef struct {
   int64_t last_tri;     /* index (within the mesh) of the triangle that won the last mesh_intersect */
   float *uv;            /* optional output: texture coordinates of the primary hit, 2 floats per pixel */
   int ignore_transparent_primary; /* the kernel.hpp:52 cast is made with ignore_transparent = true (orc_render_ex) */
+  int pow_rounded_once;  /* NOT the reference: the specular pow as the f64 pow rounded once (orc_render_pow) */
 } octx;
 
 /* ---- inc/default_schema.hpp primitives ------------------------------------ */
@@ -251,7 +252,9 @@ static vec phong(octx *cx, const ray *incoming, const vec *hit, uint64_t hit_id,
       float fd = smax(0.0f, vdot(nn, nd));
       vec ld = vmul(diffuse, color);
       vec h = vnormalized(vadd(vscale(vnormalized(incoming->dir), -1.0f), nd));
-      float fs = powf(smax(0.0f, vdot(nn, h)), phong_exp);
+      float sx = smax(0.0f, vdot(nn, h));
+      /* (pow_rounded_once: see orc_render_pow; off, this is the reference's powf) */
+      float fs = cx->pow_rounded_once ? (float)pow((double)sx, (double)phong_exp) : powf(sx, phong_exp);
       vec ls = vmul(specular, color);
       /* final += (1 - shadow_fac) * (fd * ld + fs * ls) */
       vec term = vscale(vadd(vscale(ld, fd), vscale(ls, fs)), 1 - shadow_fac);
@@ -366,12 +369,12 @@ typedef struct {
   uint64_t *next;        /* shared atomic row counter */
   uint64_t casts, alg_bytes;
   float *uv;
-  int ign;
+  int ign, pow_once;
 } job;
 
 static void *worker(void *arg) {
   job *j = (job *)arg;
-  octx cx = {j->s, 0, 0, 0, -1, j->uv, j->ign};
+  octx cx = {j->s, 0, 0, 0, -1, j->uv, j->ign, j->pow_once};
   uint64_t w = j->s->cam.w;
   for (;;) {
     uint64_t k = __atomic_fetch_add(j->next, 1, __ATOMIC_RELAXED);
@@ -412,8 +415,21 @@ int orc_render_uv(const ctr_scene_desc *s, float fudge, int bounces, const ctr_r
 /* ... plus ignore_transparent_primary: the cast of kernel.hpp:52 (depth, normal, hit id, uv) is made with ray_cast's
  * ignore_transparent = true (ray_cast.hpp:30,39-40) — objects whose material is transparent do not exist for it; ray_color's
  * own casts stay as the reference's shading code makes them (shading.hpp:32,123 pass false) */
+int orc_render_pow(const ctr_scene_desc *s, float fudge, int bounces, const ctr_rows *rows_in, int n_threads, float *depth, float *color3,
+                   float *normal3, int64_t *hit_ids, uint64_t *counters, float *uv2, int ignore_transparent_primary, int pow_rounded_once);
 int orc_render_ex(const ctr_scene_desc *s, float fudge, int bounces, const ctr_rows *rows_in, int n_threads,
                   float *depth, float *color3, float *normal3, int64_t *hit_ids, uint64_t *counters, float *uv2, int ignore_transparent_primary) {
+  return orc_render_pow(s, fudge, bounces, rows_in, n_threads, depth, color3, normal3, hit_ids, counters, uv2, ignore_transparent_primary, 0);
+}
+
+/* ... plus pow_rounded_once — with it on this is NOT the reference.  glibc's powf is not correctly rounded: about one result
+ * in a thousand is the float on the other side of the exact value from (float)pow((double)x, (double)e), which is what
+ * CTR_VAR_EXACT_POW computes on the device.  With the flag on the specular term is the latter and nothing else changes.  Two
+ * uses, both in tests/: to tell on the CPU which frames depend on the choice (tests/test_render_ranges_cpu.py), and, on
+ * exactly those frames, as what the device's exact-pow colour is compared with bit for bit — beside, never instead of, the
+ * comparison with the reference's frame within the colour tolerance (tests/test_gpu_render_ranges.py). */
+int orc_render_pow(const ctr_scene_desc *s, float fudge, int bounces, const ctr_rows *rows_in, int n_threads, float *depth, float *color3,
+                   float *normal3, int64_t *hit_ids, uint64_t *counters, float *uv2, int ignore_transparent_primary, int pow_rounded_once) {
   ctr_rows rr = {0, s->cam.h, s->cam.h ? s->cam.h : 1, 0, 1};
   if (rows_in && rows_in->row_end > rows_in->row_begin) {
     rr = *rows_in;
@@ -430,7 +446,7 @@ int orc_render_ex(const ctr_scene_desc *s, float fudge, int bounces, const ctr_r
   job *jobs = (job *)calloc((size_t)n_threads, sizeof(job));
   pthread_t *th = (pthread_t *)calloc((size_t)n_threads, sizeof(pthread_t));
   for (int t = 0; t < n_threads; t++) {
-    job jj = {s, fudge, bounces, sel, n, depth, (vec *)color3, (vec *)normal3, hit_ids, &next, 0, 0, uv2, ignore_transparent_primary};
+    job jj = {s, fudge, bounces, sel, n, depth, (vec *)color3, (vec *)normal3, hit_ids, &next, 0, 0, uv2, ignore_transparent_primary, pow_rounded_once};
     jobs[t] = jj;
   }
   if (n_threads == 1) worker(&jobs[0]);

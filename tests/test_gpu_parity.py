@@ -15,7 +15,7 @@ import oracle
 
 from tests.conftest import load_scene
 from tests.test_oracle_golden import GOLD, parse
-from tests.util import (assert_parity, same_bits, mesh_scene as _mesh_scene, corner_meshes, _random_scene, _coplanar_scene,
+from tests.util import (assert_parity, same_bits, uv_close, mesh_scene as _mesh_scene, corner_meshes, _random_scene, _coplanar_scene,
                         _mirror_coplanar_scene)
 
 pytestmark = pytest.mark.gpu
@@ -589,14 +589,7 @@ def test_delivery_self_check(ca, monkeypatch):
         assert r["ray_count"] > 0
 
 
-def _uv_close(got, want, tol=1e-4):
-    """uv within the parity bar; NaN where the reference has NaN (plane normal without x and y, default_schema.hpp:170)"""
-    nan_g, nan_w = np.isnan(got), np.isnan(want)
-    assert np.array_equal(nan_g, nan_w), f"{int((nan_g != nan_w).sum())} uv values are NaN on one side only"
-    d = np.abs(np.where(nan_w, 0, got) - np.where(nan_w, 0, want))
-    lim = tol * np.maximum(1.0, np.abs(np.where(nan_w, 0, want)))
-    assert (d <= lim).all(), f"uv differs by up to {float(d.max()):.3e}"
-    return float(d.max())
+_uv_close = uv_close
 
 
 @pytest.mark.parametrize("name,w,h", [("triangle", 20, 20), ("sphere_plane", 96, 54), ("bunny", 96, 54)])

@@ -11,7 +11,7 @@ import pytest
 from tests import ray_ref, shade_ref
 from tests.conftest import load_scene
 from tests.util import (DIR_EXPONENTS, SCALE_EXPONENTS, TOL, _random_scene, assert_bitwise, assert_same, corner_meshes, f32,
-                        f32_bits, first_hit_same, hall_of_mirrors_json, max_diff, pow2, ref_dict, scaled_scene_json, sphere_mask,
+                        f32_bits, first_hit_same, hall_of_mirrors_json, max_diff, pow2, range_offset, ref_dict, render_range_scene_json, scaled_scene_json, sphere_mask,
                         sweep_max_t, sweep_min_t, sweep_rays, to_np)
 
 pytestmark = pytest.mark.gpu
@@ -92,6 +92,22 @@ def test_scenes_scaled_by_2_to_the_k(ca, tmp_path, k):
     o, d, sel = sweep_rays(4, N, base)
     sk = pow2(k)
     check_batch(ds, sc, o * sk, d, sweep_min_t(sel, 0) * sk, sweep_max_t(sel, 0) * sk, float(f32(1e-3) * sk), f"scale k={k}")
+    ds.close()
+
+
+@pytest.mark.parametrize("e", [10, 18])
+def test_a_scene_2_to_the_e_off_the_origin(ca, tmp_path, e):
+    """the scene of the render range sweep (tests/util.py render_range_scene_json) moved 2^e * (1, -0.75, 0.5) off the origin,
+    the rays' origins with it.  The node boxes' margin of the default walk (ray_walk.h cast_mesh) is folded into the ray
+    origin's own term, whose rounding grows with the origin's coordinates: before the margin covered that, the default walk
+    differed from the linear one at e = 18 (seen on the thin-lens rays of tests/test_gpu_render_ranges.py)."""
+    base = shade_ref.ShadeScene(ca.HostScene.parse(render_range_scene_json(tmp_path, 0, None, w=32, h=32)))
+    s = ca.HostScene.parse(render_range_scene_json(tmp_path, 0, e, w=32, h=32))
+    assert s.ok
+    sc = shade_ref.ShadeScene(s)
+    ds = ca.DeviceScene(s)
+    o, d, sel = sweep_rays(7, N, base)
+    check_batch(ds, sc, (o + range_offset(0, e)).astype(f32), d, sweep_min_t(sel, 0), sweep_max_t(sel, 0), 1e-3, f"offset e={e}")
     ds.close()
 
 

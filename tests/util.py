@@ -51,6 +51,16 @@ def assert_parity(got, want, what="", color_tol=TOL):
     return dict(depth=dr, normal=nr, color=cr)
 
 
+def uv_close(got, want, tol=1e-4):
+    """uv within the parity bar; NaN where the reference has NaN (plane normal without x and y, default_schema.hpp:170)"""
+    nan_g, nan_w = np.isnan(got), np.isnan(want)
+    assert np.array_equal(nan_g, nan_w), f"{int((nan_g != nan_w).sum())} uv values are NaN on one side only"
+    d = np.abs(np.where(nan_w, 0, got) - np.where(nan_w, 0, want))
+    lim = tol * np.maximum(1.0, np.abs(np.where(nan_w, 0, want)))
+    assert (d <= lim).all(), f"uv differs by up to {float(d.max()):.3e}"
+    return float(d.max())
+
+
 def mesh_scene(stl_path, w, h, tris, extra_objects=(), fudge_note=""):
     import json
     from cutrace_amd import scenes
@@ -423,6 +433,80 @@ def scaled_scene_json(tmp_path, k, w=32, h=32):
     cam = {"eye": p(0.5, 0.75, 4.0), "up": [0, 1, 0], "look": [-0.05, -0.15, -1.0], "near_plane": 0.1, "far_plane": 100.0,
            "width": w, "height": h, "ambient": 0.1}
     return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
+
+
+# ---- the render-side range sweeps of tests/test_gpu_render_ranges.py.  tests/test_render_ranges_cpu.py proves, case by
+# case, that the oracle stays inside its own arithmetic and that its frame shows every kind of object: a case that fails
+# there leaves the list with a comment that says why, it is not tolerated ----
+OFFSET_CASES = ((0, 10), (0, 14), (0, 18), (12, 10), (-12, 14))   # (k, e): the scene scaled by 2^k sits 2^e * 2^k off the origin
+# (k, offset exponent or None, whether fudge scales with the scene: 1e-3 * 2^k, or stays 1e-3)
+RENDER_RANGE_CASES = (tuple((k, None, True) for k in SCALE_EXPONENTS) + tuple((k, e, True) for k, e in OFFSET_CASES) +
+                      tuple((k, None, False) for k in (-20, -12, 12, 24)))
+RANGE_FLAVOURS = ("mixed", "opaque")
+ALL_MISS_CASE = (-20, None, False)   # the scene is 2^-20 across and min_t is 1e-3: everything is nearer than min_t
+
+
+# Supersampled frames (case, flavour, samples per axis) whose REDUCED oracle frame changes in some bit when the oracle's
+# specular term is (float)pow((double)x, (double)e) — what VAR_EXACT_POW computes — in place of glibc's powf, which is not
+# correctly rounded (about one result in a thousand is the neighbouring float).  tests/test_render_ranges_cpu.py proves on
+# the CPU that these are exactly the frames that do: on them the bitwise colour comparison under VAR_EXACT_POW says nothing
+# about the kernel; there the exact-pow launch is compared bit for bit with the oracle whose specular term is that rounded-once
+# pow (oracle_render(pow_rounded_once=True), proved there to differ from the oracle in those colour words only), and with
+# the oracle itself within TOL.  They stay in every other comparison.
+# No 48 x 48 frame of any case depends on it.  (colour words that differ: 1, 1, 3, 1)
+RANGE_POW_DEPENDENT = (((0, 10, True), "mixed", 2), ((0, 10, True), "opaque", 2), ((12, 10, True), "mixed", 2), ((12, 10, True), "opaque", 2))
+
+
+def range_fudge(case):
+    k, _, scaled = case
+    return float(f32(1e-3) * pow2(k)) if scaled else 1e-3
+
+
+def range_case_id(case):
+    k, e, scaled = case
+    return f"k={k},e={e},fudge={'1e-3*2^k' if scaled else '1e-3'}"
+
+
+def range_offset(k, offset_exp):
+    """the float32 offset of a case: 2^e * (1, -0.75, 0.5) * 2^k, or zeros"""
+    if offset_exp is None:
+        return np.zeros(3, f32)
+    return (np.array([1.0, -0.75, 0.5], f32) * pow2(offset_exp)) * pow2(k)
+
+
+def render_range_scene_json(tmp_path, k, offset_exp=None, opaque=False, w=48, h=48):
+    """scaled_scene_json for the render: the mesh is two meshes (the even and the odd triangles of scene/bunny.stl, 1000
+    triangles together), the camera's look point scales with the scene, so that every k shows the same view, and an
+    offset 2^offset_exp * (1, -0.75, 0.5) * 2^k is added in float32 to every position: the mesh vertices after scaling, the
+    plane's point, the triangle's corners, the sphere's centre, the point light, the eye and the look point.
+    opaque: every transparency is 0."""
+    from cutrace_amd import scenes
+    s, off = pow2(k), range_offset(k, offset_exp)
+    tris = scenes.read_stl(os.path.join(ROOT, "scene", "bunny.stl"))
+    stls = []
+    for part in (0, 1):
+        stl = str(tmp_path / f"range_{k}_{offset_exp}_{part}.stl")
+        scenes.write_stl(stl, ((tris[part::2] * s).astype(f32) + off).astype(f32))
+        stls.append(stl)
+
+    def p(*v):
+        return [float(x) for x in (np.array(v, f32) * s + off).astype(f32)]
+    mats = [{"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.0, "phong": 40},
+            {"type": "solid", "color": [0.9, 0.9, 0.95], "specular": 0.3, "reflect": 0.7, "phong": 60},
+            {"type": "solid", "color": [0.3, 0.8, 0.5], "specular": 0.6, "reflect": 0.0, "phong": 30, "transparency": 0.0 if opaque else 0.5}]
+    objs = [{"type": "mesh", "file": stls[0], "material": 0},
+            {"type": "mesh", "file": stls[1], "material": 0},
+            {"type": "plane", "point": p(0, -1.25, 0), "normal": [0.0, 1.0, 0.0], "material": 1},
+            {"type": "triangle", "p1": p(-2.5, -1, -1.5), "p2": p(2.5, -1, -1.5), "p3": p(0.25, 2.5, -1.75), "material": 2},
+            {"type": "sphere", "center": p(1.5, 0.25, 0.5), "radius": float(f32(0.5) * s), "material": 2}]
+    lights = [{"type": "point", "point": p(0.5, 2.5, 2.0), "color": [0.8, 0.8, 0.8]},
+              {"type": "sun", "direction": [-0.3, -1.0, -0.2], "color": [0.4, 0.4, 0.4]}]
+    cam = {"eye": p(0.5, 0.75, 4.0), "up": [0, 1, 0], "look": p(-0.05, -0.15, -1.0), "near_plane": 0.1, "far_plane": 100.0,
+           "width": w, "height": h, "ambient": 0.1}
+    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
+
+
+RANGE_KINDS = {"mesh": (0, 1), "plane": (2,), "triangle": (3,), "sphere": (4,)}   # object indices of render_range_scene_json
 
 
 def hall_of_mirrors_json(w, h, middle=None):
