@@ -203,7 +203,7 @@ void fill_launch(const ctr_scene *s, RenderLaunch &L) {
 KernelFacts kernel_facts(const ctr_scene *s, KernelEntry entry, int bounces, bool deliverable) {
   const FlatScene &F = s->flat;
   return {s->user_variant, F.all_opaque, F.mesh_tris >= ctr_scene::occ6_min_tris(), F.merged.built && F.merged.usable, entry, deliverable,
-          stack_shape(bounces, F.any_bounce, F.need_cold)};
+          stack_shape(bounces, F.any_bounce, F.need_cold), F.fast_pow_ok};
 }
 
 // The launch's top-level root and scene head.  A build that walks the merged tree (scene_flatten.h Merged) starts at the merged

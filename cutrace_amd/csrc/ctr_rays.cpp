@@ -122,7 +122,7 @@ extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_
   L.frame_dwords = s->flat.need_cold ? 10u : 4u;
   L.all_opaque = s->flat.all_opaque ? 1u : 0u;
   L.n_rays = (uint32_t)q->n_rays;
-  L.flags = q->flags;
+  L.flags = q->flags | (s->flat.fast_pow_ok ? 0u : CTR_SHADE_EXACT_POW);  // (outside the fast path's domain: the exact one)
   L.bounces = q->bounces;
   L.min_t = q->min_t;
   L.ambient = q->ambient;

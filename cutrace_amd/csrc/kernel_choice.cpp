@@ -23,7 +23,9 @@ KernelChoice choose_kernel(const KernelFacts &f) {
   // shadow any-hit is result-identical only when every material is exactly opaque; with any transparency the ordered
   // nearest-hit loop is kept
   const uint32_t anyhit = f.all_opaque && !(u & CTR_VAR_NO_ANYHIT) ? KV_ANYHIT : 0u;
-  const uint32_t pow = u & CTR_VAR_EXACT_POW ? 0u : KV_FASTPOW;
+  // the fast specular path: unless the caller wants the exact one, or the scene's exponents and colours would take it out of
+  // the colour tolerance (then the launch is the one CTR_VAR_EXACT_POW would get)
+  const uint32_t pow = (u & CTR_VAR_EXACT_POW) || !f.fast_pow_ok ? 0u : KV_FASTPOW;
   // the build for 6 waves per SIMD: for large meshes, of the default variant only, and only when the stacks leave it room
   const uint32_t occ6 = f.big_mesh && !(u & CTR_VAR_NO_OCC6) && walk == SHIPPED && anyhit && pow && occ6_fits(f.stack) ? KV_OCC6 : 0u;
 

@@ -95,6 +95,7 @@ struct KernelFacts {
   KernelEntry entry;
   bool deliverable;     // KE_HOST: the caller's buffers are page-locked and visible to the device
   StackShape stack;
+  bool fast_pow_ok = true;  // the fast specular path stays inside the colour tolerance on this scene (scene_flatten.h fast_pow_in_bar)
 };
 struct KernelChoice {
   uint32_t kv;          // the build, one of CTR_RENDER_KERNELS — of CTR_LENS_KERNELS for the lens entries — (reject == KR_NONE)

@@ -326,10 +326,13 @@ void reserve_merged(const ctr_scene_desc &d, const std::vector<DObj> &by_rank, F
 }
 
 void lights_and_materials(const ctr_scene_desc &d, FlatScene &F) {
+  auto largest = [](const ctr_vec3 &c) { return std::max(std::fabs((double)c.x), std::max(std::fabs((double)c.y), std::fabs((double)c.z))); };
+  double lambda = 0.0, worst = 0.0;
   F.lights.resize(d.n_lights);
   for (uint64_t i = 0; i < d.n_lights; i++) {
     const ctr_light &l = d.lights[i];
     F.lights[i] = DLight{l.type, l.v.x, l.v.y, l.v.z, l.color.x, l.color.y, l.color.z, 0.f};
+    lambda += largest(l.color);
   }
   F.mats.resize(d.n_materials);
   for (uint64_t i = 0; i < d.n_materials; i++) {
@@ -338,7 +341,9 @@ void lights_and_materials(const ctr_scene_desc &d, FlatScene &F) {
     if (!(m.transparency == 0.0f)) F.all_opaque = false;
     if ((double)m.transparency >= 1e-6 && (double)m.reflexivity >= 1e-6) F.need_cold = true;
     if ((double)m.transparency >= 1e-6 || (double)m.reflexivity >= 1e-6) F.any_bounce = true;
+    worst = std::max(worst, std::fabs((double)m.phong_exp * (double)m.specular) * largest(m.color));
   }
+  F.fast_pow_ok = fast_pow_in_bar(worst, lambda);
 }
 
 // FlatScene::ray_slots

@@ -80,6 +80,10 @@ struct FlatScene {
   bool all_opaque = true;
   bool need_cold = false;   // some material both reflects and transmits (>= 1e-6 each)
   bool any_bounce = false;  // some material reflects or transmits (>= 1e-6): the recursion can go below depth 0
+  // the fast specular path, exp2(e * log2(x)) on a half vector normalised with v_rsq_f32, stays inside the colour tolerance:
+  // x^e has condition number e, so its error is CTR_FAST_POW_KAPPA * e per unit of specular colour and light colour
+  // (fast_pow_in_bar below; DESIGN.md "Shading parameters the kernels are pinned over")
+  bool fast_pow_ok = true;
   uint64_t mesh_tris = 0;   // triangles in meshes
   size_t mesh_bytes = 0;    // triangles + BVH nodes
   std::vector<MeshGuard> guards;  // one per mesh object, scene order
@@ -90,6 +94,16 @@ struct FlatScene {
   // root.  The trees' SHAPES never change after flatten_scene (only boxes and guard leaves do).
   uint32_t ray_slots = 0;
 };
+
+// max |fs_fast - fs_reference| / e of the specular term fs = x^e, measured on one MI355X over the highlight rays of
+// tests/test_gpu_shading_ranges.py at e = 32 ... 100 000: 2.38e-7 ... 2.41e-7 (profiles/shading_ranges/fastpow.txt; below e = 32
+// the difference is the colour's own last bit, 2.4e-7 ... 4.8e-7 whatever e, and has nothing to do with the exponent)
+constexpr double CTR_FAST_POW_KAPPA = 2.42e-7;
+constexpr double CTR_COLOUR_TOL = 1e-4;  // the parity bar of the colour, per channel
+// worst: the largest phong_exp * specular * colour channel of any material; lambda: the sum over the lights of the largest
+// |colour channel| (the colour is linear in both).  The factor 2: a finite sample of highlight geometries underestimates
+// the maximum.
+inline bool fast_pow_in_bar(double worst, double lambda) { return 2.0 * CTR_FAST_POW_KAPPA * worst * lambda <= CTR_COLOUR_TOL; }
 
 // The checks the kernel relies on (it trusts these indices).  CTR_OK, or CTR_E_INVALID and the message in `err`.
 int validate_desc(const ctr_scene_desc &d, std::string &err);

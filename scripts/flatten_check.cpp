@@ -85,8 +85,8 @@ int main(int argc, char **argv) {
   out = fopen(argv[2], "wb");
   if (!out) { perror(argv[2]); return 3; }
   dump_arrays(F);
-  const uint64_t sc[16] = {F.n_mesh, F.tlas_root, F.tlas_begin, F.n_axis_recs, F.has_mesh, F.all_opaque, F.need_cold, F.any_bounce, F.mesh_tris,
-                           F.mesh_bytes, F.ray_slots, F.merged.reserved, F.merged.tri_begin, F.merged.tri_count, F.merged.node_begin, F.merged.node_cap};
+  const uint64_t sc[17] = {F.n_mesh, F.tlas_root, F.tlas_begin, F.n_axis_recs, F.has_mesh, F.all_opaque, F.need_cold, F.any_bounce, F.mesh_tris,
+                           F.mesh_bytes, F.ray_slots, F.merged.reserved, F.merged.tri_begin, F.merged.tri_count, F.merged.node_begin, F.merged.node_cap, F.fast_pow_ok};
   section("scalars", sc, sizeof(sc));
   std::vector<uint32_t> g;
   for (const MeshGuard &m : F.guards) g.insert(g.end(), {m.node_begin, m.node_count, m.tri_begin, m.tri_count, m.obj_index, (uint32_t)m.mesh_pos});

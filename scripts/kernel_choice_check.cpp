@@ -8,7 +8,8 @@
 // (bit 0 all_opaque, bit 1 big mesh, bit 2 merged tree usable) x deliverable (no, yes) x 4 stack shapes (SHAPES).
 // A line is the build's KV in hex, or 0xf000 + KernelReject for a combination without a build.  After the cases: "list"
 // and the KVs of CTR_RENDER_KERNELS; then "neutral" and how many of the sampled cases CTR_VAR_NO_REORDER and
-// CTR_VAR_IMAGE_ORDER_FIRST changed (must be 0).
+// CTR_VAR_IMAGE_ORDER_FIRST changed (must be 0); then "slowpow" and how many cases, with fast_pow_ok false (every case above
+// has it true), get another answer than the same case with CTR_VAR_EXACT_POW among the caller's bits (must be 0).
 #include <cstdio>
 #include <initializer_list>
 
@@ -29,7 +30,7 @@ static unsigned answer(const KernelFacts &f) {
 }
 
 int main() {
-  unsigned n = 0, moved = 0;
+  unsigned n = 0, moved = 0, slowpow = 0;
   for (int entry = 0; entry < 6; entry++)
     for (unsigned m = 0; m < 512; m++) {
       uint32_t user = 0;
@@ -41,6 +42,12 @@ int main() {
             KernelFacts f{user, (flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0, (KernelEntry)entry, deliverable != 0, st};
             const unsigned a = answer(f);
             printf("%04x\n", a);
+            {  // a scene outside the fast specular path's domain: the launch CTR_VAR_EXACT_POW would get
+              KernelFacts slow = f, exact = f;
+              slow.fast_pow_ok = false;
+              exact.user = user | CTR_VAR_EXACT_POW;
+              slowpow += answer(slow) != answer(exact);
+            }
             if (n++ % 7 == 0)  // a sample: the bits that order the tiles choose no build
               for (uint32_t extra : {CTR_VAR_NO_REORDER, CTR_VAR_IMAGE_ORDER_FIRST, CTR_VAR_NO_REORDER | CTR_VAR_IMAGE_ORDER_FIRST}) {
                 f.user = user | extra;
@@ -53,5 +60,6 @@ int main() {
   CTR_RENDER_KERNELS(X)
 #undef X
   printf("neutral\n%u\n", moved);
+  printf("slowpow\n%u\n", slowpow);
   return 0;
 }

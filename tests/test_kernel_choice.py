@@ -16,7 +16,8 @@ REJECTED = 0xF000          # + KernelReject; 0xFFFF: the chooser's outputs contr
 
 
 def choices(tmp_path):
-    """(cases in SHAPE as uint16, the KVs of CTR_RENDER_KERNELS, cases the tile-order bits changed)"""
+    """(cases in SHAPE as uint16, the KVs of CTR_RENDER_KERNELS, cases the tile-order bits changed, cases in which a scene
+    outside the fast specular path's domain gets another build than CTR_VAR_EXACT_POW would)"""
     if not shutil.which("g++"):
         pytest.skip("no g++ here")
     exe = str(tmp_path / "kernel_choice_check")
@@ -27,15 +28,19 @@ def choices(tmp_path):
     at_list, at_neutral = words.index("list"), words.index("neutral")
     got = np.array([int(x, 16) for x in words[:at_list]], np.uint16)
     assert got.size == int(np.prod(SHAPE))
-    return got.reshape(SHAPE), [int(x, 16) for x in words[at_list + 1:at_neutral]], int(words[at_neutral + 1])
+    at_slow = words.index("slowpow")
+    return got.reshape(SHAPE), [int(x, 16) for x in words[at_list + 1:at_neutral]], int(words[at_neutral + 1]), int(words[at_slow + 1])
 
 
 def test_every_launch_gets_the_build_it_got_before_the_chooser(tmp_path):
-    got, builds, moved = choices(tmp_path)
+    got, builds, moved, slowpow = choices(tmp_path)
     want = np.load(GOLDEN)["choice"].reshape(SHAPE)
     diff = np.argwhere(got != want)
     assert diff.size == 0, [(tuple(i), hex(want[tuple(i)]), hex(got[tuple(i)])) for i in diff[:10]]
     assert moved == 0  # CTR_VAR_NO_REORDER, CTR_VAR_IMAGE_ORDER_FIRST
+    # KernelFacts::fast_pow_ok: true in every row of the fixture (the scenes it was recorded from are inside the fast
+    # specular path's domain: tests/test_scene_flatten.py); false, the launch is the one CTR_VAR_EXACT_POW gets
+    assert slowpow == 0
     assert len(builds) == len(set(builds)) == 43
     chosen = set(int(x) for x in np.unique(got[got < REJECTED]))
     assert chosen <= set(builds), sorted(chosen - set(builds))   # every KV the chooser returns is in the list

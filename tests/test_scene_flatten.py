@@ -29,7 +29,7 @@ DPLANE = np.dtype([("p", "f4", (3, 2)), ("n", "f4", (3, 2)), ("index", "u4", 2),
 DMAT = np.dtype([("color", "f4", 3), ("specular", "f4"), ("reflexivity", "f4"), ("phong_exp", "f4"), ("transparency", "f4"), ("pad", "f4")])
 ARRAYS = {"objs": DOBJ, "oloop": DOBJ, "meshes": DOBJ, "planes": DPLANE, "tris": DTRI, "nodes4": DNODE4, "gn": np.dtype("f4"), "mats": DMAT}
 SCALARS = ["n_mesh", "tlas_root", "tlas_begin", "n_axis_recs", "has_mesh", "all_opaque", "need_cold", "any_bounce", "mesh_tris",
-           "mesh_bytes", "ray_slots", "merged_reserved", "merged_tri_begin", "merged_tri_count", "merged_node_begin", "merged_node_cap"]
+           "mesh_bytes", "ray_slots", "merged_reserved", "merged_tri_begin", "merged_tri_count", "merged_node_begin", "merged_node_cap", "fast_pow_ok"]
 GUARD = ["node_begin", "node_count", "tri_begin", "tri_count", "obj_index", "mesh_pos"]
 
 

@@ -524,3 +524,343 @@ def hall_of_mirrors_json(w, h, middle=None):
     cam = {"eye": [0.9, 0.4, 4.0], "up": [0, 1, 0], "look": [-0.6, -0.2, -1.0], "near_plane": 0.1, "far_plane": 100.0,
            "width": w, "height": h, "ambient": 0.1}
     return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs})
+
+
+# ---- the shading-parameter sweeps of tests/test_gpu_shading_ranges.py: materials, lights and phong exponents outside the
+# box every other scene draws them from.  tests/test_shading_ranges_cpu.py proves the builders' claims (which sheet's
+# partial sum reaches 1, how many occluders lie over which floor pixel, how many constructed rays sit in a highlight) and
+# pins tests/shade_ref.py and, where built, the reference's own headers to the oracle on every case.  Out of scope, because
+# they put NaN rays into the kernels: a sun of zero direction, a light exactly on a hit point, non-finite parameters, a
+# negative phong exponent (DESIGN.md "Shading parameters the kernels are pinned over") ----
+SHADE_W, SHADE_H = 48, 36
+
+
+def _solid(color=(0.8, 0.8, 0.8), specular=0.0, reflect=0.0, phong=10.0, transparency=0.0):
+    return {"type": "solid", "color": [float(x) for x in color], "specular": float(specular), "reflect": float(reflect),
+            "phong": float(phong), "transparency": float(transparency)}
+
+
+def _camera(eye, look, up=(0, 1, 0), w=SHADE_W, h=SHADE_H, ambient=0.1):
+    return {"eye": [float(x) for x in eye], "up": [float(x) for x in up], "look": [float(x) for x in look], "near_plane": 0.1,
+            "far_plane": 100.0, "width": w, "height": h, "ambient": float(ambient)}
+
+
+def light_scale(host_scene):
+    """Lambda: the sum over the lights of the largest |colour channel|.  The colour is linear in the light colours, so the
+    colour bar of a case is TOL * max(1, Lambda)."""
+    d = host_scene.desc.contents
+    return float(sum(max(abs(c) for c in d.lights[i].color.tup()) for i in range(d.n_lights)))
+
+
+# scene_flatten.h CTR_FAST_POW_KAPPA, restated: max |fs_fast - fs_ref| / e of the fast specular term, measured
+# (profiles/shading_ranges/fastpow.txt)
+FAST_POW_KAPPA = 2.42e-7
+
+
+def fast_pow_kept(host_scene):
+    """the chooser's rule (scene_flatten.h fast_pow_in_bar), restated: the fast specular path stays while
+    2 kappa * max over the materials of |phong * specular| * largest |colour channel| * Lambda <= TOL"""
+    d = host_scene.desc.contents
+    worst = max((abs(float(d.materials[i].phong_exp) * float(d.materials[i].specular)) * max(abs(c) for c in d.materials[i].color.tup())
+                 for i in range(d.n_materials)), default=0.0)
+    return 2.0 * FAST_POW_KAPPA * worst * light_scale(host_scene) <= TOL
+
+
+def _quad(x0, x1, y, z0, z1):
+    return [[[x0, y, z0], [x1, y, z0], [x1, y, z1]], [[x0, y, z0], [x1, y, z1], [x0, y, z1]]]
+
+
+# family 1, occluder stacks: sheets from the floor upwards, (kind, transparency).  "meshA" / "meshB": one quad of that mesh per
+# entry — several entries of one name are several quads of ONE mesh, which share its material; "sphere": two crossings;
+# "plane": horizontal and unbounded, so every floor point lies under it and the counts of such a stack start at 1.
+# gaps: vertical distance to the sheet below (default 0.4); light_above: the point light sits above that many sheets.
+STACK_CASES = {
+    "0.75x4": dict(sheets=[("triangle", 0.75), ("meshA", 0.75), ("meshB", 0.75), ("meshA", 0.75)]),   # the sum IS 1.0 at sheet 4
+    "0.5x2": dict(sheets=[("triangle", 0.5), ("meshA", 0.5)]),
+    "0.9x12": dict(sheets=[("meshA", 0.9)] * 12),           # twelve quads of one mesh; the f32 sum of 1 - 0.9f
+    "0.7x4": dict(sheets=[("triangle", 0.7), ("meshA", 0.7), ("meshA", 0.7), ("plane", 0.7)]),   # passes 1 between sheets
+    "1.0x5": dict(sheets=[("triangle", 1.0), ("meshA", 1.0), ("meshB", 1.0), ("sphere", 1.0)]),   # never reaches 1
+    "1.5x3": dict(sheets=[("meshA", 1.5), ("meshB", 1.5), ("triangle", 1.5)]),   # negative intensity, factor above 1
+    "1e-7x2": dict(sheets=[("triangle", 1e-7), ("meshA", 1e-7)]),   # 1 - 1e-7 rounds below 1: an ordered loop, no bounce
+    "mixed": dict(sheets=[("triangle", 0.9), ("meshA", 0.2), ("meshB", 0.6)]),
+    "mixed_reversed": dict(sheets=[("triangle", 0.6), ("meshA", 0.2), ("meshB", 0.9)]),
+    "close": dict(sheets=[("triangle", 0.6), ("meshA", 0.6)], gaps=[None, 5e-4]),   # the restart at last_hit + 1e-3 skips the second
+    # the point light between sheets 2 and 3, over the staircase's second step, so that the floor lies under 0, 1 or 2 on its way
+    "light_between": dict(sheets=[("triangle", 0.75), ("meshA", 0.75), ("meshB", 0.75), ("meshA", 0.75)], gaps=[None, 0.4, 1.2, 0.4],
+                          light_above=2, light_x=-1.0),
+}
+# the sum is exactly 1.0 at the second sheet and a factor above 1 follows: a loop that went on at == 1.0 would come back below 1
+STACK_CASES["exact_then_negative"] = dict(sheets=[("triangle", 0.5), ("meshA", 0.5), ("meshB", 1.5)])
+# two unbounded, slightly tilted sheets, the first between 1.06e-3 and 1.94e-3 above the floor, the second 1e-3 above the first,
+# under a vertical sun: the second is met at t1 + 1e-3 to within a few float32 ulps, t1 changing from pixel to pixel.  For t1 in
+# [2^-10, 2^-9) the float sum t1 + 1e-3f is a tie for every other t1 while the DOUBLE sum t1 + 1e-3, narrowed once, never is:
+# whether the loop sees the second sheet depends, on some pixels, on the restart being the double sum.
+# (No camera fits beneath it: this case has the upper camera only, and no point light.)
+STACK_CASES["restart_step"] = dict(sheets=[("plane", 0.5), ("plane", 0.5)], y0=1.5e-3, gaps=[None, 1e-3], sun=[0.0, -1.0, 0.0], plane_normal=[1.5e-4, 1.0, 5e-5],
+                                   cameras=("above",), no_point=True)
+STACK_CAMERAS = ("below", "above")
+
+
+def stack_cameras(name):
+    return STACK_CASES[name].get("cameras", STACK_CAMERAS)
+STACK_FLOOR = 0   # the floor's object index in every stack scene
+STACK_Y0 = 2.0    # height of the lowest sheet; the lower camera sits beneath it
+
+
+def stack_crossings(name):
+    """occluder crossings of a vertical ray through the whole stack (a sphere counts twice)"""
+    return sum(2 if kind == "sphere" else 1 for kind, _ in STACK_CASES[name]["sheets"])
+
+
+def stack_partial_sums(transparencies):
+    """the shadow loop's float32 running sum of 1 - transparency, sheet after sheet (no early exit)"""
+    s, out = f32(0.0), []
+    for t in transparencies:
+        s = f32(s + (f32(1.0) - f32(t)))
+        out.append(s)
+    return out
+
+
+def first_full_sheet(transparencies):
+    """1-based index of the sheet at which the running sum first reaches 1.0f, or None"""
+    return next((i + 1 for i, s in enumerate(stack_partial_sums(transparencies)) if s >= f32(1.0)), None)
+
+
+def stack_scene_json(tmp_path, name, camera, w=SHADE_W, h=SHADE_H):
+    """(scene JSON, bounces).  An opaque matte floor y = 0, a point light and a sun above it, and between them the sheets of
+    STACK_CASES[name]: flat sheet j of n covers x >= -1.5 + 3 j / n, so the floor under x in step j lies under j of them (a
+    sphere over the last two steps adds two).  camera "below": under the lowest sheet, looking at the floor, so only
+    shadow rays traverse the stack; "above": looking down through it, bounces = min(6, crossings)."""
+    from cutrace_amd import scenes
+    case = STACK_CASES[name]
+    sheets = case["sheets"]
+    gaps = case.get("gaps") or [None] * len(sheets)
+    n_flat = sum(1 for kind, _ in sheets if kind in ("triangle", "meshA", "meshB"))
+    mats = [_solid((0.9, 0.85, 0.8))]
+    objs = [{"type": "plane", "point": [0, 0, 0], "normal": [0, 1, 0], "material": 0}]
+    mesh_tris, mesh_mat, heights = {}, {}, []
+    y, j = case.get("y0", STACK_Y0), 0
+    for i, (kind, tr) in enumerate(sheets):
+        if i:
+            y += 0.4 if gaps[i] is None else gaps[i]
+        heights.append(y)
+        if kind in mesh_tris:
+            assert mats[mesh_mat[kind]]["transparency"] == float(tr), "the quads of one mesh share its material"
+        else:
+            mats.append(_solid((0.3 + 0.1 * (i % 5), 0.8 - 0.1 * (i % 4), 0.5), specular=0.5, phong=30.0, transparency=tr))
+        m = len(mats) - 1
+        x0 = -1.5 + 3.0 * j / max(n_flat, 1)
+        if kind == "triangle":
+            objs.append({"type": "triangle", "p1": [x0, y, -9.0], "p2": [x0, y, 9.0], "p3": [x0 + 18.0, y, 0.0], "material": m})
+            j += 1
+        elif kind in ("meshA", "meshB"):
+            if kind not in mesh_tris:
+                mesh_tris[kind], mesh_mat[kind] = [], m
+                objs.append({"type": "mesh", "file": str(tmp_path / f"stack_{name}_{kind}.stl"), "material": m})
+            mesh_tris[kind] += _quad(x0, 5.0, y, -4.0, 4.0)
+            j += 1
+        elif kind == "sphere":
+            objs.append({"type": "sphere", "center": [0.5, y + 1.0, 1.4], "radius": 0.9, "material": m})
+            y += 2.0
+        else:
+            objs.append({"type": "plane", "point": [0, y, 0], "normal": case.get("plane_normal", [0, 1, 0]), "material": m})
+    for kind, tris in mesh_tris.items():
+        scenes.write_stl(str(tmp_path / f"stack_{name}_{kind}.stl"), np.asarray(tris, f32))
+    top = y
+    above = case.get("light_above")
+    ly = top + 6.0 if above is None else 0.5 * (heights[above - 1] + heights[above])
+    lights = [{"type": "point", "point": [case.get("light_x", -0.4), ly, 0.5], "color": [0.9, 0.9, 0.9]},
+              {"type": "sun", "direction": case.get("sun", [0.15, -1.0, -0.1]), "color": [0.5, 0.5, 0.5]}][1 if case.get("no_point") else 0:]
+    if camera == "below":
+        cam, bounces = _camera((-3.5, STACK_Y0 - 0.2, 2.5), (-1.2, 0.0, 0.8), w=w, h=h), 2
+    else:
+        cam, bounces = _camera((-0.2, top + 3.0, 0.4), (-0.19, 0.0, 0.4), up=(0, 0, -1), w=w, h=h), min(6, stack_crossings(name))
+    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs}), bounces
+
+
+# family 2, bounce thresholds: reflect, transparency, or both of one material take each of these values
+_E6 = f32(1e-6)   # below the double 1e-6 the reference compares with: off; the next float up is on
+THRESHOLD_VALUES = tuple(float(f32(v)) for v in (0.0, -0.0, 1e-7, _E6, np.nextafter(_E6, f32(1.0)), 0.25, 1.0, 1.5, -0.5))   # float32 values
+THRESHOLD_MODES = ("reflect", "transparency", "both")
+THRESHOLD_BOUNCES = (0, 1, 4)
+THRESHOLD_MATERIAL = 2
+THR_W, THR_H = 32, 24
+
+
+def threshold_room_json(mode, value, w=THR_W, h=THR_H):
+    """hall_of_mirrors_json closed to a room (a back wall, a ceiling, a wall behind the camera; the point light is inside,
+    the sun is shut out); the middle sphere's material gets `value` as reflect, transparency or both"""
+    sc = json.loads(hall_of_mirrors_json(w, h))
+    m = sc["materials"][THRESHOLD_MATERIAL]
+    m["reflect"], m["transparency"] = 0.0, 0.0
+    for key in (("reflect", "transparency") if mode == "both" else (mode,)):
+        m[key] = float(value)
+    sc["objects"] += [{"type": "plane", "point": [0, 0, -3], "normal": [0, 0, 1], "material": 1},
+                      {"type": "plane", "point": [0, 3, 0], "normal": [0, -1, 0], "material": 1},
+                      {"type": "plane", "point": [0, 0, 6], "normal": [0, 0, -1], "material": 1}]
+    return json.dumps(sc)
+
+
+# family 3, the phong exponent
+PHONG_EXPONENTS = (0.0, 0.5, 1.0, 2.0, 32.0, 300.0, 1000.0, 3000.0, 10000.0, 100000.0)
+PHONG_LIGHTS = ("point", "sun")
+PHONG_FRAME_MAX = 3000.0          # plain camera frames up to here: above it the highlight is narrower than a pixel
+PHONG_THETAS = np.concatenate([[0.0], np.logspace(-5, np.log10(0.35), 15)])   # half vector off the normal by these angles
+PHONG_POINTS = 72                 # 24 per surface: the plane, the sphere, the quad mesh
+PHONG_RAYS_W, PHONG_RAYS_H = 48, 24   # the constructed rays as a lens frame: 72 * 16 = 48 * 24
+_PHONG_POINT = np.array([0.5, 8.0, 3.0])
+_PHONG_SUN = np.array([-0.05, -1.0, -0.35])
+_PHONG_SPHERE = (np.array([-1.6, 0.2, 0.0]), 0.8)
+_PHONG_QUAD = np.array([[0.8, -0.3, 1.0], [2.4, -0.5, 0.6], [2.6, 0.3, -0.8], [1.0, 0.5, -0.4]])   # a planar quad facing the lights
+
+
+def _phong_quad_tris():
+    """the quad as two triangles, wound so that the reference's normal (ray_ref.tri_normal) faces the lights"""
+    from tests import ray_ref
+    q = _PHONG_QUAD.copy()
+    q[3] = q[0] + (q[2] - q[1])   # a parallelogram: planar
+    q = q.astype(f32)
+    tris = np.array([[q[0], q[1], q[2]], [q[0], q[2], q[3]]], f32)
+    if ray_ref.tri_normal(tris[0, 0], tris[0, 1], tris[0, 2])[1] < 0:
+        tris = tris[:, ::-1].copy()
+    return tris
+
+
+def phong_scene_json(tmp_path, e, light, w=SHADE_W, h=SHADE_H):
+    """a plane, a sphere and a quad mesh of ONE material (specular 1, colour (1, 1, 1), phong e), one light of colour (1, 1, 1)"""
+    from cutrace_amd import scenes
+    stl = str(tmp_path / "phong_quad.stl")
+    scenes.write_stl(stl, _phong_quad_tris())
+    c, r = _PHONG_SPHERE
+    objs = [{"type": "plane", "point": [0, -1, 0], "normal": [0, 1, 0], "material": 0},
+            {"type": "sphere", "center": [float(x) for x in c], "radius": r, "material": 0},
+            {"type": "mesh", "file": stl, "material": 0},
+            # a triangle that turns its back on the camera and on the light: there max(0, n.h) is 0, and 0^e is 1 at e = 0
+            {"type": "triangle", "p1": [0.6, 0.9, -1.5], "p2": [-0.6, 0.9, -1.5], "p3": [0.0, 1.9, -1.5], "material": 0}]
+    lights = [{"type": "point", "point": [float(x) for x in _PHONG_POINT], "color": [1, 1, 1]} if light == "point" else
+              {"type": "sun", "direction": [float(x) for x in _PHONG_SUN], "color": [1, 1, 1]}]
+    cam = _camera((0.3, 2.5, 5.0), (0.2, -0.4, 0.0), w=w, h=h)
+    return json.dumps({"camera": cam, "lights": lights, "materials": [_solid((1, 1, 1), specular=1.0, phong=e)], "objects": objs})
+
+
+def phong_rays(light, seed=5):
+    """(origins, directions), float32 (PHONG_POINTS * len(PHONG_THETAS), 3): per surface point p with normal n and unit
+    direction l to the light, and per angle theta of PHONG_THETAS, the half vector h is n turned by theta about a random
+    axis, the view direction v = 2 (l.h) h - l, the ray starts at p + 3 v and runs along -v.  Ray k * 16 + i: point k, angle i."""
+    rng = np.random.RandomState(seed)
+    tris = _phong_quad_tris().astype(np.float64)
+    qn = np.cross(tris[0, 1] - tris[0, 0], tris[0, 2] - tris[0, 0])
+    qn = qn / np.linalg.norm(qn) * (1 if qn[1] > 0 else -1)
+    c, r = _PHONG_SPHERE
+    pts = []
+    for k in range(PHONG_POINTS):
+        kind = k % 3
+        if kind == 0:
+            p, n = np.array([rng.uniform(-3, 3), -1.0, rng.uniform(-1.5, 2.5)]), np.array([0.0, 1.0, 0.0])
+        elif kind == 1:
+            to_l = _PHONG_POINT - c if light == "point" else -_PHONG_SUN
+            n = to_l / np.linalg.norm(to_l) + rng.uniform(-0.3, 0.3, 3)   # within about 25 degrees of the light
+            n = n / np.linalg.norm(n)
+            p = c + r * n
+        else:
+            a, b = rng.uniform(0.15, 0.85, 2)
+            p, n = tris[0, 0] + a * (tris[0, 1] - tris[0, 0]) + b * (tris[1, 2] - tris[0, 0]), qn
+        pts.append((p, n))
+    o, d = [], []
+    for p, n in pts:
+        l = (_PHONG_POINT - p) if light == "point" else -_PHONG_SUN
+        l = l / np.linalg.norm(l)
+        t1 = np.cross(n, [1.0, 0.0, 0.0] if abs(n[0]) < 0.9 else [0.0, 1.0, 0.0])
+        t1 = t1 / np.linalg.norm(t1)
+        t2 = np.cross(n, t1)
+        for th in PHONG_THETAS:
+            phi = rng.uniform(0, 2 * np.pi)
+            for turn in (0.0, np.pi):   # the axis that leaves the view direction further above the surface
+                hv = np.cos(th) * n + np.sin(th) * (np.cos(phi + turn) * t1 + np.sin(phi + turn) * t2)
+                v = 2.0 * np.dot(l, hv) * hv - l
+                if turn == 0.0 or np.dot(n, v) > best[0]:
+                    best = (np.dot(n, v), v)
+            v = best[1]
+            assert np.dot(n, v) > 0.05, "a view direction below the surface"
+            o.append(p + 3.0 * v)
+            d.append(-v)
+    return np.asarray(o, f32), np.asarray(d, f32)
+
+
+# family 4, lights and ambient
+def _many_lights(n, seed=2):
+    rng = np.random.RandomState(seed)
+    out = []
+    for i in range(n):
+        col = [float(x) for x in rng.uniform(0.05, 0.4, 3)]
+        if i % 2 == 0:
+            out.append({"type": "point", "point": [float(x) for x in rng.uniform([-3, 1, -1], [3, 5, 4])], "color": col})
+        else:
+            out.append({"type": "sun", "direction": [float(x) for x in rng.uniform([-1, -1, -1], [1, -0.2, 1])], "color": col})
+    return out
+
+
+def _sun(j):
+    s = float(pow2(j))
+    return [{"type": "sun", "direction": [-0.3 * s, -1.0 * s, -0.25 * s], "color": [0.6, 0.6, 0.5]},
+            {"type": "point", "point": [1.5, 2.5, 2.0], "color": [0.3, 0.3, 0.4]}]
+
+
+_FAR = float(pow2(20))
+LIGHT_CASES = {
+    **{f"n{n}": dict(lights=_many_lights(n)) for n in (0, 1, 2, 3, 8, 33)},
+    "colours": dict(lights=[{"type": "point", "point": [1.5, 2.5, 2.0], "color": [0, 0, 0]},
+                            {"type": "sun", "direction": [-0.3, -1.0, -0.2], "color": [64.0, 32.0, 16.0]},
+                            {"type": "point", "point": [-1.0, 3.0, 1.5], "color": [0.5, -0.7, 0.2]}]),
+    "sun_2^-10": dict(lights=_sun(-10)), "sun_1": dict(lights=_sun(0)), "sun_2^10": dict(lights=_sun(10)),
+    "point_2^20_away": dict(lights=[{"type": "point", "point": [0.25 * _FAR, 0.75 * _FAR, 0.5 * _FAR], "color": [0.8, 0.8, 0.8]}]),
+    "point_2e-3_above_the_floor": dict(lights=[{"type": "point", "point": [1.5, -1.0 + 2e-3, 1.0], "color": [0.8, 0.8, 0.8]},
+                                               {"type": "sun", "direction": [-0.3, -1.0, -0.2], "color": [0.3, 0.3, 0.3]}]),
+    "point_inside_the_sphere": dict(lights=[{"type": "point", "point": [0.35, 0.1, 0.05], "color": [0.8, 0.8, 0.8]},
+                                            {"type": "sun", "direction": [-0.3, -1.0, -0.2], "color": [0.3, 0.3, 0.3]}]),
+    "point_inside_the_glass_sphere": dict(lights=[{"type": "point", "point": [0.35, 0.1, 0.05], "color": [0.8, 0.8, 0.8]}], glass=0.5),
+    "point_behind_the_wall": dict(lights=[{"type": "point", "point": [-3.5, 0.5, 0.0], "color": [0.8, 0.8, 0.8]}]),
+    **{f"ambient_{a}": dict(lights=_many_lights(2), ambient=a) for a in (0.0, 1.0, 2.5, -0.25)},
+}
+LIGHT_SUN_LENGTH_CASES = ("sun_2^-10", "sun_1", "sun_2^10")   # one frame, bit for bit: v / |v| does not see a power of two
+
+
+def lights_scene_json(tmp_path, name, w=SHADE_W, h=SHADE_H):
+    """a reflecting floor, a sphere (opaque, or transmitting `glass`), an opaque wall (a quad mesh) at x = -2.5, and the lights
+    and the ambient factor of LIGHT_CASES[name]"""
+    from cutrace_amd import scenes
+    case = LIGHT_CASES[name]
+    stl = str(tmp_path / "lights_wall.stl")
+    scenes.write_stl(stl, np.asarray([[[-2.5, -1, -2], [-2.5, -1, 2], [-2.5, 2, 2]], [[-2.5, -1, -2], [-2.5, 2, 2], [-2.5, 2, -2]]], f32))
+    mats = [_solid((0.7, 0.6, 0.5), specular=0.3, reflect=0.2, phong=20.0),
+            _solid((0.3, 0.6, 0.9), specular=0.5, phong=40.0, transparency=case.get("glass", 0.0)),
+            _solid((0.8, 0.3, 0.3), specular=0.2, phong=5.0)]
+    objs = [{"type": "plane", "point": [0, -1, 0], "normal": [0, 1, 0], "material": 0},
+            {"type": "sphere", "center": [0.3, 0.0, 0.0], "radius": 0.9, "material": 1},
+            {"type": "mesh", "file": stl, "material": 2}]
+    cam = _camera((1.0, 1.2, 5.0), (-0.5, -0.2, 0.0), w=w, h=h, ambient=case.get("ambient", 0.1))
+    return json.dumps({"camera": cam, "lights": case["lights"], "materials": mats, "objects": objs})
+
+
+# every frame case of the sweep: (family, ...) tuples, their ids, and one builder
+SHADING_FRAME_CASES = (tuple(("stack", n, c) for n in STACK_CASES for c in stack_cameras(n)) +
+                       tuple(("threshold", m, i, b) for m in THRESHOLD_MODES for i in range(len(THRESHOLD_VALUES)) for b in THRESHOLD_BOUNCES) +
+                       tuple(("phong", e, l) for e in PHONG_EXPONENTS if e <= PHONG_FRAME_MAX for l in PHONG_LIGHTS) +
+                       tuple(("lights", n) for n in LIGHT_CASES))
+
+
+def shading_case_id(case):
+    if case[0] == "threshold":
+        return f"threshold,{case[1]}={THRESHOLD_VALUES[case[2]]!r},bounces={case[3]}"
+    return ",".join(str(x) for x in case)
+
+
+def shading_case_json(tmp_path, case):
+    """(scene JSON, bounces) of a frame case"""
+    if case[0] == "stack":
+        return stack_scene_json(tmp_path, case[1], case[2])
+    if case[0] == "threshold":
+        return threshold_room_json(case[1], THRESHOLD_VALUES[case[2]]), case[3]
+    if case[0] == "phong":
+        return phong_scene_json(tmp_path, case[1], case[2]), 2
+    return lights_scene_json(tmp_path, case[1]), 3
