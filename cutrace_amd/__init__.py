@@ -37,6 +37,8 @@ RAY_OUTPUTS = ("t", "object", "prim", "point", "normal", "uv")
 SHADE_LINEAR = 1
 SHADE_EXACT_POW = 2
 SHADE_OUTPUTS = ("color", "t", "object", "normal")
+# the display planes of render_images / quantise (include/cutrace_images.h)
+IMAGE_PLANES = ("color", "depth", "normal")
 
 
 @contextlib.contextmanager
@@ -215,6 +217,88 @@ class DeviceScene:
         return dict(depth=depth, color=color, normal=normal, ray_count=int(stats.ray_count),
                     kernel_ms=stats.kernel_ms, total_ms=stats.total_ms, max_depth=float(stats.max_depth),
                     rows=int(stats.rows))
+
+    def render_images(self, fudge=1e-3, bounces=5, rows=None, samples=1, planes=IMAGE_PLANES, pinned=False):
+        """ctr_render_images (include/cutrace_images.h): the frame quantised to display bytes on the GPU, as the host's
+        ctr_quantise_color / _depth / _normal quantise what render() returns — byte for byte — but only 3 bytes per pixel and
+        plane cross to the host.  Returns a dict with a (rows, w, 3) uint8 numpy array per name in `planes` (a non-empty
+        subset of "color", "depth", "normal"; depth is replicated to R = G = B) plus render()'s stats.  pinned=True: the
+        arrays are page-locked (torch's pinned memory), their copies are queued instead of staged."""
+        samples = self._samples(samples)
+        planes = tuple(planes)
+        if not planes or len(set(planes)) != len(planes) or any(k not in IMAGE_PLANES for k in planes):
+            raise ValueError(f"planes: a non-empty subset of {IMAGE_PLANES}, got {planes}")
+        L = _lib.hip_lib()
+        r = make_rows(self.h, rows)
+        n = rows_count(self.h, rows)
+        if pinned:
+            import torch
+            keep = {k: torch.empty(n, self.w, 3, dtype=torch.uint8).pin_memory() for k in planes}
+            out = {k: v.numpy() for k, v in keep.items()}
+        else:
+            out = {k: np.empty((n, self.w, 3), np.uint8) for k in planes}
+        ptr = {k: (out[k].ctypes.data if k in out else None) for k in IMAGE_PLANES}
+        stats = RenderStats()
+        st = L.ctr_render_images(self._h, C.c_float(fudge), bounces, samples, C.byref(r), ptr["depth"], ptr["color"],
+                                 ptr["normal"], C.byref(stats))
+        if st:
+            raise RuntimeError(f"ctr_render_images failed ({st}): {L.ctr_last_error().decode()}")
+        return dict(out, ray_count=int(stats.ray_count), kernel_ms=stats.kernel_ms, total_ms=stats.total_ms,
+                    max_depth=float(stats.max_depth), rows=int(stats.rows))
+
+    def quantise(self, depth=None, color=None, normal=None, counters=None, max_depth=None, out=None, stream=None):
+        """ctr_quantise_device (include/cutrace_images.h): float planes on the scene's device to display bytes there — what
+        follows render_device, render_device_batch and render_lens.  depth (..., ) and color / normal (..., 3): contiguous
+        float32 torch tensors on the scene's device, of the same number of pixels; at least one.  With depth, exactly one
+        of `counters` (the 16-word int64 block the render accumulated into, read on the device: no synchronisation) and
+        `max_depth` (a float).  out: a dict of contiguous uint8 tensors (pixels * 3 bytes each) to write instead of new
+        ones.  Returns a dict of uint8 tensors of shape (..., 3) under the names given.  Asynchronous on `stream` (a
+        torch.cuda.Stream; default: torch's current stream of the scene's device)."""
+        import torch
+        dev = self._torch_device()
+        given = {k: v for k, v in (("depth", depth), ("color", color), ("normal", normal)) if v is not None}
+        if not given:
+            raise ValueError("quantise: at least one of depth, color, normal")
+        if depth is not None and (counters is None) == (max_depth is None):
+            raise ValueError("quantise: depth needs exactly one of counters and max_depth")
+        px = None
+        for k, v in given.items():
+            if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype != torch.float32 or not v.is_contiguous():
+                raise ValueError(f"{k}: expected a contiguous float32 tensor on {dev}")
+            if k != "depth" and (v.dim() < 1 or v.shape[-1] != 3):
+                raise ValueError(f"{k}: expected shape (..., 3), got {tuple(v.shape)}")
+            n = v.numel() if k == "depth" else v.numel() // 3
+            if px is not None and n != px:
+                raise ValueError(f"{k}: {n} pixels, the other planes have {px}")
+            px = n
+        if counters is not None and (not isinstance(counters, torch.Tensor) or counters.device != dev or counters.dtype != torch.int64
+                                     or counters.numel() < 2 or not counters.is_contiguous()):
+            raise ValueError(f"counters: expected a contiguous int64 tensor of at least 2 words on {dev}")
+        res = {}
+        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            q = _lib.ImagePlanes()
+            q.n_pixels = px
+            for k, v in given.items():
+                shape = (tuple(v.shape) + (3,)) if k == "depth" else tuple(v.shape)
+                if out is not None and k in out:
+                    o = out[k]
+                    if not isinstance(o, torch.Tensor) or o.device != dev or o.dtype != torch.uint8 or not o.is_contiguous() or o.numel() != 3 * px:
+                        raise ValueError(f"out[{k!r}]: expected a contiguous uint8 tensor of {3 * px} bytes on {dev}")
+                else:
+                    o = torch.empty(shape, dtype=torch.uint8, device=dev)
+                res[k] = o
+                setattr(q, {"depth": "d_depth", "color": "d_color3", "normal": "d_normal3"}[k], v.data_ptr() or None)
+                setattr(q, {"depth": "d_depth8", "color": "d_color8", "normal": "d_normal8"}[k], o.data_ptr() or None)
+            if depth is not None:
+                if counters is not None:
+                    q.d_counters = counters.data_ptr()
+                else:
+                    q.max_depth = float(max_depth)
+            if px:
+                st = _lib.hip_lib().ctr_quantise_device(self.device, C.byref(q), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                if st:
+                    raise RuntimeError(f"ctr_quantise_device failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
+        return res
 
     def render_uv(self, fudge=1e-3, bounces=5, rows=None):
         """ctr_render_uv: the three buffers plus `uv` (n, w, 2): ray_cast's texture coordinates of the primary hit."""

@@ -86,6 +86,13 @@ class Lens(C.Structure):
                 ("d_dir", C.c_void_p)]
 
 
+class ImagePlanes(C.Structure):
+    """ctr_image_planes (include/cutrace_images.h)"""
+    _fields_ = [("n_pixels", C.c_uint64), ("d_depth", C.c_void_p), ("d_color3", C.c_void_p), ("d_normal3", C.c_void_p),
+                ("d_depth8", C.c_void_p), ("d_color8", C.c_void_p), ("d_normal8", C.c_void_p), ("d_counters", C.c_void_p),
+                ("max_depth", C.c_float), ("reserved", C.c_uint32)]
+
+
 HOST_SYMBOLS = [
     "ctr_host_scene_load", "ctr_host_scene_parse", "ctr_host_scene_free", "ctr_host_scene_desc",
     "ctr_host_scene_set_size", "ctr_host_scene_set_material", "ctr_stl_read", "ctr_stl_write",
@@ -110,6 +117,8 @@ RAY_SYMBOLS = ["ctr_cast_rays", "ctr_shade_rays"]
 AA_SYMBOLS = ["ctr_render_aa", "ctr_render_device_aa"]
 # include/cutrace_lens.h
 LENS_SYMBOLS = ["ctr_render_device_lens"]
+# include/cutrace_images.h
+IMAGES_SYMBOLS = ["ctr_quantise_device", "ctr_render_images"]
 
 _host = None
 _hip = None
@@ -208,6 +217,9 @@ def hip_lib():
                                       C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
             "ctr_render_device_lens": ([C.c_void_p, C.c_float, C.c_int, C.POINTER(Lens), C.POINTER(Rows), C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+            "ctr_quantise_device": ([C.c_int, C.POINTER(ImagePlanes), C.c_void_p], C.c_int),
+            "ctr_render_images": ([C.c_void_p, C.c_float, C.c_int, C.c_uint32, C.POINTER(Rows), C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.POINTER(RenderStats)], C.c_int),
         }
         for name, (argt, rest) in opt.items():
             if hasattr(L, name):

@@ -19,7 +19,9 @@
 #include "ctr_internal.h"
 #include "cutrace_aa.h"
 #include "cutrace_amd.h"
+#include "cutrace_images.h"
 #include "cutrace_lens.h"
+#include "frame_images.h"
 #include "guard.h"
 #include "kernel_choice.h"
 #include "scene_device.h"
@@ -412,6 +414,33 @@ int copy_out(ctr_scene *s, const RenderLaunch &L, const HostFrame &o, size_t px)
   return CTR_OK;
 }
 
+// ---- display frames (include/cutrace_images.h) ----
+// the caller's byte planes of ctr_render_images (null: not asked for)
+struct HostImages { uint8_t *depth8, *color8, *normal8; };
+
+// In place of copy_out: the frame the launch left in d_out is quantised behind it on the same stream, with the largest depth
+// the launch itself accumulated in d_counters, and only the byte planes asked for leave the device: one copy per plane,
+// queued where the destination is page-locked, staged by the runtime where it is not.
+int images_out(ctr_scene *s, const RenderLaunch &L, const HostImages &o, size_t px) {
+  if (int st = grow(px, s->img_px, {{(void **)&s->d_img, 9, false}})) return st;
+  ImagesLaunch Q{};
+  Q.n = px;
+  Q.counters = s->d_counters;
+  if (o.depth8) { Q.depth = L.depth; Q.depth8 = s->d_img; }
+  if (o.color8) { Q.color = L.color; Q.color8 = s->d_img + 3 * px; }
+  if (o.normal8) { Q.normal = L.normal; Q.normal8 = s->d_img + 6 * px; }
+  if (int e = ctr_launch_images(Q, nullptr)) return hip_fail((hipError_t)e, "quantise kernel launch");
+  auto out = [&](uint8_t *dst, const uint8_t *src) -> hipError_t {
+    if (!dst) return hipSuccess;
+    if (is_pinned(dst) && is_pinned(dst + 3 * px - 1)) return hipMemcpyAsync(dst, src, 3 * px, hipMemcpyDeviceToHost, nullptr);
+    return hipMemcpy(dst, src, 3 * px, hipMemcpyDeviceToHost);
+  };
+  HIP_TRY(out(o.depth8, Q.depth8));
+  HIP_TRY(out(o.color8, Q.color8));
+  HIP_TRY(out(o.normal8, Q.normal8));
+  return CTR_OK;
+}
+
 // A direct launch is over and h_groups holds its counters: did the whole frame reach the caller's buffers?
 int check_delivery(ctr_scene *s, const RenderLaunch &L, const HostFrame &o, size_t spx, size_t n_groups) {
   // every group of tiles must have counted all its tiles, or its pixels never left for the caller's buffers
@@ -575,7 +604,7 @@ void ctr_scene_destroy(ctr_scene *s) {
   (void)hipSetDevice(s->device);
   for (const SceneArray &a : scene_arrays(s, s->flat))
     if (*a.dev) (void)hipFree(*a.dev);
-  for (void *p : {(void *)s->d_cams, (void *)s->d_out, (void *)s->d_uv, (void *)s->d_groups, (void *)s->d_counters, (void *)s->d_shards,
+  for (void *p : {(void *)s->d_cams, (void *)s->d_out, (void *)s->d_uv, (void *)s->d_img, (void *)s->d_groups, (void *)s->d_counters, (void *)s->d_shards,
                   (void *)s->d_cost, (void *)s->d_order})
     if (p) (void)hipFree(p);
   if (s->h_counters) (void)hipHostFree(s->h_counters);
@@ -719,7 +748,7 @@ int ctr_render_device_lens(ctr_scene *s, float fudge, int bounces, const ctr_len
                                    " samples of the " + std::to_string(s->cam.w) + " x " + std::to_string(s->cam.h) + " frame are " + std::to_string(want));
   const void *const ptrs[] = {lens->d_origin, lens->d_dir};
   const char *const names[] = {"d_origin", "d_dir"};
-  if ((st = check_device_pointers(s, who, ptrs, names, 2))) return st;
+  if ((st = check_device_pointers(s->device, who, ptrs, names, 2))) return st;
   return render_device(s, fudge, bounces, rows, 0, 1, 0, 0, d_depth, d_color3, d_normal3, d_counters, hip_stream, ls, lens);
 }
 
@@ -729,8 +758,9 @@ int ctr_render_device(ctr_scene *s, float fudge, int bounces, const ctr_rows *ro
 }
 
 // ss_log2 != 0: a supersampled frame (ctr_render_aa, whose checks have passed): rows, px and the buffers are the output's
+// images: the frame leaves as byte planes (ctr_render_images): chosen for as a render into pageable memory, `out` empty
 static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, const HostFrame &out, ctr_render_stats *stats,
-                       bool count, unsigned long long *aabb_tris, uint32_t ss_log2 = 0) {
+                       bool count, unsigned long long *aabb_tris, uint32_t ss_log2 = 0, const HostImages *images = nullptr) {
   auto t0 = std::chrono::high_resolution_clock::now();
   int st = check_args(s, bounces);
   if (st) return st;
@@ -743,7 +773,7 @@ static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *r
   HostFrame z{};
   if (ss_log2 && (st = aa_scale(L, ss_log2))) return st;
   // an empty selection launches nothing and has no fourth output: it is chosen for as a plain render
-  KernelFacts facts = kernel_facts(s, count ? KE_COUNT : ss_log2 ? KE_HOST_SS : out.uv2 && px ? KE_UV : KE_HOST, bounces, true);
+  KernelFacts facts = kernel_facts(s, count ? KE_COUNT : ss_log2 ? KE_HOST_SS : out.uv2 && px ? KE_UV : KE_HOST, bounces, !images);
   if (!px) facts.user &= ~CTR_VAR_IGNORE_TRANSPARENT;
   KernelChoice choice = choose_kernel(facts);
   // (the caller's buffers are looked at only where everything else allows delivery by the kernel)
@@ -770,7 +800,7 @@ static int render_host(ctr_scene *s, float fudge, int bounces, const ctr_rows *r
   int e = ctr_launch_render(L, nullptr);
   if (e) return hip_fail((hipError_t)e, "render kernel launch");
   HIP_TRY(hipEventRecord(s->ev1, nullptr));
-  if (px && !direct && (st = copy_out(s, L, out, px))) return st;
+  if (px && !direct && (st = images ? images_out(s, L, *images, px) : copy_out(s, L, out, px))) return st;
   HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
   const size_t n_groups = direct ? (size_t)ctr_staging_groups(L) : 0;
   if (direct) HIP_TRY(hipMemcpyAsync(s->h_groups, s->d_groups, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
@@ -789,6 +819,36 @@ int ctr_render_aa(ctr_scene *s, float fudge, int bounces, uint32_t samples, cons
   uint32_t ls = 0;
   if (int st = aa_precheck(s, KE_HOST_SS, bounces, samples, rows, ls)) return st;
   return render_host(s, fudge, bounces, rows, {depth, color3, normal3, nullptr}, stats, false, nullptr, ls);
+}
+
+// include/cutrace_images.h
+int ctr_render_images(ctr_scene *s, float fudge, int bounces, uint32_t samples, const ctr_rows *rows, uint8_t *depth8,
+                      uint8_t *color8, uint8_t *normal8, ctr_render_stats *stats) {
+  if (!depth8 && !color8 && !normal8) return fail(CTR_E_INVALID, "ctr_render_images: no destination plane");
+  uint32_t ls = 0;
+  if (int st = aa_precheck(s, KE_HOST_SS, bounces, samples, rows, ls)) return st;
+  const HostImages images{depth8, color8, normal8};
+  return render_host(s, fudge, bounces, rows, {}, stats, false, nullptr, ls, &images);
+}
+
+int ctr_quantise_device(int device, const ctr_image_planes *p, void *hip_stream) {
+  const std::string who = "ctr_quantise_device: ";
+  if (!p) return fail(CTR_E_INVALID, who + "null planes");
+  if (p->reserved) return fail(CTR_E_INVALID, who + "reserved must be 0");
+  const void *const ptrs[] = {p->d_depth, p->d_color3, p->d_normal3, p->d_depth8, p->d_color8, p->d_normal8, p->d_counters};
+  const char *const names[] = {"d_depth", "d_color3", "d_normal3", "d_depth8", "d_color8", "d_normal8", "d_counters"};
+  for (int k = 0; k < 3; k++)
+    if (!ptrs[k] != !ptrs[3 + k])
+      return fail(CTR_E_INVALID, who + (ptrs[k] ? names[k] : names[3 + k]) + " without " + (ptrs[k] ? names[3 + k] : names[k]));
+  if (!p->d_depth && !p->d_color3 && !p->d_normal3) return fail(CTR_E_INVALID, who + "no plane");
+  if (p->n_pixels == 0) return CTR_OK;
+  if (int st = check_device_pointers(device, who, ptrs, names, 7, ("device " + std::to_string(device)).c_str())) return st;
+  int cur = -1;
+  if (hipGetDevice(&cur) != hipSuccess || cur != device) HIP_TRY(hipSetDevice(device));
+  const ImagesLaunch Q{p->n_pixels, p->d_depth, p->d_color3, p->d_normal3, p->d_depth8, p->d_color8, p->d_normal8,
+                       (const unsigned long long *)p->d_counters, p->max_depth};
+  if (int e = ctr_launch_images(Q, hip_stream)) return hip_fail((hipError_t)e, "quantise kernel launch");
+  return CTR_OK;
 }
 
 int ctr_render_uv(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, float *depth, float *color3,

@@ -32,8 +32,9 @@ bool is_pinned(const void *p);
 bool device_view(float *host, float **dev);
 // the scene's device becomes the calling thread's current one, unless it is already
 int use_device(const ctr_scene *s);
-// CTR_E_INVALID "<who><name> is not device memory of the scene's device" for the first non-null pointer that is not (ctr_rays.cpp)
-int check_device_pointers(const ctr_scene *s, const std::string &who, const void *const *ptrs, const char *const *names, size_t n);
+// CTR_E_INVALID "<who><name> is not device memory of <whose>" for the first non-null pointer that is not memory of `device` (ctr_rays.cpp)
+int check_device_pointers(int device, const std::string &who, const void *const *ptrs, const char *const *names, size_t n,
+                          const char *whose = "the scene's device");
 #pragma GCC visibility pop
 
 struct ctr_scene {
@@ -60,6 +61,8 @@ struct ctr_scene {
   float *d_out = nullptr;
   float *d_uv = nullptr;      // ctr_render_uv: 2 floats per pixel, allocated on first use
   size_t uv_px = 0;
+  uint8_t *d_img = nullptr;   // ctr_render_images: the three byte planes [depth8 | color8 | normal8], 9 bytes per pixel, grown on use
+  size_t img_px = 0;
   std::vector<DCam> h_cams;     // host copy of d_cams: the eyes the guard checks (refresh_linear_meshes)
   unsigned long long *h_counters = nullptr;  // pinned landing zone of the 16 counter words
   unsigned long long last_cnt[16] = {0};     // the counter words of the last host-form render

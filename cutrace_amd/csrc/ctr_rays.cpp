@@ -22,15 +22,16 @@ int check_rays(const ctr_scene *s, const std::string &who, uint64_t n_rays, cons
 }  // namespace
 
 // every pointer the kernel touches must be device memory of the scene's device (no size check is possible here)
-// (ctr_internal.h: the lens render checks its ray arrays with it)
-int check_device_pointers(const ctr_scene *s, const std::string &who, const void *const *ptrs, const char *const *names, size_t n) {
+// (ctr_internal.h: the lens render checks its ray arrays with it, ctr_quantise_device its planes)
+int check_device_pointers(int device, const std::string &who, const void *const *ptrs, const char *const *names, size_t n,
+                          const char *whose) {
   for (size_t k = 0; k < n; k++) {
     if (!ptrs[k]) continue;
     hipPointerAttribute_t at{};
-    const bool ok = hipPointerGetAttributes(&at, ptrs[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == s->device;
+    const bool ok = hipPointerGetAttributes(&at, ptrs[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == device;
     if (!ok) {
       (void)hipGetLastError();  // plain host memory: "invalid value", not an error of the stream
-      return fail(CTR_E_INVALID, who + names[k] + " is not device memory of the scene's device");
+      return fail(CTR_E_INVALID, who + names[k] + " is not device memory of " + whose);
     }
   }
   return CTR_OK;
@@ -76,7 +77,7 @@ extern "C" int ctr_cast_rays(ctr_scene *s, const ctr_ray_query *q, void *hip_str
                         q->d_normal, q->d_uv, q->d_shadow};
   const char *names[] = {"d_origin", "d_dir", "d_min_t", "d_max_t", "d_t", "d_object", "d_prim", "d_point",
                          "d_normal", "d_uv", "d_shadow"};
-  if (int st = check_device_pointers(s, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
+  if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
   if (int st = use_device(s)) return st;
   RayLaunch L{};
   L.scene = ray_scene(s);
@@ -113,7 +114,7 @@ extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_
   if (q->n_rays == 0) return CTR_OK;
   const void *ptrs[] = {q->d_origin, q->d_dir, q->d_color, q->d_t, q->d_object, q->d_normal};
   const char *names[] = {"d_origin", "d_dir", "d_color", "d_t", "d_object", "d_normal"};
-  if (int st = check_device_pointers(s, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
+  if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
   ShadeLaunch L{};
   L.scene = ray_scene(s);
   L.lights = s->d_lights;

@@ -5,9 +5,12 @@
 // Extras (ignored by anything that drives the reference): environment overrides
 //   CUTRACE_BOUNCES, CUTRACE_WIDTH, CUTRACE_HEIGHT, CUTRACE_DEVICE
 //   CUTRACE_SAMPLES=2|4|8   that many rays per axis through every pixel, averaged in the kernel (ctr_render_aa; one device only)
+//   CUTRACE_GPU_IMAGES=1    the three pictures are quantised to bytes on the GPU (ctr_render_images, cutrace_images.h) and only those
+//                           cross to the host; same three files, byte for byte (one device only; off by default)
 // because the reference has no flags (main.cu:8-12) and benchmarking needs them, and
 //   CUTRACE_DEVICES=N   row-tile the frame over the first N GPUs of the node (ctr_render_multi: one RCCL
 //                       gather to GPU 0, same three files); CUTRACE_DEVICE_LIST=0,2,... names them instead
+#include <chrono>
 #include <cstdlib>
 #include <iostream>
 #include <thread>
@@ -15,6 +18,7 @@
 
 #include "cutrace_amd.h"
 #include "cutrace_host.h"
+#include "cutrace_images.h"
 #include "grid.hpp"
 #include "render.hpp"
 
@@ -33,6 +37,26 @@ static void write_images(cutrace::grid<float> &depth_map, cutrace::grid<cutrace:
   ctr_write_colorized("./frame.jpg", &color_map.data()->x, color_map.cols(), color_map.rows());
   t_depth.join();
   t_normal.join();
+}
+
+// CUTRACE_GPU_IMAGES=1: the same three files from byte planes the GPU quantised; the writers are the encoder threads of write_images
+static int render_and_write_images(ctr_scene *scene, int bounces, uint32_t samples) {
+  auto start = std::chrono::high_resolution_clock::now();
+  uint64_t w = 0, h = 0;
+  ctr_scene_size(scene, &w, &h);
+  std::vector<unsigned char> px(9 * w * h);
+  unsigned char *depth8 = px.data(), *color8 = depth8 + 3 * w * h, *normal8 = color8 + 3 * w * h;
+  ctr_render_stats st{};
+  if (ctr_render_images(scene, 1e-3, bounces, samples, nullptr, depth8, color8, normal8, &st) != CTR_OK) return -5;
+  auto end = std::chrono::high_resolution_clock::now();
+  std::cout << "Render time was " << (size_t)st.kernel_ms << " ms; kernel time with setup/teardown was "
+            << (size_t)std::chrono::duration_cast<std::chrono::milliseconds>(end - start).count() << " ms.\n";
+  std::thread t_depth([&] { ctr_write_jpg("./depth_map.jpg", (int)w, (int)h, depth8, 90); });
+  std::thread t_normal([&] { ctr_write_jpg("./normal_map.jpg", (int)w, (int)h, normal8, 90); });
+  ctr_write_jpg("./frame.jpg", (int)w, (int)h, color8, 90);
+  t_depth.join();
+  t_normal.join();
+  return 0;
 }
 
 int main(int argc, const char **argv) {
@@ -78,6 +102,12 @@ int main(int argc, const char **argv) {
     ctr_host_scene_free(hs);
     return -4;
   }
+  const bool gpu_images = env_long("CUTRACE_GPU_IMAGES", 0) != 0;
+  if (n_dev > 1 && gpu_images) {
+    std::cerr << "CUTRACE_GPU_IMAGES applies to one device only (CUTRACE_DEVICES / CUTRACE_DEVICE_LIST name " << n_dev << ")\n";
+    ctr_host_scene_free(hs);
+    return -4;
+  }
   if (n_dev > 1) {
     ctr_multi *group = nullptr;
     if (ctr_multi_create(desc, devs.data(), (int)n_dev, &group) != CTR_OK) {
@@ -108,6 +138,13 @@ int main(int argc, const char **argv) {
   }
 
   ctr_dump_scene(desc);
+
+  if (gpu_images) {
+    const int rc = render_and_write_images(scene, (int)env_long("CUTRACE_BOUNCES", 5), (uint32_t)samples);
+    ctr_scene_destroy(scene);
+    ctr_host_scene_free(hs);
+    return rc;
+  }
 
   float max_d;
   cutrace::grid<float> depth_map;
