@@ -27,7 +27,7 @@ HOST_SRCS = [os.path.join(HOST, "scene_host.cpp"), os.path.join(HOST, "images.cp
 HIP_SRCS = [os.path.join(CSRC, "render_kernel.hip"), os.path.join(CSRC, "ctr_api.cpp"), os.path.join(CSRC, "bvh.cpp"),
             os.path.join(CSRC, "ctr_multi.hip"), os.path.join(CSRC, "ray_query.hip"), os.path.join(CSRC, "scene_flatten.cpp"),
             os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "ray_shade.hip"), os.path.join(CSRC, "ctr_rays.cpp"),
-            os.path.join(CSRC, "kernel_choice.cpp"), os.path.join(CSRC, "frame_images.hip")]
+            os.path.join(CSRC, "kernel_choice.cpp"), os.path.join(CSRC, "frame_images.hip"), os.path.join(CSRC, "tile_order.hip")]
 CLI_SRCS = [os.path.join(HOST, "main.cpp")]
 
 HOST_FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-pthread", "-Wall", "-I" + INC]

@@ -26,6 +26,7 @@
 #include "kernel_choice.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
+#include "tile_order.h"
 
 namespace {
 thread_local std::string g_err;
@@ -242,7 +243,7 @@ int attach_order(ctr_scene *s, RenderLaunch &L, bool count) {
   if (same) L.order = s->d_order;
   else {
     s->order_age = 0;
-    // a shape nothing is known about: centre-out instead of image order (render_kernel.hip first_order) — for
+    // a shape nothing is known about: centre-out instead of image order (tile_order.hip first_order) — for
     // launches large enough to have a tail and scenes heavy enough (the triangle count that also picks the 6-wave
     // build) for the ~8 us of the order kernel to pay: bunny -5.5 %, 64k bunny -2 %, C4 -2 %, but mirror.json (924
     // triangles, 0.2 ms) +4 % (profiles/r02/first_launch_centre_out.txt)

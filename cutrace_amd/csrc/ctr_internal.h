@@ -74,7 +74,7 @@ struct ctr_scene {
   size_t groups_cap = 0;
   bool poison_next_order = false;  // test hook (ctr_debug_poison_next_order)
   uint32_t last_kernel = 0;        // the KV of the most recent launch (ctr_debug_last_kernel)
-  // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling")
+  // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling"; tile_order.hip)
   uint32_t *d_cost = nullptr, *d_order = nullptr;
   uint32_t order_age = 0;  // launches of the current shape
   uint64_t order_view = 0; // camera set + first frame of the previous launch

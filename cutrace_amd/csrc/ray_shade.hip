@@ -38,7 +38,6 @@ enum : uint32_t { RS_LINEAR = 1u, RS_EXACT = 2u };
 enum { F_R = 0, F_G, F_B, F_MAT, F_PX, F_PY, F_PZ, F_DX, F_DY, F_DZ };
 enum { ACT_CAST = 0, ACT_LIGHT, ACT_BOUNCE, ACT_UNWIND };
 
-__device__ __forceinline__ V3 vmul(V3 a, V3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
 __device__ __forceinline__ void store3(float *p, size_t i, V3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
 
 template <uint32_t K>

@@ -38,8 +38,6 @@
 //    to the reference's linear walk (ties broken by file order).
 //  * shadow rays stop at the first occluder when no material is transparent.
 //  * the duplicated primary cast (kernel.hpp:52 + shading.hpp:123) is done once.
-//  * tiles are dispatched expensive-first from the costs the previous launch recorded (after_render),
-//    which removes the tail of slow waves at the end of a frame.
 //  * arguments that only the continuation or the start of a cast needs are re-read from the kernarg
 //    segment instead of living in SGPRs across the inner loops (no spill reloads by v_readlane); the
 //    build avoids SLP vectorisation (compiler-made v_pk_* cost more in shuffles than they save).
@@ -69,6 +67,9 @@
 #include "scene_device.h"
 #include "bvh.h"
 #include "kernel_choice.h"
+#include "tile_order.h"
+#include "tile_shape.h"
+#include "vec3.h"
 
 #define CADDR __attribute__((address_space(4)))
 #define BALLOT(p) __builtin_amdgcn_ballot_w64(p)
@@ -129,24 +130,9 @@ do {                                                                            
 #define CTR_MARK(n)
 #endif
 
-#ifndef CTR_TW
-#define CTR_TW 8
-#endif
-#ifndef CTR_TH
-#define CTR_TH 8
-#endif
-#ifndef CTR_WAVES_PER_WG
-#define CTR_WAVES_PER_WG 1
-#endif
 #ifndef CTR_MIN_WAVES_EU
 #define CTR_MIN_WAVES_EU 4
 #endif
-constexpr int TW = CTR_TW, TH = CTR_TH;  // pixel tile of one wave (TW*TH == 64)
-static_assert(TW * TH == 64, "one wave = one TW x TH tile");
-constexpr int WAVES_PER_WG = CTR_WAVES_PER_WG;
-constexpr int WG_THREADS = 64 * WAVES_PER_WG;
-
-struct V3 { float x, y, z; };
 typedef float float2_ __attribute__((ext_vector_type(2)));
 template <int N> struct SiteTag { static constexpr int value = N; };  // which inlined copy of a lambda (CTR_MARK ids)
 #define SITE(n) SiteTag<n>()
@@ -219,18 +205,6 @@ __device__ __forceinline__ TriR load_tri(const CADDR DTri &T) {
   return r;
 }
 
-// ---- inc/vector.hpp, same operation order -------------------------------------
-__device__ __forceinline__ V3 mk(float x, float y, float z) { V3 r; r.x = x; r.y = y; r.z = z; return r; }
-__device__ __forceinline__ V3 vadd(V3 a, V3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 vsub(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 vscale(V3 a, float f) { return mk(f * a.x, f * a.y, f * a.z); }
-__device__ __forceinline__ V3 vmul(V3 a, V3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }
-__device__ __forceinline__ float vdot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 vcross(V3 a, V3 o) {
-  return mk(a.y * o.z - a.z * o.y, a.z * o.x - a.x * o.z, a.x * o.y - a.y * o.x);
-}
-__device__ __forceinline__ float vnorm(V3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
-__device__ __forceinline__ V3 vnormalized(V3 a) { return vscale(a, 1.0f / vnorm(a)); }
 // The same two IEEE results — n = sqrtf(x) and 1.0f / n, correctly rounded — for the whole wave at about half
 // the instructions when every active lane's x lies in [2^-80, 2^80].  hipcc's correctly rounded sqrtf / division
 // wrap the arithmetic below in denormal scaling (v_div_scale, a pre-multiply by 2^32) and special-case fix-ups
@@ -269,15 +243,6 @@ __device__ __forceinline__ V3 vnormalized_n(V3 a, float &n) {
   norm_and_inverse(a.x * a.x + a.y * a.y + a.z * a.z, n, inv);
   return vscale(a, inv);
 }
-// matrix::determinant, vector.hpp:218-224 (columns c0,c1,c2)
-__device__ __forceinline__ float det3(V3 c0, V3 c1, V3 c2) {
-  float a = c0.x, b = c1.x, c = c2.x, d = c0.y, e = c1.y, f = c2.y, g = c0.z, h = c1.z, i = c2.z;
-  return a * e * i + b * f * g + c * d * h - c * e * g - a * f * h - b * d * i;
-}
-// std::min / std::max as the host-compiled reference binds the unqualified calls
-__device__ __forceinline__ float smin(float a, float b) { return (b < a) ? b : a; }
-__device__ __forceinline__ float smax(float a, float b) { return (a < b) ? b : a; }
-
 // A suspended ray_color activation (shading.hpp:116-154) lives in LDS, never in scratch:
 //   hot  fields 0..3 : rgb so far (3), material index | stage << 30 (stage 1 = waiting for the
 //                      reflection child, 2 = for the pass-through child; the material record says
@@ -359,11 +324,7 @@ static_assert(sizeof(KArgs) % 64 == 0 && offsetof(KArgs, head) % 64 == 0 && offs
 // makes 56 (scripts/pcie_store.hip).  So the tiles go to a tile-major staging area in device memory, and the wave
 // that completes a GROUP of 64/TW horizontally adjacent tiles (64 x TH pixels; a counter per group) copies the
 // group into the host buffers in runs of 256 / 768 bytes — the DMA's rate, but spread over the whole launch instead
-// of after it.  The order the tiles are dispatched in keeps the tiles of a group together (order_block).
-constexpr uint32_t GROUP_TILES = 64 / TW;
-#ifndef CTR_CHEAP_FIRST_PCT
-#define CTR_CHEAP_FIRST_PCT 25u  // order_block_groups: share of the groups, the cheapest, dispatched before the dear ones
-#endif
+// of after it.  The order the tiles are dispatched in keeps the tiles of a group together (tile_order.hip order_block).
 
 // What a lane casts its next ray for, and how deep its recursion stack is, share ONE register (a VGPR less to carry
 // through the cast loops): low 16 bits = stack depth; bit 31 = a shadow-loop cast, bit 30 = the pixel is finished,
@@ -496,10 +457,10 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     if (HOSTOUT) return (size_t)wave * 64u + l;  // tile-major staging ("Host delivery")
     if constexpr (SS) {  // the output pixel the lane's sample belongs to: (k_row / s) * (w / s) + x_id / s
       const uint32_t ls = ((const CADDR KArgs *)__builtin_amdgcn_kernarg_segment_ptr())->ss_log2;
-      if constexpr (RAYS) return (size_t)(tile_px0 + ((l / TW) >> ls) * (w >> ls) + ((l % TW) >> ls));  // (one frame: launch<KV>)
+      if constexpr (RAYS) return (size_t)(tile_px0 + ((l / TW) >> ls) * (w >> ls) + ((l % TW) >> ls));  // (one frame: launch)
       return (size_t)frame * A.frame_stride_px + (size_t)(tile_px0 + ((l / TW) >> ls) * (w >> ls) + ((l % TW) >> ls));
     }
-    // (RAYS: one frame, launch<KV> checks; the frame offset, computed before the loop for a masked pixel, would be kept for the
+    // (RAYS: one frame, launch checks; the frame offset, computed before the loop for a masked pixel, would be kept for the
     //  stores inside it — in scratch, in the 6-wave build)
     if constexpr (RAYS) return (size_t)(tile_px0 + (l / TW) * w + (l % TW));
     return (size_t)frame * A.frame_stride_px + (size_t)(tile_px0 + (l / TW) * w + (l % TW));
@@ -1999,7 +1960,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
 #endif
   // ---- per-wave reductions -> 2-3 atomics per wave, spread over CTR_SHARDS cache lines ----
   // (all waves adding into ONE address serialise at the memory side: 0.76 ms per 1080p frame,
-  //  measured; one 128-byte shard per wave%CTR_SHARDS costs nothing measurable.  after_render
+  //  measured; one 128-byte shard per wave%CTR_SHARDS costs nothing measurable.  tile_order.hip after_render
   //  then adds the shards into the caller's counters and clears them.)
   if (counters) {
     const unsigned long long c = n_casts;
@@ -2026,248 +1987,11 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   }
 }
 #undef CTR_MARK
-// ---- after_render: block 0 folds the counter shards, block 1 builds the next dispatch order ----
-// block of CTR_SHARDS threads: thread t owns shard t; wave-level reduction, then one LDS atomic per
-// wave and word; adds into out[0..14] (max for word 1) and zeroes the shards for the next launch
-__device__ void fold_block(unsigned long long *__restrict__ shards, unsigned long long *__restrict__ out) {
-  constexpr int NW = 15;
-  __shared__ unsigned long long acc[NW];
-  if (threadIdx.x < NW) acc[threadIdx.x] = 0ull;
-  __syncthreads();
-  unsigned long long *sh = shards + (size_t)threadIdx.x * CTR_SHARD_WORDS;
-  unsigned long long v[NW];
-#pragma unroll
-  for (int q = 0; q < NW; q++) {
-    v[q] = sh[q];
-    if (v[q]) sh[q] = 0ull;
-  }
-#pragma unroll
-  for (int q = 0; q < NW; q++) {
-    unsigned long long x = v[q];
-    if (__builtin_amdgcn_ballot_w64(x != 0ull) == 0ull) continue;  // word unused by this build (wave-uniform)
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned long long o = __shfl_xor(x, off);
-      x = (q == 1) ? (o > x ? o : x) : x + o;
-    }
-    if ((threadIdx.x & 63) == 0) {
-      if (q == 1) atomicMax(&acc[q], x); else atomicAdd(&acc[q], x);
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < NW) {
-    const unsigned long long r = acc[threadIdx.x];
-    if (r) {
-      if (threadIdx.x == 1) atomicMax(&out[1], r); else atomicAdd(&out[threadIdx.x], r);
-    }
-  }
-}
 
-// The same counting sort (see order_block) over groups of GROUP_TILES horizontally adjacent tiles: a group's key is
-// the cost of its most expensive tile, its tiles are emitted consecutively.
-__device__ void order_block_groups(const uint32_t *__restrict__ cost, uint32_t *__restrict__ order, uint32_t n, uint32_t tiles_x) {
-  __shared__ uint32_t scan[CTR_COST_BINS];
-  __shared__ uint32_t wsum[CTR_COST_BINS / 64];
-  __shared__ uint32_t smax;
-  const uint32_t t = threadIdx.x, ln = t & 63u, wv = t >> 6;
-  const uint32_t groups_x = (tiles_x + GROUP_TILES - 1) / GROUP_TILES;
-  const uint32_t n_groups = (n / tiles_x) * groups_x;  // (single frame: n = tiles_x * tiles_y)
-  auto group = [&](uint32_t g, uint32_t &tile0, uint32_t &nt) -> uint32_t {  // -> the group's key
-    const uint32_t gy = g / groups_x, gx = g - gy * groups_x;
-    tile0 = gy * tiles_x + gx * GROUP_TILES;
-    nt = tiles_x - gx * GROUP_TILES < GROUP_TILES ? tiles_x - gx * GROUP_TILES : GROUP_TILES;
-    uint32_t c = 0;
-    for (uint32_t k = 0; k < nt; k++) c = cost[tile0 + k] > c ? cost[tile0 + k] : c;
-    return c;
-  };
-  scan[t] = 0u;
-  if (t == 0) smax = 1u;
-  __syncthreads();
-  uint32_t m = 0;
-  for (uint32_t g = t; g < n_groups; g += CTR_COST_BINS) {
-    uint32_t tile0, nt;
-    const uint32_t c = group(g, tile0, nt);
-    m = c > m ? c : m;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
-    m = o > m ? o : m;
-  }
-  if (ln == 0) atomicMax(&smax, m);
-  __syncthreads();
-  const uint32_t top = __float_as_uint((float)smax);
-  auto bin = [&](uint32_t c, uint32_t i) -> uint32_t {
-    const uint32_t fb = __float_as_uint((float)c);
-    uint32_t cls = fb < top ? (top - fb) >> 20 : 0u;
-    cls = cls > 63u ? 63u : cls;
-    return cls * 16u + (i & 15u);
-  };
-  for (uint32_t g = t; g < n_groups; g += CTR_COST_BINS) {
-    uint32_t tile0, nt;
-    const uint32_t c = group(g, tile0, nt);
-    atomicAdd(&scan[bin(c, g)], nt);
-  }
-  __syncthreads();
-  const uint32_t v = scan[t];
-  uint32_t x = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)x, off);
-    if (ln >= (uint32_t)off) x += o;
-  }
-  if (ln == 63u) wsum[wv] = x;
-  __syncthreads();
-  uint32_t base = 0;
-  for (uint32_t q = 0; q < wv; q++) base += wsum[q];
-  scan[t] = base + x - v;
-  __syncthreads();
-  for (uint32_t g = t; g < n_groups; g += CTR_COST_BINS) {
-    uint32_t tile0, nt;
-    const uint32_t c = group(g, tile0, nt);
-    uint32_t at = atomicAdd(&scan[bin(c, g)], nt);
-    if (CTR_CHEAP_FIRST_PCT && tiles_x % GROUP_TILES == 0) {  // (every group is whole)
-      // the cheapest groups first, then the rest from the dearest down: the link to the host has something to carry
-      // from the start, while the dear tiles — which complete late whatever the order — are under way
-      const uint32_t tail = (uint32_t)((uint64_t)n_groups * CTR_CHEAP_FIRST_PCT / 100u) * GROUP_TILES;  // tiles moved to the front
-      at = at >= n - tail ? (n - nt - at) : at + tail;   // (the front in ascending cost)
-    }
-    for (uint32_t k = 0; k < nt; k++) order[at + k] = tile0 + k;
-  }
-}
-
-// block of CTR_COST_BINS threads: counting sort of the launch's waves by cost class, expensive first:
-// order[slot] = wave.  64 classes (8 per octave below the maximum) x 16 sub-bins by wave index —
-// the sub-bins only spread the LDS atomics of neighbouring waves, which usually share a class.
-// Any permutation is a correct order; cost only shapes the tail of the next launches.
-// tiles_x != 0: keep the GROUP_TILES tiles of a host-delivery group together (sorted by the group's cost), so that
-// a group completes — and its pixels leave for the host — soon after its first tile starts.
-__device__ void order_block(const uint32_t *__restrict__ cost, uint32_t *__restrict__ order, uint32_t n, uint32_t tiles_x) {
-  if (tiles_x) {
-    order_block_groups(cost, order, n, tiles_x);
-    return;
-  }
-  __shared__ uint32_t scan[CTR_COST_BINS];
-  __shared__ uint32_t wsum[CTR_COST_BINS / 64];
-  __shared__ uint32_t smax;
-  constexpr uint32_t U = 8;
-  const uint32_t t = threadIdx.x, ln = t & 63u, wv = t >> 6;
-  scan[t] = 0u;
-  if (t == 0) smax = 1u;
-  __syncthreads();
-  uint32_t m = 0;
-  for (uint32_t b0 = 0; b0 < n; b0 += U * CTR_COST_BINS) {
-    uint32_t c[U];
-#pragma unroll
-    for (uint32_t k = 0; k < U; k++) {
-      const uint32_t i = b0 + k * CTR_COST_BINS + t;
-      c[k] = i < n ? cost[i] : 0u;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < U; k++) m = c[k] > m ? c[k] : m;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)m, off);
-    m = o > m ? o : m;
-  }
-  if (ln == 0) atomicMax(&smax, m);
-  __syncthreads();
-  const uint32_t top = __float_as_uint((float)smax);
-  auto bin = [&](uint32_t c, uint32_t i) -> uint32_t {
-    const uint32_t fb = __float_as_uint((float)c);       // exponent | mantissa: log-linear in c
-    uint32_t cls = fb < top ? (top - fb) >> 20 : 0u;     // 1/8 octave steps below the maximum
-    cls = cls > 63u ? 63u : cls;
-    return cls * 16u + (i & 15u);
-  };
-  for (uint32_t b0 = 0; b0 < n; b0 += U * CTR_COST_BINS) {
-    uint32_t c[U];
-#pragma unroll
-    for (uint32_t k = 0; k < U; k++) {
-      const uint32_t i = b0 + k * CTR_COST_BINS + t;
-      c[k] = i < n ? cost[i] : 0u;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < U; k++) {
-      const uint32_t i = b0 + k * CTR_COST_BINS + t;
-      if (i < n) atomicAdd(&scan[bin(c[k], i)], 1u);
-    }
-  }
-  __syncthreads();
-  const uint32_t v = scan[t];
-  uint32_t x = v;  // inclusive scan inside the wave, then across the 16 waves
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t o = (uint32_t)__shfl_up((int)x, off);
-    if (ln >= (uint32_t)off) x += o;
-  }
-  if (ln == 63u) wsum[wv] = x;
-  __syncthreads();
-  uint32_t base = 0;
-  for (uint32_t q = 0; q < wv; q++) base += wsum[q];
-  scan[t] = base + x - v;  // exclusive offset of bin t
-  __syncthreads();
-  for (uint32_t b0 = 0; b0 < n; b0 += U * CTR_COST_BINS) {
-    uint32_t c[U];
-#pragma unroll
-    for (uint32_t k = 0; k < U; k++) {
-      const uint32_t i = b0 + k * CTR_COST_BINS + t;
-      c[k] = i < n ? cost[i] : 0u;
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < U; k++) {
-      const uint32_t i = b0 + k * CTR_COST_BINS + t;
-      if (i < n) order[atomicAdd(&scan[bin(c[k], i)], 1u)] = i;
-    }
-  }
-}
-
-// ---- first_order: the dispatch order of a shape nothing is known about yet ----
-// Without measured costs the expensive tiles cannot be started first, but a prior helps: what a frame is about sits
-// near its centre, walls and sky at its borders.  Tiles are dispatched in blocks of 16x16 tiles, the blocks by their
-// (aspect-normalised) distance from the image centre; list-scheduling the measured costs of the shipped scenes puts
-// this 6-15 % below image order (border-in: 5-13 % above; DESIGN.md "First launch").  One thread per tile.
-__global__ __launch_bounds__(256) void first_order(uint32_t *__restrict__ order, uint32_t tiles_x, uint32_t tiles_y, uint32_t n_frames) {
-  const uint32_t tiles_frame = tiles_x * tiles_y;
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= tiles_frame) return;
-  constexpr uint32_t B = 16;
-  const uint32_t nbx = (tiles_x + B - 1) / B, nby = (tiles_y + B - 1) / B;
-  const uint32_t tx = t % tiles_x, ty = t / tiles_x, bx = tx / B, by = ty / B, me = by * nbx + bx;
-  const float aspect = (float)nbx / (float)nby;
-  auto key = [&](uint32_t x, uint32_t y) -> float {
-    const float dx = ((float)x + 0.5f) - 0.5f * (float)nbx, dy = (((float)y + 0.5f) - 0.5f * (float)nby) * aspect;
-    return dx * dx + dy * dy;
-  };
-  const float km = key(bx, by);
-  uint32_t before = 0;  // tiles of the blocks that come first
-  for (uint32_t y = 0; y < nby; y++)
-    for (uint32_t x = 0; x < nbx; x++) {
-      const float k = key(x, y);
-      if (k < km || (k == km && y * nbx + x < me)) {
-        const uint32_t cw = tiles_x - x * B < B ? tiles_x - x * B : B, ch = tiles_y - y * B < B ? tiles_y - y * B : B;
-        before += cw * ch;
-      }
-    }
-  const uint32_t bw = tiles_x - bx * B < B ? tiles_x - bx * B : B;
-  const uint32_t slot = before + (ty - by * B) * bw + (tx - bx * B);
-  for (uint32_t f = 0; f < n_frames; f++) order[f * tiles_frame + slot] = f * tiles_frame + t;
-}
-
-static_assert(CTR_SHARDS == CTR_COST_BINS, "after_render uses one block size for both jobs");
-__global__ __launch_bounds__(CTR_SHARDS) void after_render(unsigned long long *__restrict__ shards,
-                                                           unsigned long long *__restrict__ counters,
-                                                           const uint32_t *__restrict__ cost,
-                                                           uint32_t *__restrict__ order, uint32_t n, uint32_t group_tiles_x) {
-  if (blockIdx.x == 0) {
-    if (shards) fold_block(shards, counters);
-  } else {
-    if (cost) order_block(cost, order, n, group_tiles_x);
-  }
-}
-
-uint64_t launch_waves(const RenderLaunch &L) {
-  const uint32_t tiles_x = (L.w + TW - 1) / TW, tiles_y = (L.rows.n_rows + TH - 1) / TH;
-  return (uint64_t)tiles_x * tiles_y * L.n_frames;
-}
-
-template <uint32_t KV>
-int launch(const RenderLaunch &L, hipStream_t stream) {
+// One launch of `kernel` = render_kernel<kv> (ctr_launch_render): the launch's buffers are cross-checked against the build, then
+// up to three kernels go onto the stream — the first order of a new shape, the render, the fold of its counters and the
+// next order (tile_order.hip).
+int launch(const RenderLaunch &L, uint32_t kv, const void *kernel, hipStream_t stream) {
   KArgs A;
   A.objs = (const CADDR DObj *)L.objs;
   A.oloop = (const CADDR DObj *)L.oloop;
@@ -2308,7 +2032,7 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
   A.frames = stack.frames;
   A.order = (const CADDR uint32_t *)L.order;
   A.cost = L.cost;
-  const bool host_delivery = (KV & KV_HOSTOUT) != 0;
+  const bool host_delivery = (kv & KV_HOSTOUT) != 0;
   if (host_delivery != (L.group_done != nullptr)) return (int)hipErrorInvalidValue;
   if (host_delivery && (L.n_frames != 1 || !L.host_depth || !L.host_color || !L.host_normal)) return (int)hipErrorInvalidValue;
   A.host_depth = L.host_depth;
@@ -2316,43 +2040,39 @@ int launch(const RenderLaunch &L, hipStream_t stream) {
   A.host_normal = L.host_normal;
   A.group_done = L.group_done;
   A.uv_out = L.uv;
-  if (((KV & KV_UV) != 0) != (L.uv != nullptr)) return (int)hipErrorInvalidValue;
+  if (((kv & KV_UV) != 0) != (L.uv != nullptr)) return (int)hipErrorInvalidValue;
   // "Supersampling": s = 2, 4 or 8 must divide the tile (a block of samples inside one wave) and the sample frame; one frame
-  A.ss_log2 = (KV & KV_SS) ? L.ss_log2 : 0u;
+  A.ss_log2 = (kv & KV_SS) ? L.ss_log2 : 0u;
   // "Lens render": the caller's rays, one pair per pixel (sample) of the one frame
-  A.ray_origin = (KV & KV_RAYS) ? L.ray_origin : nullptr;
-  A.ray_dir = (KV & KV_RAYS) ? L.ray_dir : nullptr;
-  A.ray_ambient = (KV & KV_RAYS) ? L.ray_ambient : 0.f;
-  if (((KV & KV_RAYS) != 0) != (L.ray_origin != nullptr) || ((KV & KV_RAYS) != 0) != (L.ray_dir != nullptr)) return (int)hipErrorInvalidValue;
-  if ((KV & KV_RAYS) && L.n_frames != 1) return (int)hipErrorInvalidValue;
-  if (((KV & KV_SS) != 0) != (L.ss_log2 != 0u)) return (int)hipErrorInvalidValue;
-  if (KV & KV_SS) {
+  A.ray_origin = (kv & KV_RAYS) ? L.ray_origin : nullptr;
+  A.ray_dir = (kv & KV_RAYS) ? L.ray_dir : nullptr;
+  A.ray_ambient = (kv & KV_RAYS) ? L.ray_ambient : 0.f;
+  if (((kv & KV_RAYS) != 0) != (L.ray_origin != nullptr) || ((kv & KV_RAYS) != 0) != (L.ray_dir != nullptr)) return (int)hipErrorInvalidValue;
+  if ((kv & KV_RAYS) && L.n_frames != 1) return (int)hipErrorInvalidValue;
+  if (((kv & KV_SS) != 0) != (L.ss_log2 != 0u)) return (int)hipErrorInvalidValue;
+  if (kv & KV_SS) {
     const uint32_t m = (1u << L.ss_log2) - 1u;
     if (L.ss_log2 > 3u || ((TW | TH) & m) || ((L.w | L.h | L.rows.n_rows | L.rows.row_begin | L.rows.row_end | L.rows.block_rows) & m) || L.n_frames != 1)
       return (int)hipErrorInvalidValue;
   }
   size_t lds_bytes = (size_t)WAVES_PER_WG * stack.bytes_per_wave();
-  if (KV & KV_OCC6) lds_bytes += (size_t)WAVES_PER_WG * 5 * 64 * sizeof(float);  // PARK
+  if (kv & KV_OCC6) lds_bytes += (size_t)WAVES_PER_WG * 5 * 64 * sizeof(float);  // PARK
   // diagnostic only: extra dynamic LDS per workgroup caps the waves resident per CU (occupancy sweeps)
   if (const char *pad = getenv("CUTRACE_LDS_PAD")) lds_bytes += (size_t)atol(pad);
-  const uint64_t waves = launch_waves(L);
+  const uint64_t waves = ctr_launch_waves(L);
   if (waves > 0x7FFFFFFFull) return (int)hipErrorInvalidValue;
   if (waves == 0) return 0;
   const uint32_t grid = (uint32_t)((waves + WAVES_PER_WG - 1) / WAVES_PER_WG);
   // counters go through the scene's shard buffer and are folded into the caller's words afterwards
   unsigned long long *shards = L.counters ? L.shards : nullptr;
-  if (L.order_init && L.order) {
-    const uint32_t tiles_x = (L.w + TW - 1) / TW, tiles_y = (L.rows.n_rows + TH - 1) / TH;
-    hipLaunchKernelGGL(first_order, dim3((tiles_x * tiles_y + 255) / 256), dim3(256), 0, stream, const_cast<uint32_t *>(L.order),
-                       tiles_x, tiles_y, L.n_frames);
-  }
-  hipLaunchKernelGGL(render_kernel<KV>, dim3(grid), dim3(WG_THREADS), lds_bytes, stream, A, L.depth, L.color, L.normal,
-                     shards);
+  if (L.order_init && L.order) ctr_launch_first_order(L, stream);
+  float *depth = L.depth, *color = L.color, *normal = L.normal;
+  void *args[] = {&A, &depth, &color, &normal, &shards};  // render_kernel's parameter list (KParams)
+  (void)hipLaunchKernel(kernel, dim3(grid), dim3(WG_THREADS), args, lds_bytes, stream);
   const bool reorder = L.cost && L.order_next;
   if (shards || reorder)
-    hipLaunchKernelGGL(after_render, dim3(reorder ? 2 : 1), dim3(CTR_SHARDS), 0, stream, shards, L.counters,
-                       reorder ? L.cost : nullptr, L.order_next, (uint32_t)waves,
-                       host_delivery ? (L.w + TW - 1) / TW : 0u);
+    ctr_launch_after_render(shards, L.counters, reorder ? L.cost : nullptr, L.order_next, (uint32_t)waves,
+                            host_delivery ? tiles_x(L.w) : 0u, stream);
   return (int)hipGetLastError();
 }
 
@@ -2423,30 +2143,16 @@ extern "C" int ctr_selftest_exact_math(uint64_t *n_mismatch) {
   return CTR_OK;
 }
 
-uint64_t ctr_launch_waves(const RenderLaunch &L) { return launch_waves(L); }
-uint64_t ctr_staging_pixels(const RenderLaunch &L) { return launch_waves(L) * 64u; }
-uint64_t ctr_staging_groups(const RenderLaunch &L) {
-  const uint64_t tiles_x = (L.w + TW - 1) / TW, tiles_y = (L.rows.n_rows + TH - 1) / TH;
-  return ((tiles_x + GROUP_TILES - 1) / GROUP_TILES) * tiles_y;
-}
-
-uint32_t ctr_group_tile_count(const RenderLaunch &L, uint64_t group) {
-  const uint32_t tiles_x = (L.w + TW - 1) / TW, groups_x = (tiles_x + GROUP_TILES - 1) / GROUP_TILES;
-  const uint32_t gx = (uint32_t)(group % groups_x);
-  return tiles_x - gx * GROUP_TILES < GROUP_TILES ? tiles_x - gx * GROUP_TILES : GROUP_TILES;
-}
-uint64_t ctr_staging_index(const RenderLaunch &L, uint32_t x, uint32_t k_row) {
-  const uint64_t tiles_x = (L.w + TW - 1) / TW;
-  return ((uint64_t)(k_row / TH) * tiles_x + x / TW) * 64u + (k_row % TH) * TW + x % TW;
-}
-
-// L.variant is the build (kernel_choice.h choose_kernel decides; launch<KV> cross-checks the launch's buffers against it)
+// L.variant is the build (kernel_choice.h choose_kernel decides; launch cross-checks the launch's buffers against it).  The
+// switch is what instantiates the kernels — and what makes a table entry listed twice a compile error.
 int ctr_launch_render(const RenderLaunch &L, void *stream) {
+  const void *kernel;
   switch (L.variant) {
-#define X(kv) case (kv): return launch<(kv)>(L, (hipStream_t)stream);
+#define X(kv) case (kv): kernel = (const void *)render_kernel<(kv)>; break;
     CTR_RENDER_KERNELS(X)
     CTR_LENS_KERNELS(X)
 #undef X
     default: return (int)hipErrorInvalidValue;
   }
+  return launch(L, L.variant, kernel, (hipStream_t)stream);
 }

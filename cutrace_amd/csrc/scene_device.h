@@ -193,15 +193,15 @@ struct RenderLaunch {
   unsigned long long *shards;    // scene-owned CTR_SHARDS x CTR_SHARD_WORDS scratch the kernel adds into
   unsigned long long *counters;  // [0] ray_count, [1] max-depth bits, [2] AABB-hit triangle count (KV_COUNT), [4..9] KV_STATS
   uint32_t variant;               // the build: exactly one KV of kernel_choice.h CTR_RENDER_KERNELS, not a wish (choose_kernel)
-  // tile scheduling (render_kernel.hip "Dispatch order"): all three may be null
+  // tile scheduling (tile_order.hip; render_kernel.hip "Dispatch order"): all three may be null
   const uint32_t *order;  // dispatch slot -> wave index for THIS launch (a permutation of 0..waves-1)
   uint32_t *cost;         // out: per-wave cost of this launch
   uint32_t *order_next;   // out (or null = keep the old order): waves sorted by descending cost
                           // (may alias `order`: written after the render)
   uint32_t order_init;    // 1: no costs are known for this shape — fill `order` (writable then) with the centre-out
-                          // order before the render (render_kernel.hip first_order)
+                          // order before the render (tile_order.hip first_order)
   // Host delivery (render_kernel.hip "Host delivery"; single frame only): when group_done is set, depth / color /
-  // normal above are a TILE-MAJOR staging area of ctr_staging_pixels() pixels each (x1, x3, x3 floats), and the
+  // normal above are a TILE-MAJOR staging area of ctr_staging_pixels() pixels each (tile_order.h; x1, x3, x3 floats), and the
   // frame is written into host_* — device-visible page-locked host memory, compact row-major as in ctr_render — by
   // the wave that completes each group of tiles.  group_done: ctr_staging_groups() zeroed words (left zeroed).
   float *host_depth, *host_color, *host_normal;
@@ -217,22 +217,14 @@ struct RenderLaunch {
   const float *ray_origin, *ray_dir;
   float ray_ambient;
 };
-uint64_t ctr_staging_pixels(const RenderLaunch &L);
-uint64_t ctr_staging_groups(const RenderLaunch &L);
-uint32_t ctr_group_tile_count(const RenderLaunch &L, uint64_t group);          // tiles group `group` counts when it is complete
-uint64_t ctr_staging_index(const RenderLaunch &L, uint32_t x, uint32_t k_row); // staging pixel of compact pixel (x, k_row)
 
 // keeps `msg` for ctr_last_error() (ctr_api.cpp); used by the other translation units of the library
 void ctr_internal_set_error(const char *msg);
 // host-callable launcher implemented in render_kernel.hip; returns a hipError_t as int
 int ctr_launch_render(const RenderLaunch &L, void *stream);
-// number of waves (tiles x frames) the launch will dispatch
-uint64_t ctr_launch_waves(const RenderLaunch &L);
-// counters are accumulated in CTR_SHARDS 128-byte shards (see render_kernel.hip) and folded afterwards
+// counters are accumulated in CTR_SHARDS 128-byte shards (see render_kernel.hip) and folded afterwards (tile_order.hip after_render)
 #define CTR_SHARDS 1024
 #define CTR_SHARD_WORDS 16
-// counters of the tile scheduler's counting sort (64 cost classes x 16 sub-bins)
-#define CTR_COST_BINS 1024u
 // maximum `bounces` the kernel supports (explicit per-lane stack depth - 1)
 #define CTR_MAX_BOUNCES 15
 

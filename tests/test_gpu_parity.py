@@ -353,20 +353,26 @@ def test_mesh_corner_cases(gpu, tmp_path):
         _check_all_ways(gpu, s, f"fudge {fudge}", bounces=2, fudge=fudge)
 
 
-@pytest.mark.parametrize("w,h", [(1001, 777), (2048, 1536), (8, 8), (1, 4000)])
+@pytest.mark.parametrize("w,h", [(1001, 777), (2048, 1536), (8, 8), (1, 4000), (64, 8), (72, 16), (520, 24)])
 def test_tile_order_is_a_permutation_at_odd_and_large_sizes(gpu, w, h):
-    """The counting sort behind the tile order (after_render) at wave counts that are not multiples of its
-    block size, at one wave, and at ~49k waves: every launch must still write every pixel exactly once."""
+    """The counting sorts behind the tile order (tile_order.hip after_render) at wave counts that are not multiples of
+    their block size, at one wave, and at ~49k waves: every launch must still write every pixel exactly once.  The plain
+    render sorts tile by tile; the pinned one (host delivery) sorts by groups of 8 tiles, whose smallest shapes are
+    64x8 (exactly one group), 72x16 (a whole group and a ragged one of one tile, two tile rows) and 520x24 (eight
+    groups and a ragged one)."""
     s = load_scene(gpu, "sphere_plane", w, h)
     ref_ds = gpu.DeviceScene(s)
     ref_ds.set_variant(gpu.VAR_NO_REORDER)
     ref = ref_ds.render(bounces=3)
-    ds = gpu.DeviceScene(s)
-    for i in range(3):
-        r = ds.render(bounces=3)
-        for k in ("depth", "normal", "color"):
-            assert same_bits(r[k], ref[k]), (k, i, w, h)
-        assert r["ray_count"] == ref["ray_count"]
+    tiles = ((w + 7) // 8) * ((h + 7) // 8)
+    for pinned in (False, True):
+        ds = gpu.DeviceScene(s)
+        for i in range(3):
+            r = ds.render(bounces=3, pinned=pinned)
+            for k in ("depth", "normal", "color"):
+                assert same_bits(r[k], ref[k]), (k, i, w, h, pinned)
+            assert r["ray_count"] == ref["ray_count"]
+        assert len(ds.tile_costs()) == tiles, (w, h, pinned)
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -528,7 +534,7 @@ def test_host_delivery_odd_sizes_and_separate_buffers(ca, w, h):
 
 @pytest.mark.parametrize("w,h,rows", [(1000, 700, None), (1920, 1080, (0, 1080, 8, 1, 2)), (1027, 1033, (16, 1001))])
 def test_first_launch_centre_out_order_is_a_permutation(ca, w, h, rows):
-    """The first launch of a shape dispatches its tiles centre-out (render_kernel.hip first_order; scenes with >= 1000 mesh
+    """The first launch of a shape dispatches its tiles centre-out (tile_order.hip first_order; scenes with >= 1000 mesh
     triangles, >= 8192 tiles).  A tile left out or visited twice would show as a wrong pixel: the first frame of a fresh
     handle — ragged blocks of tiles, interleaved row parts, a row sub-range — against image order, bitwise, plus the ray
     count; then the second frame (measured order)."""
