@@ -51,6 +51,125 @@ def _cwd(path):
         os.chdir(old)
 
 
+def _check(name, st):
+    """The one place where a status of the HIP library becomes an exception."""
+    if st:
+        raise RuntimeError(f"{name} failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
+
+
+def _stats_dict(stats):
+    """A RenderStats as the statistics every host-form render returns."""
+    return dict(ray_count=int(stats.ray_count), kernel_ms=stats.kernel_ms, total_ms=stats.total_ms,
+                max_depth=float(stats.max_depth), rows=int(stats.rows))
+
+
+def _frame_views(blk, px, n, w):
+    """depth (n, w), color (n, w, 3), normal (n, w, 3): views of a block of 7 floats per pixel (depth at 0, color at px,
+    normal at 4 * px)."""
+    if not n:
+        return dict(depth=np.empty((0, w), np.float32), color=np.empty((0, w, 3), np.float32), normal=np.empty((0, w, 3), np.float32))
+    return dict(depth=blk[:px].reshape(n, w), color=blk[px:4 * px].reshape(n, w, 3), normal=blk[4 * px:7 * px].reshape(n, w, 3))
+
+
+def _empty_frame(n, w, uv=False):
+    """The pageable frame: fresh numpy buffers."""
+    fr = dict(depth=np.empty((n, w), np.float32), color=np.empty((n, w, 3), np.float32), normal=np.empty((n, w, 3), np.float32))
+    if uv:
+        fr["uv"] = np.empty((n, w, 2), np.float32)
+    return fr
+
+
+def _frame_alloc(px):
+    """A page-locked block of 7 * px floats (ctr_frame_alloc): (pointer for ctr_frame_free, the block as a numpy array)."""
+    d, c, n = (C.POINTER(C.c_float)() for _ in range(3))
+    _check("ctr_frame_alloc", _lib.hip_lib().ctr_frame_alloc(px, C.byref(d), C.byref(c), C.byref(n)))
+    return d, np.ctypeslib.as_array(d, shape=(7 * px,))
+
+
+def _pinned_block(owner, px, grow_only):
+    """The page-locked block a DeviceScene / MultiScene keeps for its pinned renders: allocated again when the request
+    grows (grow_only) or differs, freed by _free_pinned_block."""
+    have = getattr(owner, "_pin_px", 0)
+    if have < px or (have != px and not grow_only):
+        _free_pinned_block(owner)
+        owner._pin_ptr, owner._pin = _frame_alloc(px)
+        owner._pin_px = px
+    return owner._pin
+
+
+def _free_pinned_block(owner):
+    if getattr(owner, "_pin_px", 0):
+        owner._pin = None
+        _lib.hip_lib().ctr_frame_free(owner._pin_ptr)
+        owner._pin_px = 0
+
+
+@contextlib.contextmanager
+def _on_stream(dev, stream):
+    """Enter the device and the stream (None: torch's current stream of that device); yields the raw stream handle."""
+    import torch
+    with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        yield C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _subset(what, names, allowed, allow_empty=False, unique=False):
+    """`names` as a tuple, if it is a subset of `allowed` (non-empty unless allow_empty; unique: no name twice)."""
+    names = tuple(names)
+    if (not names and not allow_empty) or (unique and len(set(names)) != len(names)) or any(k not in allowed for k in names):
+        raise ValueError(f"{what}: a {'' if allow_empty else 'non-empty '}subset of {allowed}, got {names}")
+    return names
+
+
+# what cast_rays and shade_rays return per ray: (trailing shape, dtype)
+_RAY_OUT = {"t": ((), "float32"), "object": ((), "int32"), "prim": ((), "int32"), "point": ((3,), "float32"),
+            "normal": ((3,), "float32"), "uv": ((2,), "float32"), "color": ((3,), "float32")}
+
+
+def _ray_outputs(names, n, dev):
+    import torch
+    return {k: torch.empty((n,) + _RAY_OUT[k][0], dtype=getattr(torch, _RAY_OUT[k][1]), device=dev) for k in names}
+
+
+def _rays_check(x, what, cols, dev):
+    """x as a float32 tensor of shape (n, cols) (cols 0: (n,)), still where it was: a tensor on another GPU than `dev`,
+    another type, dtype or shape raise."""
+    import torch
+    if isinstance(x, torch.Tensor):
+        if x.device.type != "cpu" and x.device != dev:
+            raise ValueError(f"{what}: tensor on {x.device}, the scene lives on {dev}")
+    elif isinstance(x, np.ndarray):
+        x = torch.from_numpy(x)
+    else:
+        raise TypeError(f"{what}: expected a torch tensor or a numpy array, got {type(x).__name__}")
+    shape_ok = x.dim() == 1 if cols == 0 else (x.dim() == 2 and x.shape[1] == cols)
+    if x.dtype != torch.float32 or not shape_ok:
+        raise ValueError(f"{what}: expected float32 of shape {'(n,)' if cols == 0 else f'(n, {cols})'}, "
+                         f"got {x.dtype} {tuple(x.shape)}")
+    return x
+
+
+def _ray_pair(origins, dirs, dev, frame=None):
+    """(o, d, n): origins and dirs, (n, 3) float32 each, contiguous on `dev` (a tensor already there is used in place, a CPU
+    tensor or a numpy array is copied over) once both are valid.  frame = (H, W): the lens render's rays, which may also be
+    (H, W, 3) and must be H * W."""
+    import torch
+    H, W = frame or (0, 0)
+    pair = []
+    for x, what in ((origins, "origins"), (dirs, "dirs")):
+        if frame and isinstance(x, (np.ndarray, torch.Tensor)) and len(x.shape) == 3:
+            if tuple(x.shape) != (H, W, 3):
+                raise ValueError(f"{what}: expected shape ({H}, {W}, 3) or ({H * W}, 3), got {tuple(x.shape)}")
+            x = x.reshape(H * W, 3)
+        x = _rays_check(x, what, 3, dev)
+        if frame and x.shape[0] != H * W:
+            raise ValueError(f"{what}: {x.shape[0]} rays for the {W} x {H} frame ({H * W})")
+        pair.append(x)
+    o, d = pair
+    if d.shape[0] != o.shape[0]:
+        raise ValueError(f"dirs: {d.shape[0]} rays for {o.shape[0]} origins")
+    return o.to(dev, non_blocking=False).contiguous(), d.to(dev, non_blocking=False).contiguous(), o.shape[0]
+
+
 class HostScene:
     """A scene loaded by the C++ loader (libcutrace_host.so): owns the flat arrays."""
 
@@ -139,40 +258,25 @@ class DeviceScene:
     def __init__(self, host_scene, device=0):
         L = _lib.hip_lib()
         h = C.c_void_p()
-        st = L.ctr_scene_create(host_scene.desc, device, C.byref(h))
-        if st:
-            raise RuntimeError(f"ctr_scene_create failed ({st}): {L.ctr_last_error().decode()}")
+        _check("ctr_scene_create", L.ctr_scene_create(host_scene.desc, device, C.byref(h)))
         self._h = h
         self.device = device
         self.w, self.h = host_scene.size
         self._ambient = float(host_scene.desc.contents.cam.ambient)  # shade_rays' default
 
     def set_variant(self, bits):
-        st = _lib.hip_lib().ctr_set_variant(self._h, bits)
-        if st:
-            raise RuntimeError(f"ctr_set_variant failed: {_lib.hip_lib().ctr_last_error().decode()}")
+        _check("ctr_set_variant", _lib.hip_lib().ctr_set_variant(self._h, bits))
 
     def set_size(self, w, h):
-        st = _lib.hip_lib().ctr_scene_set_size(self._h, w, h)
-        if st:
-            raise RuntimeError("ctr_scene_set_size failed")
+        _check("ctr_scene_set_size", _lib.hip_lib().ctr_scene_set_size(self._h, w, h))
         self.w, self.h = w, h
 
     def _pinned_frame(self, px):
         """One page-locked block for a frame's three buffers (ctr_frame_alloc), kept with the scene handle."""
-        if getattr(self, "_pin_px", 0) < px:
-            self._free_pinned()
-            d, c, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)()
-            st = _lib.hip_lib().ctr_frame_alloc(px, C.byref(d), C.byref(c), C.byref(n))
-            if st:
-                raise RuntimeError("ctr_frame_alloc failed")
-            self._pin, self._pin_px = d, px
-        return np.ctypeslib.as_array(self._pin, shape=(7 * self._pin_px,))
+        return _pinned_block(self, px, grow_only=True)
 
     def _free_pinned(self):
-        if getattr(self, "_pin_px", 0):
-            _lib.hip_lib().ctr_frame_free(self._pin)
-            self._pin_px = 0
+        _free_pinned_block(self)
 
     @staticmethod
     def _samples(samples):
@@ -191,32 +295,20 @@ class DeviceScene:
         r = make_rows(self.h, rows)
         n = rows_count(self.h, rows)
         if into is not None:
-            depth, color, normal = into["depth"], into["color"], into["normal"]
-            assert depth.shape == (n, self.w) and color.shape == (n, self.w, 3) and normal.shape == (n, self.w, 3)
+            fr = dict(depth=into["depth"], color=into["color"], normal=into["normal"])
+            assert fr["depth"].shape == (n, self.w) and fr["color"].shape == (n, self.w, 3) and fr["normal"].shape == (n, self.w, 3)
         elif pinned:
             px = max(n * self.w, 1)
-            blk = self._pinned_frame(px)
-            depth = blk[:px].reshape(n, self.w) if n else np.empty((0, self.w), np.float32)
-            color = blk[px:4 * px].reshape(n, self.w, 3) if n else np.empty((0, self.w, 3), np.float32)
-            normal = blk[4 * px:7 * px].reshape(n, self.w, 3) if n else np.empty((0, self.w, 3), np.float32)
+            fr = _frame_views(self._pinned_frame(px), px, n, self.w)
         else:
-            depth = np.empty((n, self.w), np.float32)
-            color = np.empty((n, self.w, 3), np.float32)
-            normal = np.empty((n, self.w, 3), np.float32)
+            fr = _empty_frame(n, self.w)
+        ptrs = fr["depth"].ctypes.data, fr["color"].ctypes.data, fr["normal"].ctypes.data
         stats = RenderStats()
         if samples != 1:
-            st = L.ctr_render_aa(self._h, C.c_float(fudge), bounces, samples, C.byref(r), depth.ctypes.data, color.ctypes.data,
-                                 normal.ctypes.data, C.byref(stats))
-            if st:
-                raise RuntimeError(f"ctr_render_aa failed ({st}): {L.ctr_last_error().decode()}")
+            _check("ctr_render_aa", L.ctr_render_aa(self._h, C.c_float(fudge), bounces, samples, C.byref(r), *ptrs, C.byref(stats)))
         else:
-            st = L.ctr_render(self._h, C.c_float(fudge), bounces, C.byref(r), depth.ctypes.data, color.ctypes.data,
-                              normal.ctypes.data, C.byref(stats))
-            if st:
-                raise RuntimeError(f"ctr_render failed ({st}): {L.ctr_last_error().decode()}")
-        return dict(depth=depth, color=color, normal=normal, ray_count=int(stats.ray_count),
-                    kernel_ms=stats.kernel_ms, total_ms=stats.total_ms, max_depth=float(stats.max_depth),
-                    rows=int(stats.rows))
+            _check("ctr_render", L.ctr_render(self._h, C.c_float(fudge), bounces, C.byref(r), *ptrs, C.byref(stats)))
+        return dict(fr, **_stats_dict(stats))
 
     def render_images(self, fudge=1e-3, bounces=5, rows=None, samples=1, planes=IMAGE_PLANES, pinned=False):
         """ctr_render_images (include/cutrace_images.h): the frame quantised to display bytes on the GPU, as the host's
@@ -225,9 +317,7 @@ class DeviceScene:
         subset of "color", "depth", "normal"; depth is replicated to R = G = B) plus render()'s stats.  pinned=True: the
         arrays are page-locked (torch's pinned memory), their copies are queued instead of staged."""
         samples = self._samples(samples)
-        planes = tuple(planes)
-        if not planes or len(set(planes)) != len(planes) or any(k not in IMAGE_PLANES for k in planes):
-            raise ValueError(f"planes: a non-empty subset of {IMAGE_PLANES}, got {planes}")
+        planes = _subset("planes", planes, IMAGE_PLANES, unique=True)
         L = _lib.hip_lib()
         r = make_rows(self.h, rows)
         n = rows_count(self.h, rows)
@@ -239,12 +329,9 @@ class DeviceScene:
             out = {k: np.empty((n, self.w, 3), np.uint8) for k in planes}
         ptr = {k: (out[k].ctypes.data if k in out else None) for k in IMAGE_PLANES}
         stats = RenderStats()
-        st = L.ctr_render_images(self._h, C.c_float(fudge), bounces, samples, C.byref(r), ptr["depth"], ptr["color"],
-                                 ptr["normal"], C.byref(stats))
-        if st:
-            raise RuntimeError(f"ctr_render_images failed ({st}): {L.ctr_last_error().decode()}")
-        return dict(out, ray_count=int(stats.ray_count), kernel_ms=stats.kernel_ms, total_ms=stats.total_ms,
-                    max_depth=float(stats.max_depth), rows=int(stats.rows))
+        _check("ctr_render_images", L.ctr_render_images(self._h, C.c_float(fudge), bounces, samples, C.byref(r), ptr["depth"],
+                                                        ptr["color"], ptr["normal"], C.byref(stats)))
+        return dict(out, **_stats_dict(stats))
 
     def quantise(self, depth=None, color=None, normal=None, counters=None, max_depth=None, out=None, stream=None):
         """ctr_quantise_device (include/cutrace_images.h): float planes on the scene's device to display bytes there — what
@@ -275,7 +362,7 @@ class DeviceScene:
                                      or counters.numel() < 2 or not counters.is_contiguous()):
             raise ValueError(f"counters: expected a contiguous int64 tensor of at least 2 words on {dev}")
         res = {}
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        with _on_stream(dev, stream) as raw:
             q = _lib.ImagePlanes()
             q.n_pixels = px
             for k, v in given.items():
@@ -295,9 +382,7 @@ class DeviceScene:
                 else:
                     q.max_depth = float(max_depth)
             if px:
-                st = _lib.hip_lib().ctr_quantise_device(self.device, C.byref(q), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-                if st:
-                    raise RuntimeError(f"ctr_quantise_device failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
+                _check("ctr_quantise_device", _lib.hip_lib().ctr_quantise_device(self.device, C.byref(q), raw))
         return res
 
     def render_uv(self, fudge=1e-3, bounces=5, rows=None):
@@ -305,17 +390,11 @@ class DeviceScene:
         L = _lib.hip_lib()
         r = make_rows(self.h, rows)
         n = rows_count(self.h, rows)
-        depth = np.empty((n, self.w), np.float32)
-        color = np.empty((n, self.w, 3), np.float32)
-        normal = np.empty((n, self.w, 3), np.float32)
-        uv = np.empty((n, self.w, 2), np.float32)
+        fr = _empty_frame(n, self.w, uv=True)
         stats = RenderStats()
-        st = L.ctr_render_uv(self._h, C.c_float(fudge), bounces, C.byref(r), depth.ctypes.data, color.ctypes.data,
-                             normal.ctypes.data, uv.ctypes.data, C.byref(stats))
-        if st:
-            raise RuntimeError(f"ctr_render_uv failed ({st}): {L.ctr_last_error().decode()}")
-        return dict(depth=depth, color=color, normal=normal, uv=uv, ray_count=int(stats.ray_count),
-                    kernel_ms=stats.kernel_ms, total_ms=stats.total_ms, max_depth=float(stats.max_depth), rows=int(stats.rows))
+        _check("ctr_render_uv", L.ctr_render_uv(self._h, C.c_float(fudge), bounces, C.byref(r), fr["depth"].ctypes.data,
+                                                fr["color"].ctypes.data, fr["normal"].ctypes.data, fr["uv"].ctypes.data, C.byref(stats)))
+        return dict(fr, **_stats_dict(stats))
 
     def render_device(self, d_depth, d_color, d_normal, d_counters=0, stream=0, fudge=1e-3, bounces=5, rows=None, samples=1):
         """Device-buffer form (ctr_render_device): raw device pointers, async on `stream`.  samples = 2, 4 or 8:
@@ -324,22 +403,16 @@ class DeviceScene:
         L = _lib.hip_lib()
         r = make_rows(self.h, rows)
         if samples != 1:
-            st = L.ctr_render_device_aa(self._h, C.c_float(fudge), bounces, samples, C.byref(r), d_depth, d_color, d_normal,
-                                        d_counters, stream)
-            if st:
-                raise RuntimeError(f"ctr_render_device_aa failed ({st}): {L.ctr_last_error().decode()}")
-            return
-        st = L.ctr_render_device(self._h, C.c_float(fudge), bounces, C.byref(r), d_depth, d_color, d_normal,
-                                 d_counters, stream)
-        if st:
-            raise RuntimeError(f"ctr_render_device failed ({st}): {L.ctr_last_error().decode()}")
+            _check("ctr_render_device_aa", L.ctr_render_device_aa(self._h, C.c_float(fudge), bounces, samples, C.byref(r), d_depth,
+                                                                  d_color, d_normal, d_counters, stream))
+        else:
+            _check("ctr_render_device", L.ctr_render_device(self._h, C.c_float(fudge), bounces, C.byref(r), d_depth, d_color,
+                                                            d_normal, d_counters, stream))
 
     def set_cameras(self, cams):
         """Upload a camera path (list of _lib.Camera, same w/h): frames of ctr_render_device_batch."""
         arr = (Camera * len(cams))(*cams)
-        st = _lib.hip_lib().ctr_scene_set_cameras(self._h, arr, len(cams))
-        if st:
-            raise RuntimeError(f"ctr_scene_set_cameras failed: {_lib.hip_lib().ctr_last_error().decode()}")
+        _check("ctr_scene_set_cameras", _lib.hip_lib().ctr_scene_set_cameras(self._h, arr, len(cams)))
         self.n_cams = len(cams)
 
     def render_device_batch(self, d_depth, d_color, d_normal, n_frames, frame_stride_px, first_frame=0, d_counters=0,
@@ -347,19 +420,16 @@ class DeviceScene:
         """n_frames frames in ONE launch (ctr_render_device_batch)."""
         L = _lib.hip_lib()
         r = make_rows(self.h, rows)
-        st = L.ctr_render_device_batch(self._h, C.c_float(fudge), bounces, C.byref(r), first_frame, n_frames,
-                                       frame_stride_px, part_stride, d_depth, d_color, d_normal, d_counters, stream)
-        if st:
-            raise RuntimeError(f"ctr_render_device_batch failed ({st}): {L.ctr_last_error().decode()}")
+        _check("ctr_render_device_batch", L.ctr_render_device_batch(self._h, C.c_float(fudge), bounces, C.byref(r), first_frame, n_frames,
+                                                                    frame_stride_px, part_stride, d_depth, d_color, d_normal, d_counters,
+                                                                    stream))
 
     def algorithmic_bytes(self, fudge=1e-3, bounces=5, rows=None):
         L = _lib.hip_lib()
         r = make_rows(self.h, rows)
         b = C.c_uint64()
         n = C.c_uint64()
-        st = L.ctr_algorithmic_bytes(self._h, C.c_float(fudge), bounces, C.byref(r), C.byref(b), C.byref(n))
-        if st:
-            raise RuntimeError(f"ctr_algorithmic_bytes failed ({st}): {L.ctr_last_error().decode()}")
+        _check("ctr_algorithmic_bytes", L.ctr_algorithmic_bytes(self._h, C.c_float(fudge), bounces, C.byref(r), C.byref(b), C.byref(n)))
         return int(b.value), int(n.value)
 
     def last_counters(self):
@@ -371,16 +441,14 @@ class DeviceScene:
     def last_kernel(self):
         """The build (KV_* bits) of the handle's most recent launch (ctr_debug_last_kernel)."""
         kv = C.c_uint32()
-        if _lib.hip_lib().ctr_debug_last_kernel(self._h, C.byref(kv)):
-            raise RuntimeError("ctr_debug_last_kernel failed")
+        _check("ctr_debug_last_kernel", _lib.hip_lib().ctr_debug_last_kernel(self._h, C.byref(kv)))
         return int(kv.value)
 
     @staticmethod
     def lane_stats(reset=True):
         """Live-lane statistics of the VAR_STATS launches since the last reset (ctr_debug_lane_stats), decoded."""
         raw = np.zeros(96, np.uint64)
-        if _lib.hip_lib().ctr_debug_lane_stats(raw.ctypes.data, 1 if reset else 0):
-            raise RuntimeError("ctr_debug_lane_stats failed")
+        _check("ctr_debug_lane_stats", _lib.hip_lib().ctr_debug_lane_stats(raw.ctypes.data, 1 if reset else 0))
         c = [int(x) for x in raw]
         trips, live = c[72], c[73]
         out = {"wave_trips": trips, "live_lanes_per_trip": live / trips if trips else None,
@@ -408,29 +476,14 @@ class DeviceScene:
     def _rays_arg(self, x, what, cols):
         """(n, cols) float32 (cols 0: (n,)) on the scene's device: a tensor already there is used in place (made contiguous),
         a CPU tensor or a numpy array is copied over; another GPU, another shape or dtype raise."""
-        import torch
         dev = self._torch_device()
-        if isinstance(x, torch.Tensor):
-            if x.device.type != "cpu" and x.device != dev:
-                raise ValueError(f"{what}: tensor on {x.device}, the scene lives on {dev}")
-        elif isinstance(x, np.ndarray):
-            x = torch.from_numpy(x)
-        else:
-            raise TypeError(f"{what}: expected a torch tensor or a numpy array, got {type(x).__name__}")
-        shape_ok = x.dim() == 1 if cols == 0 else (x.dim() == 2 and x.shape[1] == cols)
-        if x.dtype != torch.float32 or not shape_ok:
-            raise ValueError(f"{what}: expected float32 of shape {'(n,)' if cols == 0 else f'(n, {cols})'}, "
-                             f"got {x.dtype} {tuple(x.shape)}")
-        return x.to(dev, non_blocking=False).contiguous()
+        return _rays_check(x, what, cols, dev).to(dev, non_blocking=False).contiguous()
 
     def _cast(self, q, keep, stream):
-        """Fill the query's ray pointers from `keep` and launch on the stream (torch's current one of the scene's device)."""
-        import torch
+        """Fill the query's ray pointers from `keep` and launch on the raw stream handle."""
         q.n_rays = keep[0].shape[0]
         q.d_origin, q.d_dir = keep[0].data_ptr() or None, keep[1].data_ptr() or None
-        st = _lib.hip_lib().ctr_cast_rays(self._h, C.byref(q), C.c_void_p(stream.cuda_stream))
-        if st:
-            raise RuntimeError(f"ctr_cast_rays failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
+        _check("ctr_cast_rays", _lib.hip_lib().ctr_cast_rays(self._h, C.byref(q), stream))
 
     def _per_ray(self, x, n, what):
         """A scalar, or (n,) float32 per-ray values: (scalar, tensor or None)."""
@@ -448,29 +501,19 @@ class DeviceScene:
         min_t: a scalar or (n,) float32.  Directions need not be normalised (a sphere measures t along dir/|dir|).
         linear=True: meshes walked linearly — bit-identical to the reference also for rays in a triangle's plane.
         Asynchronous on `stream` (a torch.cuda.Stream; default: torch's current stream of the scene's device)."""
-        import torch
-        outputs = RAY_OUTPUTS if outputs is None else tuple(outputs)
-        bad = [k for k in outputs if k not in RAY_OUTPUTS]
-        if bad or not outputs:
-            raise ValueError(f"outputs: a non-empty subset of {RAY_OUTPUTS}, got {outputs}")
+        outputs = RAY_OUTPUTS if outputs is None else _subset("outputs", outputs, RAY_OUTPUTS)
         dev = self._torch_device()
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
-            o = self._rays_arg(origins, "origins", 3)
-            d = self._rays_arg(dirs, "dirs", 3)
-            n = o.shape[0]
-            if d.shape[0] != n:
-                raise ValueError(f"dirs: {d.shape[0]} rays for {n} origins")
+        with _on_stream(dev, stream) as raw:
+            o, d, n = _ray_pair(origins, dirs, dev)
             q = _lib.RayQuery()
             q.flags = (RAY_IGNORE_TRANSPARENT if ignore_transparent else 0) | (RAY_LINEAR if linear else 0)
             q.min_t, mt = self._per_ray(min_t, n, "min_t")
             q.d_min_t = mt.data_ptr() if mt is not None and n else None
-            shapes = {"t": ((n,), torch.float32), "object": ((n,), torch.int32), "prim": ((n,), torch.int32),
-                      "point": ((n, 3), torch.float32), "normal": ((n, 3), torch.float32), "uv": ((n, 2), torch.float32)}
-            out = {k: torch.empty(*shapes[k][0], dtype=shapes[k][1], device=dev) for k in outputs}
+            out = _ray_outputs(outputs, n, dev)
             for k, v in out.items():
                 setattr(q, "d_" + k, v.data_ptr() if n else None)
             if n:
-                self._cast(q, (o, d, mt), torch.cuda.current_stream(dev))
+                self._cast(q, (o, d, mt), raw)
         return out
 
     def shadow(self, origins, dirs, max_t, linear=False, stream=None):
@@ -478,12 +521,8 @@ class DeviceScene:
         max_t: a scalar or (n,) float32.  The loop's first cast starts at (float)(0.0 + 1e-3), as the reference's does."""
         import torch
         dev = self._torch_device()
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
-            o = self._rays_arg(origins, "origins", 3)
-            d = self._rays_arg(dirs, "dirs", 3)
-            n = o.shape[0]
-            if d.shape[0] != n:
-                raise ValueError(f"dirs: {d.shape[0]} rays for {n} origins")
+        with _on_stream(dev, stream) as raw:
+            o, d, n = _ray_pair(origins, dirs, dev)
             q = _lib.RayQuery()
             q.flags = RAY_SHADOW | (RAY_LINEAR if linear else 0)
             q.max_t, mx = self._per_ray(max_t, n, "max_t")
@@ -491,7 +530,7 @@ class DeviceScene:
             out = torch.empty(n, dtype=torch.float32, device=dev)
             q.d_shadow = out.data_ptr() if n else None
             if n:
-                self._cast(q, (o, d, mx), torch.cuda.current_stream(dev))
+                self._cast(q, (o, d, mx), raw)
         return out
 
     def shade_rays(self, origins, dirs, bounces=5, min_t=1e-3, ambient=None, exact_pow=False, linear=False, outputs=None,
@@ -504,37 +543,25 @@ class DeviceScene:
         factor; None: that of the camera the scene was created with.  exact_pow=True: the specular term as under
         VAR_EXACT_POW (bitwise the reference's); linear=True: meshes walked linearly, exact also for rays in a triangle's
         plane.  Asynchronous on `stream` (a torch.cuda.Stream; default: torch's current stream of the scene's device)."""
-        import torch
-        outputs = ("color",) if outputs is None else tuple(outputs)
-        bad = [k for k in outputs if k not in SHADE_OUTPUTS]
-        if bad:
-            raise ValueError(f"outputs: a subset of {SHADE_OUTPUTS}, got {outputs}")
+        outputs = ("color",) if outputs is None else _subset("outputs", outputs, SHADE_OUTPUTS, allow_empty=True)
         outputs = ("color",) + tuple(k for k in outputs if k != "color")
         if not 0 <= int(bounces) <= 15:
             raise ValueError(f"bounces: 0 .. 15, got {bounces}")
         dev = self._torch_device()
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
-            o = self._rays_arg(origins, "origins", 3)
-            d = self._rays_arg(dirs, "dirs", 3)
-            n = o.shape[0]
-            if d.shape[0] != n:
-                raise ValueError(f"dirs: {d.shape[0]} rays for {n} origins")
+        with _on_stream(dev, stream) as raw:
+            o, d, n = _ray_pair(origins, dirs, dev)
             q = _lib.ShadeQuery()
             q.n_rays = n
             q.flags = (SHADE_LINEAR if linear else 0) | (SHADE_EXACT_POW if exact_pow else 0)
             q.bounces = int(bounces)
             q.min_t = float(min_t)
             q.ambient = float(self._ambient if ambient is None else ambient)
-            shapes = {"color": ((n, 3), torch.float32), "t": ((n,), torch.float32), "object": ((n,), torch.int32),
-                      "normal": ((n, 3), torch.float32)}
-            out = {k: torch.empty(*shapes[k][0], dtype=shapes[k][1], device=dev) for k in outputs}
+            out = _ray_outputs(outputs, n, dev)
             if n:
                 q.d_origin, q.d_dir = o.data_ptr(), d.data_ptr()
                 for k, v in out.items():
                     setattr(q, "d_" + k, v.data_ptr())
-                st = _lib.hip_lib().ctr_shade_rays(self._h, C.byref(q), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-                if st:
-                    raise RuntimeError(f"ctr_shade_rays failed ({st}): {_lib.hip_lib().ctr_last_error().decode()}")
+                _check("ctr_shade_rays", _lib.hip_lib().ctr_shade_rays(self._h, C.byref(q), raw))
         return out
 
     # ---- the lens render (ctr_render_device_lens, include/cutrace_lens.h) ----
@@ -556,23 +583,8 @@ class DeviceScene:
         n = rows_count(self.h, rows)
         dev = self._torch_device()
         H, W = samples * self.h, samples * self.w
-
-        def flat(x, what):
-            if not isinstance(x, (np.ndarray, torch.Tensor)):
-                raise TypeError(f"{what}: expected a torch tensor or a numpy array, got {type(x).__name__}")
-            shape = tuple(x.shape)
-            if len(shape) == 3:
-                if shape != (H, W, 3):
-                    raise ValueError(f"{what}: expected shape ({H}, {W}, 3) or ({H * W}, 3), got {shape}")
-                x = x.reshape(H * W, 3)
-            x = self._rays_arg(x, what, 3)
-            if x.shape[0] != H * W:
-                raise ValueError(f"{what}: {x.shape[0]} rays for the {W} x {H} frame ({H * W})")
-            return x
-
-        with torch.cuda.device(dev), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
-            o = flat(origins, "origins")
-            d = flat(dirs, "dirs")
+        with _on_stream(dev, stream) as raw:
+            o, d, _ = _ray_pair(origins, dirs, dev, frame=(H, W))
             depth = torch.empty(n, self.w, dtype=torch.float32, device=dev)
             color = torch.empty(n, self.w, 3, dtype=torch.float32, device=dev)
             normal = torch.empty(n, self.w, 3, dtype=torch.float32, device=dev)
@@ -582,11 +594,9 @@ class DeviceScene:
             q.samples = samples
             q.ambient = float(self._ambient if ambient is None else ambient)
             q.d_origin, q.d_dir = o.data_ptr() or None, d.data_ptr() or None
-            st = L.ctr_render_device_lens(self._h, C.c_float(fudge), int(bounces), C.byref(q), C.byref(r), depth.data_ptr() or None,
-                                          color.data_ptr() or None, normal.data_ptr() or None, counters.data_ptr(),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if st:
-                raise RuntimeError(f"ctr_render_device_lens failed ({st}): {L.ctr_last_error().decode()}")
+            _check("ctr_render_device_lens", L.ctr_render_device_lens(self._h, C.c_float(fudge), int(bounces), C.byref(q), C.byref(r),
+                                                                      depth.data_ptr() or None, color.data_ptr() or None,
+                                                                      normal.data_ptr() or None, counters.data_ptr(), raw))
             # (the rays must outlive the launch: tensors made here are kept until the counters have been read)
             c = counters.cpu()
         md = np.array([int(c[1]) & 0xFFFFFFFF], np.uint32).view(np.float32)[0]
@@ -623,9 +633,7 @@ class MultiScene:
         L = _lib.hip_lib()
         h = C.c_void_p()
         devs = (C.c_int * len(devices))(*devices)
-        st = L.ctr_multi_create(host_scene.desc, devs, len(devices), C.byref(h))
-        if st:
-            raise RuntimeError(f"ctr_multi_create failed ({st}): {L.ctr_last_error().decode()}")
+        _check("ctr_multi_create", L.ctr_multi_create(host_scene.desc, devs, len(devices), C.byref(h)))
         self._h = h
         self.devices = list(devices)
         self.w, self.h = host_scene.size
@@ -635,57 +643,34 @@ class MultiScene:
         return _lib.hip_lib().ctr_multi_transport(self._h).decode()
 
     def set_variant(self, bits):
-        if _lib.hip_lib().ctr_multi_set_variant(self._h, bits):
-            raise RuntimeError(f"ctr_multi_set_variant failed: {_lib.hip_lib().ctr_last_error().decode()}")
+        _check("ctr_multi_set_variant", _lib.hip_lib().ctr_multi_set_variant(self._h, bits))
 
     def set_size(self, w, h):
-        if _lib.hip_lib().ctr_multi_set_size(self._h, w, h):
-            raise RuntimeError("ctr_multi_set_size failed")
+        _check("ctr_multi_set_size", _lib.hip_lib().ctr_multi_set_size(self._h, w, h))
         self.w, self.h = w, h
 
     def render(self, fudge=1e-3, bounces=5, block_rows=8, pinned=False):
         """pinned=True: the buffers are views of a page-locked frame block of this group (valid until the next pinned
         render / close); device 0 then writes the frame into it directly."""
         L = _lib.hip_lib()
-        if pinned:
-            px = self.w * self.h
-            if getattr(self, "_pin_px", 0) != px:
-                self._free_pinned()
-                d, c, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)()
-                if L.ctr_frame_alloc(px, C.byref(d), C.byref(c), C.byref(n)):
-                    raise RuntimeError("ctr_frame_alloc failed")
-                self._pin_ptr, self._pin_px = d, px
-                self._pin = np.ctypeslib.as_array(d, shape=(7 * px,))
-            blk = self._pin
-            depth = blk[:px].reshape(self.h, self.w)
-            color = blk[px:4 * px].reshape(self.h, self.w, 3)
-            normal = blk[4 * px:7 * px].reshape(self.h, self.w, 3)
-        else:
-            depth = np.empty((self.h, self.w), np.float32)
-            color = np.empty((self.h, self.w, 3), np.float32)
-            normal = np.empty((self.h, self.w, 3), np.float32)
+        px = self.w * self.h
+        fr = _frame_views(_pinned_block(self, px, grow_only=False), px, self.h, self.w) if pinned else _empty_frame(self.h, self.w)
         stats = RenderStats()
-        st = L.ctr_render_multi(self._h, C.c_float(fudge), bounces, block_rows, depth.ctypes.data, color.ctypes.data,
-                                normal.ctypes.data, C.byref(stats))
-        if st:
-            raise RuntimeError(f"ctr_render_multi failed ({st})")
+        _check("ctr_render_multi", L.ctr_render_multi(self._h, C.c_float(fudge), bounces, block_rows, fr["depth"].ctypes.data,
+                                                      fr["color"].ctypes.data, fr["normal"].ctypes.data, C.byref(stats)))
+        return dict(fr, **self._stats(stats))
+
+    def _stats(self, stats):
         ms = (C.c_double * len(self.devices))()
-        L.ctr_multi_kernel_ms(self._h, ms, len(self.devices))
-        return dict(depth=depth, color=color, normal=normal, ray_count=int(stats.ray_count), kernel_ms=stats.kernel_ms,
-                    total_ms=stats.total_ms, max_depth=float(stats.max_depth), rows=int(stats.rows),
-                    kernel_ms_per_device=list(ms))
+        _lib.hip_lib().ctr_multi_kernel_ms(self._h, ms, len(self.devices))
+        return dict(_stats_dict(stats), kernel_ms_per_device=list(ms))
 
     def alloc_frame(self):
         """A page-locked frame block of the group's size (ctr_frame_alloc): dict of depth / color / normal views + a
         handle to pass to free_frame.  Page-locked destinations keep ctr_multi_submit asynchronous."""
-        L = _lib.hip_lib()
         px = self.w * self.h
-        d, c, n = C.POINTER(C.c_float)(), C.POINTER(C.c_float)(), C.POINTER(C.c_float)()
-        if L.ctr_frame_alloc(px, C.byref(d), C.byref(c), C.byref(n)):
-            raise RuntimeError("ctr_frame_alloc failed")
-        blk = np.ctypeslib.as_array(d, shape=(7 * px,))
-        return dict(depth=blk[:px].reshape(self.h, self.w), color=blk[px:4 * px].reshape(self.h, self.w, 3),
-                    normal=blk[4 * px:7 * px].reshape(self.h, self.w, 3), _ptr=d)
+        ptr, blk = _frame_alloc(px)
+        return dict(_frame_views(blk, px, self.h, self.w), _ptr=ptr)
 
     @staticmethod
     def free_frame(fr):
@@ -695,28 +680,17 @@ class MultiScene:
         """Queue one frame into the buffers of `into` (dict with depth / color / normal arrays of the group's size) and
         return at once (ctr_multi_submit); at most two frames in flight."""
         L = _lib.hip_lib()
-        st = L.ctr_multi_submit(self._h, C.c_float(fudge), bounces, block_rows, into["depth"].ctypes.data,
-                                into["color"].ctypes.data, into["normal"].ctypes.data)
-        if st:
-            raise RuntimeError(f"ctr_multi_submit failed ({st}): {L.ctr_last_error().decode()}")
+        _check("ctr_multi_submit", L.ctr_multi_submit(self._h, C.c_float(fudge), bounces, block_rows, into["depth"].ctypes.data,
+                                                      into["color"].ctypes.data, into["normal"].ctypes.data))
 
     def wait(self):
         """Block until the oldest queued frame is complete (ctr_multi_wait); returns its statistics."""
-        L = _lib.hip_lib()
         stats = RenderStats()
-        st = L.ctr_multi_wait(self._h, C.byref(stats))
-        if st:
-            raise RuntimeError(f"ctr_multi_wait failed ({st}): {L.ctr_last_error().decode()}")
-        ms = (C.c_double * len(self.devices))()
-        L.ctr_multi_kernel_ms(self._h, ms, len(self.devices))
-        return dict(ray_count=int(stats.ray_count), kernel_ms=stats.kernel_ms, total_ms=stats.total_ms,
-                    max_depth=float(stats.max_depth), rows=int(stats.rows), kernel_ms_per_device=list(ms))
+        _check("ctr_multi_wait", _lib.hip_lib().ctr_multi_wait(self._h, C.byref(stats)))
+        return self._stats(stats)
 
     def _free_pinned(self):
-        if getattr(self, "_pin_px", 0):
-            self._pin = None
-            _lib.hip_lib().ctr_frame_free(self._pin_ptr)
-            self._pin_px = 0
+        _free_pinned_block(self)
 
     def close(self):
         if self._h:

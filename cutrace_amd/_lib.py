@@ -93,35 +93,110 @@ class ImagePlanes(C.Structure):
                 ("max_depth", C.c_float), ("reserved", C.c_uint32)]
 
 
-HOST_SYMBOLS = [
-    "ctr_host_scene_load", "ctr_host_scene_parse", "ctr_host_scene_free", "ctr_host_scene_desc",
-    "ctr_host_scene_set_size", "ctr_host_scene_set_material", "ctr_stl_read", "ctr_stl_write",
-    "ctr_dump_scene", "ctr_dump_schema", "ctr_quantise_depth", "ctr_quantise_normal", "ctr_quantise_color",
-    "ctr_write_jpg", "ctr_write_depth_map", "ctr_write_normal_map", "ctr_write_colorized",
-    "ctr_camera_look_at", "ctr_mesh_bounds", "ctr_rows_count",
-]
-HIP_SYMBOLS = [
-    "ctr_abi_version", "ctr_last_error", "ctr_device_count", "ctr_scene_create", "ctr_scene_destroy",
-    "ctr_scene_size", "ctr_scene_set_size", "ctr_render", "ctr_render_device", "ctr_set_variant",
-    "ctr_scene_set_cameras", "ctr_render_device_batch",
-    "ctr_algorithmic_bytes", "ctr_frame_alloc", "ctr_frame_free", "ctr_tile_costs", "ctr_last_counters", "ctr_selftest_exact_math",
-    "ctr_debug_poison_next_order", "ctr_render_uv", "ctr_debug_lane_stats", "ctr_debug_last_kernel",
-    "ctr_multi_create", "ctr_multi_destroy", "ctr_multi_devices", "ctr_multi_transport", "ctr_multi_size", "ctr_multi_set_size",
-    "ctr_multi_set_variant", "ctr_render_multi", "ctr_multi_kernel_ms", "ctr_reinterleave_device",
-    "ctr_multi_submit", "ctr_multi_wait",
-]
+_int, _u32, _u64, _f32, _ptr, _str, _P = C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p, C.c_char_p, C.POINTER
+_f32p = _P(C.c_float)
 
-# include/cutrace_rays.h (kept apart from HIP_SYMBOLS, which mirrors cutrace_amd.h)
-RAY_SYMBOLS = ["ctr_cast_rays", "ctr_shade_rays"]
-# include/cutrace_aa.h
-AA_SYMBOLS = ["ctr_render_aa", "ctr_render_device_aa"]
-# include/cutrace_lens.h
-LENS_SYMBOLS = ["ctr_render_device_lens"]
-# include/cutrace_images.h
-IMAGES_SYMBOLS = ["ctr_quantise_device", "ctr_render_images"]
+# One table per library: header -> symbol -> (argtypes, restype), or None for a symbol called without a prototype.
+# argtypes None: none declared; restype None: void.  A new entry point is added here and nowhere else.
+HOST_PROTOS = {
+    "cutrace_host.h": {
+        "ctr_host_scene_load": ([_str, _P(_ptr)], _int),
+        "ctr_host_scene_parse": ([_str, _P(_ptr)], _int),
+        "ctr_host_scene_free": ([_ptr], _int),
+        "ctr_host_scene_desc": ([_ptr], _P(SceneDesc)),
+        "ctr_host_scene_set_size": ([_ptr, _u64, _u64], _int),
+        "ctr_host_scene_set_material": ([_ptr, _u64, _P(Material)], _int),
+        "ctr_stl_read": ([_str, _P(Triangle), _u64], C.c_int64),
+        "ctr_stl_write": ([_str, _P(Triangle), _u64], _int),
+        "ctr_dump_scene": ([_P(SceneDesc)], _int),
+        "ctr_dump_schema": None,
+        "ctr_quantise_depth": ([_ptr, _u64, _f32, _ptr], _int),
+        "ctr_quantise_normal": ([_ptr, _u64, _ptr], _int),
+        "ctr_quantise_color": ([_ptr, _u64, _ptr], _int),
+        "ctr_write_jpg": ([_str, _int, _int, _ptr, _int], _int),
+        "ctr_write_depth_map": ([_str, _ptr, _u64, _u64, _f32], _int),
+        "ctr_write_normal_map": ([_str, _ptr, _u64, _u64], _int),
+        "ctr_write_colorized": ([_str, _ptr, _u64, _u64], _int),
+        "ctr_camera_look_at": ([_P(Camera), Vec3, Vec3, Vec3], _int),
+        "ctr_mesh_bounds": ([_P(Triangle), _u64, _P(Vec3), _P(Vec3)], _int),
+        "ctr_rows_count": ([_P(Rows), _u64], _u64),
+    },
+}
+HIP_PROTOS = {
+    "cutrace_amd.h": {
+        "ctr_abi_version": None,
+        "ctr_last_error": (None, _str),
+        "ctr_device_count": None,
+        "ctr_scene_create": ([_P(SceneDesc), _int, _P(_ptr)], _int),
+        "ctr_scene_destroy": ([_ptr], _int),
+        "ctr_scene_size": ([_ptr, _P(_u64), _P(_u64)], _int),
+        "ctr_scene_set_size": ([_ptr, _u64, _u64], _int),
+        "ctr_render": ([_ptr, _f32, _int, _P(Rows), _ptr, _ptr, _ptr, _P(RenderStats)], _int),
+        "ctr_render_device": ([_ptr, _f32, _int, _P(Rows), _ptr, _ptr, _ptr, _ptr, _ptr], _int),
+        "ctr_set_variant": ([_ptr, _u32], _int),
+        "ctr_scene_set_cameras": ([_ptr, _P(Camera), _u32], _int),
+        "ctr_render_device_batch": ([_ptr, _f32, _int, _P(Rows), _u32, _u32, _u64, _u32, _ptr, _ptr, _ptr, _ptr, _ptr], _int),
+        "ctr_algorithmic_bytes": ([_ptr, _f32, _int, _P(Rows), _P(_u64), _P(_u64)], _int),
+        "ctr_frame_alloc": ([_u64, _P(_f32p), _P(_f32p), _P(_f32p)], _int),
+        "ctr_frame_free": ([_f32p], None),
+        "ctr_tile_costs": ([_ptr, _ptr, _u64, _P(_u64)], _int),
+        "ctr_last_counters": ([_ptr, _ptr], _int),
+        "ctr_selftest_exact_math": ([_P(_u64)], _int),
+        "ctr_debug_poison_next_order": ([_ptr], _int),
+        "ctr_render_uv": ([_ptr, _f32, _int, _P(Rows), _ptr, _ptr, _ptr, _ptr, _P(RenderStats)], _int),
+        "ctr_debug_lane_stats": ([_ptr, _int], _int),
+        "ctr_debug_last_kernel": ([_ptr, _P(_u32)], _int),
+        "ctr_multi_create": ([_P(SceneDesc), _P(_int), _int, _P(_ptr)], _int),
+        "ctr_multi_destroy": ([_ptr], None),
+        "ctr_multi_devices": ([_ptr], _int),
+        "ctr_multi_transport": ([_ptr], _str),
+        "ctr_multi_size": ([_ptr, _P(_u64), _P(_u64)], _int),
+        "ctr_multi_set_size": ([_ptr, _u64, _u64], _int),
+        "ctr_multi_set_variant": ([_ptr, _u32], _int),
+        "ctr_render_multi": ([_ptr, _f32, _int, _u64, _ptr, _ptr, _ptr, _P(RenderStats)], _int),
+        "ctr_multi_kernel_ms": ([_ptr, _P(C.c_double), _int], _int),
+        "ctr_reinterleave_device": ([_P(ReintPart), _u32, _u64, _u64, _u64, _ptr, _ptr, _ptr, _ptr], _int),
+        "ctr_multi_submit": ([_ptr, _f32, _int, _u64, _ptr, _ptr, _ptr], _int),
+        "ctr_multi_wait": ([_ptr, _P(RenderStats)], _int),
+    },
+    "cutrace_rays.h": {
+        "ctr_cast_rays": ([_ptr, _P(RayQuery), _ptr], _int),
+        "ctr_shade_rays": ([_ptr, _P(ShadeQuery), _ptr], _int),
+    },
+    "cutrace_aa.h": {
+        "ctr_render_aa": ([_ptr, _f32, _int, _u32, _P(Rows), _ptr, _ptr, _ptr, _P(RenderStats)], _int),
+        "ctr_render_device_aa": ([_ptr, _f32, _int, _u32, _P(Rows), _ptr, _ptr, _ptr, _ptr, _ptr], _int),
+    },
+    "cutrace_lens.h": {
+        "ctr_render_device_lens": ([_ptr, _f32, _int, _P(Lens), _P(Rows), _ptr, _ptr, _ptr, _ptr, _ptr], _int),
+    },
+    "cutrace_images.h": {
+        "ctr_quantise_device": ([_int, _P(ImagePlanes), _ptr], _int),
+        "ctr_render_images": ([_ptr, _f32, _int, _u32, _P(Rows), _ptr, _ptr, _ptr, _P(RenderStats)], _int),
+    },
+}
+
+# the symbols each header declares (the tests compare them with the headers)
+HOST_SYMBOLS = list(HOST_PROTOS["cutrace_host.h"])
+HIP_SYMBOLS = list(HIP_PROTOS["cutrace_amd.h"])
+RAY_SYMBOLS = list(HIP_PROTOS["cutrace_rays.h"])
+AA_SYMBOLS = list(HIP_PROTOS["cutrace_aa.h"])
+LENS_SYMBOLS = sorted(HIP_PROTOS["cutrace_lens.h"])
+IMAGES_SYMBOLS = list(HIP_PROTOS["cutrace_images.h"])
 
 _host = None
 _hip = None
+
+
+def _declare(L, protos):
+    """Give every symbol of the table that L exports its prototype; an older build (loaded through CUTRACE_AMD_LIB for A/B
+    timing) may lack the later entry points."""
+    for symbols in protos.values():
+        for name, proto in symbols.items():
+            if proto is not None and hasattr(L, name):
+                fn = getattr(L, name)
+                fn.argtypes, fn.restype = proto
+    return L
 
 
 def host_lib():
@@ -130,30 +205,7 @@ def host_lib():
         path = os.environ.get("CUTRACE_HOST_LIB") or os.path.join(PKG, "libcutrace_host.so")  # override: sanitizer builds (scripts/cpu_sanitize.sh)
         if not os.path.exists(path):
             raise RuntimeError(f"{path} missing: run `python -m cutrace_amd.build` (or __graft_entry__.build())")
-        L = C.CDLL(path)
-        L.ctr_host_scene_load.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        L.ctr_host_scene_parse.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
-        L.ctr_host_scene_free.argtypes = [C.c_void_p]
-        L.ctr_host_scene_desc.argtypes = [C.c_void_p]
-        L.ctr_host_scene_desc.restype = C.POINTER(SceneDesc)
-        L.ctr_host_scene_set_size.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
-        L.ctr_host_scene_set_material.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(Material)]
-        L.ctr_stl_read.argtypes = [C.c_char_p, C.POINTER(Triangle), C.c_uint64]
-        L.ctr_stl_read.restype = C.c_int64
-        L.ctr_stl_write.argtypes = [C.c_char_p, C.POINTER(Triangle), C.c_uint64]
-        L.ctr_dump_scene.argtypes = [C.POINTER(SceneDesc)]
-        L.ctr_camera_look_at.argtypes = [C.POINTER(Camera), Vec3, Vec3, Vec3]
-        L.ctr_mesh_bounds.argtypes = [C.POINTER(Triangle), C.c_uint64, C.POINTER(Vec3), C.POINTER(Vec3)]
-        L.ctr_rows_count.argtypes = [C.POINTER(Rows), C.c_uint64]
-        L.ctr_rows_count.restype = C.c_uint64
-        for fn in ("ctr_quantise_normal", "ctr_quantise_color"):
-            getattr(L, fn).argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-        L.ctr_quantise_depth.argtypes = [C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]
-        L.ctr_write_jpg.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        L.ctr_write_depth_map.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float]
-        L.ctr_write_normal_map.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64]
-        L.ctr_write_colorized.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64]
-        _host = L
+        _host = _declare(C.CDLL(path), HOST_PROTOS)
     return _host
 
 
@@ -166,65 +218,5 @@ def hip_lib():
             raise RuntimeError(f"{path} missing: the HIP extension is not built; refusing to fall back to CPU")
         # the CLI links both libs; load host first so shared symbols resolve identically
         host_lib()
-        L = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        L.ctr_last_error.restype = C.c_char_p
-        L.ctr_scene_create.argtypes = [C.POINTER(SceneDesc), C.c_int, C.POINTER(C.c_void_p)]
-        L.ctr_scene_destroy.argtypes = [C.c_void_p]
-        L.ctr_scene_size.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.ctr_scene_set_size.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
-        L.ctr_render.argtypes = [C.c_void_p, C.c_float, C.c_int, C.POINTER(Rows), C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.POINTER(RenderStats)]
-        L.ctr_render_device.argtypes = [C.c_void_p, C.c_float, C.c_int, C.POINTER(Rows), C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ctr_set_variant.argtypes = [C.c_void_p, C.c_uint32]
-        L.ctr_scene_set_cameras.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_uint32]
-        L.ctr_render_device_batch.argtypes = [C.c_void_p, C.c_float, C.c_int, C.POINTER(Rows), C.c_uint32, C.c_uint32,
-                                              C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ctr_algorithmic_bytes.argtypes = [C.c_void_p, C.c_float, C.c_int, C.POINTER(Rows), C.POINTER(C.c_uint64),
-                                            C.POINTER(C.c_uint64)]
-        # entry points added after round 1 (an older build may be loaded through CUTRACE_AMD_LIB for A/B timing)
-        opt = {
-            "ctr_frame_alloc": ([C.c_uint64, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float)),
-                                 C.POINTER(C.POINTER(C.c_float))], C.c_int),
-            "ctr_frame_free": ([C.POINTER(C.c_float)], None),
-            "ctr_multi_create": ([C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-            "ctr_multi_destroy": ([C.c_void_p], None),
-            "ctr_multi_devices": ([C.c_void_p], C.c_int),
-            "ctr_multi_transport": ([C.c_void_p], C.c_char_p),
-            "ctr_multi_size": ([C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)], C.c_int),
-            "ctr_multi_set_size": ([C.c_void_p, C.c_uint64, C.c_uint64], C.c_int),
-            "ctr_multi_set_variant": ([C.c_void_p, C.c_uint32], C.c_int),
-            "ctr_render_multi": ([C.c_void_p, C.c_float, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.POINTER(RenderStats)], C.c_int),
-            "ctr_multi_submit": ([C.c_void_p, C.c_float, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-            "ctr_multi_wait": ([C.c_void_p, C.POINTER(RenderStats)], C.c_int),
-            "ctr_reinterleave_device": ([C.POINTER(ReintPart), C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-            "ctr_multi_kernel_ms": ([C.c_void_p, C.POINTER(C.c_double), C.c_int], C.c_int),
-            "ctr_selftest_exact_math": ([C.POINTER(C.c_uint64)], C.c_int),
-            "ctr_last_counters": ([C.c_void_p, C.c_void_p], C.c_int),
-            "ctr_debug_poison_next_order": ([C.c_void_p], C.c_int),
-            "ctr_debug_lane_stats": ([C.c_void_p, C.c_int], C.c_int),
-            "ctr_debug_last_kernel": ([C.c_void_p, C.POINTER(C.c_uint32)], C.c_int),
-            "ctr_render_uv": ([C.c_void_p, C.c_float, C.c_int, C.POINTER(Rows), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.POINTER(RenderStats)], C.c_int),
-            "ctr_tile_costs": ([C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int),
-            "ctr_cast_rays": ([C.c_void_p, C.POINTER(RayQuery), C.c_void_p], C.c_int),
-            "ctr_shade_rays": ([C.c_void_p, C.POINTER(ShadeQuery), C.c_void_p], C.c_int),
-            "ctr_render_aa": ([C.c_void_p, C.c_float, C.c_int, C.c_uint32, C.POINTER(Rows), C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.POINTER(RenderStats)], C.c_int),
-            "ctr_render_device_aa": ([C.c_void_p, C.c_float, C.c_int, C.c_uint32, C.POINTER(Rows), C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-            "ctr_render_device_lens": ([C.c_void_p, C.c_float, C.c_int, C.POINTER(Lens), C.POINTER(Rows), C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-            "ctr_quantise_device": ([C.c_int, C.POINTER(ImagePlanes), C.c_void_p], C.c_int),
-            "ctr_render_images": ([C.c_void_p, C.c_float, C.c_int, C.c_uint32, C.POINTER(Rows), C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.POINTER(RenderStats)], C.c_int),
-        }
-        for name, (argt, rest) in opt.items():
-            if hasattr(L, name):
-                fn = getattr(L, name)
-                fn.argtypes = argt
-                fn.restype = rest
-        _hip = L
+        _hip = _declare(C.CDLL(path, mode=C.RTLD_GLOBAL), HIP_PROTOS)
     return _hip

@@ -220,7 +220,7 @@ class FrameTiler:
     def _assemble_hip(self, slot):
         """On the GPU: one launch of the library's re-interleave kernel per frame (ctr_reinterleave_device)
         instead of three torch.index_select passes — each row is read and written once, 16 bytes per lane."""
-        from . import _lib
+        from . import _check, _lib
         L = _lib.hip_lib()
         W = self.world
         stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -233,7 +233,6 @@ class FrameTiler:
                     r = (p - f * self.part_stride) % W  # the rank that rendered part p of frame f
                     parts[p].d_depth, parts[p].d_color3, parts[p].d_normal3 = (t.data_ptr() for t in src[r])
                 self._parts[(slot, i)] = parts
-            st = L.ctr_reinterleave_device(parts, W, self.block_rows, self.w, self.h, self.final["depth"][i].data_ptr(),
-                                           self.final["color"][i].data_ptr(), self.final["normal"][i].data_ptr(), stream)
-            if st:
-                raise RuntimeError("ctr_reinterleave_device failed")
+            _check("ctr_reinterleave_device", L.ctr_reinterleave_device(parts, W, self.block_rows, self.w, self.h,
+                                                                        self.final["depth"][i].data_ptr(), self.final["color"][i].data_ptr(),
+                                                                        self.final["normal"][i].data_ptr(), stream))
