@@ -37,6 +37,10 @@ RAY_OUTPUTS = ("t", "object", "prim", "point", "normal", "uv")
 SHADE_LINEAR = 1
 SHADE_EXACT_POW = 2
 SHADE_OUTPUTS = ("color", "t", "object", "normal")
+# ctr_shade_points flags and outputs (include/cutrace_rays.h)
+POINTS_LINEAR = 1
+POINTS_EXACT_POW = 2
+POINTS_OUTPUTS = ("color", "light_shadow")
 # the display planes of render_images / quantise (include/cutrace_images.h)
 IMAGE_PLANES = ("color", "depth", "normal")
 
@@ -262,7 +266,8 @@ class DeviceScene:
         self._h = h
         self.device = device
         self.w, self.h = host_scene.size
-        self._ambient = float(host_scene.desc.contents.cam.ambient)  # shade_rays' default
+        self._ambient = float(host_scene.desc.contents.cam.ambient)  # shade_rays' and shade_points' default
+        self.n_lights = int(host_scene.desc.contents.n_lights)       # the width of shade_points' light_shadow
 
     def set_variant(self, bits):
         _check("ctr_set_variant", _lib.hip_lib().ctr_set_variant(self._h, bits))
@@ -562,6 +567,90 @@ class DeviceScene:
                 for k, v in out.items():
                     setattr(q, "d_" + k, v.data_ptr())
                 _check("ctr_shade_rays", _lib.hip_lib().ctr_shade_rays(self._h, C.byref(q), raw))
+        return out
+
+    # ---- surface shading queries (ctr_shade_points, include/cutrace_rays.h) ----
+    @staticmethod
+    def _index_check(x, what, dev):
+        """x as an int32 tensor of shape (n,), still where it was (as _rays_check leaves float arrays)."""
+        import torch
+        if isinstance(x, torch.Tensor):
+            if x.device.type != "cpu" and x.device != dev:
+                raise ValueError(f"{what}: tensor on {x.device}, the scene lives on {dev}")
+        elif isinstance(x, np.ndarray):
+            x = torch.from_numpy(x)
+        else:
+            raise TypeError(f"{what}: expected an int, a torch tensor or a numpy array, got {type(x).__name__}")
+        if x.dtype != torch.int32 or x.dim() != 1:
+            raise ValueError(f"{what}: expected int32 of shape (n,), got {x.dtype} {tuple(x.shape)}")
+        return x
+
+    def shade_points(self, points, normals=None, view_dirs=None, materials=None, objects=None, ambient=None, exact_pow=False,
+                     linear=False, outputs=("color",), stream=None):
+        """phong (inc/shading.hpp:64-99) at caller-supplied surface points: the direct lighting of points[k] with normal
+        normals[k], seen along view_dirs[k] (incoming->dir), over every light of the scene, each with its own shadow loop
+        through the scene — with the numerics of shade_rays.  points, normals, view_dirs: (n, 3) float32, normals and view
+        directions of any length.  materials: an int (every point's material) or (n,) int32 indices into the scene's
+        materials; objects: (n,) int32 indices into the scene's objects — the point gets that object's material, and -1
+        (cast_rays' `object` on a miss) gives (0, 0, 0): shade_points on the output of cast_rays is
+        shade_rays(bounces=0).  An index outside its range gives NaN.  outputs: a non-empty subset of "color" (n, 3) and
+        "light_shadow" (n, n_lights): shadow_intensity towards every light, in light order; for "light_shadow" alone only
+        `points` is needed.  ambient: phong's ambient factor; None: that of the camera the scene was created with.
+        exact_pow=True: the specular term as under VAR_EXACT_POW (bitwise the reference's); linear=True: meshes walked
+        linearly (the default walk is exact for every point already: every ray cast here ends at a light, and the lights
+        are guarded).  Returns a dict of tensors on the scene's device.  Asynchronous on `stream` (a torch.cuda.Stream;
+        default: torch's current stream of the scene's device)."""
+        import torch
+        outputs = _subset("outputs", outputs, POINTS_OUTPUTS, unique=True)
+        dev = self._torch_device()
+        want_color = "color" in outputs
+        if materials is not None and objects is not None:
+            raise ValueError("materials and objects exclude each other")
+        if want_color and materials is None and objects is None:
+            raise ValueError("color needs materials or objects")
+        if want_color and (normals is None or view_dirs is None):
+            raise ValueError("color needs normals and view_dirs")
+        pts = _rays_check(points, "points", 3, dev)
+        n = pts.shape[0]
+        vec = {}
+        for x, what in ((normals, "normals"), (view_dirs, "view_dirs")):
+            if x is not None:
+                vec[what] = _rays_check(x, what, 3, dev)
+                if vec[what].shape[0] != n:
+                    raise ValueError(f"{what}: {vec[what].shape[0]} rows for {n} points")
+        scalar_mat, idx, idx_name = 0, None, None
+        if isinstance(materials, (int, np.integer)) and not isinstance(materials, bool):
+            scalar_mat = int(materials)
+        elif materials is not None:
+            idx, idx_name = self._index_check(materials, "materials", dev), "d_material"
+        elif objects is not None:
+            idx, idx_name = self._index_check(objects, "objects", dev), "d_object"
+        if idx is not None and idx.shape[0] != n:
+            raise ValueError(f"{'materials' if idx_name == 'd_material' else 'objects'}: {idx.shape[0]} indices for {n} points")
+        with _on_stream(dev, stream) as raw:
+            # (the inputs must outlive the launch: `keep` holds what was copied over until the call returns, and the
+            # stream orders the caching allocator's reuse after it)
+            keep = [pts.to(dev).contiguous()]
+            q = _lib.PointQuery()
+            q.n_points = n
+            q.flags = (POINTS_LINEAR if linear else 0) | (POINTS_EXACT_POW if exact_pow else 0)
+            q.material = scalar_mat
+            q.ambient = float(self._ambient if ambient is None else ambient)
+            shape = {"color": (n, 3), "light_shadow": (n, self.n_lights)}
+            out = {k: torch.empty(shape[k], dtype=torch.float32, device=dev) for k in outputs}
+            if want_color:
+                keep += list(_ray_pair(vec["normals"], vec["view_dirs"], dev)[:2])
+                if idx is not None:
+                    keep.append(idx.to(dev).contiguous())
+            if n and (want_color or self.n_lights):
+                q.d_point = keep[0].data_ptr()
+                if want_color:
+                    q.d_normal, q.d_view, q.d_color = keep[1].data_ptr(), keep[2].data_ptr(), out["color"].data_ptr()
+                    if idx is not None:
+                        setattr(q, idx_name, keep[3].data_ptr())
+                if "light_shadow" in out and self.n_lights:
+                    q.d_light_shadow = out["light_shadow"].data_ptr()
+                _check("ctr_shade_points", _lib.hip_lib().ctr_shade_points(self._h, C.byref(q), raw))
         return out
 
     # ---- the lens render (ctr_render_device_lens, include/cutrace_lens.h) ----

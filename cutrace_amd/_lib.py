@@ -80,6 +80,13 @@ class ShadeQuery(C.Structure):
                 ("d_t", C.c_void_p), ("d_object", C.c_void_p), ("d_normal", C.c_void_p)]
 
 
+class PointQuery(C.Structure):
+    """ctr_point_query (include/cutrace_rays.h)"""
+    _fields_ = [("n_points", C.c_uint64), ("flags", C.c_uint32), ("material", C.c_int32), ("ambient", C.c_float),
+                ("reserved", C.c_uint32), ("d_point", C.c_void_p), ("d_normal", C.c_void_p), ("d_view", C.c_void_p),
+                ("d_material", C.c_void_p), ("d_object", C.c_void_p), ("d_color", C.c_void_p), ("d_light_shadow", C.c_void_p)]
+
+
 class Lens(C.Structure):
     """ctr_lens (include/cutrace_lens.h)"""
     _fields_ = [("n_rays", C.c_uint64), ("samples", C.c_uint32), ("ambient", C.c_float), ("d_origin", C.c_void_p),
@@ -162,6 +169,7 @@ HIP_PROTOS = {
     "cutrace_rays.h": {
         "ctr_cast_rays": ([_ptr, _P(RayQuery), _ptr], _int),
         "ctr_shade_rays": ([_ptr, _P(ShadeQuery), _ptr], _int),
+        "ctr_shade_points": ([_ptr, _P(PointQuery), _ptr], _int),
     },
     "cutrace_aa.h": {
         "ctr_render_aa": ([_ptr, _f32, _int, _u32, _P(Rows), _ptr, _ptr, _ptr, _P(RenderStats)], _int),

@@ -1,7 +1,7 @@
 """Build the native libraries in-tree (no network, no cmake needed).
 
   libcutrace_host.so   g++    host side: JSON loader, STL reader, image writers
-  libcutrace_amd.so    hipcc  gfx950 render, ray-query and display-quantise kernels + the C-ABI of include/cutrace_amd.h (csrc/ctr_api.cpp,
+  libcutrace_amd.so    hipcc  gfx950 render, ray-query, surface-shading and display-quantise kernels + the C-ABI of include/cutrace_amd.h (csrc/ctr_api.cpp,
                               csrc/ctr_multi.hip) and cutrace_rays.h (csrc/ctr_rays.cpp); what those three share: csrc/ctr_internal.h
   cutrace              hipcc  the drop-in CLI (`cutrace <scene.json>`, reference main.cu)
 
@@ -27,7 +27,8 @@ HOST_SRCS = [os.path.join(HOST, "scene_host.cpp"), os.path.join(HOST, "images.cp
 HIP_SRCS = [os.path.join(CSRC, "render_kernel.hip"), os.path.join(CSRC, "ctr_api.cpp"), os.path.join(CSRC, "bvh.cpp"),
             os.path.join(CSRC, "ctr_multi.hip"), os.path.join(CSRC, "ray_query.hip"), os.path.join(CSRC, "scene_flatten.cpp"),
             os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "ray_shade.hip"), os.path.join(CSRC, "ctr_rays.cpp"),
-            os.path.join(CSRC, "kernel_choice.cpp"), os.path.join(CSRC, "frame_images.hip"), os.path.join(CSRC, "tile_order.hip")]
+            os.path.join(CSRC, "kernel_choice.cpp"), os.path.join(CSRC, "frame_images.hip"), os.path.join(CSRC, "tile_order.hip"),
+            os.path.join(CSRC, "ray_points.hip")]
 CLI_SRCS = [os.path.join(HOST, "main.cpp")]
 
 HOST_FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-pthread", "-Wall", "-I" + INC]

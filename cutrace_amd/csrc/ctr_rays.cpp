@@ -1,11 +1,12 @@
-// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h: ctr_cast_rays and ctr_shade_rays check a query, describe the
-// uploaded scene to the kernel (RayScene, ray_query.h) and launch it (ray_query.hip, ray_shade.hip).
+// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h: ctr_cast_rays, ctr_shade_rays and ctr_shade_points check a query,
+// describe the uploaded scene to the kernel (RayScene, ray_query.h) and launch it (ray_query.hip, ray_shade.hip, ray_points.hip).
 #include <hip/hip_runtime_api.h>
 
 #include <string>
 
 #include "ctr_internal.h"
 #include "cutrace_rays.h"
+#include "ray_points.h"
 #include "ray_query.h"
 #include "ray_shade.h"
 
@@ -141,5 +142,53 @@ extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_
   if (int st = use_device(s)) return st;
   const int e = ctr_launch_shade(L, hip_stream);
   if (e) return hip_fail((hipError_t)e, "radiance query kernel launch");
+  return CTR_OK;
+}
+
+extern "C" int ctr_shade_points(ctr_scene *s, const ctr_point_query *q, void *hip_stream) {
+  const std::string who = "ctr_shade_points: ";
+  if (!q) return fail(CTR_E_INVALID, who + "null query");
+  constexpr uint32_t KNOWN = CTR_POINTS_LINEAR | CTR_POINTS_EXACT_POW;
+  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(q->flags & ~KNOWN));
+  if (!q->d_color && !q->d_light_shadow) return fail(CTR_E_INVALID, who + "no output: one of d_color and d_light_shadow is required");
+  if (q->d_color && (!q->d_normal || !q->d_view)) return fail(CTR_E_INVALID, who + "d_color needs d_normal and d_view");
+  if (q->d_material && q->d_object) return fail(CTR_E_INVALID, who + "d_material and d_object exclude each other");
+  if (!s) return fail(CTR_E_INVALID, who + "null scene");
+  if (q->n_points >= 0x80000000ull) return fail(CTR_E_INVALID, who + "n_points must be below 2^31");
+  if (q->n_points && !q->d_point) return fail(CTR_E_INVALID, who + "null d_point");
+  const size_t n_mat = s->flat.mats.size();
+  if (q->d_color && !q->d_material && !q->d_object && (q->material < 0 || (size_t)q->material >= n_mat))
+    return fail(CTR_E_INVALID, who + "material " + std::to_string(q->material) + " outside [0, " + std::to_string(n_mat) + ")");
+  if (q->n_points == 0) return CTR_OK;
+  const void *ptrs[] = {q->d_point, q->d_normal, q->d_view, q->d_material, q->d_object, q->d_color, q->d_light_shadow};
+  const char *names[] = {"d_point", "d_normal", "d_view", "d_material", "d_object", "d_color", "d_light_shadow"};
+  if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
+  PointsLaunch L{};
+  L.scene = ray_scene(s);
+  L.lights = s->d_lights;
+  L.n_light = (uint32_t)s->flat.lights.size();
+  L.n_mat = (uint32_t)n_mat;
+  L.n_obj = (uint32_t)s->flat.objs.size();
+  L.all_opaque = s->flat.all_opaque ? 1u : 0u;
+  L.n_points = (uint32_t)q->n_points;
+  L.flags = q->flags | (s->flat.fast_pow_ok ? 0u : CTR_POINTS_EXACT_POW);  // (outside the fast path's domain: the exact one)
+  L.material = q->material;
+  L.ambient = q->ambient;
+  L.point = q->d_point;
+  // without d_color the kernel reads none of these
+  L.normal = q->d_color ? q->d_normal : nullptr;
+  L.view = q->d_color ? q->d_view : nullptr;
+  L.mat_arr = q->d_color ? q->d_material : nullptr;
+  L.obj_arr = q->d_color ? q->d_object : nullptr;
+  L.color = q->d_color;
+  L.light_shadow = L.n_light ? q->d_light_shadow : nullptr;
+  if (ctr_points_lds_bytes(L) > CTR_POINTS_LDS_MAX)
+    return fail(CTR_E_INVALID, who + "the walk stack of this scene's mesh trees needs " + std::to_string(ctr_points_lds_bytes(L)) +
+                                   " bytes of LDS per workgroup, more than " + std::to_string(CTR_POINTS_LDS_MAX) +
+                                   " (CTR_POINTS_LINEAR needs none)");
+  if (!L.color && !L.light_shadow) return CTR_OK;  // a scene without lights: the rows of d_light_shadow are empty
+  if (int st = use_device(s)) return st;
+  const int e = ctr_launch_points(L, hip_stream);
+  if (e) return hip_fail((hipError_t)e, "surface shading kernel launch");
   return CTR_OK;
 }

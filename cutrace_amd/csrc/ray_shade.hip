@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "cutrace_rays.h"
+#include "phong_light.h"
 #include "ray_shade.h"
 #include "ray_walk.h"
 
@@ -140,23 +141,8 @@ __global__ __launch_bounds__(RS_THREADS) void ray_shade_kernel(ShadeLaunch L) {
       }
       if (done_shadow) {
         if (shadow_fac < 1.0f) {
-          // shading.hpp:86-95
-          const DMat M = mats[mat_i];
-          const DLight Lg = lights[li];
-          const V3 diffuse = mk(M.cx, M.cy, M.cz);
-          const V3 specular = vscale(diffuse, M.specular);  // default_schema.hpp:328
-          const V3 color = mk(Lg.cx, Lg.cy, Lg.cz);
-          const V3 nd = rd;  // the shadow ray's direction IS direction.normalized()
-          const float fd_ = smax(0.0f, vdot(nn, nd));
-          const V3 ld = vmul(diffuse, color);
-          const V3 hsum = vadd(vscale(in_dn, -1.0f), nd);
-          const V3 hv = EXACT ? vnormalized(hsum) : vscale(hsum, __builtin_amdgcn_rsqf(vdot(hsum, hsum)));
-          const float sx = smax(0.0f, vdot(nn, hv));
-          float fs;
-          if (EXACT) fs = (float)pow((double)sx, (double)M.phong_exp);  // f64, rounded once
-          else fs = (M.phong_exp == 0.0f) ? 1.0f : __builtin_amdgcn_exp2f(M.phong_exp * __builtin_amdgcn_logf(sx));
-          const V3 ls = vmul(specular, color);
-          fin = vadd(fin, vscale(vadd(vscale(ld, fd_), vscale(ls, fs)), 1 - shadow_fac));
+          // shading.hpp:86-95 (phong_light.h); the shadow ray's direction IS direction.normalized()
+          fin = vadd(fin, lit_term<EXACT>(mats[mat_i], lights[li], nn, in_dn, rd, shadow_fac));
         }
         li++;
         act = ACT_LIGHT;
@@ -165,22 +151,10 @@ __global__ __launch_bounds__(RS_THREADS) void ray_shade_kernel(ShadeLaunch L) {
 
     if (act == ACT_LIGHT) {
       if (li < n_light) {
-        // shading.hpp:79-85: direction and distance to light li, the shadow ray from *hit (ro)
-        const DLight Lg = lights[li];
-        const V3 lg_v = mk(Lg.vx, Lg.vy, Lg.vz);
-        V3 direction;
-        float distance;
-        if (Lg.type == CTR_LIGHT_SUN) {  // default_schema.hpp:280-283
-          direction = vscale(lg_v, -1.0f);
-          distance = INFINITY;
-        } else {                         // default_schema.hpp:305-308
-          const V3 diff = vsub(lg_v, ro);
-          distance = vnorm(diff);
-          direction = vscale(diff, 1.0f / distance);
-        }
-        const float dir_norm = vnorm(direction);
-        rd = vscale(direction, 1.0f / dir_norm);  // shadow ray {*hit, direction.normalized()}, shading.hpp:80
-        light_dist = distance * dir_norm;
+        // shading.hpp:79-85: direction and distance to light li, the shadow ray from *hit (ro) (phong_light.h)
+        const LightRay lr = light_ray(lights[li], ro);
+        rd = lr.dir;
+        light_dist = lr.dist;
         intensity = 0.0f;
         min_t = (float)(0.0 + 1e-3);  // last_hit = 0
         t_lim = light_dist;

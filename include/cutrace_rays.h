@@ -1,5 +1,6 @@
 /*
- * cutrace_rays.h — cast and shade caller-supplied rays against a scene uploaded with ctr_scene_create.
+ * cutrace_rays.h — cast and shade caller-supplied rays, and shade caller-supplied surface points (ctr_shade_points, below),
+ * against a scene uploaded with ctr_scene_create.
  *
  * ctr_cast_rays answers per ray what the reference answers for its own rays:
  *
@@ -121,6 +122,67 @@ typedef struct ctr_shade_query {
  * n_rays >= 2^31; a scene whose mesh trees are so deep that the walk's stack and `bounces` frames do not fit one
  * workgroup's 64 KiB of LDS (CTR_SHADE_LINEAR needs no walk stack). */
 int ctr_shade_rays(ctr_scene *scene, const ctr_shade_query *q, void *hip_stream);
+
+/*
+ * Surface shading queries: ctr_shade_points answers per caller-supplied surface point the reference's fourth per-ray
+ * function, the one the three calls above only reach behind a cast,
+ *
+ *   phong(scene, incoming, hit, hit_id, normal, ambient)                                inc/shading.hpp:64-99
+ *
+ * the direct lighting of one point over every light, each light with its own shadow loop through the scene
+ * (shadow_intensity, shading.hpp:22-45).  Point, normal, view direction (incoming->dir) and material are the caller's:
+ * a rasteriser's G-buffer, the vertices or texel centres of a mesh to be baked, probe points in free space, or the
+ * output of ctr_cast_rays after the caller changed normals or swapped materials.  Restated operation for operation:
+ * final = ambient * diffuse; per light, direction and distance as `sun` and `point_light` give them, the shadow ray
+ * {point, direction.normalized()} with max_dist = distance * |direction|, the shadow loop from (float)(0.0 + 1e-3) in
+ * steps of a double add, stopping at the first occluder only when every material of the scene is opaque; the lit term
+ * is added when shadow < 1.  Numerics are ctr_shade_rays': the render's fast specular term by default,
+ * CTR_POINTS_EXACT_POW for the IEEE half vector and the f64 pow rounded once (chosen by itself for a scene outside the
+ * fast term's domain).  With d_object, the material is that object's and -1 ("a miss", what ctr_cast_rays writes)
+ * gives (0, 0, 0), ray_color's answer: ctr_shade_points on the output of ctr_cast_rays is ctr_shade_rays with
+ * bounces = 0, bit for bit.  A material or object index outside its range reads nothing and gives a quiet NaN in all
+ * three colour channels (it cannot be checked on the host without a synchronisation).  A zero normal, a zero view
+ * direction, a NaN or infinite point and a point exactly at a light get what the reference's arithmetic gives (NaNs
+ * where it gives NaNs) and do not disturb the other points of their batch.
+ *
+ * d_light_shadow receives shadow_intensity towards every light, in light order, a row of n_lights per point — also
+ * for the lights whose term is skipped, for a "miss" and for a bad index.
+ *
+ * Exactness: every ray this call casts ends at a light.  The guard of the BVH culling (guard.h)
+ * covers every triangle whose plane holds a point light or is parallel to a sun WHATEVER the ray's origin — a ray
+ * towards a light can lie in a triangle's plane only if the light does — so the default walk is exact for every
+ * point, not only for guarded origins.  CTR_POINTS_LINEAR is the cross-check (and what a mesh that went linear walks
+ * anyway); the tests compare the two bit for bit.
+ *
+ * The contract is ctr_cast_rays': asynchronous on `hip_stream`, no allocation, no synchronisation (capturable into a
+ * graph), no per-handle scratch (later renders, their counters and the tile scheduler are undisturbed).
+ */
+#define CTR_POINTS_LINEAR 1u    /* walk meshes linearly, as CTR_SHADE_LINEAR                                       */
+#define CTR_POINTS_EXACT_POW 2u /* half vector and specular term as under CTR_VAR_EXACT_POW                        */
+
+typedef struct ctr_point_query {
+  uint64_t n_points;         /* < 2^31; 0: nothing is launched                                                     */
+  uint32_t flags;            /* CTR_POINTS_*                                                                       */
+  int32_t material;          /* every point's material when d_material and d_object are both NULL                 */
+  float ambient;             /* phong's ambient factor                                                             */
+  uint32_t reserved;         /* 0                                                                                  */
+  const float *d_point;      /* n x 3: phong's *hit; required when n_points > 0                                    */
+  const float *d_normal;     /* n x 3: phong's *normal, need not be unit; required with d_color                    */
+  const float *d_view;       /* n x 3: incoming->dir, need not be unit; required with d_color                      */
+  const int32_t *d_material; /* optional: n indices into ctr_scene_desc.materials                                  */
+  const int32_t *d_object;   /* optional: n indices into ctr_scene_desc.objects, -1 = a miss; excludes d_material  */
+  float *d_color;            /* n x 3                                                                              */
+  float *d_light_shadow;     /* n x n_lights, row per point: shadow_intensity towards each light, in light order   */
+} ctr_point_query;
+
+/* Shades q->n_points points on `hip_stream` (NULL: the null stream of the scene's device).  d_color and d_light_shadow
+ * are each optional, one of them is required; when only d_light_shadow is asked for, d_normal, d_view and the material
+ * inputs may be NULL and are not read.  CTR_E_INVALID, with a ctr_last_error message, before the GPU is touched, for: a
+ * NULL scene or query; a NULL d_point when n_points > 0; unknown flag bits; no output at all; d_color without d_normal
+ * or d_view; both d_material and d_object; a scalar `material` outside [0, n_materials) when it is the one in use;
+ * n_points >= 2^31; a pointer that is not device memory of the scene's device; a scene whose mesh trees are so deep
+ * that the walk's stack does not fit one workgroup's 64 KiB of LDS (CTR_POINTS_LINEAR needs none). */
+int ctr_shade_points(ctr_scene *scene, const ctr_point_query *q, void *hip_stream);
 
 #ifdef __cplusplus
 }
