@@ -24,6 +24,7 @@
 #include "frame_images.h"
 #include "guard.h"
 #include "kernel_choice.h"
+#include "row_parts.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
 #include "tile_order.h"
@@ -59,6 +60,21 @@ bool device_view(float *host, float **dev) {
   }
   *dev = (float *)d;
   return true;
+}
+
+bool all_pinned(const HostFrame &o, size_t px) {
+  return px && o.depth && o.color3 && o.normal3 &&
+         is_pinned(o.depth) && is_pinned(o.depth + px - 1) && is_pinned(o.color3) && is_pinned(o.color3 + 3 * px - 1) &&
+         is_pinned(o.normal3) && is_pinned(o.normal3 + 3 * px - 1);
+}
+
+// Page-locked destinations (ctr_frame_alloc, hipHostMalloc, mapped hipHostRegister) are visible to the device:
+// the kernel then delivers the frame ITSELF, group of tiles by group of tiles while it renders (render_kernel.hip
+// "Host delivery"), so the 28 bytes per pixel cross PCIe underneath the rendering instead of in a DMA after it.
+// Any other destination: device buffers + copies (copy_out).
+bool device_visible(const HostFrame &o, size_t px, HostFrame &z) {
+  return all_pinned(o, px) && device_view(o.depth, &z.depth) && device_view(o.color3, &z.color3) &&
+         device_view(o.normal3, &z.normal3);
 }
 
 int use_device(const ctr_scene *s) {
@@ -153,16 +169,9 @@ int make_rows(const ctr_scene *s, const ctr_rows *rin, DRows &R) {
     R.n_parts = 1;
     R.part = 0;
   } else {
-    uint64_t b0 = r.row_begin / r.block_rows;
-    uint64_t first = b0 + ((r.part + r.n_parts - (b0 % r.n_parts)) % r.n_parts);
-    R.first_block = (uint32_t)first;
-    uint64_t n = 0;
-    for (uint64_t b = first; b * r.block_rows < r.row_end; b += r.n_parts) {
-      uint64_t lo = b * r.block_rows, hi = lo + r.block_rows;
-      if (hi > r.row_end) hi = r.row_end;
-      n += hi - lo;
-    }
-    R.n_rows = (uint32_t)n;
+    const PartRows own = part_rows(r.row_begin, r.row_end, r.block_rows, r.part, r.n_parts);
+    R.first_block = (uint32_t)own.first_block;
+    R.n_rows = (uint32_t)own.n_rows;
   }
   return CTR_OK;
 }
@@ -358,20 +367,6 @@ int aa_precheck(ctr_scene *s, KernelEntry entry, int bounces, uint32_t samples, 
   return aa_scale(L, ls);
 }
 
-// the caller's buffers of a host-form render; device_visible: the same buffers as the device sees them
-struct HostFrame { float *depth, *color3, *normal3, *uv2; };
-
-// Page-locked destinations (ctr_frame_alloc, hipHostMalloc, mapped hipHostRegister) are visible to the device:
-// the kernel then delivers the frame ITSELF, group of tiles by group of tiles while it renders (render_kernel.hip
-// "Host delivery"), so the 28 bytes per pixel cross PCIe underneath the rendering instead of in a DMA after it.
-// Any other destination: device buffers + copies (copy_out).
-bool device_visible(const HostFrame &o, size_t px, HostFrame &z) {
-  return px && o.depth && o.color3 && o.normal3 &&
-         is_pinned(o.depth) && is_pinned(o.depth + px - 1) && is_pinned(o.color3) && is_pinned(o.color3 + 3 * px - 1) &&
-         is_pinned(o.normal3) && is_pinned(o.normal3 + 3 * px - 1) && device_view(o.depth, &z.depth) &&
-         device_view(o.color3, &z.color3) && device_view(o.normal3, &z.normal3);
-}
-
 // What the launch writes on the device: `spx` pixels per output buffer in d_out; for a direct launch (z: the caller's
 // buffers as the device sees them, else null) also the groups' completion counters.
 int prepare_outputs(ctr_scene *s, RenderLaunch &L, size_t spx, const HostFrame *z) {
@@ -500,10 +495,7 @@ int report(ctr_scene *s, const RenderLaunch &L, std::chrono::high_resolution_clo
     stats->total_ms = std::chrono::duration<double, std::milli>(t1 - t0).count();
     stats->ray_count = cnt[0];
     stats->rows = L.rows.n_rows >> L.ss_log2;  // (output rows)
-    uint32_t bits = (uint32_t)cnt[1];
-    float md;
-    memcpy(&md, &bits, 4);
-    stats->max_depth = md;  // largest finite depth, 0 if none (kernel.hpp:120-125)
+    stats->max_depth = depth_of_counter(cnt[1]);
     stats->reserved = 0;
   }
   return CTR_OK;

@@ -6,6 +6,7 @@
 #define CUTRACE_AMD_CTR_INTERNAL_H
 
 #include <hip/hip_runtime_api.h>
+#include <string.h>
 
 #include <mutex>
 #include <string>
@@ -30,6 +31,14 @@ int hip_fail(hipError_t e, const char *what);
 bool is_pinned(const void *p);
 // the device's address of page-locked host memory (false: not mapped for this device)
 bool device_view(float *host, float **dev);
+// the caller's buffers of a host-form render (uv2: ctr_render_uv only)
+struct HostFrame { float *depth, *color3, *normal3, *uv2; };
+// are the `px` pixels of all three buffers page-locked, first byte to last?
+bool all_pinned(const HostFrame &o, size_t px);
+// ... and mapped for the current device?  Then z = the same buffers as the device sees them, and its kernels can write them.
+bool device_visible(const HostFrame &o, size_t px, HostFrame &z);
+// counter word 1 of a launch as the float whose bits it carries: the largest finite depth, 0 if none (kernel.hpp:120-125)
+inline float depth_of_counter(unsigned long long word) { const uint32_t bits = (uint32_t)word; float d; memcpy(&d, &bits, 4); return d; }
 // the scene's device becomes the calling thread's current one, unless it is already
 int use_device(const ctr_scene *s);
 // CTR_E_INVALID "<who><name> is not device memory of <whose>" for the first non-null pointer that is not memory of `device` (ctr_rays.cpp)

@@ -408,3 +408,54 @@ def test_bench_two_steps_in_flight_two_ranks(ca):
         assert "gathered frame(s) bitwise equal" in r.stderr
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert line["n_gpus"] == 2 and line["config"]["steps_in_flight"] == 2
+
+
+def test_grow_refusal_keeps_the_queued_frame_intact(ca):
+    """A submit that would have to regrow the compact buffers while a frame is in flight is refused (64 x 20 on two parts:
+    at block_rows 8 part 0 owns 12 rows, at block_rows 20 all 20) — and the frame already queued arrives untouched; once it
+    has been waited for, the larger partition renders."""
+    s = load_scene(ca, "bunny", 64, 20)
+    want = ca.DeviceScene(s).render(bounces=2)
+    m = ca.MultiScene(s, [0, 0])
+    frames = [m.alloc_frame() for _ in range(2)]
+    m.submit(frames[0], bounces=2, block_rows=8)
+    with pytest.raises(RuntimeError):
+        m.submit(frames[1], bounces=2, block_rows=20)
+    st = m.wait()
+    for key in ("depth", "color", "normal"):
+        assert same_bits(frames[0][key], want[key]), key
+    assert st["ray_count"] == want["ray_count"]
+    assert _same(m.render(bounces=2, block_rows=20), want)
+    for f in frames:
+        m.free_frame(f)
+    m.close()
+
+
+def test_rccl_self_and_peer_copy_agree_through_two_slots(ca):
+    """Three frames through submit / wait with two in flight, on an rccl-self group (the RCCL gather, rank 0 to itself) and on
+    a peer-copy group of three parts: every frame of both is bitwise the single-device frame."""
+    s = load_scene(ca, "bunny", 40, 16)
+    want = ca.DeviceScene(s).render(bounces=1)
+    for transport, devices in (("rccl-self", [0]), ("peer-copy", [0, 0, 0])):
+        if transport == "rccl-self":
+            os.environ["CUTRACE_MULTI_TRANSPORT"] = transport
+        try:
+            m = ca.MultiScene(s, devices)
+        finally:
+            os.environ.pop("CUTRACE_MULTI_TRANSPORT", None)
+        if m.transport != transport:   # librccl.so could not be loaded on this box: the peer-copy half still runs
+            assert transport == "rccl-self"
+            m.close()
+            continue
+        frames = [m.alloc_frame() for _ in range(3)]
+        m.submit(frames[0], bounces=1)
+        for k in range(1, 4):
+            if k < 3:
+                m.submit(frames[k], bounces=1)
+            st = m.wait()
+            for key in ("depth", "color", "normal"):
+                assert same_bits(frames[k - 1][key], want[key]), (transport, k - 1, key)
+            assert st["ray_count"] == want["ray_count"], (transport, k - 1)
+        for f in frames:
+            m.free_frame(f)
+        m.close()
