@@ -1,8 +1,8 @@
 """Build the native libraries in-tree (no network, no cmake needed).
 
   libcutrace_host.so   g++    host side: JSON loader, STL reader, image writers
-  libcutrace_amd.so    hipcc  gfx950 render, ray-query, surface-shading and display-quantise kernels + the C-ABI of include/cutrace_amd.h (csrc/ctr_api.cpp,
-                              csrc/ctr_multi.hip) and cutrace_rays.h (csrc/ctr_rays.cpp); what those three share: csrc/ctr_internal.h
+  libcutrace_amd.so    hipcc  gfx950 render, ray-query, surface-shading and display-quantise kernels + the C-ABI of include/cutrace_amd.h (csrc/ctr_scene.cpp,
+                              csrc/ctr_render.cpp, csrc/ctr_multi.hip) and cutrace_rays.h (csrc/ctr_rays.cpp); what they share: csrc/ctr_internal.h
   cutrace              hipcc  the drop-in CLI (`cutrace <scene.json>`, reference main.cu)
 
 Everything float-sensitive is compiled with -ffp-contract=off so that each float
@@ -24,11 +24,9 @@ HIP_LIB = os.path.join(PKG, "libcutrace_amd.so")
 CLI = os.path.join(PKG, "cutrace")
 
 HOST_SRCS = [os.path.join(HOST, "scene_host.cpp"), os.path.join(HOST, "images.cpp")]
-HIP_SRCS = [os.path.join(CSRC, "render_kernel.hip"), os.path.join(CSRC, "ctr_api.cpp"), os.path.join(CSRC, "bvh.cpp"),
-            os.path.join(CSRC, "ctr_multi.hip"), os.path.join(CSRC, "ray_query.hip"), os.path.join(CSRC, "scene_flatten.cpp"),
-            os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "ray_shade.hip"), os.path.join(CSRC, "ctr_rays.cpp"),
-            os.path.join(CSRC, "kernel_choice.cpp"), os.path.join(CSRC, "frame_images.hip"), os.path.join(CSRC, "tile_order.hip"),
-            os.path.join(CSRC, "ray_points.hip")]
+HIP_SRCS = [os.path.join(CSRC, f) for f in (
+    "render_kernel.hip", "ctr_scene.cpp", "ctr_render.cpp", "bvh.cpp", "ctr_multi.hip", "ray_query.hip", "scene_flatten.cpp", "guard.cpp",
+    "ray_shade.hip", "ctr_rays.cpp", "kernel_choice.cpp", "frame_images.hip", "tile_order.hip", "tile_order_host.cpp", "ray_points.hip")]
 CLI_SRCS = [os.path.join(HOST, "main.cpp")]
 
 HOST_FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-pthread", "-Wall", "-I" + INC]

@@ -1,7 +1,8 @@
 // ctr_internal.h — what the host translation units of the library share: the scene handle and the error / device helpers.
 //
-// Defined in ctr_api.cpp; used by ctr_api.cpp (the render path), ctr_rays.cpp (the ray queries) and ctr_multi.hip (the
-// multi-device path).  Nothing here is part of the C-ABI.
+// Defined in ctr_scene.cpp; used by ctr_scene.cpp (handle lifetime and uploads), ctr_render.cpp (the render path),
+// tile_order_host.cpp (the tile scheduler's host half), ctr_rays.cpp (the ray queries) and ctr_multi.hip (the multi-device
+// path).  Nothing here is part of the C-ABI.
 #ifndef CUTRACE_AMD_CTR_INTERNAL_H
 #define CUTRACE_AMD_CTR_INTERNAL_H
 
@@ -15,6 +16,7 @@
 #include "cutrace_amd.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
+#include "tile_order_policy.h"
 
 #pragma GCC visibility push(hidden)
 // keeps `msg` for ctr_last_error(), prints it, returns `code`
@@ -44,57 +46,66 @@ int use_device(const ctr_scene *s);
 // CTR_E_INVALID "<who><name> is not device memory of <whose>" for the first non-null pointer that is not memory of `device` (ctr_rays.cpp)
 int check_device_pointers(int device, const std::string &who, const void *const *ptrs, const char *const *names, size_t n,
                           const char *whose = "the scene's device");
+
+// A buffer that only grows: reserve(n) frees and allocates anew when `n` elements exceed the capacity, and is free
+// otherwise.  An allocation that fails leaves capacity 0 and a null pointer, so that the next call comes back here whatever
+// its size.  Owned by the handle; ctr_scene_destroy releases it with the handle (the scene's device being current).
+struct GrowBuf {
+  void *p = nullptr;
+  size_t cap = 0;     // elements
+  size_t elem;        // bytes per element
+  bool pinned;        // page-locked host memory instead of device memory
+  GrowBuf(size_t elem_bytes, bool pinned_host = false) : elem(elem_bytes), pinned(pinned_host) {}
+  GrowBuf(const GrowBuf &) = delete;
+  ~GrowBuf() { release(); }
+  int reserve(size_t n);
+  void release();
+  template <class T> T *as() const { return (T *)p; }
+};
+// two buffers that grow as a pair: both hold `n` elements, or the next call tries again
+inline int reserve_both(GrowBuf &a, GrowBuf &b, size_t n) { const int st = a.reserve(n); return st ? st : b.reserve(n); }
 #pragma GCC visibility pop
 
 struct ctr_scene {
   int device = 0;
-  FlatScene flat;             // the host copy of every scene array below, and what the guard knows of it (scene_flatten.h)
-  // the scene arrays on the device (ctr_api.cpp scene_arrays: upload, partial re-upload, free)
-  DObj *d_objs = nullptr;
-  DObj *d_oloop = nullptr;
-  DObj *d_meshes = nullptr;
-  DPlanePair *d_planes = nullptr;
-  DTri *d_tris = nullptr;
-  DNode *d_nodes = nullptr;
-  DNode4 *d_nodes4 = nullptr;
-  float *d_gnorm = nullptr;
-  DLight *d_lights = nullptr;
-  DMat *d_mats = nullptr;
+  FlatScene flat;             // the host copy of every scene array, and what the guard knows of it (scene_flatten.h)
+  DScene dev{};               // the scene arrays on the device (ctr_scene.cpp scene_arrays: upload, partial re-upload, free);
+                              // its counts and flags are filled per call: device_scene() below
   DCam cam{};                 // camera 0 (image size of every camera)
   DCam *d_cams = nullptr;     // device camera array (>= 1 entry)
   uint32_t n_cams = 0;
+  uint32_t cams_epoch = 0;    // bumped by ctr_scene_set_cameras / ctr_scene_set_size
+  std::vector<DCam> h_cams;   // host copy of d_cams: the eyes the guard checks (refresh_linear_meshes)
   uint32_t user_variant = CTR_VAR_AUTO;
   bool no_scene_head = false;  // CUTRACE_NO_SCENE_HEAD=1 when the handle was created: launches carry an empty scene head
-  // cached device outputs for the host-buffer form: ONE allocation, a call's buffers are its consecutive
-  // parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
-  float *d_out = nullptr;
-  float *d_uv = nullptr;      // ctr_render_uv: 2 floats per pixel, allocated on first use
-  size_t uv_px = 0;
-  uint8_t *d_img = nullptr;   // ctr_render_images: the three byte planes [depth8 | color8 | normal8], 9 bytes per pixel, grown on use
-  size_t img_px = 0;
-  std::vector<DCam> h_cams;     // host copy of d_cams: the eyes the guard checks (refresh_linear_meshes)
+  // cached device outputs for the host-buffer form: ONE allocation of 7 floats per pixel, a call's buffers are its
+  // consecutive parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
+  GrowBuf out{7 * sizeof(float)};
+  GrowBuf uv{2 * sizeof(float)};  // ctr_render_uv: 2 floats per pixel, allocated on first use
+  GrowBuf img{9};                 // ctr_render_images: the three byte planes [depth8 | color8 | normal8], 9 bytes per pixel
+  GrowBuf d_groups{sizeof(uint32_t)};        // host delivery: one completion counter per group of tiles (render_kernel.hip)
+  GrowBuf h_groups{sizeof(uint32_t), true};  // page-locked landing zone of the counters (checked after every direct launch)
   unsigned long long *h_counters = nullptr;  // pinned landing zone of the 16 counter words
   unsigned long long last_cnt[16] = {0};     // the counter words of the last host-form render
   unsigned long long *d_counters = nullptr;
   unsigned long long *d_shards = nullptr;  // CTR_SHARDS x CTR_SHARD_WORDS, zero between launches
-  size_t out_px = 0;
-  uint32_t *d_groups = nullptr;  // host delivery: one completion counter per group of tiles (render_kernel.hip)
-  uint32_t *h_groups = nullptr;  // page-locked landing zone of the counters (checked after every direct launch)
-  size_t groups_cap = 0;
-  bool poison_next_order = false;  // test hook (ctr_debug_poison_next_order)
   uint32_t last_kernel = 0;        // the KV of the most recent launch (ctr_debug_last_kernel)
-  // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling"; tile_order.hip)
-  uint32_t *d_cost = nullptr, *d_order = nullptr;
-  uint32_t order_age = 0;  // launches of the current shape
-  uint64_t order_view = 0; // camera set + first frame of the previous launch
-  uint32_t cams_epoch = 0; // bumped by ctr_scene_set_cameras / ctr_scene_set_size
-  size_t order_cap = 0;
-  uint64_t order_key[6] = {0, 0, 0, 0, 0, 0};
-  bool order_valid = false;
+  // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling"; tile_order_policy.h, tile_order_host.cpp)
+  OrderState order;
+  GrowBuf d_cost{sizeof(uint32_t)}, d_order{sizeof(uint32_t)};  // order.cap tiles each
+  bool poison_next_order = false;  // test hook (ctr_debug_poison_next_order)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::mutex mtx;
 
   static uint64_t occ6_min_tris();  // CTR_OCC6_MIN_TRIS, or CUTRACE_OCC6_MIN_TRIS from the environment
+  __attribute__((visibility("hidden"))) ~ctr_scene() = default;  // (releases every GrowBuf above; called by ctr_scene_destroy alone)
 };
+
+// the scene on the device as a launch or a query sees it now: the handle's arrays, the counts and flags of their host copy
+inline DScene device_scene(const ctr_scene *s) {
+  DScene D = s->dev;
+  fill_scene_counts(s->flat, D);
+  return D;
+}
 
 #endif

@@ -40,21 +40,9 @@ int check_device_pointers(int device, const std::string &who, const void *const 
 
 namespace {
 
-RayScene ray_scene(const ctr_scene *s) {
-  RayScene R{};
-  R.objs = s->d_objs;
-  R.oloop = s->d_oloop;
-  R.meshes = s->d_meshes;
-  R.planes = s->d_planes;
-  R.tris = s->d_tris;
-  R.nodes4 = s->d_nodes4;
-  R.gnorm = s->d_gnorm;
-  R.mats = s->d_mats;
-  R.n_oloop = (uint32_t)s->flat.oloop.size();
-  R.n_plane_recs = (uint32_t)s->flat.planes.size();
-  R.n_mesh = s->flat.n_mesh;
-  R.stack_slots = s->flat.ray_slots;
-  return R;
+// what the walk of ray_walk.h needs of the scene on the device (ctr_internal.h device_scene)
+RayScene ray_scene(const ctr_scene *s, const DScene &D) {
+  return {D.objs, D.oloop, D.meshes, D.planes, D.tris, D.nodes4, D.gnorm, D.mats, D.n_oloop, D.n_plane_recs, D.n_mesh, s->flat.ray_slots};
 }
 
 }  // namespace
@@ -81,7 +69,7 @@ extern "C" int ctr_cast_rays(ctr_scene *s, const ctr_ray_query *q, void *hip_str
   if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
   if (int st = use_device(s)) return st;
   RayLaunch L{};
-  L.scene = ray_scene(s);
+  L.scene = ray_scene(s, device_scene(s));
   L.n_rays = (uint32_t)q->n_rays;
   L.flags = q->flags;
   L.anyhit = shadow && s->flat.all_opaque;
@@ -116,10 +104,11 @@ extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_
   const void *ptrs[] = {q->d_origin, q->d_dir, q->d_color, q->d_t, q->d_object, q->d_normal};
   const char *names[] = {"d_origin", "d_dir", "d_color", "d_t", "d_object", "d_normal"};
   if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
+  const DScene D = device_scene(s);
   ShadeLaunch L{};
-  L.scene = ray_scene(s);
-  L.lights = s->d_lights;
-  L.n_light = (uint32_t)s->flat.lights.size();
+  L.scene = ray_scene(s, D);
+  L.lights = D.lights;
+  L.n_light = D.n_light;
   L.frames = ctr_shade_frames(q->bounces, s->flat.any_bounce);
   L.frame_dwords = s->flat.need_cold ? 10u : 4u;
   L.all_opaque = s->flat.all_opaque ? 1u : 0u;
@@ -163,12 +152,13 @@ extern "C" int ctr_shade_points(ctr_scene *s, const ctr_point_query *q, void *hi
   const void *ptrs[] = {q->d_point, q->d_normal, q->d_view, q->d_material, q->d_object, q->d_color, q->d_light_shadow};
   const char *names[] = {"d_point", "d_normal", "d_view", "d_material", "d_object", "d_color", "d_light_shadow"};
   if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
+  const DScene D = device_scene(s);
   PointsLaunch L{};
-  L.scene = ray_scene(s);
-  L.lights = s->d_lights;
-  L.n_light = (uint32_t)s->flat.lights.size();
-  L.n_mat = (uint32_t)n_mat;
-  L.n_obj = (uint32_t)s->flat.objs.size();
+  L.scene = ray_scene(s, D);
+  L.lights = D.lights;
+  L.n_light = D.n_light;
+  L.n_mat = D.n_mat;
+  L.n_obj = D.n_obj;
   L.all_opaque = s->flat.all_opaque ? 1u : 0u;
   L.n_points = (uint32_t)q->n_points;
   L.flags = q->flags | (s->flat.fast_pow_ok ? 0u : CTR_POINTS_EXACT_POW);  // (outside the fast path's domain: the exact one)

@@ -1,4 +1,4 @@
-// frame_images.h — what ctr_quantise_device and ctr_render_images (ctr_api.cpp) hand the quantise kernel (frame_images.hip).
+// frame_images.h — what ctr_quantise_device and ctr_render_images (ctr_render.cpp) hand the quantise kernel (frame_images.hip).
 #ifndef CUTRACE_AMD_FRAME_IMAGES_H
 #define CUTRACE_AMD_FRAME_IMAGES_H
 

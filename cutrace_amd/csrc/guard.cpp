@@ -214,7 +214,7 @@ std::vector<DirtyRange> apply_guards(FlatScene &F, const GuardPlan &plan) {
     }
     if (m.risky != g.guarded) apply_mesh(F, g, m.risky, dirty);
   }
-  // a mesh that went linear or more risky triangles than records -> the merged tree is not walked (ctr_api.cpp kernel_facts: merged_usable)
+  // a mesh that went linear or more risky triangles than records -> the merged tree is not walked (ctr_render.cpp kernel_facts: merged_usable)
   if (F.merged.built) {
     F.merged.usable = plan.merged_usable();
     if (F.merged.usable && plan.merged_keys != F.merged.guarded) apply_merged(F, plan.merged_keys, dirty);

@@ -1,7 +1,7 @@
 // kernel_choice.h — which build of render_kernel<KV> a launch gets: the list of builds, the stack shape of a launch, and the
 // ONE function that knows which combination of caller's wishes, scene facts and entry point has a build.
 //
-// Host only, no HIP: ctr_api.cpp asks choose_kernel() and hands the answer to ctr_launch_render (render_kernel.hip), whose
+// Host only, no HIP: ctr_render.cpp asks choose_kernel() and hands the answer to ctr_launch_render (render_kernel.hip), whose
 // switch is generated from the same list; scripts/kernel_choice_check.cpp prints the answer for the whole input space.
 #ifndef CUTRACE_AMD_KERNEL_CHOICE_H
 #define CUTRACE_AMD_KERNEL_CHOICE_H

@@ -29,7 +29,7 @@
 //    a four-wide BVH (a node holds its four children's boxes, wave-uniform stack in the lanes of one
 //    VGPR) walked by the whole wave, two child boxes per packed FMA; triangles whose plane contains an
 //    eye or a light are additionally handed to every lane (guard records: the one regime where culling
-//    could differ from the linear walk, ctr_api.cpp refresh_linear_meshes); per triangle a
+//    could differ from the linear walk, ctr_scene.cpp refresh_linear_meshes); per triangle a
 //    conservative FMA prefilter for the whole wave (barycentrics, then — only if a lane survives —
 //    the ray parameter), then the reference's exact Cramer/determinant test
 //    (default_schema.hpp:57-78) in the reference's operation order for surviving lanes, its three
@@ -1013,7 +1013,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
           // Everything in this branch works on 64-bit lane masks (v_cmp results kept in SGPRs and
           // combined on the scalar unit) instead of per-lane booleans.
           const mask_t live_m = alive_m;
-          // One tree over the triangles of ALL meshes stands behind the pseudo mesh (ctr_api.cpp ctr_scene::Merged): every
+          // One tree over the triangles of ALL meshes stands behind the pseudo mesh (scene_flatten.h Merged): every
           // live lane enters it; the AABB test of the mesh a lane's triangle belongs to is made after the walk, for the
           // lanes the walk decided something for ("merged walk" below).  A real mesh: the reference's test first.
           mask_t bb_m;
@@ -1321,7 +1321,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
               // one dependent round trip each — then find their lines in the scalar cache.  64 000 triangles -3 %, first
               // launch -5 %; a 1 000-triangle mesh, which stays in the scalar cache anyway, +-0.5 %
               // (profiles/r03/exp_leaf_touch.txt).  The wait is part of the statement, so the unread register is dead when it
-              // ends.  (ctr_api.cpp allocates 256 bytes beyond every array for requests past the last triangle.)
+              // ends.  (ctr_scene.cpp allocates 256 bytes beyond every array for requests past the last triangle.)
               // (no early exit for an empty leaf — the unused slots of a node, whose far-away point box no ray enters: it
               //  would only re-test the mesh's first triangle, which changes nothing, and the extra edge costs six register
               //  copies per leaf visit in the compiler's output)
@@ -1362,7 +1362,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
               sp++;
             };
             // node 0 is the root (a mesh that fits one leaf has a root with one child).  A mesh with guard
-            // records (triangles every lane must meet whatever their box, ctr_api.cpp refresh_linear_meshes)
+            // records (triangles every lane must meet whatever their box, ctr_scene.cpp refresh_linear_meshes)
             // starts one node earlier, at an extra node whose children are the guard leaf and the root.
             uint32_t cur = o_bvh_root;
 #ifdef CTR_TIMING
@@ -1558,7 +1558,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     float first_depth = 0.f;  // primary-hit depth of this lane, alive in the first trip only
     // the light the NEXT shadow ray goes to (type and position / direction), requested together with whatever else this
     // continuation reads first — the hit record, or the material and light being shaded — instead of in a round trip of its
-    // own afterwards.  (lights[n_light] is inside the allocation: ctr_api.cpp pads every array.)
+    // own afterwards.  (lights[n_light] is inside the allocation: ctr_scene.cpp pads every array.)
     uint32_t nl_type = 0u;
     V3 nl_v = mk(0.f, 0.f, 0.f);
     if (MSP_IS_RADIANCE(msp)) {
@@ -1888,7 +1888,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     old = __builtin_amdgcn_readfirstlane(old);
     if (old == nt - 1) {
       CTR_MARK(57);  // host delivery: copy a group
-      // (the counter keeps its final value nt: ctr_api.cpp clears the counters before every launch and, after it, checks
+      // (the counter keeps its final value nt: ctr_render.cpp clears the counters before every launch and, after it, checks
       //  that every group counted all its tiles — a launch cut short cannot leave a later one a poisoned counter, and a
       //  group that was never delivered is an error, not stale pixels)
       const uint32_t row0 = e_ty * TH, n_rows = AE->rows.n_rows;
@@ -1993,30 +1993,31 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
 // next order (tile_order.hip).
 int launch(const RenderLaunch &L, uint32_t kv, const void *kernel, hipStream_t stream) {
   KArgs A;
-  A.objs = (const CADDR DObj *)L.objs;
-  A.oloop = (const CADDR DObj *)L.oloop;
-  A.meshes = (const CADDR DObj *)L.meshes;
-  A.n_mesh = L.n_mesh;
+  const DScene &S = L.scene;
+  A.objs = (const CADDR DObj *)S.objs;
+  A.oloop = (const CADDR DObj *)S.oloop;
+  A.meshes = (const CADDR DObj *)S.meshes;
+  A.n_mesh = S.n_mesh;
   // "Scene head": the flags ride in words of the hot block the trip head has anyway
   A.head = L.head;
-  const bool head_mesh = L.head.n_mesh == 1u && (L.tlas_root & BVH_LEAF_FLAG) && L.n_mesh != 0u;
-  const bool head_axis = L.head.n_axis_recs == 3u && L.n_axis_recs >= 3u && L.n_plane_recs >= 3u;
-  A.tlas_root = L.tlas_root | (head_mesh ? CTR_TL_HEAD_FLAG : 0u);
-  A.tlas_root2 = L.tlas_root_regular;
-  A.tlas_begin = L.tlas_begin;
-  for (int q = 0; q < 3; q++) { A.tl_mn[q] = L.tl_mn[q]; A.tl_mx[q] = L.tl_mx[q]; }
-  A.planes = (const CADDR DPlanePair *)L.planes;
-  A.n_oloop = L.n_oloop;
-  A.n_plane_recs = L.n_plane_recs;
-  A.n_axis_recs = L.n_axis_recs;
-  A.tris = (const CADDR DTri *)L.tris;
-  A.nodes = (const CADDR DNode *)L.nodes;
-  A.nodes4 = (const CADDR DNode4 *)L.nodes4;
-  A.gnorm = (const CADDR float *)L.gnorm;
-  A.lights = (const CADDR DLight *)L.lights;
-  A.mats = (const CADDR DMat *)L.mats;
-  A.n_obj = L.n_obj;
-  A.n_light = L.n_light;
+  const bool head_mesh = L.head.n_mesh == 1u && (S.tlas_root & BVH_LEAF_FLAG) && S.n_mesh != 0u;
+  const bool head_axis = L.head.n_axis_recs == 3u && S.n_axis_recs >= 3u && S.n_plane_recs >= 3u;
+  A.tlas_root = S.tlas_root | (head_mesh ? CTR_TL_HEAD_FLAG : 0u);
+  A.tlas_root2 = S.tlas_root_regular;
+  A.tlas_begin = S.tlas_begin;
+  for (int q = 0; q < 3; q++) { A.tl_mn[q] = S.tl_mn[q]; A.tl_mx[q] = S.tl_mx[q]; }
+  A.planes = (const CADDR DPlanePair *)S.planes;
+  A.n_oloop = S.n_oloop;
+  A.n_plane_recs = S.n_plane_recs;
+  A.n_axis_recs = S.n_axis_recs;
+  A.tris = (const CADDR DTri *)S.tris;
+  A.nodes = (const CADDR DNode *)S.nodes;
+  A.nodes4 = (const CADDR DNode4 *)S.nodes4;
+  A.gnorm = (const CADDR float *)S.gnorm;
+  A.lights = (const CADDR DLight *)S.lights;
+  A.mats = (const CADDR DMat *)S.mats;
+  A.n_obj = S.n_obj;
+  A.n_light = S.n_light;
   A.cams = (const CADDR DCam *)L.cams;
   A.w = L.w;
   A.h = L.h;
@@ -2026,8 +2027,8 @@ int launch(const RenderLaunch &L, uint32_t kv, const void *kernel, hipStream_t s
   A.rows = L.rows;
   A.fudge = L.fudge;
   A.bounces = L.bounces;
-  A.has_mesh = (L.has_mesh ? 1u : 0u) | (head_axis ? 2u : 0u);
-  const StackShape stack = stack_shape(L.bounces, L.any_bounce != 0, L.need_cold_frames != 0);
+  A.has_mesh = (S.has_mesh ? 1u : 0u) | (head_axis ? 2u : 0u);
+  const StackShape stack = stack_shape(L.bounces, S.any_bounce != 0, S.need_cold_frames != 0);
   A.nf = stack.nf;
   A.frames = stack.frames;
   A.order = (const CADDR uint32_t *)L.order;

@@ -53,7 +53,7 @@ struct DObj {
   uint32_t node_count;  // mesh: number of BVH nodes
   uint32_t bvh_root;    // mesh: node the walk starts at: 0 = the root, or node_count = the mesh's spare node, which leads
                         // to its GUARD records (triangles every lane that enters the mesh must meet, whatever their
-                        // box; ctr_api.cpp refresh_linear_meshes) and then to the root
+                        // box; ctr_scene.cpp refresh_linear_meshes) and then to the root
   uint32_t index;       // position in the scene's object list (hit_id; ties on t go to the lower index)
   // triangle: f[0..2] p1, f[3..5] p3 (p2 is in its DTri): triangle::uv_for needs the vertices themselves (KV_UV only)
   // mesh    : f[0..2] bbox.min, f[3..5] bbox.max
@@ -160,25 +160,32 @@ struct alignas(64) DSceneHead {
 static_assert(sizeof(DSceneHead) == 192 && offsetof(DSceneHead, mesh) == 128, "DSceneHead: two 64-byte lines of planes, one of mesh");
 #define CTR_TL_HEAD_FLAG 0x40000000u  /* kernel-side only: the top-level leaf whose record is DSceneHead::mesh */
 
-struct RenderLaunch {
+// The scene on the device, ONCE: the ten arrays of ctr_scene_create's upload, owned by the handle (ctr_internal.h ctr_scene::dev),
+// and the counts and flags of their host copy, filled per call (scene_flatten.h fill_scene_counts) so that no edit of that copy
+// leaves stale ones behind.  A launch carries a copy (RenderLaunch::scene); the ray queries take from it what RayScene holds.
+struct DScene {
   const DObj *objs;        // every object, scene order (hit records)
   const DObj *oloop;       // spheres and stand-alone triangles, scene order (sequential loop)
   const DObj *meshes;      // non-empty meshes in top-level-BVH leaf order; [n_mesh] the merged pseudo mesh, [n_mesh + 1 + r] mesh r in scene order
-  uint32_t n_mesh, tlas_root, tlas_begin;
-  uint32_t tlas_root_regular;  // the top-level tree over the meshes when tlas_root names the merged tree (else the same)
-  float tl_mn[3], tl_mx[3];
   const DPlanePair *planes;  // n_plane_recs records, the first n_axis_recs of them axis triples
-  uint32_t n_oloop, n_plane_recs, n_axis_recs;
   const DTri *tris;
   const void *nodes;    // DNode[] (bvh.h): top-level tree over the meshes
   const void *nodes4;   // DNode4[] (bvh.h): per-mesh trees
   const float *gnorm;   // 4 floats per triangle
   const DLight *lights;
   const DMat *mats;
+  uint32_t n_mesh, tlas_root, tlas_begin;
+  uint32_t tlas_root_regular;  // the top-level tree over the meshes when tlas_root names the merged tree (else the same)
+  float tl_mn[3], tl_mx[3];
+  uint32_t n_oloop, n_plane_recs, n_axis_recs;
   uint32_t n_obj, n_light, n_mat;
   uint32_t has_mesh;
   uint32_t need_cold_frames;  // some material both reflects and transmits (>= 1e-6 each)
   uint32_t any_bounce;        // some material reflects or transmits: only then does ray_color recurse at all
+};
+
+struct RenderLaunch {
+  DScene scene;               // (tlas_root: of THIS launch, the merged tree where the build walks it)
   const DCam *cams;           // device array, one camera per frame
   uint32_t w, h;
   uint32_t first_frame, n_frames;
@@ -218,7 +225,7 @@ struct RenderLaunch {
   float ray_ambient;
 };
 
-// keeps `msg` for ctr_last_error() (ctr_api.cpp); used by the other translation units of the library
+// keeps `msg` for ctr_last_error() (ctr_scene.cpp); used by the other translation units of the library
 void ctr_internal_set_error(const char *msg);
 // host-callable launcher implemented in render_kernel.hip; returns a hipError_t as int
 int ctr_launch_render(const RenderLaunch &L, void *stream);

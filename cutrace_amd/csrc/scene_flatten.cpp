@@ -453,6 +453,16 @@ std::vector<DirtyRange> build_merged_tree(FlatScene &F) {
           {DirtyRange::MESHES, F.n_mesh, 1, {}}};
 }
 
+void fill_scene_counts(const FlatScene &F, DScene &D) {
+  D.n_mesh = F.n_mesh;
+  D.tlas_root = D.tlas_root_regular = F.tlas_root;  // (a launch of a build that walks the merged tree puts that tree into tlas_root)
+  D.tlas_begin = F.tlas_begin;
+  for (int q = 0; q < 3; q++) { D.tl_mn[q] = F.tl_mn[q]; D.tl_mx[q] = F.tl_mx[q]; }
+  D.n_oloop = (uint32_t)F.oloop.size(); D.n_plane_recs = (uint32_t)F.planes.size(); D.n_axis_recs = F.n_axis_recs;
+  D.n_obj = (uint32_t)F.objs.size(); D.n_light = (uint32_t)F.lights.size(); D.n_mat = (uint32_t)F.mats.size();
+  D.has_mesh = F.has_mesh ? 1u : 0u; D.need_cold_frames = F.need_cold ? 1u : 0u; D.any_bounce = F.any_bounce ? 1u : 0u;
+}
+
 void fill_scene_head(const FlatScene &F, uint32_t tlas_root, DSceneHead &H) {
   H = DSceneHead{};
   if (F.n_axis_recs >= 3u && F.planes.size() >= 3u) {

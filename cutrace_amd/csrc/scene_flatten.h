@@ -1,6 +1,6 @@
 // scene_flatten.h — a ctr_scene_desc flattened into the arrays of scene_device.h, on the host, without a device.
 //
-// Everything ctr_scene_create (ctr_api.cpp) uploads is built here, and stays here as the host copy that the guard of
+// Everything ctr_scene_create (ctr_scene.cpp) uploads is built here, and stays here as the host copy that the guard of
 // the BVH culling (guard.h) and the ray queries read and edit.  No HIP: scripts/flatten_check.cpp and
 // tests/test_scene_flatten.py run this code on any CPU.
 #ifndef CUTRACE_AMD_SCENE_FLATTEN_H
@@ -112,6 +112,10 @@ int flatten_scene(const ctr_scene_desc &d, FlatScene &F, std::string &err);
 // The merged tree of a scene that has room for it (Merged::reserved), built into the reserved ranges.  Returns the
 // ranges it filled; none when there is nothing to build (not reserved, built already, or the tree outgrew its room).
 std::vector<DirtyRange> build_merged_tree(FlatScene &F);
+
+// The counts and flags of a device scene record (scene_device.h DScene) from the host copy its arrays mirror; the ten pointers
+// stay as they are.  Called per launch and per query, so that it is right after build_merged_tree and every guard refresh.
+__attribute__((visibility("hidden"))) void fill_scene_counts(const FlatScene &F, DScene &D);
 
 // The scene head of a launch whose top-level walk starts at `tlas_root` (scene_device.h DSceneHead): copies of planes[0..2]
 // and of the mesh record behind a leaf root, as far as the scene has them; everything else zero.

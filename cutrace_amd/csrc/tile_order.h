@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "cutrace_amd.h"
 #include "scene_device.h"
 
 #pragma GCC visibility push(hidden)
@@ -24,6 +25,11 @@ void ctr_launch_first_order(const RenderLaunch &L, hipStream_t stream);
 // of a host-delivery group stay together, the frame being group_tiles_x tiles wide
 void ctr_launch_after_render(unsigned long long *shards, unsigned long long *counters, const uint32_t *cost, uint32_t *order,
                              uint32_t n, uint32_t group_tiles_x, hipStream_t stream);
+
+// tile_order_host.cpp: attaches the handle's tile-order buffers to a launch by the rule of tile_order_policy.h: the launch uses the
+// stored order when it has the shape the order was measured on, records its costs and sorts them for the next one.  heavy: the
+// scene has the triangle count that also picks the 6-wave build.
+int attach_order(ctr_scene *s, RenderLaunch &L, bool heavy, bool count);
 #pragma GCC visibility pop
 
 #endif

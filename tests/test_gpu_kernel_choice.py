@@ -1,4 +1,4 @@
-"""The wiring of the kernel choice on the GPU (-m gpu): ctr_api.cpp must hand choose_kernel (csrc/kernel_choice.h) the right
+"""The wiring of the kernel choice on the GPU (-m gpu): ctr_render.cpp must hand choose_kernel (csrc/kernel_choice.h) the right
 facts.  16x16 frames through every entry point under the variant masks that steer the choice; the build each launch ran
 (ctr_debug_last_kernel) against the row of tests/golden/kernel_choice.npz that the test works out itself from the scene's
 materials and triangle count, the entry and `bounces`; where the row says "rejected", the call fails with the message it

@@ -1,5 +1,5 @@
 """Host logic (CPU, no GPU): the row-partition rule the library's host code shares (cutrace_amd/csrc/row_parts.h: make_rows of
-ctr_api.cpp, the part sizes of ctr_multi.hip) against its Python statement, cutrace_amd.tiling.part_rows, restricted to the row
+ctr_render.cpp, the part sizes of ctr_multi.hip) against its Python statement, cutrace_amd.tiling.part_rows, restricted to the row
 range — every h in 0..40, block_rows in 1..9, n_parts in 1..5, every part, row_begin in {0, block_rows, 2 block_rows} and
 row_end in {h, h - 3 where positive} (scripts/row_parts_check.cpp prints the cases)."""
 import os
