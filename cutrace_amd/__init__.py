@@ -691,6 +691,40 @@ class DeviceScene:
         md = np.array([int(c[1]) & 0xFFFFFFFF], np.uint32).view(np.float32)[0]
         return dict(depth=depth, color=color, normal=normal, ray_count=int(c[0]), max_depth=float(md), rows=n)
 
+    # ---- mesh updates (ctr_scene_update_mesh, include/cutrace_update.h) ----
+    def update_mesh(self, obj, triangles, stream=None):
+        """New vertices for mesh `obj` (its index in the scene's objects): `triangles` is (n, 3, 3) float32 — n the mesh's
+        triangle count, file order, [triangle][p1, p2, p3][x, y, z] — either a contiguous torch tensor on the scene's device
+        (read in place) or a numpy array.  The mesh's tree keeps its shape and is refitted on the GPU; afterwards every
+        render and query gives, bit for bit, what a scene created with these triangles gives.  The device work is queued on
+        `stream` (a torch.cuda.Stream; default: torch's current stream of the scene's device), after whatever produced the
+        tensor there; the call returns when the handle is consistent again.  A wrong count, an object that is not a mesh
+        or a vertex that is not finite raise RuntimeError and leave the scene as it was."""
+        import torch
+        dev = self._torch_device()
+        if isinstance(triangles, torch.Tensor):
+            if triangles.device != dev:
+                raise ValueError(f"triangles: tensor on {triangles.device}, the scene lives on {dev}")
+            if not triangles.is_contiguous():
+                raise ValueError("triangles: expected a contiguous tensor")
+            dtype_ok, ptr = triangles.dtype == torch.float32, triangles.data_ptr()
+        elif isinstance(triangles, np.ndarray):
+            triangles = np.ascontiguousarray(triangles)
+            dtype_ok, ptr = triangles.dtype == np.float32, triangles.ctypes.data
+        else:
+            raise TypeError(f"triangles: expected a torch tensor or a numpy array, got {type(triangles).__name__}")
+        if not dtype_ok or len(triangles.shape) != 3 or tuple(triangles.shape[1:]) != (3, 3):
+            raise ValueError(f"triangles: expected float32 of shape (n, 3, 3), got {triangles.dtype} {tuple(triangles.shape)}")
+        with _on_stream(dev, stream) as raw:
+            _check("ctr_scene_update_mesh", _lib.hip_lib().ctr_scene_update_mesh(self._h, int(obj), C.c_void_p(ptr or None),
+                                                                                 int(triangles.shape[0]), raw))
+
+    def mesh_box(self, obj):
+        """The current box of mesh `obj` as the kernels use it (ctr_scene_mesh_box): (min, max), two float32 arrays of 3."""
+        lo, hi = Vec3(), Vec3()
+        _check("ctr_scene_mesh_box", _lib.hip_lib().ctr_scene_mesh_box(self._h, int(obj), C.byref(lo), C.byref(hi)))
+        return np.array(lo.tup(), np.float32), np.array(hi.tup(), np.float32)
+
     def tile_costs(self):
         """Per-tile cost of the last launch (ctr_tile_costs), as a uint32 array."""
         L = _lib.hip_lib()

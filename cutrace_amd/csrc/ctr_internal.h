@@ -9,11 +9,13 @@
 #include <hip/hip_runtime_api.h>
 #include <string.h>
 
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "cutrace_amd.h"
+#include "mesh_refit.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
 #include "tile_order_policy.h"
@@ -64,7 +66,19 @@ struct GrowBuf {
 };
 // two buffers that grow as a pair: both hold `n` elements, or the next call tries again
 inline int reserve_both(GrowBuf &a, GrowBuf &b, size_t n) { const int st = a.reserve(n); return st ? st : b.reserve(n); }
+
+struct ctr_scene;
+// the device receives the records a host-side edit changed (scene_flatten.h DirtyRange), in the order of the list
+int upload_dirty(ctr_scene *s, const std::vector<DirtyRange> &dirty);
+// the guard of the BVH culling: plan for the handle's cameras, apply to the host copy, upload what changed
+int refresh_linear_meshes(ctr_scene *s);
 #pragma GCC visibility pop
+
+// what ctr_scene_update_mesh keeps per mesh: the level schedule of its tree (mesh_refit.h) on the host and on the device
+struct MeshRefit {
+  LevelSchedule sched;
+  GrowBuf d_nodes{sizeof(uint32_t)};  // sched.nodes, uploaded once
+};
 
 struct ctr_scene {
   int device = 0;
@@ -94,6 +108,12 @@ struct ctr_scene {
   OrderState order;
   GrowBuf d_cost{sizeof(uint32_t)}, d_order{sizeof(uint32_t)};  // order.cap tiles each
   bool poison_next_order = false;  // test hook (ctr_debug_poison_next_order)
+  // mesh updates (include/cutrace_update.h, ctr_update.cpp): everything is allocated at the first update that needs it
+  std::vector<std::unique_ptr<MeshRefit>> refit;  // one per FlatScene::guards entry; null until that mesh's first update
+  GrowBuf upd_verts{sizeof(ctr_triangle)};         // a host input's vertices on the device
+  GrowBuf upd_planes{7 * sizeof(double)};          // the guard's plane records as update_tris writes them
+  GrowBuf upd_words{sizeof(uint32_t)};             // [0] the finiteness flag, [2..7] the mesh box
+  GrowBuf upd_back{1, true};                       // page-locked landing zone of the copy-back, bytes
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::mutex mtx;
 

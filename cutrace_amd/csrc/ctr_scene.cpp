@@ -113,10 +113,12 @@ std::vector<SceneArray> scene_arrays(ctr_scene *s, const FlatScene &F) {
   };
   DScene &D = s->dev;
   return {row(D.objs, F.objs, DirtyRange::OBJS), row(D.oloop, F.oloop), row(D.meshes, F.meshes, DirtyRange::MESHES),
-          row(D.planes, F.planes), row(D.tris, F.tris, DirtyRange::TRIS), row(D.nodes, F.nodes),
+          row(D.planes, F.planes), row(D.tris, F.tris, DirtyRange::TRIS), row(D.nodes, F.nodes, DirtyRange::NODES),
           row(D.nodes4, F.nodes4, DirtyRange::NODES4), row(D.gnorm, F.gn, DirtyRange::GNORM, 4 * sizeof(float)),
           row(D.lights, F.lights), row(D.mats, F.mats)};
 }
+
+}  // namespace
 
 // the device receives the records a host-side edit changed (scene_flatten.h DirtyRange), in the order of the list
 int upload_dirty(ctr_scene *s, const std::vector<DirtyRange> &dirty) {
@@ -130,8 +132,8 @@ int upload_dirty(ctr_scene *s, const std::vector<DirtyRange> &dirty) {
   return CTR_OK;
 }
 
-// The guard of the BVH culling (guard.cpp): at upload and whenever the cameras change — plan, apply to the host copy,
-// upload what changed.
+// The guard of the BVH culling (guard.cpp): at upload, whenever the cameras change and after a mesh update (ctr_update.cpp)
+// — plan, apply to the host copy, upload what changed.
 int refresh_linear_meshes(ctr_scene *s) {
   const GuardPlan plan = plan_guards(s->flat, s->h_cams);
   const std::vector<DirtyRange> dirty = apply_guards(s->flat, plan);
@@ -143,6 +145,8 @@ int refresh_linear_meshes(ctr_scene *s) {
   }
   return upload_dirty(s, dirty);
 }
+
+namespace {
 
 // The merged tree of a scene that has room for it (scene_flatten.h Merged): built, uploaded, guarded.
 int build_merged_tree(ctr_scene *s) {

@@ -12,36 +12,9 @@
 #include <cstring>
 #include <thread>
 
+#include "tri_record.h"  // make_tri, guard_plane: shared with the device side of ctr_scene_update_mesh (mesh_update.hip)
+
 namespace {
-
-constexpr float KAPPA = 1.0f / 16384.0f;  // prefilter slack factor 2^-14 (≈1000 ulp), see DESIGN.md
-
-struct f3 { float x, y, z; };
-inline f3 sub(ctr_vec3 a, ctr_vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline f3 cross(f3 a, f3 o) { return {a.y * o.z - a.z * o.y, a.z * o.x - a.x * o.z, a.x * o.y - a.y * o.x}; }
-
-void make_tri(const ctr_vec3 &p1, const ctr_vec3 &p2, const ctr_vec3 &p3, uint32_t orig, DTri &T, float *gn) {
-  f3 a = sub(p2, p1), b = sub(p2, p3);  // default_schema.hpp:58
-  T.ab[0][0] = a.x; T.ab[1][0] = a.y; T.ab[2][0] = a.z;
-  T.ab[0][1] = b.x; T.ab[1][1] = b.y; T.ab[2][1] = b.z;
-  T.px = p2.x; T.py = p2.y; T.pz = p2.z;
-  f3 n = cross(a, b);
-  T.nx = n.x; T.ny = n.y; T.nz = n.z;
-  float emax = 0.f;
-  for (float v : {a.x, a.y, a.z, b.x, b.y, b.z}) emax = fmaxf(emax, fabsf(v));
-  T.ke = KAPPA * emax;
-  T.ke2 = KAPPA * emax * emax;
-  T.orig = orig;
-  T.pad1 = 0.f;
-  // default_schema.hpp:72: -1.0f * (p2 - p3).cross(p1 - p3).normalized()
-  f3 c = cross(sub(p2, p3), sub(p1, p3));
-  float nrm = sqrtf(c.x * c.x + c.y * c.y + c.z * c.z);
-  float f = 1.0f / nrm;
-  gn[0] = -1.0f * (f * c.x);
-  gn[1] = -1.0f * (f * c.y);
-  gn[2] = -1.0f * (f * c.z);
-  gn[3] = 0.f;
-}
 
 // what the BVH builders want to know of each triangle: its box and the box's centre
 std::vector<BvhInput> tri_boxes(const ctr_triangle *src, size_t n) {
@@ -87,17 +60,10 @@ std::vector<MeshTree> mesh_trees(const ctr_scene_desc &d) {
 // What the guard (guard.h) checks eyes and lights against: per triangle, in leaf order like the DTri records, its plane
 // in double precision
 std::vector<double> guard_planes(const ctr_triangle *src, const std::vector<uint32_t> &order) {
-  std::vector<double> planes(7 * order.size());
+  std::vector<double> planes(CTR_PLANE_DOUBLES * order.size());
   for (size_t k = 0; k < order.size(); k++) {
     const ctr_triangle &t = src[order[k]];
-    const double ax = (double)t.p2.x - t.p1.x, ay = (double)t.p2.y - t.p1.y, az = (double)t.p2.z - t.p1.z;
-    const double bx = (double)t.p2.x - t.p3.x, by = (double)t.p2.y - t.p3.y, bz = (double)t.p2.z - t.p3.z;
-    double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-    const double len = sqrt(nx * nx + ny * ny + nz * nz);
-    double *q = &planes[7 * k];
-    if (len > 0.0) { q[0] = nx / len; q[1] = ny / len; q[2] = nz / len; } else { q[0] = q[1] = q[2] = 0.0; }
-    q[3] = t.p2.x; q[4] = t.p2.y; q[5] = t.p2.z;
-    q[6] = fmax(fmax(fmax(fabs(ax), fabs(ay)), fabs(az)), fmax(fmax(fabs(bx), fabs(by)), fabs(bz)));
+    guard_plane(t.p1, t.p2, t.p3, &planes[CTR_PLANE_DOUBLES * k]);
   }
   return planes;
 }
@@ -451,6 +417,71 @@ std::vector<DirtyRange> build_merged_tree(FlatScene &F) {
   return {{DirtyRange::TRIS, M.tri_begin, (size_t)total + CTR_GUARD_SLOTS, {}},
           {DirtyRange::NODES4, M.node_begin, M.node_count, {}},
           {DirtyRange::MESHES, F.n_mesh, 1, {}}};
+}
+
+namespace {
+// the box of the subtree behind top-level descriptor `d`, its nodes' boxes recomputed on the way (same shape, new boxes)
+void refit_top(FlatScene &F, uint32_t d, float *mn, float *mx) {
+  for (int a = 0; a < 3; a++) { mn[a] = INFINITY; mx[a] = -INFINITY; }
+  if (d & BVH_LEAF_FLAG) {
+    const uint32_t first = d & 0xFFFFFFu, count = (d >> 24) & 0x7Fu;
+    for (uint32_t k = first; k < first + count && k < F.n_mesh; k++)
+      for (int a = 0; a < 3; a++) { mn[a] = fminf(mn[a], F.meshes[k].f[a]); mx[a] = fmaxf(mx[a], F.meshes[k].f[3 + a]); }
+    return;
+  }
+  DNode &N = F.nodes[F.tlas_begin + d];
+  const uint32_t kid[2] = {N.left, N.right};
+  for (int c = 0; c < 2; c++) {
+    float lo[3], hi[3];
+    refit_top(F, kid[c], lo, hi);
+    for (int a = 0; a < 3; a++) {
+      N.mn[a][c] = lo[a]; N.mx[a][c] = hi[a];
+      mn[a] = fminf(mn[a], lo[a]); mx[a] = fmaxf(mx[a], hi[a]);
+    }
+  }
+}
+}  // namespace
+
+std::vector<DirtyRange> mesh_updated(FlatScene &F, size_t gi, const float *box) {
+  std::vector<DirtyRange> dirty;
+  MeshGuard &g = F.guards[gi];
+  if (g.mesh_pos < 0) return dirty;
+  // the mesh's box, wherever a record of the mesh is kept (apply_guards uploads objs[] and meshes[mesh_pos] with bvh_root)
+  for (int q = 0; q < 6; q++) F.objs[g.obj_index].f[q] = F.meshes[g.mesh_pos].f[q] = box[q];
+  for (size_t k = F.n_mesh + 1; k < F.meshes.size(); k++)
+    if (F.meshes[k].index == g.obj_index) {
+      for (int q = 0; q < 6; q++) F.meshes[k].f[q] = box[q];
+      dirty.push_back({DirtyRange::MESHES, k, 1, {}});
+    }
+  dirty.push_back({DirtyRange::OBJS, g.obj_index, 1, {}});
+  dirty.push_back({DirtyRange::MESHES, (size_t)g.mesh_pos, 1, {}});
+  // the top-level tree over the meshes' boxes, and the box of all meshes
+  refit_top(F, F.tlas_root, F.tl_mn, F.tl_mx);
+  if (F.nodes.size() > F.tlas_begin) dirty.push_back({DirtyRange::NODES, F.tlas_begin, F.nodes.size() - F.tlas_begin, {}});
+  if (F.meshes.size() > F.n_mesh) {  // the merged pseudo mesh carries the box of all meshes
+    for (int a = 0; a < 3; a++) { F.meshes[F.n_mesh].f[a] = F.tl_mn[a]; F.meshes[F.n_mesh].f[3 + a] = F.tl_mx[a]; }
+    dirty.push_back({DirtyRange::MESHES, F.n_mesh, 1, {}});
+  }
+  // unused guard records: copies of the first triangle, as mesh_record leaves them
+  const uint32_t slot0 = g.tri_begin + g.tri_count;
+  for (uint32_t k = 0; k < CTR_GUARD_SLOTS; k++) {
+    F.tris[slot0 + k] = F.tris[g.tri_begin];
+    for (int q = 0; q < 4; q++) F.gn[4 * (slot0 + k) + q] = F.gn[4 * g.tri_begin + q];
+  }
+  dirty.push_back({DirtyRange::TRIS, slot0, CTR_GUARD_SLOTS, {}});
+  dirty.push_back({DirtyRange::GNORM, slot0, CTR_GUARD_SLOTS, {}});
+  // The guard state describes records that no longer exist.  guarded: no list of triangles equals this one, so apply_guards
+  // writes the mesh's guard records, spare node and bvh_root whatever the new plan says.  linear: the refit wrote REAL boxes
+  // into the device's nodes, so a mesh that was linear is not any more — left at true, a plan that keeps it linear would find
+  // nothing to do and the device would cull a mesh whose in-plane triangles need every lane.  At false the plan's `linear`
+  // differs and apply_guards sends the unbounded payload again.
+  g.guarded.assign(1, 0xFFFFFFFFu);
+  g.linear = false;
+  // the merged tree holds the old triangles: retired for good (ctr_set_variant: not reserved, so never built again;
+  // kernel_facts: not usable, so CTR_VAR_MERGE takes the two-level walk)
+  F.merged.reserved = F.merged.built = F.merged.usable = false;
+  std::vector<ctr_triangle>().swap(F.merged.src);
+  return dirty;
 }
 
 void fill_scene_counts(const FlatScene &F, DScene &D) {

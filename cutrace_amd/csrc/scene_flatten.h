@@ -57,7 +57,7 @@ struct Merged {
 
 // Records of a FlatScene array that a host-side edit changed: what the device copy has to receive, in this order.
 struct DirtyRange {
-  enum Array { OBJS, MESHES, TRIS, GNORM, NODES4 } array;
+  enum Array { OBJS, MESHES, TRIS, GNORM, NODES4, NODES } array;
   size_t begin, count;          // in records (GNORM: four floats per record)
   std::vector<DNode4> payload;  // not empty: the device gets THESE nodes, FlatScene::nodes4 keeps the real boxes (a linear mesh)
 };
@@ -112,6 +112,16 @@ int flatten_scene(const ctr_scene_desc &d, FlatScene &F, std::string &err);
 // The merged tree of a scene that has room for it (Merged::reserved), built into the reserved ranges.  Returns the
 // ranges it filled; none when there is nothing to build (not reserved, built already, or the tree outgrew its room).
 std::vector<DirtyRange> build_merged_tree(FlatScene &F);
+
+// After the triangle records, normals, guard planes and node boxes of mesh guards[gi] were replaced (ctr_scene_update_mesh,
+// ctr_update.cpp: the device computed them, the host copy received them back) and `box` is the mesh's new box (min, max):
+// everything else the host copy derives from them.  The box goes into the mesh's records (objs, meshes, its scene-order copy
+// behind the merged pseudo mesh); the top-level tree keeps its shape and gets its boxes recomputed bottom-up, tl_mn / tl_mx
+// with it; the mesh's unused guard records repeat its first triangle again, and its guard state is forgotten so that the next
+// apply_guards writes the records, the spare node and — for a mesh that is linear — the unbounded payload anew; the merged
+// tree is retired for the life of the scene (its triangles are stale: no room reserved, nothing built, nothing usable).
+// Returns what the device has to receive.  ray_slots stays: no tree changed its shape.
+std::vector<DirtyRange> mesh_updated(FlatScene &F, size_t gi, const float *box);
 
 // The counts and flags of a device scene record (scene_device.h DScene) from the host copy its arrays mirror; the ten pointers
 // stay as they are.  Called per launch and per query, so that it is right after build_merged_tree and every guard refresh.
