@@ -134,9 +134,9 @@ def _ray_outputs(names, n, dev):
     return {k: torch.empty((n,) + _RAY_OUT[k][0], dtype=getattr(torch, _RAY_OUT[k][1]), device=dev) for k in names}
 
 
-def _rays_check(x, what, cols, dev):
-    """x as a float32 tensor of shape (n, cols) (cols 0: (n,)), still where it was: a tensor on another GPU than `dev`,
-    another type, dtype or shape raise."""
+def _array_check(x, what, dev, dtype, cols):
+    """x as a tensor of `dtype` and shape (n, cols) (cols 0: (n,)), still where it was: a tensor on another GPU than `dev`,
+    another type, dtype or shape raise.  (Where indices are asked for, an int is welcome too: the caller has dealt with it.)"""
     import torch
     if isinstance(x, torch.Tensor):
         if x.device.type != "cpu" and x.device != dev:
@@ -144,10 +144,10 @@ def _rays_check(x, what, cols, dev):
     elif isinstance(x, np.ndarray):
         x = torch.from_numpy(x)
     else:
-        raise TypeError(f"{what}: expected a torch tensor or a numpy array, got {type(x).__name__}")
+        raise TypeError(f"{what}: expected {'an int, ' if dtype == 'int32' else ''}a torch tensor or a numpy array, got {type(x).__name__}")
     shape_ok = x.dim() == 1 if cols == 0 else (x.dim() == 2 and x.shape[1] == cols)
-    if x.dtype != torch.float32 or not shape_ok:
-        raise ValueError(f"{what}: expected float32 of shape {'(n,)' if cols == 0 else f'(n, {cols})'}, "
+    if x.dtype != getattr(torch, dtype) or not shape_ok:
+        raise ValueError(f"{what}: expected {dtype} of shape {'(n,)' if cols == 0 else f'(n, {cols})'}, "
                          f"got {x.dtype} {tuple(x.shape)}")
     return x
 
@@ -164,7 +164,7 @@ def _ray_pair(origins, dirs, dev, frame=None):
             if tuple(x.shape) != (H, W, 3):
                 raise ValueError(f"{what}: expected shape ({H}, {W}, 3) or ({H * W}, 3), got {tuple(x.shape)}")
             x = x.reshape(H * W, 3)
-        x = _rays_check(x, what, 3, dev)
+        x = _array_check(x, what, dev, "float32", 3)
         if frame and x.shape[0] != H * W:
             raise ValueError(f"{what}: {x.shape[0]} rays for the {W} x {H} frame ({H * W})")
         pair.append(x)
@@ -482,7 +482,7 @@ class DeviceScene:
         """(n, cols) float32 (cols 0: (n,)) on the scene's device: a tensor already there is used in place (made contiguous),
         a CPU tensor or a numpy array is copied over; another GPU, another shape or dtype raise."""
         dev = self._torch_device()
-        return _rays_check(x, what, cols, dev).to(dev, non_blocking=False).contiguous()
+        return _array_check(x, what, dev, "float32", cols).to(dev, non_blocking=False).contiguous()
 
     def _cast(self, q, keep, stream):
         """Fill the query's ray pointers from `keep` and launch on the raw stream handle."""
@@ -570,21 +570,6 @@ class DeviceScene:
         return out
 
     # ---- surface shading queries (ctr_shade_points, include/cutrace_rays.h) ----
-    @staticmethod
-    def _index_check(x, what, dev):
-        """x as an int32 tensor of shape (n,), still where it was (as _rays_check leaves float arrays)."""
-        import torch
-        if isinstance(x, torch.Tensor):
-            if x.device.type != "cpu" and x.device != dev:
-                raise ValueError(f"{what}: tensor on {x.device}, the scene lives on {dev}")
-        elif isinstance(x, np.ndarray):
-            x = torch.from_numpy(x)
-        else:
-            raise TypeError(f"{what}: expected an int, a torch tensor or a numpy array, got {type(x).__name__}")
-        if x.dtype != torch.int32 or x.dim() != 1:
-            raise ValueError(f"{what}: expected int32 of shape (n,), got {x.dtype} {tuple(x.shape)}")
-        return x
-
     def shade_points(self, points, normals=None, view_dirs=None, materials=None, objects=None, ambient=None, exact_pow=False,
                      linear=False, outputs=("color",), stream=None):
         """phong (inc/shading.hpp:64-99) at caller-supplied surface points: the direct lighting of points[k] with normal
@@ -610,27 +595,27 @@ class DeviceScene:
             raise ValueError("color needs materials or objects")
         if want_color and (normals is None or view_dirs is None):
             raise ValueError("color needs normals and view_dirs")
-        pts = _rays_check(points, "points", 3, dev)
+        pts = _array_check(points, "points", dev, "float32", 3)
         n = pts.shape[0]
         vec = {}
         for x, what in ((normals, "normals"), (view_dirs, "view_dirs")):
             if x is not None:
-                vec[what] = _rays_check(x, what, 3, dev)
+                vec[what] = _array_check(x, what, dev, "float32", 3)
                 if vec[what].shape[0] != n:
                     raise ValueError(f"{what}: {vec[what].shape[0]} rows for {n} points")
         scalar_mat, idx, idx_name = 0, None, None
         if isinstance(materials, (int, np.integer)) and not isinstance(materials, bool):
             scalar_mat = int(materials)
         elif materials is not None:
-            idx, idx_name = self._index_check(materials, "materials", dev), "d_material"
+            idx, idx_name = _array_check(materials, "materials", dev, "int32", 0), "d_material"
         elif objects is not None:
-            idx, idx_name = self._index_check(objects, "objects", dev), "d_object"
+            idx, idx_name = _array_check(objects, "objects", dev, "int32", 0), "d_object"
         if idx is not None and idx.shape[0] != n:
             raise ValueError(f"{'materials' if idx_name == 'd_material' else 'objects'}: {idx.shape[0]} indices for {n} points")
         with _on_stream(dev, stream) as raw:
-            # (the inputs must outlive the launch: `keep` holds what was copied over until the call returns, and the
-            # stream orders the caching allocator's reuse after it)
-            keep = [pts.to(dev).contiguous()]
+            # the query's arrays by the name of their field.  (The inputs must outlive the launch: `keep` holds what was
+            # copied over until the call returns, and the stream orders the caching allocator's reuse after it)
+            keep = {"d_point": pts.to(dev).contiguous()}
             q = _lib.PointQuery()
             q.n_points = n
             q.flags = (POINTS_LINEAR if linear else 0) | (POINTS_EXACT_POW if exact_pow else 0)
@@ -639,17 +624,15 @@ class DeviceScene:
             shape = {"color": (n, 3), "light_shadow": (n, self.n_lights)}
             out = {k: torch.empty(shape[k], dtype=torch.float32, device=dev) for k in outputs}
             if want_color:
-                keep += list(_ray_pair(vec["normals"], vec["view_dirs"], dev)[:2])
+                keep["d_normal"], keep["d_view"] = _ray_pair(vec["normals"], vec["view_dirs"], dev)[:2]
+                keep["d_color"] = out["color"]
                 if idx is not None:
-                    keep.append(idx.to(dev).contiguous())
+                    keep[idx_name] = idx.to(dev).contiguous()
+            if "light_shadow" in out and self.n_lights:
+                keep["d_light_shadow"] = out["light_shadow"]
             if n and (want_color or self.n_lights):
-                q.d_point = keep[0].data_ptr()
-                if want_color:
-                    q.d_normal, q.d_view, q.d_color = keep[1].data_ptr(), keep[2].data_ptr(), out["color"].data_ptr()
-                    if idx is not None:
-                        setattr(q, idx_name, keep[3].data_ptr())
-                if "light_shadow" in out and self.n_lights:
-                    q.d_light_shadow = out["light_shadow"].data_ptr()
+                for field, t in keep.items():
+                    setattr(q, field, t.data_ptr())
                 _check("ctr_shade_points", _lib.hip_lib().ctr_shade_points(self._h, C.byref(q), raw))
         return out
 

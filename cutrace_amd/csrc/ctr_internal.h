@@ -30,9 +30,17 @@ int hip_fail(hipError_t e, const char *what);
     hipError_t _e = (expr);                               \
     if (_e != hipSuccess) return hip_fail(_e, #expr);     \
   } while (0)
+// the status of a launcher's return value (a hipError_t as int): CTR_OK, or hip_fail() with `what`
+inline int launched(int e, const char *what) { return e ? hip_fail((hipError_t)e, what) : CTR_OK; }
 
-// is `p` page-locked host memory (hipHostMalloc / hipHostRegister)?  Then a D2H copy is one direct DMA.
-bool is_pinned(const void *p);
+// What kind of memory `p` names: the library's one hipPointerGetAttributes call.  A pointer the runtime does not know (plain
+// malloc'ed memory: "invalid value", swallowed here, not an error of ours) is HOST_OTHER, as is memory it reports as
+// unregistered; HOST_PINNED is hipHostMalloc / hipHostRegister memory; `device` is meaningful for DEVICE alone; ELSEWHERE is
+// the rest (managed memory, arrays).
+struct MemKind { enum Kind { HOST_PINNED, HOST_OTHER, DEVICE, ELSEWHERE } kind; int device; };
+MemKind memory_kind(const void *p);
+// is `p` page-locked host memory?  Then a D2H copy is one direct DMA.
+inline bool is_pinned(const void *p) { return memory_kind(p).kind == MemKind::HOST_PINNED; }
 // the device's address of page-locked host memory (false: not mapped for this device)
 bool device_view(float *host, float **dev);
 // the caller's buffers of a host-form render (uv2: ctr_render_uv only)
@@ -45,9 +53,16 @@ bool device_visible(const HostFrame &o, size_t px, HostFrame &z);
 inline float depth_of_counter(unsigned long long word) { const uint32_t bits = (uint32_t)word; float d; memcpy(&d, &bits, 4); return d; }
 // the scene's device becomes the calling thread's current one, unless it is already
 int use_device(const ctr_scene *s);
-// CTR_E_INVALID "<who><name> is not device memory of <whose>" for the first non-null pointer that is not memory of `device` (ctr_rays.cpp)
-int check_device_pointers(int device, const std::string &who, const void *const *ptrs, const char *const *names, size_t n,
-                          const char *whose = "the scene's device");
+// a pointer of a query and the name its error messages give it
+struct NamedPtr { const void *p; const char *name; };
+// CTR_E_INVALID "<who><name> is not device memory of <whose>" for the first non-null pointer that is not memory of `device`
+// (no size check is possible here): every pointer a kernel touches, for the ray queries (ctr_rays.cpp), the lens render's
+// ray arrays and ctr_quantise_device's planes (ctr_render.cpp)
+int check_device_pointers(int device, const std::string &who, const NamedPtr *ptrs, size_t n, const char *whose = "the scene's device");
+template <size_t N>
+int check_device_pointers(int device, const std::string &who, const NamedPtr (&ptrs)[N], const char *whose = "the scene's device") {
+  return check_device_pointers(device, who, ptrs, N, whose);
+}
 
 // A buffer that only grows: reserve(n) frees and allocates anew when `n` elements exceed the capacity, and is free
 // otherwise.  An allocation that fails leaves capacity 0 and a null pointer, so that the next call comes back here whatever

@@ -12,37 +12,49 @@
 
 namespace {
 
-// what both queries check after their own flags and outputs: the scene, the number of rays and, when there are any, the rays
-int check_rays(const ctr_scene *s, const std::string &who, uint64_t n_rays, const float *d_origin, const float *d_dir) {
-  if (!s) return fail(CTR_E_INVALID, who + "null scene");
-  if (n_rays >= 0x80000000ull) return fail(CTR_E_INVALID, who + "n_rays must be below 2^31");
-  if (n_rays && (!d_origin || !d_dir)) return fail(CTR_E_INVALID, who + "null rays");
+// What the three entry points check alike, once the query is known not to be null: the record of one call.
+struct QueryHead {
+  const std::string &who;   // "ctr_...: ", the prefix of every message
+  uint32_t flags, known;    // the query's flag word, the bits its entry point knows
+  std::string broken;       // the first rule of the entry point's own (outputs, bounces) that the query breaks; empty: none
+  uint64_t count;           // rays or points, and what the header calls the field
+  const char *count_name;
+  bool inputs;              // are the arrays every element is read from all there?  What to say when not
+  const char *no_inputs;
+};
+
+// The checks in the order every entry point makes them: flag bits, its own rules, the scene, the count, the inputs.
+int check_query(const ctr_scene *s, const QueryHead &h) {
+  if (h.flags & ~h.known) return fail(CTR_E_INVALID, h.who + "unknown flag bits " + std::to_string(h.flags & ~h.known));
+  if (!h.broken.empty()) return fail(CTR_E_INVALID, h.who + h.broken);
+  if (!s) return fail(CTR_E_INVALID, h.who + "null scene");
+  if (h.count >= 0x80000000ull) return fail(CTR_E_INVALID, h.who + h.count_name + " must be below 2^31");
+  if (h.count && !h.inputs) return fail(CTR_E_INVALID, h.who + h.no_inputs);
   return CTR_OK;
 }
-
-}  // namespace
-
-// every pointer the kernel touches must be device memory of the scene's device (no size check is possible here)
-// (ctr_internal.h: the lens render checks its ray arrays with it, ctr_quantise_device its planes)
-int check_device_pointers(int device, const std::string &who, const void *const *ptrs, const char *const *names, size_t n,
-                          const char *whose) {
-  for (size_t k = 0; k < n; k++) {
-    if (!ptrs[k]) continue;
-    hipPointerAttribute_t at{};
-    const bool ok = hipPointerGetAttributes(&at, ptrs[k]) == hipSuccess && at.type == hipMemoryTypeDevice && at.device == device;
-    if (!ok) {
-      (void)hipGetLastError();  // plain host memory: "invalid value", not an error of the stream
-      return fail(CTR_E_INVALID, who + names[k] + " is not device memory of " + whose);
-    }
-  }
-  return CTR_OK;
-}
-
-namespace {
 
 // what the walk of ray_walk.h needs of the scene on the device (ctr_internal.h device_scene)
 RayScene ray_scene(const ctr_scene *s, const DScene &D) {
   return {D.objs, D.oloop, D.meshes, D.planes, D.tris, D.nodes4, D.gnorm, D.mats, D.n_oloop, D.n_plane_recs, D.n_mesh, s->flat.ray_slots};
+}
+
+// what ShadeLaunch and PointsLaunch have in common: the scene, its lights, and the query's flags with `exact_pow` forced for
+// a scene outside the fast specular path's domain.  Returns the device scene for what else the caller needs of it.
+template <class Launch>
+DScene fill_lit(Launch &L, const ctr_scene *s, uint32_t flags, uint32_t exact_pow) {
+  const DScene D = device_scene(s);
+  L.scene = ray_scene(s, D);
+  L.lights = D.lights;
+  L.n_light = D.n_light;
+  L.all_opaque = s->flat.all_opaque ? 1u : 0u;
+  L.flags = flags | (s->flat.fast_pow_ok ? 0u : exact_pow);
+  return D;
+}
+
+// CTR_E_INVALID "<who><what> <bytes> bytes of LDS per workgroup, more than <most> (<way_out>)"
+int lds_fail(const std::string &who, const std::string &what, size_t bytes, size_t most, const char *way_out) {
+  return fail(CTR_E_INVALID, who + what + " " + std::to_string(bytes) + " bytes of LDS per workgroup, more than " + std::to_string(most) +
+                                 " (" + way_out + ")");
 }
 
 }  // namespace
@@ -50,23 +62,20 @@ RayScene ray_scene(const ctr_scene *s, const DScene &D) {
 extern "C" int ctr_cast_rays(ctr_scene *s, const ctr_ray_query *q, void *hip_stream) {
   const std::string who = "ctr_cast_rays: ";
   if (!q) return fail(CTR_E_INVALID, who + "null query");
-  constexpr uint32_t KNOWN = CTR_RAY_IGNORE_TRANSPARENT | CTR_RAY_LINEAR | CTR_RAY_SHADOW;
-  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(q->flags & ~KNOWN));
   const bool shadow = (q->flags & CTR_RAY_SHADOW) != 0;
   const bool any_nearest = q->d_t || q->d_object || q->d_prim || q->d_point || q->d_normal || q->d_uv;
-  if (shadow && (q->flags & CTR_RAY_IGNORE_TRANSPARENT))
-    return fail(CTR_E_INVALID, who + "CTR_RAY_SHADOW and CTR_RAY_IGNORE_TRANSPARENT exclude each other");
-  if (shadow && (any_nearest || !q->d_shadow))
-    return fail(CTR_E_INVALID, who + "CTR_RAY_SHADOW writes d_shadow only, and needs it");
-  if (!shadow && (!any_nearest || q->d_shadow))
-    return fail(CTR_E_INVALID, who + "a nearest-hit query needs at least one of its outputs and no d_shadow");
-  if (int st = check_rays(s, who, q->n_rays, q->d_origin, q->d_dir)) return st;
+  const char *broken = "";
+  if (shadow && (q->flags & CTR_RAY_IGNORE_TRANSPARENT)) broken = "CTR_RAY_SHADOW and CTR_RAY_IGNORE_TRANSPARENT exclude each other";
+  else if (shadow && (any_nearest || !q->d_shadow)) broken = "CTR_RAY_SHADOW writes d_shadow only, and needs it";
+  else if (!shadow && (!any_nearest || q->d_shadow)) broken = "a nearest-hit query needs at least one of its outputs and no d_shadow";
+  if (int st = check_query(s, {who, q->flags, CTR_RAY_IGNORE_TRANSPARENT | CTR_RAY_LINEAR | CTR_RAY_SHADOW, broken, q->n_rays, "n_rays",
+                               q->d_origin && q->d_dir, "null rays"}))
+    return st;
   if (q->n_rays == 0) return CTR_OK;
-  const void *ptrs[] = {q->d_origin, q->d_dir, q->d_min_t, q->d_max_t, q->d_t, q->d_object, q->d_prim, q->d_point,
-                        q->d_normal, q->d_uv, q->d_shadow};
-  const char *names[] = {"d_origin", "d_dir", "d_min_t", "d_max_t", "d_t", "d_object", "d_prim", "d_point",
-                         "d_normal", "d_uv", "d_shadow"};
-  if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
+  const NamedPtr ptrs[] = {{q->d_origin, "d_origin"}, {q->d_dir, "d_dir"}, {q->d_min_t, "d_min_t"}, {q->d_max_t, "d_max_t"},
+                           {q->d_t, "d_t"}, {q->d_object, "d_object"}, {q->d_prim, "d_prim"}, {q->d_point, "d_point"},
+                           {q->d_normal, "d_normal"}, {q->d_uv, "d_uv"}, {q->d_shadow, "d_shadow"}};
+  if (int st = check_device_pointers(s->device, who, ptrs)) return st;
   if (int st = use_device(s)) return st;
   RayLaunch L{};
   L.scene = ray_scene(s, device_scene(s));
@@ -86,34 +95,28 @@ extern "C" int ctr_cast_rays(ctr_scene *s, const ctr_ray_query *q, void *hip_str
   L.normal = q->d_normal;
   L.uv = q->d_uv;
   L.shadow = q->d_shadow;
-  const int e = ctr_launch_rays(L, hip_stream);
-  if (e) return hip_fail((hipError_t)e, "ray query kernel launch");
-  return CTR_OK;
+  return launched(ctr_launch_rays(L, hip_stream), "ray query kernel launch");
 }
 
 extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_stream) {
   const std::string who = "ctr_shade_rays: ";
   if (!q) return fail(CTR_E_INVALID, who + "null query");
-  constexpr uint32_t KNOWN = CTR_SHADE_LINEAR | CTR_SHADE_EXACT_POW;
-  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(q->flags & ~KNOWN));
+  std::string broken;
   if (q->bounces < 0 || q->bounces > CTR_MAX_BOUNCES)
-    return fail(CTR_E_INVALID, who + "bounces " + std::to_string(q->bounces) + " outside [0, " + std::to_string(CTR_MAX_BOUNCES) + "]");
-  if (!q->d_color) return fail(CTR_E_INVALID, who + "d_color is required");
-  if (int st = check_rays(s, who, q->n_rays, q->d_origin, q->d_dir)) return st;
+    broken = "bounces " + std::to_string(q->bounces) + " outside [0, " + std::to_string(CTR_MAX_BOUNCES) + "]";
+  else if (!q->d_color) broken = "d_color is required";
+  if (int st = check_query(s, {who, q->flags, CTR_SHADE_LINEAR | CTR_SHADE_EXACT_POW, broken, q->n_rays, "n_rays",
+                               q->d_origin && q->d_dir, "null rays"}))
+    return st;
   if (q->n_rays == 0) return CTR_OK;
-  const void *ptrs[] = {q->d_origin, q->d_dir, q->d_color, q->d_t, q->d_object, q->d_normal};
-  const char *names[] = {"d_origin", "d_dir", "d_color", "d_t", "d_object", "d_normal"};
-  if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
-  const DScene D = device_scene(s);
+  const NamedPtr ptrs[] = {{q->d_origin, "d_origin"}, {q->d_dir, "d_dir"}, {q->d_color, "d_color"},
+                           {q->d_t, "d_t"}, {q->d_object, "d_object"}, {q->d_normal, "d_normal"}};
+  if (int st = check_device_pointers(s->device, who, ptrs)) return st;
   ShadeLaunch L{};
-  L.scene = ray_scene(s, D);
-  L.lights = D.lights;
-  L.n_light = D.n_light;
+  fill_lit(L, s, q->flags, CTR_SHADE_EXACT_POW);
   L.frames = ctr_shade_frames(q->bounces, s->flat.any_bounce);
   L.frame_dwords = s->flat.need_cold ? 10u : 4u;
-  L.all_opaque = s->flat.all_opaque ? 1u : 0u;
   L.n_rays = (uint32_t)q->n_rays;
-  L.flags = q->flags | (s->flat.fast_pow_ok ? 0u : CTR_SHADE_EXACT_POW);  // (outside the fast path's domain: the exact one)
   L.bounces = q->bounces;
   L.min_t = q->min_t;
   L.ambient = q->ambient;
@@ -124,44 +127,34 @@ extern "C" int ctr_shade_rays(ctr_scene *s, const ctr_shade_query *q, void *hip_
   L.object = q->d_object;
   L.normal = q->d_normal;
   if (ctr_shade_lds_bytes(L) > CTR_SHADE_LDS_MAX)
-    return fail(CTR_E_INVALID, who + "the walk stack of this scene's mesh trees and " + std::to_string(L.frames) +
-                                   " recursion frames need " + std::to_string(ctr_shade_lds_bytes(L)) +
-                                   " bytes of LDS per workgroup, more than " + std::to_string(CTR_SHADE_LDS_MAX) +
-                                   " (fewer bounces or CTR_SHADE_LINEAR fit)");
+    return lds_fail(who, "the walk stack of this scene's mesh trees and " + std::to_string(L.frames) + " recursion frames need",
+                    ctr_shade_lds_bytes(L), CTR_SHADE_LDS_MAX, "fewer bounces or CTR_SHADE_LINEAR fit");
   if (int st = use_device(s)) return st;
-  const int e = ctr_launch_shade(L, hip_stream);
-  if (e) return hip_fail((hipError_t)e, "radiance query kernel launch");
-  return CTR_OK;
+  return launched(ctr_launch_shade(L, hip_stream), "radiance query kernel launch");
 }
 
 extern "C" int ctr_shade_points(ctr_scene *s, const ctr_point_query *q, void *hip_stream) {
   const std::string who = "ctr_shade_points: ";
   if (!q) return fail(CTR_E_INVALID, who + "null query");
-  constexpr uint32_t KNOWN = CTR_POINTS_LINEAR | CTR_POINTS_EXACT_POW;
-  if (q->flags & ~KNOWN) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(q->flags & ~KNOWN));
-  if (!q->d_color && !q->d_light_shadow) return fail(CTR_E_INVALID, who + "no output: one of d_color and d_light_shadow is required");
-  if (q->d_color && (!q->d_normal || !q->d_view)) return fail(CTR_E_INVALID, who + "d_color needs d_normal and d_view");
-  if (q->d_material && q->d_object) return fail(CTR_E_INVALID, who + "d_material and d_object exclude each other");
-  if (!s) return fail(CTR_E_INVALID, who + "null scene");
-  if (q->n_points >= 0x80000000ull) return fail(CTR_E_INVALID, who + "n_points must be below 2^31");
-  if (q->n_points && !q->d_point) return fail(CTR_E_INVALID, who + "null d_point");
+  const char *broken = "";
+  if (!q->d_color && !q->d_light_shadow) broken = "no output: one of d_color and d_light_shadow is required";
+  else if (q->d_color && (!q->d_normal || !q->d_view)) broken = "d_color needs d_normal and d_view";
+  else if (q->d_material && q->d_object) broken = "d_material and d_object exclude each other";
+  if (int st = check_query(s, {who, q->flags, CTR_POINTS_LINEAR | CTR_POINTS_EXACT_POW, broken, q->n_points, "n_points",
+                               q->d_point != nullptr, "null d_point"}))
+    return st;
   const size_t n_mat = s->flat.mats.size();
   if (q->d_color && !q->d_material && !q->d_object && (q->material < 0 || (size_t)q->material >= n_mat))
     return fail(CTR_E_INVALID, who + "material " + std::to_string(q->material) + " outside [0, " + std::to_string(n_mat) + ")");
   if (q->n_points == 0) return CTR_OK;
-  const void *ptrs[] = {q->d_point, q->d_normal, q->d_view, q->d_material, q->d_object, q->d_color, q->d_light_shadow};
-  const char *names[] = {"d_point", "d_normal", "d_view", "d_material", "d_object", "d_color", "d_light_shadow"};
-  if (int st = check_device_pointers(s->device, who, ptrs, names, sizeof(ptrs) / sizeof(ptrs[0]))) return st;
-  const DScene D = device_scene(s);
+  const NamedPtr ptrs[] = {{q->d_point, "d_point"}, {q->d_normal, "d_normal"}, {q->d_view, "d_view"}, {q->d_material, "d_material"},
+                           {q->d_object, "d_object"}, {q->d_color, "d_color"}, {q->d_light_shadow, "d_light_shadow"}};
+  if (int st = check_device_pointers(s->device, who, ptrs)) return st;
   PointsLaunch L{};
-  L.scene = ray_scene(s, D);
-  L.lights = D.lights;
-  L.n_light = D.n_light;
+  const DScene D = fill_lit(L, s, q->flags, CTR_POINTS_EXACT_POW);
   L.n_mat = D.n_mat;
   L.n_obj = D.n_obj;
-  L.all_opaque = s->flat.all_opaque ? 1u : 0u;
   L.n_points = (uint32_t)q->n_points;
-  L.flags = q->flags | (s->flat.fast_pow_ok ? 0u : CTR_POINTS_EXACT_POW);  // (outside the fast path's domain: the exact one)
   L.material = q->material;
   L.ambient = q->ambient;
   L.point = q->d_point;
@@ -173,12 +166,9 @@ extern "C" int ctr_shade_points(ctr_scene *s, const ctr_point_query *q, void *hi
   L.color = q->d_color;
   L.light_shadow = L.n_light ? q->d_light_shadow : nullptr;
   if (ctr_points_lds_bytes(L) > CTR_POINTS_LDS_MAX)
-    return fail(CTR_E_INVALID, who + "the walk stack of this scene's mesh trees needs " + std::to_string(ctr_points_lds_bytes(L)) +
-                                   " bytes of LDS per workgroup, more than " + std::to_string(CTR_POINTS_LDS_MAX) +
-                                   " (CTR_POINTS_LINEAR needs none)");
+    return lds_fail(who, "the walk stack of this scene's mesh trees needs", ctr_points_lds_bytes(L), CTR_POINTS_LDS_MAX,
+                    "CTR_POINTS_LINEAR needs none");
   if (!L.color && !L.light_shadow) return CTR_OK;  // a scene without lights: the rows of d_light_shadow are empty
   if (int st = use_device(s)) return st;
-  const int e = ctr_launch_points(L, hip_stream);
-  if (e) return hip_fail((hipError_t)e, "surface shading kernel launch");
-  return CTR_OK;
+  return launched(ctr_launch_points(L, hip_stream), "surface shading kernel launch");
 }

@@ -236,7 +236,7 @@ int images_out(ctr_scene *s, const RenderLaunch &L, const HostImages &o, size_t 
   if (o.depth8) { Q.depth = L.depth; Q.depth8 = img; }
   if (o.color8) { Q.color = L.color; Q.color8 = img + 3 * px; }
   if (o.normal8) { Q.normal = L.normal; Q.normal8 = img + 6 * px; }
-  if (int e = ctr_launch_images(Q, nullptr)) return hip_fail((hipError_t)e, "quantise kernel launch");
+  if (int st = launched(ctr_launch_images(Q, nullptr), "quantise kernel launch")) return st;
   HIP_TRY(d2h(o.depth8, Q.depth8, 3 * px));
   HIP_TRY(d2h(o.color8, Q.color8, 3 * px));
   HIP_TRY(d2h(o.normal8, Q.normal8, 3 * px));
@@ -340,9 +340,7 @@ int render_device(ctr_scene *s, const RenderCall &c) {
     if ((st = attach_order(s, L, big_mesh(s), false))) return st;
     s->last_kernel = L.variant;
   }
-  int e = ctr_launch_render(L, c.stream);
-  if (e) return hip_fail((hipError_t)e, "render kernel launch");
-  return CTR_OK;
+  return launched(ctr_launch_render(L, c.stream), "render kernel launch");
 }
 
 // The host form: the frame lands in the caller's host buffers (or, images, byte planes) before the call returns.
@@ -382,8 +380,7 @@ int render_host(ctr_scene *s, const RenderCall &c) {
   if ((st = attach_order(s, L, big_mesh(s), c.count))) return st;
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, 16 * sizeof(unsigned long long), nullptr));
   HIP_TRY(hipEventRecord(s->ev0, nullptr));
-  int e = ctr_launch_render(L, nullptr);
-  if (e) return hip_fail((hipError_t)e, "render kernel launch");
+  if ((st = launched(ctr_launch_render(L, nullptr), "render kernel launch"))) return st;
   HIP_TRY(hipEventRecord(s->ev1, nullptr));
   if (px && !direct && (st = c.images ? images_out(s, L, *c.images, px) : copy_out(s, L, c.out, px))) return st;
   HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
@@ -441,9 +438,8 @@ int ctr_render_device_lens(ctr_scene *s, float fudge, int bounces, const ctr_len
   if (lens->n_rays != want)
     return fail(CTR_E_INVALID, who + "n_rays is " + std::to_string(lens->n_rays) + ", the " + std::to_string(samples) + " x " + std::to_string(samples) +
                                    " samples of the " + std::to_string(s->cam.w) + " x " + std::to_string(s->cam.h) + " frame are " + std::to_string(want));
-  const void *const ptrs[] = {lens->d_origin, lens->d_dir};
-  const char *const names[] = {"d_origin", "d_dir"};
-  if ((st = check_device_pointers(s->device, who, ptrs, names, 2))) return st;
+  const NamedPtr ptrs[] = {{lens->d_origin, "d_origin"}, {lens->d_dir, "d_dir"}};
+  if ((st = check_device_pointers(s->device, who, ptrs))) return st;
   return render_device(s, c);
 }
 
@@ -479,20 +475,20 @@ int ctr_quantise_device(int device, const ctr_image_planes *p, void *hip_stream)
   const std::string who = "ctr_quantise_device: ";
   if (!p) return fail(CTR_E_INVALID, who + "null planes");
   if (p->reserved) return fail(CTR_E_INVALID, who + "reserved must be 0");
-  const void *const ptrs[] = {p->d_depth, p->d_color3, p->d_normal3, p->d_depth8, p->d_color8, p->d_normal8, p->d_counters};
-  const char *const names[] = {"d_depth", "d_color3", "d_normal3", "d_depth8", "d_color8", "d_normal8", "d_counters"};
-  for (int k = 0; k < 3; k++)
-    if (!ptrs[k] != !ptrs[3 + k])
-      return fail(CTR_E_INVALID, who + (ptrs[k] ? names[k] : names[3 + k]) + " without " + (ptrs[k] ? names[3 + k] : names[k]));
+  const NamedPtr ptrs[] = {{p->d_depth, "d_depth"}, {p->d_color3, "d_color3"}, {p->d_normal3, "d_normal3"}, {p->d_depth8, "d_depth8"},
+                           {p->d_color8, "d_color8"}, {p->d_normal8, "d_normal8"}, {p->d_counters, "d_counters"}};
+  for (int k = 0; k < 3; k++) {
+    const NamedPtr &have = ptrs[k].p ? ptrs[k] : ptrs[3 + k], &lack = ptrs[k].p ? ptrs[3 + k] : ptrs[k];
+    if (!have.p != !lack.p) return fail(CTR_E_INVALID, who + have.name + " without " + lack.name);
+  }
   if (!p->d_depth && !p->d_color3 && !p->d_normal3) return fail(CTR_E_INVALID, who + "no plane");
   if (p->n_pixels == 0) return CTR_OK;
-  if (int st = check_device_pointers(device, who, ptrs, names, 7, ("device " + std::to_string(device)).c_str())) return st;
+  if (int st = check_device_pointers(device, who, ptrs, ("device " + std::to_string(device)).c_str())) return st;
   int cur = -1;
   if (hipGetDevice(&cur) != hipSuccess || cur != device) HIP_TRY(hipSetDevice(device));
   const ImagesLaunch Q{p->n_pixels, p->d_depth, p->d_color3, p->d_normal3, p->d_depth8, p->d_color8, p->d_normal8,
                        (const unsigned long long *)p->d_counters, p->max_depth};
-  if (int e = ctr_launch_images(Q, hip_stream)) return hip_fail((hipError_t)e, "quantise kernel launch");
-  return CTR_OK;
+  return launched(ctr_launch_images(Q, hip_stream), "quantise kernel launch");
 }
 
 int ctr_algorithmic_bytes(ctr_scene *s, float fudge, int bounces, const ctr_rows *rows, uint64_t *bytes,

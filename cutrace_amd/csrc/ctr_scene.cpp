@@ -33,13 +33,25 @@ int hip_fail(hipError_t e, const char *what) {
   return fail(CTR_E_HIP_BASE + (int)e, std::string(what) + ": " + hipGetErrorName(e) + " (" + hipGetErrorString(e) + ")");
 }
 
-bool is_pinned(const void *p) {
+MemKind memory_kind(const void *p) {
   hipPointerAttribute_t at{};
   if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();  // plain malloc'ed memory: "invalid value", not an error of ours
-    return false;
+    (void)hipGetLastError();  // plain malloc'ed memory: "invalid value", not an error of ours or of the stream
+    return {MemKind::HOST_OTHER, 0};
   }
-  return at.type == hipMemoryTypeHost;
+  if (at.type == hipMemoryTypeDevice) return {MemKind::DEVICE, at.device};
+  if (at.type == hipMemoryTypeHost) return {MemKind::HOST_PINNED, 0};
+  return {at.type == hipMemoryTypeUnregistered ? MemKind::HOST_OTHER : MemKind::ELSEWHERE, 0};
+}
+
+int check_device_pointers(int device, const std::string &who, const NamedPtr *ptrs, size_t n, const char *whose) {
+  for (size_t k = 0; k < n; k++) {
+    if (!ptrs[k].p) continue;
+    const MemKind m = memory_kind(ptrs[k].p);
+    if (m.kind != MemKind::DEVICE || m.device != device)
+      return fail(CTR_E_INVALID, who + ptrs[k].name + " is not device memory of " + whose);
+  }
+  return CTR_OK;
 }
 
 bool device_view(float *host, float **dev) {

@@ -33,14 +33,9 @@ enum class Where { HOST, DEVICE, ELSEWHERE };
 // `device` (the test of check_device_pointers, at the first and the last byte), or anything else
 Where where_is(const void *p, size_t bytes, int device) {
   auto one = [&](const void *q) {
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, q) != hipSuccess) {
-      (void)hipGetLastError();  // plain malloc'ed memory: "invalid value", not an error of ours
-      return Where::HOST;
-    }
-    if (at.type == hipMemoryTypeDevice) return at.device == device ? Where::DEVICE : Where::ELSEWHERE;
-    if (at.type == hipMemoryTypeHost || at.type == hipMemoryTypeUnregistered) return Where::HOST;
-    return Where::ELSEWHERE;
+    const MemKind m = memory_kind(q);
+    if (m.kind == MemKind::DEVICE) return m.device == device ? Where::DEVICE : Where::ELSEWHERE;
+    return m.kind == MemKind::ELSEWHERE ? Where::ELSEWHERE : Where::HOST;
   };
   const Where first = one(p), last = one((const char *)p + bytes - 1);
   return first == last ? first : Where::ELSEWHERE;
@@ -79,8 +74,6 @@ struct Stamps {
     t0 = now;
   }
 };
-
-int launched(int e, const char *what) { return e ? hip_fail((hipError_t)e, what) : CTR_OK; }
 
 }  // namespace
 

@@ -23,6 +23,7 @@
 
 #include "cutrace_rays.h"
 #include "phong_light.h"
+#include "ray_launch.h"
 #include "ray_points.h"
 #include "ray_walk.h"
 
@@ -116,23 +117,16 @@ __global__ __launch_bounds__(RP_THREADS) void ray_points_kernel(PointsLaunch L) 
   }
 }
 
-template <uint32_t K>
-int launch(const PointsLaunch &L, hipStream_t stream) {
-  const uint32_t grid = (L.n_points + RP_THREADS - 1) / RP_THREADS;
-  hipLaunchKernelGGL(ray_points_kernel<K>, dim3(grid), dim3(RP_THREADS), ctr_points_lds_bytes(L), stream, L);
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 size_t ctr_points_lds_bytes(const PointsLaunch &L) {
-  return (L.flags & CTR_POINTS_LINEAR) ? 0 : (size_t)L.scene.stack_slots * RP_THREADS * sizeof(uint32_t);
+  return walk_stack_bytes(L.scene.stack_slots, RP_THREADS, (L.flags & CTR_POINTS_LINEAR) != 0);
 }
 
 int ctr_launch_points(const PointsLaunch &L, void *stream) {
   if (L.n_points == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
   const bool lin = (L.flags & CTR_POINTS_LINEAR) != 0, exact = (L.flags & CTR_POINTS_EXACT_POW) != 0;
-  if (lin) return exact ? launch<RP_LINEAR | RP_EXACT>(L, s) : launch<RP_LINEAR>(L, s);
-  return exact ? launch<RP_EXACT>(L, s) : launch<0u>(L, s);
+  void (*const kernel)(PointsLaunch) = lin ? (exact ? ray_points_kernel<RP_LINEAR | RP_EXACT> : ray_points_kernel<RP_LINEAR>)
+                                           : (exact ? ray_points_kernel<RP_EXACT> : ray_points_kernel<0u>);
+  return launch_lanes(kernel, L, L.n_points, RP_THREADS, ctr_points_lds_bytes(L), (hipStream_t)stream);
 }

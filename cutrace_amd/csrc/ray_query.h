@@ -3,6 +3,7 @@
 #ifndef CUTRACE_AMD_RAY_QUERY_H
 #define CUTRACE_AMD_RAY_QUERY_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "scene_device.h"
@@ -20,6 +21,11 @@ struct RayScene {
   uint32_t n_oloop, n_plane_recs, n_mesh;
   uint32_t stack_slots;      // LDS stack entries per lane the deepest mesh tree needs (scene_flatten.h FlatScene::ray_slots)
 };
+
+// dynamic LDS of the walk's stack for one workgroup of `lanes` lanes, in bytes: [entry][lane] dwords, none for a linear walk
+constexpr size_t walk_stack_bytes(uint32_t slots, uint32_t lanes, bool linear) {
+  return linear ? 0 : (size_t)slots * lanes * sizeof(uint32_t);
+}
 
 struct RayLaunch {
   RayScene scene;

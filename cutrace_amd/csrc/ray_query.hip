@@ -36,6 +36,7 @@
 
 #include "bvh.h"
 #include "cutrace_rays.h"
+#include "ray_launch.h"
 #include "ray_query.h"
 #include "ray_walk.h"
 #include "scene_device.h"
@@ -129,21 +130,14 @@ __global__ __launch_bounds__(RQ_THREADS) void ray_query_kernel(RayLaunch L) {
   if (L.uv) { L.uv[2 * (size_t)i] = u; L.uv[2 * (size_t)i + 1] = v; }
 }
 
-template <uint32_t V>
-int launch(const RayLaunch &L, hipStream_t stream) {
-  const size_t lds = (V & RQ_LINEAR) ? 0 : (size_t)L.scene.stack_slots * RQ_THREADS * sizeof(uint32_t);
-  const uint32_t grid = (L.n_rays + RQ_THREADS - 1) / RQ_THREADS;
-  hipLaunchKernelGGL(ray_query_kernel<V>, dim3(grid), dim3(RQ_THREADS), lds, stream, L);
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 int ctr_launch_rays(const RayLaunch &L, void *stream) {
   if (L.n_rays == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  const uint32_t lin = (L.flags & CTR_RAY_LINEAR) ? RQ_LINEAR : 0u;
-  if (!(L.flags & CTR_RAY_SHADOW)) return lin ? launch<RQ_LINEAR>(L, s) : launch<0u>(L, s);
-  if (L.anyhit) return lin ? launch<RQ_SHADOW | RQ_ANYHIT | RQ_LINEAR>(L, s) : launch<RQ_SHADOW | RQ_ANYHIT>(L, s);
-  return lin ? launch<RQ_SHADOW | RQ_LINEAR>(L, s) : launch<RQ_SHADOW>(L, s);
+  const bool lin = (L.flags & CTR_RAY_LINEAR) != 0;
+  void (*kernel)(RayLaunch);
+  if (!(L.flags & CTR_RAY_SHADOW)) kernel = lin ? ray_query_kernel<RQ_LINEAR> : ray_query_kernel<0u>;
+  else if (L.anyhit) kernel = lin ? ray_query_kernel<RQ_SHADOW | RQ_ANYHIT | RQ_LINEAR> : ray_query_kernel<RQ_SHADOW | RQ_ANYHIT>;
+  else kernel = lin ? ray_query_kernel<RQ_SHADOW | RQ_LINEAR> : ray_query_kernel<RQ_SHADOW>;
+  return launch_lanes(kernel, L, L.n_rays, RQ_THREADS, walk_stack_bytes(L.scene.stack_slots, RQ_THREADS, lin), (hipStream_t)stream);
 }

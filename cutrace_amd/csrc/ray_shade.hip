@@ -29,6 +29,7 @@
 
 #include "cutrace_rays.h"
 #include "phong_light.h"
+#include "ray_launch.h"
 #include "ray_shade.h"
 #include "ray_walk.h"
 
@@ -229,24 +230,17 @@ __global__ __launch_bounds__(RS_THREADS) void ray_shade_kernel(ShadeLaunch L) {
   store3(L.color, i, out_rgb);
 }
 
-template <uint32_t K>
-int launch(const ShadeLaunch &L, hipStream_t stream) {
-  const uint32_t grid = (L.n_rays + RS_THREADS - 1) / RS_THREADS;
-  hipLaunchKernelGGL(ray_shade_kernel<K>, dim3(grid), dim3(RS_THREADS), ctr_shade_lds_bytes(L), stream, L);
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 size_t ctr_shade_lds_bytes(const ShadeLaunch &L) {
-  const size_t stack = (L.flags & CTR_SHADE_LINEAR) ? 0 : L.scene.stack_slots;
-  return (stack + (size_t)L.frames * L.frame_dwords) * RS_THREADS * sizeof(uint32_t);
+  return walk_stack_bytes(L.scene.stack_slots, RS_THREADS, (L.flags & CTR_SHADE_LINEAR) != 0) +
+         (size_t)L.frames * L.frame_dwords * RS_THREADS * sizeof(uint32_t);
 }
 
 int ctr_launch_shade(const ShadeLaunch &L, void *stream) {
   if (L.n_rays == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
   const bool lin = (L.flags & CTR_SHADE_LINEAR) != 0, exact = (L.flags & CTR_SHADE_EXACT_POW) != 0;
-  if (lin) return exact ? launch<RS_LINEAR | RS_EXACT>(L, s) : launch<RS_LINEAR>(L, s);
-  return exact ? launch<RS_EXACT>(L, s) : launch<0u>(L, s);
+  void (*const kernel)(ShadeLaunch) = lin ? (exact ? ray_shade_kernel<RS_LINEAR | RS_EXACT> : ray_shade_kernel<RS_LINEAR>)
+                                          : (exact ? ray_shade_kernel<RS_EXACT> : ray_shade_kernel<0u>);
+  return launch_lanes(kernel, L, L.n_rays, RS_THREADS, ctr_shade_lds_bytes(L), (hipStream_t)stream);
 }

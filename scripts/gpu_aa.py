@@ -15,49 +15,24 @@ render_kernel instantiation into <out>/resources.txt (`--csrc DIR`: of another t
 import argparse
 import json
 import os
-import re
 import statistics
-import subprocess
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import gpu_common  # noqa: E402  (beside this file)
 
 KV_NAMES = ((1, "PREFILTER"), (2, "ANYHIT"), (4, "COUNT"), (8, "BVH"), (16, "STATS"), (32, "FASTPOW"), (64, "OCC6"),
             (128, "HOSTOUT"), (256, "UV"), (512, "MERGE"), (1024, "IGNTR"), (2048, "SS"))
 
 
 def resources(out, csrc=None, name="resources.txt"):
-    from cutrace_amd import build as b
-    csrc = csrc or b.CSRC
-    flags = [f for f in b.HIP_FLAGS if f != "-I" + b.CSRC] + ["-I" + csrc]
-    cmd = [b.hipcc(), *flags, "--offload-device-only", "-c", "-o", os.devnull, os.path.join(csrc, "render_kernel.hip"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, check=True)
-    blocks, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize|Occupancy|LDS Size|TotalSGPRs)(?: \[[^\]]*\])?: (\S+)", line)
-        if not m:
-            continue
-        key, val = m.group(1), m.group(2)
-        if key == "Function Name":
-            v = re.search(r"render_kernelILj(\d+)E", val)
-            cur = None
-            if v:
-                bits = int(v.group(1))
-                cur = blocks.setdefault(bits, [])
-        elif cur is not None:
-            cur.append(f"    {key}: {val}")
-    lines = []
-    for bits in sorted(blocks):  # by variant number: a new instantiation adds a block and moves no other
-        lines.append(f"render_kernel<{bits}> ({' | '.join(n for bit, n in KV_NAMES if bits & bit) or 'plain'})")
-        lines += blocks[bits]
-    txt = "\n".join(lines) + ("\n(LDS Size is the static part: the recursion stack is dynamic, frames x frame_dwords x 64 lanes x 4 bytes per wave,\n"
-                              " plus 1280 bytes under OCC6; frames = bounces, frame_dwords = 4, or 10 when a material both reflects and transmits)\n")
-    with open(os.path.join(out, name), "w") as f:
-        f.write(txt)
-    print(txt)
+    gpu_common.write_report(out, name, gpu_common.resource_report(
+        "render_kernel.hip", "render_kernel", KV_NAMES, "plain",
+        "\n(LDS Size is the static part: the recursion stack is dynamic, frames x frame_dwords x 64 lanes x 4 bytes per wave,\n"
+        " plus 1280 bytes under OCC6; frames = bounces, frame_dwords = 4, or 10 when a material both reflects and transmits)\n",
+        csrc=csrc, by_number=True))
 
 
 def main():

@@ -16,43 +16,24 @@ instantiation of the kernel into <out>/resources.txt.
 import argparse
 import json
 import os
-import re
-import statistics
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import gpu_common  # noqa: E402  (beside this file)
 ORDERS = ("image_order", "permuted")
 
 
 def resources(out):
-    from cutrace_amd import build as b
-    cmd = [b.hipcc(), *b.HIP_FLAGS, "--offload-device-only", "-c", "-o", os.devnull, os.path.join(b.CSRC, "ray_points.hip"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, check=True)
-    lines = []
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize|Occupancy|LDS Size|TotalSGPRs)(?: \[[^\]]*\])?: (\S+)", line)
-        if m:
-            key, val = m.group(1), m.group(2)
-            if key == "Function Name":
-                v = re.search(r"ray_points_kernelILj(\d+)E", val)
-                bits = int(v.group(1)) if v else -1
-                names = [n for bit, n in ((1, "LINEAR"), (2, "EXACT_POW")) if bits & bit] or ["default"]
-                lines.append(f"ray_points_kernel<{bits}> ({' | '.join(names)})")
-            else:
-                lines.append(f"    {key}: {val}")
-    txt = "\n".join(lines) + (
+    gpu_common.write_report(out, "resources.txt", gpu_common.resource_report(
+        "ray_points.hip", "ray_points_kernel", ((1, "LINEAR"), (2, "EXACT_POW")), "default",
         "\n(hipcc --offload-arch=gfx950 with the library's flags.  Occupancy is waves per SIMD; ScratchSize is bytes per lane.  LDS Size\n"
         " is the static part: the walk stack is dynamic, stack_slots x 128 lanes x 4 bytes per workgroup, none under LINEAR.\n"
         " Workgroup: 128 lanes = 2 waves, as ray_query.hip's.  The VGPRs set 4 (default, LINEAR | EXACT_POW), 3 (EXACT_POW) and 6\n"
         " (LINEAR) waves per SIMD, i.e. 16 / 12 / 24 per CU: each a whole number of two-wave workgroups, so the block size costs\n"
         " no occupancy; the walk stack takes the same LDS per wave whatever the block size; and a finished workgroup frees its\n"
-        " registers and its stack after two waves' tails instead of four or more.  No kernel uses scratch.)\n")
-    with open(os.path.join(out, "resources.txt"), "w") as f:
-        f.write(txt)
-    print(txt)
+        " registers and its stack after two waves' tails instead of four or more.  No kernel uses scratch.)\n"))
 
 
 def measure(a, only_shade_rays=False):
@@ -63,17 +44,7 @@ def measure(a, only_shade_rays=False):
     dev = torch.device("cuda", 0)
 
     def timed(fn):
-        for _ in range(a.warmup):
-            fn()
-        ts = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+        return dict(zip(("median_ms", "min_ms", "max_ms"), gpu_common.timed(fn, a.reps, a.warmup)))
 
     s = ca.HostScene.load(os.path.join(ROOT, "scene", "bunny.json"))
     assert s.ok

@@ -14,36 +14,17 @@ ray-query kernel instantiation into <out>/resources.txt.
 import argparse
 import json
 import os
-import re
-import statistics
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import gpu_common  # noqa: E402  (beside this file)
 
 
 def resources(out):
-    from cutrace_amd import build as b
-    cmd = [b.hipcc(), *b.HIP_FLAGS, "--offload-device-only", "-c", "-o", os.devnull, os.path.join(b.CSRC, "ray_query.hip"),
-           "-Rpass-analysis=kernel-resource-usage"]
-    r = subprocess.run(cmd, capture_output=True, text=True, check=True)
-    lines = []
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|ScratchSize|Occupancy|LDS Size|TotalSGPRs)(?: \[[^\]]*\])?: (\S+)", line)
-        if m:
-            key, val = m.group(1), m.group(2)
-            if key == "Function Name":
-                v = re.search(r"ray_query_kernelILj(\d+)E", val)
-                bits = int(v.group(1)) if v else -1
-                names = [n for bit, n in ((1, "LINEAR"), (2, "SHADOW"), (4, "ANYHIT")) if bits & bit] or ["nearest"]
-                lines.append(f"ray_query_kernel<{bits}> ({' | '.join(names)})")
-            else:
-                lines.append(f"    {key}: {val}")
-    txt = "\n".join(lines) + "\n(LDS Size is the static part: the stack is dynamic, stack_slots x 128 lanes x 4 bytes per workgroup)\n"
-    with open(os.path.join(out, "resources.txt"), "w") as f:
-        f.write(txt)
-    print(txt)
+    gpu_common.write_report(out, "resources.txt", gpu_common.resource_report(
+        "ray_query.hip", "ray_query_kernel", ((1, "LINEAR"), (2, "SHADOW"), (4, "ANYHIT")), "nearest",
+        "\n(LDS Size is the static part: the stack is dynamic, stack_slots x 128 lanes x 4 bytes per workgroup)\n"))
 
 
 def main():
@@ -66,17 +47,7 @@ def main():
     dev = torch.device("cuda", 0)
 
     def timed(fn):
-        for _ in range(a.warmup):
-            fn()
-        ts = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            ts.append(e0.elapsed_time(e1))
-        return statistics.median(ts), min(ts), max(ts)
+        return gpu_common.timed(fn, a.reps, a.warmup)
 
     dense_dir = os.path.join(a.out, "_scenes")
     cases = [("bunny", os.path.join(ROOT, "scene", "bunny.json")),

@@ -2,7 +2,7 @@
 
   isa_diff.py asm <tree> <out_dir> [file.hip ...]    assembly of <tree>/cutrace_amd/csrc/<file.hip> -> <out_dir>/<file>.s, with
                                                      the flags of THIS tree's cutrace_amd/build.py (default: every .hip of the
-                                                     tree that holds a kernel of the render path or the ray queries)
+                                                     tree's cutrace_amd/csrc that defines a kernel)
   isa_diff.py diff <parent_dir> <new_dir>            the table, then every differing line of every kernel that differs
 
 A tree of another commit: `git archive <rev> | tar -x -C <dir>`.  Kernels are matched by their (mangled) name across all
@@ -19,7 +19,11 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT = ("render_kernel.hip", "tile_order.hip", "ray_query.hip", "ray_shade.hip")
+
+
+def kernel_files(tree):
+    """every .hip of the tree's cutrace_amd/csrc that defines a kernel"""
+    return sorted(os.path.basename(p) for p in glob.glob(os.path.join(tree, "cutrace_amd", "csrc", "*.hip")) if "__global__" in open(p).read())
 
 
 def make_asm(tree, out_dir, files):
@@ -105,7 +109,7 @@ def diff(parent_dir, new_dir):
 
 if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "asm":
-        make_asm(os.path.abspath(sys.argv[2]), sys.argv[3], sys.argv[4:] or DEFAULT)
+        make_asm(os.path.abspath(sys.argv[2]), sys.argv[3], sys.argv[4:] or kernel_files(os.path.abspath(sys.argv[2])))
     elif len(sys.argv) == 4 and sys.argv[1] == "diff":
         diff(sys.argv[2], sys.argv[3])
     else:

@@ -1,0 +1,96 @@
+// query_check.cpp — the host glue of the ray queries that needs no device, as a program of its own (meant for ASan/UBSan; the
+// record of a run: profiles/query_path/sanitizers.txt): the pointer classifier of ctr_scene.cpp and what is written on top of it
+// (memory_kind, is_pinned, all_pinned, check_device_pointers), launched(), walk_stack_bytes and the two *_lds_bytes rules of
+// ray_query.h / ray_shade.hip / ray_points.hip, and the checks ctr_cast_rays, ctr_shade_rays and ctr_shade_points make before
+// they look at the scene.  Without a device the runtime knows no pointer: everything is HOST_OTHER, which is the path that
+// swallows the runtime's error.  Linked with ctr_scene.cpp, ctr_rays.cpp, the three query .hip files (their host halves are
+// what is checked; no check gets as far as a launch) and the host files those need.
+//
+//   query_check        prints "query_check: ok" and returns 0, or says what differed and returns 1
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ctr_internal.h"
+#include "cutrace_rays.h"
+#include "ray_points.h"
+#include "ray_query.h"
+#include "ray_shade.h"
+
+static int failures = 0;
+static void expect(bool ok, const char *what) {
+  if (!ok) { fprintf(stderr, "query_check: %s\n", what); failures++; }
+}
+static void expect_error(int st, const char *text) {
+  if (st != CTR_E_INVALID || strcmp(ctr_last_error(), text) != 0) {
+    fprintf(stderr, "query_check: status %d \"%s\", expected %d \"%s\"\n", st, ctr_last_error(), CTR_E_INVALID, text);
+    failures++;
+  }
+}
+
+int main() {
+  // ---- the classifier on memory the runtime does not know ----
+  std::vector<float> heap(64);
+  float stack[8] = {0};
+  static float fixed[8];
+  for (const void *p : {(const void *)heap.data(), (const void *)(heap.data() + 63), (const void *)stack, (const void *)fixed, (const void *)nullptr}) {
+    expect(memory_kind(p).kind == MemKind::HOST_OTHER, "memory_kind: not HOST_OTHER");
+    expect(!is_pinned(p), "is_pinned: true for pageable memory");
+  }
+  const HostFrame frame{heap.data(), heap.data() + 8, heap.data() + 32, nullptr};
+  expect(!all_pinned(frame, 8) && !all_pinned(frame, 0) && !all_pinned(HostFrame{}, 8), "all_pinned");
+
+  const NamedPtr none[] = {{nullptr, "d_a"}, {nullptr, "d_b"}};
+  expect(check_device_pointers(0, "who: ", none) == CTR_OK, "check_device_pointers: null pointers are skipped");
+  expect(check_device_pointers(0, "who: ", none, 0) == CTR_OK, "check_device_pointers: empty table");
+  const NamedPtr some[] = {{nullptr, "d_a"}, {heap.data(), "d_b"}, {stack, "d_c"}};
+  expect_error(check_device_pointers(0, "who: ", some), "who: d_b is not device memory of the scene's device");
+  expect_error(check_device_pointers(3, "who: ", some + 2, 1, "device 3"), "who: d_c is not device memory of device 3");
+
+  expect(launched(0, "a launch") == CTR_OK, "launched(0)");
+  expect(launched((int)hipErrorInvalidValue, "a launch") == CTR_E_HIP_BASE + (int)hipErrorInvalidValue &&
+             strncmp(ctr_last_error(), "a launch: hipErrorInvalidValue (", 32) == 0, "launched(hipErrorInvalidValue)");
+
+  // ---- the walk stack and the LDS of a workgroup ----
+  static_assert(walk_stack_bytes(0, 128, false) == 0 && walk_stack_bytes(24, 128, true) == 0, "no stack");
+  static_assert(walk_stack_bytes(24, 128, false) == 24 * 128 * 4 && walk_stack_bytes(24, 64, false) == 24 * 64 * 4, "slots x lanes x 4");
+  static_assert(walk_stack_bytes(0xFFFFFFFFu, 128, false) == (size_t)0xFFFFFFFFu * 512, "64-bit product");
+  ShadeLaunch S{};
+  S.scene.stack_slots = 24; S.frames = 15; S.frame_dwords = 10;
+  expect(ctr_shade_lds_bytes(S) == (24 + 150) * 64 * 4, "ctr_shade_lds_bytes");
+  S.flags = CTR_SHADE_LINEAR;
+  expect(ctr_shade_lds_bytes(S) == 150 * 64 * 4, "ctr_shade_lds_bytes, linear");
+  PointsLaunch P{};
+  P.scene.stack_slots = 24;
+  expect(ctr_points_lds_bytes(P) == 24 * 128 * 4, "ctr_points_lds_bytes");
+  P.flags = CTR_POINTS_LINEAR | CTR_POINTS_EXACT_POW;
+  expect(ctr_points_lds_bytes(P) == 0, "ctr_points_lds_bytes, linear");
+
+  // ---- the three entry points up to the scene (tests/test_query_checks_cpu.py has every case; here: each path once) ----
+  float *const some_ptr = heap.data();
+  expect_error(ctr_cast_rays(nullptr, nullptr, nullptr), "ctr_cast_rays: null query");
+  expect_error(ctr_shade_rays(nullptr, nullptr, nullptr), "ctr_shade_rays: null query");
+  expect_error(ctr_shade_points(nullptr, nullptr, nullptr), "ctr_shade_points: null query");
+  ctr_ray_query r{};
+  r.n_rays = 2; r.d_origin = some_ptr; r.d_dir = some_ptr; r.d_t = some_ptr;
+  expect_error(ctr_cast_rays(nullptr, &r, nullptr), "ctr_cast_rays: null scene");
+  r.flags = 8;
+  expect_error(ctr_cast_rays(nullptr, &r, nullptr), "ctr_cast_rays: unknown flag bits 8");
+  r.flags = CTR_RAY_SHADOW;
+  expect_error(ctr_cast_rays(nullptr, &r, nullptr), "ctr_cast_rays: CTR_RAY_SHADOW writes d_shadow only, and needs it");
+  ctr_shade_query s{};
+  s.n_rays = 2; s.d_origin = some_ptr; s.d_dir = some_ptr; s.d_color = some_ptr;
+  expect_error(ctr_shade_rays(nullptr, &s, nullptr), "ctr_shade_rays: null scene");
+  s.bounces = 16;
+  expect_error(ctr_shade_rays(nullptr, &s, nullptr), "ctr_shade_rays: bounces 16 outside [0, 15]");
+  ctr_point_query p{};
+  p.n_points = 2; p.d_point = some_ptr; p.d_light_shadow = some_ptr;
+  expect_error(ctr_shade_points(nullptr, &p, nullptr), "ctr_shade_points: null scene");
+  p.d_color = some_ptr;
+  expect_error(ctr_shade_points(nullptr, &p, nullptr), "ctr_shade_points: d_color needs d_normal and d_view");
+
+  if (!failures) printf("query_check: ok\n");
+  return failures ? 1 : 0;
+}

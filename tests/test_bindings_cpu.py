@@ -97,7 +97,7 @@ def test_rays_are_validated_before_anything_moves_to_the_device(ca):
     with pytest.raises(ValueError, match="dirs: 5 rays for 4 origins"):
         ca._ray_pair(ok, np.zeros((5, 3), np.float32), dev)
     with pytest.raises(ValueError, match=r"min_t: expected float32 of shape \(n,\)"):
-        ca._rays_check(ok, "min_t", 0, dev)
+        ca._array_check(ok, "min_t", dev, "float32", 0)
     # the first error wins, as in the calls: origins before dirs, dirs before the count
     with pytest.raises(ValueError, match="origins: expected float32"):
         ca._ray_pair(ok.astype(np.float64), [1], dev)
@@ -106,3 +106,50 @@ def test_rays_are_validated_before_anything_moves_to_the_device(ca):
         ca._ray_pair(np.zeros((2, 3, 3), np.float32), ok, dev, frame=(2, 2))
     with pytest.raises(ValueError, match=r"dirs: 5 rays for the 2 x 2 frame \(4\)"):
         ca._ray_pair(ok.reshape(2, 2, 3), np.zeros((5, 3), np.float32), dev, frame=(2, 2))
+
+
+# _array_check(x, what, dev, dtype, cols): float rows of 3, per-ray scalars and int32 indices, each with a wrong type, dtype,
+# rank and column count; (dtype, cols, x, the exception, its whole message)
+_F3 = "expected float32 of shape (n, 3)"
+_F0 = "expected float32 of shape (n,)"
+_I0 = "expected int32 of shape (n,)"
+ARRAY_CHECK_CASES = [
+    ("float32", 3, [[0.0, 0.0, 0.0]], TypeError, "x: expected a torch tensor or a numpy array, got list"),
+    ("float32", 3, np.zeros((4, 3), np.float64), ValueError, f"x: {_F3}, got torch.float64 (4, 3)"),
+    ("float32", 3, np.zeros(4, np.float32), ValueError, f"x: {_F3}, got torch.float32 (4,)"),
+    ("float32", 3, np.zeros((4, 3, 1), np.float32), ValueError, f"x: {_F3}, got torch.float32 (4, 3, 1)"),
+    ("float32", 3, np.zeros((4, 2), np.float32), ValueError, f"x: {_F3}, got torch.float32 (4, 2)"),
+    ("float32", 0, 1.5, TypeError, "x: expected a torch tensor or a numpy array, got float"),
+    ("float32", 0, np.zeros(4, np.int32), ValueError, f"x: {_F0}, got torch.int32 (4,)"),
+    ("float32", 0, np.zeros((4, 1), np.float32), ValueError, f"x: {_F0}, got torch.float32 (4, 1)"),
+    ("float32", 0, np.zeros((4, 3), np.float32), ValueError, f"x: {_F0}, got torch.float32 (4, 3)"),
+    ("int32", 0, "0", TypeError, "x: expected an int, a torch tensor or a numpy array, got str"),
+    ("int32", 0, np.zeros(4, np.int64), ValueError, f"x: {_I0}, got torch.int64 (4,)"),
+    ("int32", 0, np.zeros(4, np.float32), ValueError, f"x: {_I0}, got torch.float32 (4,)"),
+    ("int32", 0, np.zeros((4, 1), np.int32), ValueError, f"x: {_I0}, got torch.int32 (4, 1)"),
+    ("int32", 0, np.zeros((4, 3), np.int32), ValueError, f"x: {_I0}, got torch.int32 (4, 3)"),
+]
+
+
+@pytest.mark.parametrize("as_tensor", [False, True], ids=["numpy", "torch"])
+def test_array_check_names_what_is_wrong(ca, as_tensor):
+    import torch
+    dev = torch.device("cuda", 0)  # (constructing the device needs no GPU, and nothing below goes there)
+    for dtype, cols, x, exc, text in ARRAY_CHECK_CASES:
+        if as_tensor and isinstance(x, np.ndarray):
+            x = torch.from_numpy(x)
+        with pytest.raises(exc) as e:
+            ca._array_check(x, "x", dev, dtype, cols)
+        assert str(e.value) == text, (dtype, cols, text)
+
+
+def test_array_check_returns_a_cpu_tensor_where_it_was(ca):
+    import torch
+    dev = torch.device("cuda", 0)
+    for dtype, cols, shape in (("float32", 3, (4, 3)), ("float32", 0, (4,)), ("int32", 0, (4,)), ("float32", 3, (0, 3))):
+        a = np.zeros(shape, dtype)
+        got = ca._array_check(a, "x", dev, dtype, cols)
+        assert isinstance(got, torch.Tensor) and got.device.type == "cpu" and tuple(got.shape) == shape
+        assert got.data_ptr() == a.ctypes.data or not a.size  # (no copy; an empty tensor has no address)
+        t = torch.from_numpy(a)
+        assert ca._array_check(t, "x", dev, dtype, cols) is t

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import oracle
-from tests import points_ref, ray_ref, shade_ref
+from tests import points_ref, ray_ref, shade_ref, util
 from tests.conftest import load_scene
 from tests.util import (LIGHT_CASES, SCALE_EXPONENTS, STACK_CASES, TOL, _random_scene, assert_bitwise as _bitwise, f32_bits as _bits,
                         fast_pow_kept, light_scale, lights_scene_json, max_diff as _max_diff, pow2, random_rays, scaled_scene_json,
@@ -347,9 +347,7 @@ def test_bad_arguments(ca):
             setattr(x, k, val)
         return x
 
-    def bad(x, text):
-        assert L.ctr_shade_points(ds._h, C.byref(x), None) == 1, text
-        assert text.encode() in L.ctr_last_error(), (text, L.ctr_last_error())
+    bad = functools.partial(util.bad, L.ctr_shade_points, ds._h)
 
     assert L.ctr_shade_points(ds._h, C.byref(q()), None) == 0
     assert L.ctr_shade_points(ds._h, C.byref(q(flags=3, d_material=idx.data_ptr())), None) == 0

@@ -3,13 +3,14 @@ shadow_intensity: the C oracle where it covers the case (camera rays), tests/ray
 against the oracle by tests/test_rays_cpu.py) everywhere else.  "Same bits": bitwise, except the sphere's texture
 coordinates (atan2f / asinf on the device, 1e-4)."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
 import oracle
-from tests import ray_ref
+from tests import ray_ref, util
 from tests.conftest import load_scene
 from tests.util import (assert_same as _assert_same, f32_bits as _bits, random_rays as _random_rays, ref_dict as _ref_dict,
                         to_np as _np)
@@ -378,9 +379,7 @@ def test_bad_arguments(ca):
             setattr(x, k, v)
         return x
 
-    def bad(x, text):
-        assert L.ctr_cast_rays(ds._h, C.byref(x), None) == 1, text
-        assert text.encode() in L.ctr_last_error(), (text, L.ctr_last_error())
+    bad = functools.partial(util.bad, L.ctr_cast_rays, ds._h)
 
     assert L.ctr_cast_rays(ds._h, C.byref(q(d_t=t.data_ptr())), None) == 0
     bad(q(d_t=t.data_ptr(), d_origin=None), "null rays")

@@ -3,13 +3,14 @@ where it covers the case (camera rays), tests/shade_ref.py (its NumPy restatemen
 tests/test_shade_cpu.py) everywhere else, and the render kernel of the same build beyond the oracle's depth.
 "Bitwise": identical float bits, NaN positions equal.  "Within TOL": tests/util.TOL per channel."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 import pytest
 
 import oracle
-from tests import ray_ref, shade_ref
+from tests import ray_ref, shade_ref, util
 from tests.conftest import load_scene
 from tests.util import (TOL, assert_bitwise as _bitwise, f32_bits as _bits, first_hit_same as _first_hit_same,
                         max_diff as _max_diff, random_rays, to_np as _np)
@@ -237,9 +238,7 @@ def test_bad_arguments(ca):
             setattr(x, k, v)
         return x
 
-    def bad(x, text):
-        assert L.ctr_shade_rays(ds._h, C.byref(x), None) == 1, text
-        assert text.encode() in L.ctr_last_error(), (text, L.ctr_last_error())
+    bad = functools.partial(util.bad, L.ctr_shade_rays, ds._h)
 
     assert L.ctr_shade_rays(ds._h, C.byref(q()), None) == 0
     bad(q(d_origin=None), "null rays")

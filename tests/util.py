@@ -325,6 +325,21 @@ def max_diff(got, want, what):
     return m
 
 
+def refusal(entry, scene, query, what=""):
+    """ctr_last_error() after `entry` (ctr_cast_rays, ctr_shade_rays or ctr_shade_points of the HIP library) refused the
+    query record (None: a null query) on the scene handle with CTR_E_INVALID"""
+    import ctypes as C
+    from cutrace_amd import _lib
+    assert entry(scene, C.byref(query) if query is not None else None, None) == 1, what
+    return _lib.hip_lib().ctr_last_error().decode()
+
+
+def bad(entry, scene, query, text):
+    """... and `text` is part of the message"""
+    msg = refusal(entry, scene, query, text)
+    assert text in msg, (text, msg)
+
+
 def first_hit_same(got, want, what):
     assert np.array_equal(got["object"], np.asarray(want["object"]).astype(np.int32)), f"{what}: object"
     assert_bitwise(got["t"], want["t"], f"{what}: t")
