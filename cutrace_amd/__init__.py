@@ -174,6 +174,18 @@ def _ray_pair(origins, dirs, dev, frame=None):
     return o.to(dev, non_blocking=False).contiguous(), d.to(dev, non_blocking=False).contiguous(), o.shape[0]
 
 
+def _records(kind, items, what=None):
+    """A ctypes array of copies of `items`, a sequence of `kind` (_lib.Light, _lib.Material); anything else raises TypeError."""
+    if isinstance(items, (str, bytes)) or not hasattr(items, "__len__") or not hasattr(items, "__getitem__"):
+        raise TypeError(f"{what or kind.__name__}: expected a sequence of {kind.__name__}, got {type(items).__name__}")
+    arr = (kind * len(items))()
+    for k in range(len(items)):
+        if not isinstance(items[k], kind):
+            raise TypeError(f"{what or kind.__name__}[{k}]: expected {kind.__name__}, got {type(items[k]).__name__}")
+        C.memmove(C.byref(arr, k * C.sizeof(kind)), C.byref(items[k]), C.sizeof(kind))
+    return arr
+
+
 class HostScene:
     """A scene loaded by the C++ loader (libcutrace_host.so): owns the flat arrays."""
 
@@ -268,6 +280,8 @@ class DeviceScene:
         self.w, self.h = host_scene.size
         self._ambient = float(host_scene.desc.contents.cam.ambient)  # shade_rays' and shade_points' default
         self.n_lights = int(host_scene.desc.contents.n_lights)       # the width of shade_points' light_shadow
+        d = host_scene.desc.contents
+        self._materials = _records(Material, [d.materials[i] for i in range(int(d.n_materials))])  # set_material edits these
 
     def set_variant(self, bits):
         _check("ctr_set_variant", _lib.hip_lib().ctr_set_variant(self._h, bits))
@@ -707,6 +721,45 @@ class DeviceScene:
         lo, hi = Vec3(), Vec3()
         _check("ctr_scene_mesh_box", _lib.hip_lib().ctr_scene_mesh_box(self._h, int(obj), C.byref(lo), C.byref(hi)))
         return np.array(lo.tup(), np.float32), np.array(hi.tup(), np.float32)
+
+    # ---- live lights and materials (include/cutrace_edit.h) ----
+    def set_lights(self, lights):
+        """Replace the scene's lights (ctr_scene_set_lights): a sequence of _lib.Light, of any length including 0.  Afterwards
+        every render and query gives, bit for bit, what a scene created with these lights gives; shade_points' light_shadow
+        has the new width.  Synchronous.  A bad light type raises RuntimeError and leaves the scene as it was."""
+        arr = _records(Light, lights, "lights")
+        _check("ctr_scene_set_lights", _lib.hip_lib().ctr_scene_set_lights(self._h, arr, len(arr)))
+        self.n_lights = len(arr)
+
+    def set_materials(self, materials):
+        """Replace the scene's materials (ctr_scene_set_materials): a sequence of _lib.Material; the count may change as long
+        as every object's material index stays below it.  Afterwards every render and query gives, bit for bit, what a scene
+        created with these materials gives.  Synchronous.  A bad material type or a count that leaves an object out of
+        range raise RuntimeError and leave the scene as it was."""
+        arr = _records(Material, materials, "materials")
+        _check("ctr_scene_set_materials", _lib.hip_lib().ctr_scene_set_materials(self._h, arr, len(arr)))
+        self._materials = arr
+
+    def set_material(self, idx, **kw):
+        """HostScene.set_material on the live scene: material `idx` with the given fields replaced (color: three floats)."""
+        if isinstance(idx, bool) or not isinstance(idx, (int, np.integer)) or not 0 <= idx < len(self._materials):
+            raise ValueError(f"bad material index {idx!r}")
+        arr = _records(Material, self._materials)
+        for k, v in kw.items():
+            if k not in ("color", "specular", "reflexivity", "phong_exp", "transparency"):
+                raise TypeError(f"set_material: no material field {k!r}")
+            setattr(arr[idx], k, Vec3(*v) if k == "color" else v)
+        self.set_materials(arr)
+
+    def guard_state(self, obj):
+        """Test hook (ctr_debug_guard_state): (file indices of mesh `obj`'s triangles in its guard records, ascending, as a
+        list; whether the mesh is walked linearly)."""
+        L = _lib.hip_lib()
+        n, linear = C.c_uint64(), C.c_int()
+        _check("ctr_debug_guard_state", L.ctr_debug_guard_state(self._h, int(obj), None, 0, C.byref(n), C.byref(linear)))
+        out = (C.c_uint32 * max(int(n.value), 1))()
+        _check("ctr_debug_guard_state", L.ctr_debug_guard_state(self._h, int(obj), out, int(n.value), C.byref(n), C.byref(linear)))
+        return [int(out[k]) for k in range(int(n.value))], bool(linear.value)
 
     def tile_costs(self):
         """Per-tile cost of the last launch (ctr_tile_costs), as a uint32 array."""

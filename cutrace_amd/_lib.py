@@ -190,6 +190,13 @@ HIP_LATER_PROTOS = {
         "ctr_scene_update_mesh": ([_ptr, _u32, _ptr, _u64, _ptr], _int),
         "ctr_scene_mesh_box": ([_ptr, _u32, _P(Vec3), _P(Vec3)], _int),
     },
+    "cutrace_edit.h": {
+        "ctr_scene_set_lights": ([_ptr, _P(Light), _u64], _int),
+        "ctr_scene_set_materials": ([_ptr, _P(Material), _u64], _int),
+        "ctr_scene_light_count": ([_ptr, _P(_u64)], _int),
+        "ctr_scene_material_count": ([_ptr, _P(_u64)], _int),
+        "ctr_debug_guard_state": ([_ptr, _u32, _P(_u32), _u64, _P(_u64), _P(_int)], _int),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -200,6 +207,7 @@ AA_SYMBOLS = list(HIP_PROTOS["cutrace_aa.h"])
 LENS_SYMBOLS = sorted(HIP_PROTOS["cutrace_lens.h"])
 IMAGES_SYMBOLS = list(HIP_PROTOS["cutrace_images.h"])
 UPDATE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_update.h"])
+EDIT_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_edit.h"])
 
 _host = None
 _hip = None

@@ -1,0 +1,105 @@
+// ctr_edit.cpp — include/cutrace_edit.h: ctr_scene_set_lights, ctr_scene_set_materials, the two counts and ctr_debug_guard_state.
+// No HIP kernels here: the records and flags are scene_flatten.cpp's (light_records, material_records: the text flatten_scene
+// runs), the guard is guard.cpp's, and its plane scan on the device is guard_scan.hip.
+//
+// An edit in four steps:
+//   1. the arguments are checked as validate_desc checks a description; nothing of the handle has changed when the call fails here
+//   2. the device is waited for, and the device array gets room for the new count (reused when it fits)
+//   3. the host copy gets the records, the flags and — materials — the objects' transparency bits; the device receives them
+//   4. refresh_linear_meshes: the lights are probes of the guard, a reflecting material makes mirrors
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+
+#include "ctr_internal.h"
+#include "cutrace_edit.h"
+
+namespace {
+
+// The device array at *dev gets room for `n` records of `rec` bytes.  *cap: the records it has room for (0: `have`, the count
+// it was created with).  Reallocated only when `n` exceeds that, with the 256 spare bytes ctr_scene_create gives every array.
+int room_for(const void **dev, size_t *cap, size_t have, size_t n, size_t rec) {
+  if (*cap == 0) *cap = have;
+  if (n <= *cap) return CTR_OK;
+  void *p = nullptr;
+  HIP_TRY(hipMalloc(&p, n * rec + 256));
+  if (*dev) (void)hipFree(const_cast<void *>(*dev));
+  *dev = p;
+  *cap = n;
+  return CTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ctr_scene_set_lights(ctr_scene *s, const ctr_light *lights, uint64_t n) {
+  const std::string who = "ctr_scene_set_lights: ";
+  if (!s || (!lights && n)) return fail(CTR_E_INVALID, who + "null argument");
+  for (uint64_t i = 0; i < n; i++)
+    if (lights[i].type > CTR_LIGHT_POINT) return fail(CTR_E_INVALID, who + "light #" + std::to_string(i) + ": bad type");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  FlatScene &F = s->flat;
+  if (int st = use_device(s)) return st;
+  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old records
+  if (int st = room_for((const void **)&s->dev.lights, &s->lights_cap, F.lights.size(), n, sizeof(DLight))) return st;
+  light_records(F, lights, n);
+  if (n) HIP_TRY(hipMemcpy(const_cast<DLight *>(s->dev.lights), F.lights.data(), n * sizeof(DLight), hipMemcpyHostToDevice));
+  return refresh_linear_meshes(s, true);
+}
+
+int ctr_scene_set_materials(ctr_scene *s, const ctr_material *mats, uint64_t n) {
+  const std::string who = "ctr_scene_set_materials: ";
+  if (!s || (!mats && n)) return fail(CTR_E_INVALID, who + "null argument");
+  for (uint64_t i = 0; i < n; i++)
+    if (mats[i].type != CTR_MAT_PHONG) return fail(CTR_E_INVALID, who + "material #" + std::to_string(i) + ": bad type");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  FlatScene &F = s->flat;
+  for (size_t i = 0; i < F.objs.size(); i++)
+    if (F.objs[i].mat >= n) return fail(CTR_E_INVALID, who + "object #" + std::to_string(i) + ": material index out of range");
+  if (int st = use_device(s)) return st;
+  HIP_TRY(hipDeviceSynchronize());
+  if (int st = room_for((const void **)&s->dev.mats, &s->mats_cap, F.mats.size(), n, sizeof(DMat))) return st;
+  const std::vector<DirtyRange> dirty = material_records(F, mats, n);
+  if (n) HIP_TRY(hipMemcpy(const_cast<DMat *>(s->dev.mats), F.mats.data(), n * sizeof(DMat), hipMemcpyHostToDevice));
+  if (int st = upload_dirty(s, dirty)) return st;
+  return refresh_linear_meshes(s, true);
+}
+
+int ctr_scene_light_count(const ctr_scene *s, uint64_t *n) {
+  if (!s || !n) return fail(CTR_E_INVALID, "ctr_scene_light_count: null argument");
+  std::lock_guard<std::mutex> lk(const_cast<ctr_scene *>(s)->mtx);
+  *n = s->flat.lights.size();
+  return CTR_OK;
+}
+
+int ctr_scene_material_count(const ctr_scene *s, uint64_t *n) {
+  if (!s || !n) return fail(CTR_E_INVALID, "ctr_scene_material_count: null argument");
+  std::lock_guard<std::mutex> lk(const_cast<ctr_scene *>(s)->mtx);
+  *n = s->flat.mats.size();
+  return CTR_OK;
+}
+
+int ctr_debug_guard_state(ctr_scene *s, uint32_t object, uint32_t *guarded, uint64_t capacity, uint64_t *n_guarded, int *linear) {
+  if (!s || !n_guarded || !linear || (!guarded && capacity)) return fail(CTR_E_INVALID, "ctr_debug_guard_state: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  const FlatScene &F = s->flat;
+  if (object >= F.objs.size() || F.objs[object].type != CTR_OBJ_MESH)
+    return fail(CTR_E_INVALID, "ctr_debug_guard_state: object #" + std::to_string(object) + " is not a mesh");
+  *n_guarded = 0;
+  *linear = 0;
+  for (const MeshGuard &g : F.guards) {
+    if (g.obj_index != object || g.mesh_pos < 0) continue;
+    std::vector<uint32_t> file;
+    for (uint32_t t : g.guarded) file.push_back(F.tris[g.tri_begin + t].orig);
+    std::sort(file.begin(), file.end());
+    *n_guarded = file.size();
+    *linear = g.linear ? 1 : 0;
+    for (uint64_t k = 0; k < file.size() && k < capacity; k++) guarded[k] = file[k];
+  }
+  return CTR_OK;
+}
+
+}  // extern "C"

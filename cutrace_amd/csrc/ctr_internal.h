@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cutrace_amd.h"
+#include "guard_scan.h"
 #include "mesh_refit.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
@@ -85,8 +86,14 @@ inline int reserve_both(GrowBuf &a, GrowBuf &b, size_t n) { const int st = a.res
 struct ctr_scene;
 // the device receives the records a host-side edit changed (scene_flatten.h DirtyRange), in the order of the list
 int upload_dirty(ctr_scene *s, const std::vector<DirtyRange> &dirty);
-// the guard of the BVH culling: plan for the handle's cameras, apply to the host copy, upload what changed
-int refresh_linear_meshes(ctr_scene *s);
+// The guard of the BVH culling: plan for the handle's cameras, lights and mirrors, apply to the host copy, upload what
+// changed.  may_scan_on_device: the caller has waited for the device and allows the plane scan to run there (guard_scan.hip)
+// when the scan is large enough to pay for a launch; false: the host scan, whatever its size.
+int refresh_linear_meshes(ctr_scene *s, bool may_scan_on_device = false);
+// ctr_scene_update_mesh: the planes of mesh guards[gi] changed, and src_dev is where the device holds the new ones already.  They
+// replace the mesh's range of the scan's flat array by a copy on the device, if that array exists yet (the first scan on the
+// device uploads every mesh from the host copy).
+int guard_planes_changed(ctr_scene *s, size_t gi, const double *src_dev);
 #pragma GCC visibility pop
 
 // what ctr_scene_update_mesh keeps per mesh: the level schedule of its tree (mesh_refit.h) on the host and on the device
@@ -129,6 +136,15 @@ struct ctr_scene {
   GrowBuf upd_planes{7 * sizeof(double)};          // the guard's plane records as update_tris writes them
   GrowBuf upd_words{sizeof(uint32_t)};             // [0] the finiteness flag, [2..7] the mesh box
   GrowBuf upd_back{1, true};                       // page-locked landing zone of the copy-back, bytes
+  // edits of the lights and materials (include/cutrace_edit.h, ctr_edit.cpp): records the device arrays have room for
+  // (0: as ctr_scene_create allocated them, the count they were created with)
+  size_t lights_cap = 0, mats_cap = 0;
+  // the guard's plane scan on the device (guard_scan.h, refresh_linear_meshes): everything is allocated at the first scan there
+  GrowBuf scan_planes{7 * sizeof(double)};         // all meshes' planes, FlatScene::guards order
+  bool scan_planes_live = false;                   // ... are on the device and current (false: the next scan uploads them all)
+  GrowBuf scan_probes{sizeof(GuardProbe)};
+  GrowBuf scan_words{sizeof(uint64_t)};            // one bit per plane
+  GrowBuf scan_back{sizeof(uint64_t), true};       // page-locked landing zone of the words
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::mutex mtx;
 

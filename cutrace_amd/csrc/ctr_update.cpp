@@ -9,7 +9,8 @@
 //      authority: the guard, the mirrors, the scene head and the payload of a linear mesh all read it
 //   4. mesh_updated (scene_flatten.cpp) derives the rest on the host: the mesh's box in its records, the top-level tree, the
 //      guard state reset, the merged tree retired
-//   5. upload_dirty and refresh_linear_meshes, the machinery ctr_scene_set_cameras ends with
+//   5. upload_dirty and refresh_linear_meshes, the machinery ctr_scene_set_cameras ends with; the guard's plane scan runs on the
+//      device when it is large enough (guard_scan.h), over the planes step 2 left there
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
@@ -170,7 +171,9 @@ int ctr_scene_update_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tri
   // ---- 4., 5. everything derived from them, then the guard ----
   if (int st = upload_dirty(s, mesh_updated(F, gi, box))) return st;
   stamp("host records + upload");
-  const int st = refresh_linear_meshes(s);
+  // (the new planes are on the device already, in upd_planes, and the stream has been waited for: the scan takes them from there)
+  if (int st = guard_planes_changed(s, gi, d_planes)) return st;
+  const int st = refresh_linear_meshes(s, true);
   stamp("guard");
   return st;
 }

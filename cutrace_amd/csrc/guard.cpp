@@ -7,8 +7,6 @@
 
 namespace {
 
-constexpr double TOL = 1.0 / 131072.0;
-
 struct P3 { double x, y, z; };
 struct Mirror { P3 p, n; };  // a point of the plane, its unit normal
 
@@ -71,32 +69,12 @@ std::vector<P3> ray_origins(const std::vector<DCam> &cams, const std::vector<Mir
   return origins;
 }
 
-// the triangles of one mesh (leaf order) whose plane holds an origin or a point light, or is parallel to a sun
-std::vector<uint32_t> risky_triangles(const MeshGuard &g, const std::vector<P3> &origins, const std::vector<DLight> &lights) {
+// the triangles of one mesh (leaf order) whose plane holds an origin or a point light, or is parallel to a sun: guard_scan.h
+std::vector<uint32_t> risky_triangles(const MeshGuard &g, const GuardProbes &P) {
   std::vector<uint32_t> risky;
-  const size_t nt = g.planes.size() / 7;
-  for (size_t t = 0; t < nt; t++) {
-    const double *q = &g.planes[7 * t];
-    if (q[0] == 0.0 && q[1] == 0.0 && q[2] == 0.0) continue;  // zero-area triangle: alpha is exactly 0, never a hit
-    auto point_in_plane = [&](double x, double y, double z) {
-      const double dx = x - q[3], dy = y - q[4], dz = z - q[5];
-      const double dist = fabs(dx * q[0] + dy * q[1] + dz * q[2]);
-      const double scale = fmax(fmax(fabs(dx), fabs(dy)), fmax(fabs(dz), q[6]));
-      return dist <= TOL * scale;
-    };
-    bool hit = false;
-    for (const P3 &o : origins)
-      if (point_in_plane(o.x, o.y, o.z)) hit = true;
-    for (const DLight &l : lights) {
-      if (l.type == CTR_LIGHT_POINT) {
-        if (point_in_plane(l.vx, l.vy, l.vz)) hit = true;
-      } else {
-        const double len = sqrt((double)l.vx * l.vx + (double)l.vy * l.vy + (double)l.vz * l.vz);
-        if (len > 0.0 && fabs(l.vx * q[0] + l.vy * q[1] + l.vz * q[2]) <= TOL * len) hit = true;
-      }
-    }
-    if (hit) risky.push_back((uint32_t)t);
-  }
+  const size_t nt = g.planes.size() / CTR_PLANE_DOUBLES;
+  for (size_t t = 0; t < nt; t++)
+    if (plane_is_risky(&g.planes[CTR_PLANE_DOUBLES * t], P.probes.data(), (uint32_t)P.n_points, (uint32_t)P.probes.size())) risky.push_back((uint32_t)t);
   return risky;
 }
 
@@ -172,20 +150,44 @@ void apply_merged(FlatScene &F, const std::vector<uint32_t> &keys, std::vector<D
 
 }  // namespace
 
-GuardPlan plan_guards(const FlatScene &F, const std::vector<DCam> &cams) {
-  GuardPlan plan;
+GuardProbes guard_probes(const FlatScene &F, const std::vector<DCam> &cams) {
+  GuardProbes P;
   const std::vector<Mirror> mirrors = flat_mirrors(F);
   const std::vector<P3> origins = ray_origins(cams, mirrors);
-  plan.n_mirrors = mirrors.size();
-  plan.n_origins = origins.size();
+  P.n_mirrors = mirrors.size();
+  P.n_origins = origins.size();
+  P.probes.reserve(origins.size() + F.lights.size());
+  for (const P3 &o : origins) P.probes.push_back({o.x, o.y, o.z, 0.0});
+  for (const DLight &l : F.lights)
+    if (l.type == CTR_LIGHT_POINT) P.probes.push_back({l.vx, l.vy, l.vz, 0.0});
+  P.n_points = P.probes.size();
+  for (const DLight &l : F.lights)
+    if (l.type != CTR_LIGHT_POINT) P.probes.push_back({l.vx, l.vy, l.vz, sqrt((double)l.vx * l.vx + (double)l.vy * l.vy + (double)l.vz * l.vz)});
+  return P;
+}
+
+uint64_t guard_plane_count(const FlatScene &F) {
+  uint64_t n = 0;
+  for (const MeshGuard &g : F.guards) n += g.planes.size() / CTR_PLANE_DOUBLES;
+  return n;
+}
+
+GuardPlan plan_guards(const FlatScene &F, const GuardProbes &P, const uint64_t *words) {
+  GuardPlan plan;
+  plan.n_mirrors = P.n_mirrors;
+  plan.n_origins = P.n_origins;
   plan.meshes.resize(F.guards.size());
   uint32_t rank = 0;  // of the current mesh among the non-empty meshes, scene order (guards are in scene order)
+  uint64_t first = 0;  // the mesh's first plane in the flat array of all meshes' planes
   for (size_t i = 0; i < F.guards.size(); i++) {
     const MeshGuard &g = F.guards[i];
+    const uint32_t n_planes = (uint32_t)(g.planes.size() / CTR_PLANE_DOUBLES);
+    const uint64_t begin = first;
+    first += n_planes;
     if (g.mesh_pos < 0) continue;
     const uint32_t g_rank = rank++;
     GuardPlan::Mesh &m = plan.meshes[i];
-    m.risky = risky_triangles(g, origins, F.lights);
+    m.risky = words ? guard_scan_cut(words, begin, n_planes) : risky_triangles(g, P);
     m.linear = m.risky.size() > CTR_GUARD_SLOTS;
     if (m.linear) {
       plan.any_linear = true;
@@ -195,6 +197,8 @@ GuardPlan plan_guards(const FlatScene &F, const std::vector<DCam> &cams) {
   }
   return plan;
 }
+
+GuardPlan plan_guards(const FlatScene &F, const std::vector<DCam> &cams) { return plan_guards(F, guard_probes(F, cams), nullptr); }
 
 std::vector<DirtyRange> apply_guards(FlatScene &F, const GuardPlan &plan) {
   std::vector<DirtyRange> dirty;

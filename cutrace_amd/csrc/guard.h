@@ -1,5 +1,5 @@
 // guard.h — the guard of the BVH culling: which triangles every lane that enters a mesh must meet whatever their box,
-// and which meshes are walked linearly.  Host only, no HIP: a plan is a pure function of the flattened scene and the
+// and which meshes are walked linearly.  Host only, no HIP (the scan of the planes may have run on the device: guard_scan.h): a plan is a pure function of the flattened scene and the
 // cameras, and applying it edits the host copy and names the records the device has to receive.
 //
 // The per-mesh BVH lets a cast skip triangles whose (widened) box its ray cannot touch.  That is the
@@ -31,6 +31,7 @@
 #ifndef CUTRACE_AMD_GUARD_H
 #define CUTRACE_AMD_GUARD_H
 
+#include "guard_scan.h"
 #include "scene_flatten.h"
 
 #define CTR_MIRROR_MESH_TRIS 16u
@@ -49,6 +50,21 @@ struct GuardPlan {
   size_t n_origins = 0, n_mirrors = 0;  // eyes + mirror images, flat mirrors (CUTRACE_DEBUG_GUARDS)
 };
 
+// What the planes are checked against (guard_scan.h), built once per plan: the eyes, their images in the scene's flat mirrors,
+// then the point lights, then the suns (each kind in the scene's order).
+struct GuardProbes {
+  std::vector<GuardProbe> probes;
+  size_t n_points = 0;  // probes[0 .. n_points) are points, the rest suns
+  size_t n_origins = 0, n_mirrors = 0;
+};
+GuardProbes guard_probes(const FlatScene &F, const std::vector<DCam> &cams);
+// the planes of all meshes, FlatScene::guards order: the length of the flat array the device scan runs over
+uint64_t guard_plane_count(const FlatScene &F);
+
+// `words`: the bits of a scan of that flat array against P.probes (guard_scan.h; the device's, read back), cut here at each
+// mesh's range; nullptr: the planes are scanned here, on the host.  The same plan either way.
+GuardPlan plan_guards(const FlatScene &F, const GuardProbes &P, const uint64_t *words);
+// guard_probes, then the host scan
 GuardPlan plan_guards(const FlatScene &F, const std::vector<DCam> &cams);
 
 // Makes the host copy what the plan asks for, touching only what differs from the guard state the scene already has

@@ -112,10 +112,6 @@ int object_records(const ctr_scene_desc &d, const std::vector<MeshTree> &trees, 
     O.type = o.type;
     O.mat = (uint32_t)o.mat_idx;
     O.index = (uint32_t)i;
-    {  // material::is_transparent (default_schema.hpp:334: `transparency >= 1e-6`, a double comparison): ray_cast's ignore_transparent
-      const uint32_t tr = ((double)d.materials[o.mat_idx].transparency >= 1e-6) ? 1u : 0u;
-      memcpy(&O.f[7], &tr, sizeof(tr));
-    }
     switch (o.type) {
       case CTR_OBJ_TRIANGLE: {
         O.tri_begin = (uint32_t)F.tris.size();
@@ -179,10 +175,7 @@ void plane_records(FlatScene &F) {
   };
   auto put = [](DPlanePair &pr, int slot, const DObj &O) {
     for (int a = 0; a < 3; a++) { pr.p[a][slot] = O.f[a]; pr.n[a][slot] = O.f[3 + a]; }
-    pr.index[slot] = O.index;
-    uint32_t tr;
-    memcpy(&tr, &O.f[7], sizeof(tr));
-    pr.transparent[slot] = tr;
+    pr.index[slot] = O.index;  // (.transparent: material_flags)
   };
   // fewer than three axis-aligned planes (a lone floor): one general record is less to fetch than a triple
   if (axis_planes[0].size() + axis_planes[1].size() + axis_planes[2].size() < 3) {
@@ -291,23 +284,19 @@ void reserve_merged(const ctr_scene_desc &d, const std::vector<DObj> &by_rank, F
   for (const DObj &O : by_rank) F.meshes.push_back(O);
 }
 
-void lights_and_materials(const ctr_scene_desc &d, FlatScene &F) {
-  auto largest = [](const ctr_vec3 &c) { return std::max(std::fabs((double)c.x), std::max(std::fabs((double)c.y), std::fabs((double)c.z))); };
+// What the kernels' choice of build reads of the lights and materials (FlatScene: all_opaque, need_cold, any_bounce,
+// fast_pow_ok), from the records alone and from the defaults: an edit can clear a flag as well as set it.
+void shading_flags(FlatScene &F) {
+  auto largest = [](float x, float y, float z) { return std::max(std::fabs((double)x), std::max(std::fabs((double)y), std::fabs((double)z))); };
   double lambda = 0.0, worst = 0.0;
-  F.lights.resize(d.n_lights);
-  for (uint64_t i = 0; i < d.n_lights; i++) {
-    const ctr_light &l = d.lights[i];
-    F.lights[i] = DLight{l.type, l.v.x, l.v.y, l.v.z, l.color.x, l.color.y, l.color.z, 0.f};
-    lambda += largest(l.color);
-  }
-  F.mats.resize(d.n_materials);
-  for (uint64_t i = 0; i < d.n_materials; i++) {
-    const ctr_material &m = d.materials[i];
-    F.mats[i] = DMat{m.color.x, m.color.y, m.color.z, m.specular, m.reflexivity, m.phong_exp, m.transparency, 0.f};
+  for (const DLight &l : F.lights) lambda += largest(l.cx, l.cy, l.cz);
+  F.all_opaque = true;
+  F.need_cold = F.any_bounce = false;
+  for (const DMat &m : F.mats) {
     if (!(m.transparency == 0.0f)) F.all_opaque = false;
     if ((double)m.transparency >= 1e-6 && (double)m.reflexivity >= 1e-6) F.need_cold = true;
     if ((double)m.transparency >= 1e-6 || (double)m.reflexivity >= 1e-6) F.any_bounce = true;
-    worst = std::max(worst, std::fabs((double)m.phong_exp * (double)m.specular) * largest(m.color));
+    worst = std::max(worst, std::fabs((double)m.phong_exp * (double)m.specular) * largest(m.cx, m.cy, m.cz));
   }
   F.fast_pow_ok = fast_pow_in_bar(worst, lambda);
 }
@@ -379,7 +368,8 @@ int flatten_scene(const ctr_scene_desc &d, FlatScene &F, std::string &err) {
   const std::vector<DObj> in_scene_order = nonempty_meshes(F);
   top_level(in_scene_order, F);
   reserve_merged(d, in_scene_order, F);
-  lights_and_materials(d, F);
+  light_records(F, d.lights, d.n_lights);
+  material_records(F, d.materials, d.n_materials);
   for (const MeshGuard &g : F.guards) F.mesh_tris += g.tri_count;
   F.mesh_bytes = F.tris.size() * sizeof(DTri) + F.nodes.size() * sizeof(DNode) + F.nodes4.size() * sizeof(DNode4);
   F.ray_slots = ray_stack_slots(F);
@@ -482,6 +472,45 @@ std::vector<DirtyRange> mesh_updated(FlatScene &F, size_t gi, const float *box) 
   F.merged.reserved = F.merged.built = F.merged.usable = false;
   std::vector<ctr_triangle>().swap(F.merged.src);
   return dirty;
+}
+
+void light_records(FlatScene &F, const ctr_light *lights, uint64_t n) {
+  F.lights.resize(n);
+  for (uint64_t i = 0; i < n; i++) {
+    const ctr_light &l = lights[i];
+    F.lights[i] = DLight{l.type, l.v.x, l.v.y, l.v.z, l.color.x, l.color.y, l.color.z, 0.f};
+  }
+  shading_flags(F);
+}
+
+std::vector<DirtyRange> material_records(FlatScene &F, const ctr_material *mats, uint64_t n) {
+  F.mats.resize(n);
+  for (uint64_t i = 0; i < n; i++) {
+    const ctr_material &m = mats[i];
+    F.mats[i] = DMat{m.color.x, m.color.y, m.color.z, m.specular, m.reflexivity, m.phong_exp, m.transparency, 0.f};
+  }
+  shading_flags(F);
+  // material::is_transparent (default_schema.hpp:334: `transparency >= 1e-6`, a double comparison), ray_cast's
+  // ignore_transparent: the bit travels with every record of an object
+  bool changed = false;
+  auto bit_of = [&](uint32_t obj) { return ((double)F.mats[F.objs[obj].mat].transparency >= 1e-6) ? 1u : 0u; };
+  auto put = [&](uint32_t &word, uint32_t tr) { changed |= word != tr; word = tr; };
+  auto put_obj = [&](DObj &O) {
+    if (O.index >= F.objs.size()) return;  // (the merged pseudo mesh)
+    uint32_t word;
+    memcpy(&word, &O.f[7], sizeof(word));
+    put(word, bit_of(O.index));
+    memcpy(&O.f[7], &word, sizeof(word));
+  };
+  for (DObj &O : F.objs) put_obj(O);
+  for (DObj &O : F.oloop) put_obj(O);
+  for (DObj &O : F.meshes) put_obj(O);
+  for (DPlanePair &pr : F.planes)
+    for (int slot = 0; slot < 2; slot++)
+      if (pr.index[slot] != CTR_PLANE_PAD) put(pr.transparent[slot], bit_of(pr.index[slot]));
+  if (!changed) return {};
+  return {{DirtyRange::OBJS, 0, F.objs.size(), {}}, {DirtyRange::OLOOP, 0, F.oloop.size(), {}},
+          {DirtyRange::MESHES, 0, F.meshes.size(), {}}, {DirtyRange::PLANES, 0, F.planes.size(), {}}};
 }
 
 void fill_scene_counts(const FlatScene &F, DScene &D) {

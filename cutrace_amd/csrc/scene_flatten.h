@@ -57,7 +57,7 @@ struct Merged {
 
 // Records of a FlatScene array that a host-side edit changed: what the device copy has to receive, in this order.
 struct DirtyRange {
-  enum Array { OBJS, MESHES, TRIS, GNORM, NODES4, NODES } array;
+  enum Array { OBJS, MESHES, TRIS, GNORM, NODES4, NODES, OLOOP, PLANES } array;
   size_t begin, count;          // in records (GNORM: four floats per record)
   std::vector<DNode4> payload;  // not empty: the device gets THESE nodes, FlatScene::nodes4 keeps the real boxes (a linear mesh)
 };
@@ -122,6 +122,15 @@ std::vector<DirtyRange> build_merged_tree(FlatScene &F);
 // tree is retired for the life of the scene (its triangles are stale: no room reserved, nothing built, nothing usable).
 // Returns what the device has to receive.  ray_slots stays: no tree changed its shape.
 std::vector<DirtyRange> mesh_updated(FlatScene &F, size_t gi, const float *box);
+
+// The lights, or the materials, of a flattened scene replaced (flatten_scene itself, and ctr_scene_set_lights and
+// ctr_scene_set_materials of include/cutrace_edit.h): the records, and all_opaque, need_cold, any_bounce and fast_pow_ok derived
+// anew from both arrays.  The caller has checked what validate_desc checks: the types, and for materials that every object's
+// index stays below `n`.  material_records also sets the "material is transparent" bit of every record of an object (objs,
+// oloop, meshes, planes) and returns what the device has to receive of those, nothing when no bit changed.  Neither touches
+// the guard: a light is a probe and a reflecting material makes a mirror, so plan_guards / apply_guards (guard.h) follow.
+void light_records(FlatScene &F, const ctr_light *lights, uint64_t n);
+std::vector<DirtyRange> material_records(FlatScene &F, const ctr_material *mats, uint64_t n);
 
 // The counts and flags of a device scene record (scene_device.h DScene) from the host copy its arrays mirror; the ten pointers
 // stay as they are.  Called per launch and per query, so that it is right after build_merged_tree and every guard refresh.
