@@ -751,6 +751,50 @@ class DeviceScene:
             setattr(arr[idx], k, Vec3(*v) if k == "color" else v)
         self.set_materials(arr)
 
+    # ---- live objects (include/cutrace_objects.h) ----
+    # what set_object may change per object type, named as the scene JSON names it -> the field of _lib.Object
+    _OBJECT_FIELDS = {0: {"p1": "v0", "p2": "v1", "p3": "v2"}, 1: {}, 2: {"point": "v0", "normal": "v1"}, 3: {"center": "v0", "radius": "f0"}}
+
+    def set_objects(self, objects):
+        """Replace the parameters of the scene's objects (ctr_scene_set_objects): a sequence of _lib.Object, one per object of
+        the scene, each of the type it was created with.  A sphere's centre and radius, a plane's point and normal, a
+        stand-alone triangle's points and any object's material index may differ; a mesh keeps its triangles, tree and box.
+        Afterwards every render and query gives, bit for bit, what a scene created with these objects gives.  Synchronous.
+        Another count or type, a mesh with another triangle count or a material index out of range raise RuntimeError and
+        leave the scene as it was."""
+        arr = _records(Object, objects, "objects")
+        _check("ctr_scene_set_objects", _lib.hip_lib().ctr_scene_set_objects(self._h, arr, len(arr)))
+
+    def object_count(self):
+        """How many objects the scene has (ctr_scene_object_count)."""
+        n = C.c_uint64()
+        _check("ctr_scene_object_count", _lib.hip_lib().ctr_scene_object_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def get_object(self, i):
+        """Object `i` as a _lib.Object that set_objects takes back unchanged (ctr_scene_get_object): its type, current material
+        index and current parameters; a mesh with its current box in v0 / v1."""
+        o = Object()
+        _check("ctr_scene_get_object", _lib.hip_lib().ctr_scene_get_object(self._h, int(i), C.byref(o)))
+        return o
+
+    def set_object(self, i, **fields):
+        """Object `i` with the given fields replaced, every other object as it is: center, radius (a sphere), point, normal (a
+        plane), p1, p2, p3 (a stand-alone triangle), material (any object: an index into the scene's materials)."""
+        n = self.object_count()
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < n:
+            raise ValueError(f"bad object index {i!r}")
+        objs = [self.get_object(k) for k in range(n)]
+        own = self._OBJECT_FIELDS.get(int(objs[i].type), {})
+        for k, v in fields.items():
+            if k == "material":
+                objs[i].mat_idx = v
+            elif k in own:
+                setattr(objs[i], own[k], v if k == "radius" else Vec3(*v))
+            else:
+                raise TypeError(f"set_object: an object of type {int(objs[i].type)} has no field {k!r}")
+        self.set_objects(objs)
+
     def guard_state(self, obj):
         """Test hook (ctr_debug_guard_state): (file indices of mesh `obj`'s triangles in its guard records, ascending, as a
         list; whether the mesh is walked linearly)."""

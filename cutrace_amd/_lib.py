@@ -197,6 +197,11 @@ HIP_LATER_PROTOS = {
         "ctr_scene_material_count": ([_ptr, _P(_u64)], _int),
         "ctr_debug_guard_state": ([_ptr, _u32, _P(_u32), _u64, _P(_u64), _P(_int)], _int),
     },
+    "cutrace_objects.h": {
+        "ctr_scene_set_objects": ([_ptr, _P(Object), _u64], _int),
+        "ctr_scene_object_count": ([_ptr, _P(_u64)], _int),
+        "ctr_scene_get_object": ([_ptr, _u64, _P(Object)], _int),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -208,6 +213,7 @@ LENS_SYMBOLS = sorted(HIP_PROTOS["cutrace_lens.h"])
 IMAGES_SYMBOLS = list(HIP_PROTOS["cutrace_images.h"])
 UPDATE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_update.h"])
 EDIT_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_edit.h"])
+OBJECT_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_objects.h"])
 
 _host = None
 _hip = None

@@ -1,12 +1,14 @@
-// ctr_edit.cpp — include/cutrace_edit.h: ctr_scene_set_lights, ctr_scene_set_materials, the two counts and ctr_debug_guard_state.
-// No HIP kernels here: the records and flags are scene_flatten.cpp's (light_records, material_records: the text flatten_scene
-// runs), the guard is guard.cpp's, and its plane scan on the device is guard_scan.hip.
+// ctr_edit.cpp — include/cutrace_edit.h: ctr_scene_set_lights, ctr_scene_set_materials, the two counts and ctr_debug_guard_state;
+// include/cutrace_objects.h: ctr_scene_set_objects, ctr_scene_object_count, ctr_scene_get_object.
+// No HIP kernels here: the records and flags are scene_flatten.cpp's (light_records, material_records, objects_edited: the text
+// flatten_scene runs), the guard is guard.cpp's, and its plane scan on the device is guard_scan.hip.
 //
 // An edit in four steps:
 //   1. the arguments are checked as validate_desc checks a description; nothing of the handle has changed when the call fails here
 //   2. the device is waited for, and the device array gets room for the new count (reused when it fits)
-//   3. the host copy gets the records, the flags and — materials — the objects' transparency bits; the device receives them
-//   4. refresh_linear_meshes: the lights are probes of the guard, a reflecting material makes mirrors
+//   3. the host copy gets the records, the flags and — materials, objects — the objects' transparency bits; the device receives them
+//   4. refresh_linear_meshes: the lights are probes of the guard, a reflecting material makes mirrors, a flat object that
+//      reflects is one and moves the eyes' images with it
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -66,6 +68,39 @@ int ctr_scene_set_materials(ctr_scene *s, const ctr_material *mats, uint64_t n) 
   if (n) HIP_TRY(hipMemcpy(const_cast<DMat *>(s->dev.mats), F.mats.data(), n * sizeof(DMat), hipMemcpyHostToDevice));
   if (int st = upload_dirty(s, dirty)) return st;
   return refresh_linear_meshes(s, true);
+}
+
+int ctr_scene_set_objects(ctr_scene *s, const ctr_object *objects, uint64_t n) {
+  const std::string who = "ctr_scene_set_objects: ";
+  if (!s) return fail(CTR_E_INVALID, who + "null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  FlatScene &F = s->flat;
+  std::string err;
+  if (int st = check_objects(F, objects, n, err)) return fail(st, who + err);
+  if (int st = use_device(s)) return st;
+  HIP_TRY(hipDeviceSynchronize());
+  // (room for the most records ANY packing of these planes needs: the count after the edit is known only once the host copy has it)
+  if (int st = room_for((const void **)&s->dev.planes, &s->planes_cap, F.planes.size(), plane_records_at_most(F), sizeof(DPlanePair))) return st;
+  const std::vector<DirtyRange> dirty = objects_edited(F, objects, n);
+  // (a no-op while plane_records_at_most holds; the upload below can never be larger than the array whatever that function says)
+  if (int st = room_for((const void **)&s->dev.planes, &s->planes_cap, 0, F.planes.size(), sizeof(DPlanePair))) return st;
+  if (int st = upload_dirty(s, dirty)) return st;
+  return refresh_linear_meshes(s, true);
+}
+
+int ctr_scene_object_count(const ctr_scene *s, uint64_t *n) {
+  if (!s || !n) return fail(CTR_E_INVALID, "ctr_scene_object_count: null argument");
+  std::lock_guard<std::mutex> lk(const_cast<ctr_scene *>(s)->mtx);
+  *n = s->flat.objs.size();
+  return CTR_OK;
+}
+
+int ctr_scene_get_object(const ctr_scene *s, uint64_t index, ctr_object *out) {
+  if (!s || !out) return fail(CTR_E_INVALID, "ctr_scene_get_object: null argument");
+  std::lock_guard<std::mutex> lk(const_cast<ctr_scene *>(s)->mtx);
+  if (index >= s->flat.objs.size()) return fail(CTR_E_INVALID, "ctr_scene_get_object: object #" + std::to_string(index) + " out of range");
+  *out = object_of(s->flat, index);
+  return CTR_OK;
 }
 
 int ctr_scene_light_count(const ctr_scene *s, uint64_t *n) {

@@ -139,6 +139,7 @@ struct ctr_scene {
   // edits of the lights and materials (include/cutrace_edit.h, ctr_edit.cpp): records the device arrays have room for
   // (0: as ctr_scene_create allocated them, the count they were created with)
   size_t lights_cap = 0, mats_cap = 0;
+  size_t planes_cap = 0;  // the same of the plane records (ctr_scene_set_objects: an edit can re-pack the planes into more records)
   // the guard's plane scan on the device (guard_scan.h, refresh_linear_meshes): everything is allocated at the first scan there
   GrowBuf scan_planes{7 * sizeof(double)};         // all meshes' planes, FlatScene::guards order
   bool scan_planes_live = false;                   // ... are on the device and current (false: the next scan uploads them all)

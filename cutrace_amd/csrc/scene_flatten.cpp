@@ -101,6 +101,31 @@ void mesh_record(const ctr_object &o, const ctr_triangle *src, const MeshTree &t
   }
 }
 
+// The analytic half of one object's records (flatten_scene through object_records, and objects_edited): the material index of
+// any object; a sphere's, a plane's or a stand-alone triangle's parameters in its DObj; the triangle's DTri and normal at
+// O.tri_begin, which the caller has set.  A mesh's triangles, tree and box are not touched here.
+void analytic_record(const ctr_object &o, DObj &O, FlatScene &F) {
+  O.mat = (uint32_t)o.mat_idx;
+  switch (O.type) {
+    case CTR_OBJ_TRIANGLE:
+      make_tri(o.v0, o.v1, o.v2, 0, F.tris[O.tri_begin], &F.gn[4 * (size_t)O.tri_begin]);
+      O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;  // p1, p3: triangle::uv_for (KV_UV)
+      O.f[3] = o.v2.x; O.f[4] = o.v2.y; O.f[5] = o.v2.z;
+      break;
+    case CTR_OBJ_MESH:
+      break;
+    case CTR_OBJ_PLANE:  // (a plane's point and normal)
+      O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;
+      O.f[3] = o.v1.x; O.f[4] = o.v1.y; O.f[5] = o.v1.z;
+      break;
+    default:
+      O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;
+      O.f[3] = o.f0;
+      O.f[4] = o.f0 * o.f0;
+      break;
+  }
+}
+
 // objs: one record per object, scene order; meshes and stand-alone triangles add their DTri records as they come
 int object_records(const ctr_scene_desc &d, const std::vector<MeshTree> &trees, FlatScene &F, std::string &err) {
   F.objs.resize(d.n_objects);
@@ -110,37 +135,23 @@ int object_records(const ctr_scene_desc &d, const std::vector<MeshTree> &trees, 
     DObj &O = F.objs[i];
     memset(&O, 0, sizeof(O));
     O.type = o.type;
-    O.mat = (uint32_t)o.mat_idx;
     O.index = (uint32_t)i;
-    switch (o.type) {
-      case CTR_OBJ_TRIANGLE: {
-        O.tri_begin = (uint32_t)F.tris.size();
-        O.tri_count = 1;
-        F.tris.emplace_back();
-        F.gn.resize(4 * F.tris.size());
-        make_tri(o.v0, o.v1, o.v2, 0, F.tris.back(), &F.gn[4 * (F.tris.size() - 1)]);
-        O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;  // p1, p3: triangle::uv_for (KV_UV)
-        O.f[3] = o.v2.x; O.f[4] = o.v2.y; O.f[5] = o.v2.z;
-        break;
+    if (o.type == CTR_OBJ_TRIANGLE) {
+      O.tri_begin = (uint32_t)F.tris.size();
+      O.tri_count = 1;
+      F.tris.emplace_back();
+      F.gn.resize(4 * F.tris.size());
+    } else if (o.type == CTR_OBJ_MESH) {
+      F.has_mesh = true;
+      if (o.tri_count > 0xFFFFFFull) {
+        err = "object #" + std::to_string(i) + ": mesh has more than 2^24 triangles";
+        return CTR_E_INVALID;
       }
-      case CTR_OBJ_MESH:
-        F.has_mesh = true;
-        if (o.tri_count > 0xFFFFFFull) {
-          err = "object #" + std::to_string(i) + ": mesh has more than 2^24 triangles";
-          return CTR_E_INVALID;
-        }
-        mesh_record(o, d.triangles + o.tri_begin, trees[i], O, F);
-        [[fallthrough]];
-      case CTR_OBJ_PLANE:  // (a plane's point and normal, a mesh's box)
-        O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;
-        O.f[3] = o.v1.x; O.f[4] = o.v1.y; O.f[5] = o.v1.z;
-        break;
-      default:
-        O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;
-        O.f[3] = o.f0;
-        O.f[4] = o.f0 * o.f0;
-        break;
+      mesh_record(o, d.triangles + o.tri_begin, trees[i], O, F);
+      O.f[0] = o.v0.x; O.f[1] = o.v0.y; O.f[2] = o.v0.z;  // the mesh's box
+      O.f[3] = o.v1.x; O.f[4] = o.v1.y; O.f[5] = o.v1.z;
     }
+    analytic_record(o, O, F);
   }
   return CTR_OK;
 }
@@ -148,6 +159,8 @@ int object_records(const ctr_scene_desc &d, const std::vector<MeshTree> &trees, 
 // planes: two per record, the axis-aligned ones first and in whole triples (scene_device.h DPlanePair); oloop: what is
 // neither a plane nor a mesh
 void plane_records(FlatScene &F) {
+  F.oloop.clear();
+  F.planes.clear();
   std::vector<const DObj *> axis_planes[3], general_planes;
   for (const DObj &O : F.objs) {
     if (O.type == CTR_OBJ_PLANE) {
@@ -483,15 +496,11 @@ void light_records(FlatScene &F, const ctr_light *lights, uint64_t n) {
   shading_flags(F);
 }
 
-std::vector<DirtyRange> material_records(FlatScene &F, const ctr_material *mats, uint64_t n) {
-  F.mats.resize(n);
-  for (uint64_t i = 0; i < n; i++) {
-    const ctr_material &m = mats[i];
-    F.mats[i] = DMat{m.color.x, m.color.y, m.color.z, m.specular, m.reflexivity, m.phong_exp, m.transparency, 0.f};
-  }
-  shading_flags(F);
-  // material::is_transparent (default_schema.hpp:334: `transparency >= 1e-6`, a double comparison), ray_cast's
-  // ignore_transparent: the bit travels with every record of an object
+namespace {
+// material::is_transparent (default_schema.hpp:334: `transparency >= 1e-6`, a double comparison), ray_cast's
+// ignore_transparent: the bit travels with every record of an object.  Returns what the device has to receive, nothing when
+// no bit changed.
+std::vector<DirtyRange> transparency_bits(FlatScene &F) {
   bool changed = false;
   auto bit_of = [&](uint32_t obj) { return ((double)F.mats[F.objs[obj].mat].transparency >= 1e-6) ? 1u : 0u; };
   auto put = [&](uint32_t &word, uint32_t tr) { changed |= word != tr; word = tr; };
@@ -511,6 +520,94 @@ std::vector<DirtyRange> material_records(FlatScene &F, const ctr_material *mats,
   if (!changed) return {};
   return {{DirtyRange::OBJS, 0, F.objs.size(), {}}, {DirtyRange::OLOOP, 0, F.oloop.size(), {}},
           {DirtyRange::MESHES, 0, F.meshes.size(), {}}, {DirtyRange::PLANES, 0, F.planes.size(), {}}};
+}
+}  // namespace
+
+std::vector<DirtyRange> material_records(FlatScene &F, const ctr_material *mats, uint64_t n) {
+  F.mats.resize(n);
+  for (uint64_t i = 0; i < n; i++) {
+    const ctr_material &m = mats[i];
+    F.mats[i] = DMat{m.color.x, m.color.y, m.color.z, m.specular, m.reflexivity, m.phong_exp, m.transparency, 0.f};
+  }
+  shading_flags(F);
+  return transparency_bits(F);
+}
+
+int check_objects(const FlatScene &F, const ctr_object *objects, uint64_t n, std::string &err) {
+  auto bad = [&](const std::string &msg) { err = msg; return CTR_E_INVALID; };
+  if (!objects && n) return bad("null argument");
+  if (n != F.objs.size()) return bad(std::to_string(n) + " objects for a scene of " + std::to_string(F.objs.size()) + ": the count is fixed");
+  for (uint64_t i = 0; i < n; i++) {
+    const ctr_object &o = objects[i];
+    const DObj &O = F.objs[i];
+    const std::string who = "object #" + std::to_string(i) + ": ";
+    if (o.type > CTR_OBJ_SPHERE) return bad(who + "bad type");
+    if (o.type != O.type) return bad(who + "type " + std::to_string(o.type) + " for an object of type " + std::to_string(O.type) + ": the type is fixed");
+    if (o.type == CTR_OBJ_MESH && o.tri_count != O.tri_count)
+      return bad(who + std::to_string(o.tri_count) + " triangles for a mesh of " + std::to_string(O.tri_count) + ": the count is fixed");
+    if (o.mat_idx >= F.mats.size()) return bad(who + "material index out of range");
+  }
+  return CTR_OK;
+}
+
+std::vector<DirtyRange> objects_edited(FlatScene &F, const ctr_object *objects, uint64_t n) {
+  std::vector<DirtyRange> dirty;
+  for (uint64_t i = 0; i < n; i++) {
+    DObj &O = F.objs[i];
+    analytic_record(objects[i], O, F);
+    if (O.type == CTR_OBJ_TRIANGLE) {
+      dirty.push_back({DirtyRange::TRIS, O.tri_begin, 1, {}});
+      dirty.push_back({DirtyRange::GNORM, O.tri_begin, 1, {}});
+    }
+    // a mesh's material, wherever a record of the mesh is kept (top-level leaf order, and scene order behind the merged pseudo mesh)
+    if (O.type == CTR_OBJ_MESH)
+      for (DObj &M : F.meshes)
+        if (M.index == O.index) M.mat = O.mat;
+  }
+  plane_records(F);  // oloop: copies of the edited records; planes: which records exist, their order and their number
+  transparency_bits(F);
+  dirty.push_back({DirtyRange::OBJS, 0, F.objs.size(), {}});
+  dirty.push_back({DirtyRange::OLOOP, 0, F.oloop.size(), {}});
+  dirty.push_back({DirtyRange::MESHES, 0, F.meshes.size(), {}});
+  dirty.push_back({DirtyRange::PLANES, 0, F.planes.size(), {}});
+  return dirty;
+}
+
+ctr_object object_of(const FlatScene &F, size_t i) {
+  const DObj &O = F.objs[i];
+  ctr_object o{};
+  o.type = O.type;
+  o.mat_idx = O.mat;
+  o.v0 = ctr_vec3{O.f[0], O.f[1], O.f[2]};
+  switch (O.type) {
+    case CTR_OBJ_TRIANGLE: {
+      const DTri &T = F.tris[O.tri_begin];
+      o.v1 = ctr_vec3{T.px, T.py, T.pz};
+      o.v2 = ctr_vec3{O.f[3], O.f[4], O.f[5]};
+      break;
+    }
+    case CTR_OBJ_MESH:
+      o.tri_count = O.tri_count;
+      [[fallthrough]];
+    case CTR_OBJ_PLANE:
+      o.v1 = ctr_vec3{O.f[3], O.f[4], O.f[5]};
+      break;
+    default:
+      o.f0 = O.f[3];
+      break;
+  }
+  return o;
+}
+
+size_t plane_records_at_most(const FlatScene &F) {
+  size_t n = 0;
+  for (const DObj &O : F.objs) n += O.type == CTR_OBJ_PLANE;
+  // `a` planes on the busiest axis cost 3 * ceil(a / 2) records (planes on the other two axes ride in the same triples), the
+  // n - a general ones ceil((n - a) / 2); fewer than three axis-aligned planes: general pairs only.  Not monotonic in `a`: four
+  // planes need 7 records with three on one axis beside a general one, 6 with all four on it.
+  size_t most = (n + 1) / 2;
+  for (size_t a = 3; a <= n; a++) most = std::max(most, 3 * ((a + 1) / 2) + (n - a + 1) / 2);
+  return most;
 }
 
 void fill_scene_counts(const FlatScene &F, DScene &D) {

@@ -132,6 +132,28 @@ std::vector<DirtyRange> mesh_updated(FlatScene &F, size_t gi, const float *box);
 void light_records(FlatScene &F, const ctr_light *lights, uint64_t n);
 std::vector<DirtyRange> material_records(FlatScene &F, const ctr_material *mats, uint64_t n);
 
+// The parameters of a flattened scene's objects replaced (ctr_scene_set_objects of include/cutrace_objects.h); topology is fixed.
+// check_objects: what validate_desc checks of an object, and that nothing but parameters differs — `n` is the scene's count,
+// every type is the object's own, a mesh keeps its triangle count, every material index is below the scene's material count.
+// CTR_OK, or CTR_E_INVALID and the message in `err`; F is not written.
+// objects_edited, for objects that passed: a sphere's centre and radius, a plane's point and normal, a stand-alone triangle's
+// three points (its DObj, its DTri and its normal at the tri_begin it has) and every object's material index through the text
+// flatten_scene runs; a mesh's material into its `meshes` records as well, its triangles, tree and box staying what they are
+// (tri_begin, v0 and v1 of a mesh are ignored); then, again with flatten_scene's text, oloop rebuilt (same count), planes and
+// n_axis_recs re-packed — a plane that becomes or stops being axis-aligned changes which records exist, their order and their
+// NUMBER, at most plane_records_at_most(F) — and the "material is transparent" bit of every record of an object.  Nothing else
+// holds an analytic object's parameter or a material index (scripts/object_edit_check.cpp compares every array with
+// flatten_scene of the edited description).  Returns what the device has to receive.  Does not touch the guard: a flat object
+// that moves, or gains or loses a reflecting material, moves the eyes' images, so plan_guards / apply_guards (guard.h) follow.
+// object_of: object `i` as a ctr_object that objects_edited would take back unchanged — a mesh with its CURRENT box in v0 / v1
+// (after mesh_updated: the refitted one), its tri_count, and tri_begin 0.
+int check_objects(const FlatScene &F, const ctr_object *objects, uint64_t n, std::string &err);
+std::vector<DirtyRange> objects_edited(FlatScene &F, const ctr_object *objects, uint64_t n);
+ctr_object object_of(const FlatScene &F, size_t i);
+// the most plane records any edit of the scene's planes can need: the maximum, over how many of them share the busiest axis, of
+// that axis's triples plus the general pairs of the rest (for an even count >= 4 one more than every plane on one axis)
+size_t plane_records_at_most(const FlatScene &F);
+
 // The counts and flags of a device scene record (scene_device.h DScene) from the host copy its arrays mirror; the ten pointers
 // stay as they are.  Called per launch and per query, so that it is right after build_merged_tree and every guard refresh.
 __attribute__((visibility("hidden"))) void fill_scene_counts(const FlatScene &F, DScene &D);

@@ -19,6 +19,9 @@
  * them.  A HIP graph captured on the handle BEFORE an edit must be captured again: kernel arguments carry the counts and the
  * flags by value, and an edit may have moved an array.
  * Not for ctr_multi groups.  CTR_ABI_VERSION is unchanged: the calls are additions.
+ *
+ * Live objects — a sphere, a plane or a stand-alone triangle moved, any object given another material — are the third edit
+ * of this header: cutrace_objects.h, included below, declares them under the same contract.
  */
 #ifndef CUTRACE_EDIT_H
 #define CUTRACE_EDIT_H
@@ -26,6 +29,7 @@
 #include <stdint.h>
 
 #include "cutrace_amd.h"
+#include "cutrace_objects.h"
 
 #ifdef __cplusplus
 extern "C" {
