@@ -697,8 +697,33 @@ class DeviceScene:
         `stream` (a torch.cuda.Stream; default: torch's current stream of the scene's device), after whatever produced the
         tensor there; the call returns when the handle is consistent again.  A wrong count, an object that is not a mesh
         or a vertex that is not finite raise RuntimeError and leave the scene as it was."""
-        import torch
         dev = self._torch_device()
+        triangles, ptr = self._mesh_triangles(triangles, dev)
+        with _on_stream(dev, stream) as raw:
+            _check("ctr_scene_update_mesh", _lib.hip_lib().ctr_scene_update_mesh(self._h, int(obj), C.c_void_p(ptr or None),
+                                                                                 int(triangles.shape[0]), raw))
+
+    def rebuild_mesh(self, obj, triangles, builder="device", stream=None):
+        """update_mesh plus a NEW tree for the mesh (ctr_scene_rebuild_mesh, include/cutrace_rebuild.h): for vertices the old
+        tree's shape no longer fits — a fold, a long twist, a cloth.  builder="device": a linear BVH built on the GPU;
+        "host": the binned-SAH builder a new scene gets.  The same inputs, stream and errors as update_mesh, the same
+        results bit for bit as a scene created with these triangles; only the frame time depends on the builder.  Returns
+        what was built: builder (0 device, 1 host), fell_back (1: the device's tree was refused by the host's checks and the
+        host built instead), node_count, levels, moved (1: the tree lives in a new range of the node array)."""
+        if builder not in ("device", "host"):
+            raise ValueError(f"builder: expected 'device' or 'host', got {builder!r}")
+        dev = self._torch_device()
+        triangles, ptr = self._mesh_triangles(triangles, dev)
+        info = _lib.RebuildInfo()
+        with _on_stream(dev, stream) as raw:
+            _check("ctr_scene_rebuild_mesh", _lib.hip_lib().ctr_scene_rebuild_mesh(
+                self._h, int(obj), C.c_void_p(ptr or None), int(triangles.shape[0]), _lib.REBUILD_HOST if builder == "host" else 0, C.byref(info), raw))
+        return {k: int(getattr(info, k)) for k in ("builder", "fell_back", "node_count", "levels", "moved")}
+
+    @staticmethod
+    def _mesh_triangles(triangles, dev):
+        """update_mesh's and rebuild_mesh's input, checked: (the array or tensor to keep alive, its address)"""
+        import torch
         if isinstance(triangles, torch.Tensor):
             if triangles.device != dev:
                 raise ValueError(f"triangles: tensor on {triangles.device}, the scene lives on {dev}")
@@ -712,9 +737,7 @@ class DeviceScene:
             raise TypeError(f"triangles: expected a torch tensor or a numpy array, got {type(triangles).__name__}")
         if not dtype_ok or len(triangles.shape) != 3 or tuple(triangles.shape[1:]) != (3, 3):
             raise ValueError(f"triangles: expected float32 of shape (n, 3, 3), got {triangles.dtype} {tuple(triangles.shape)}")
-        with _on_stream(dev, stream) as raw:
-            _check("ctr_scene_update_mesh", _lib.hip_lib().ctr_scene_update_mesh(self._h, int(obj), C.c_void_p(ptr or None),
-                                                                                 int(triangles.shape[0]), raw))
+        return triangles, ptr
 
     def mesh_box(self, obj):
         """The current box of mesh `obj` as the kernels use it (ctr_scene_mesh_box): (min, max), two float32 arrays of 3."""

@@ -65,6 +65,12 @@ class RenderStats(C.Structure):
                 ("rows", C.c_uint64), ("max_depth", C.c_float), ("reserved", C.c_uint32)]
 
 
+class RebuildInfo(C.Structure):
+    """ctr_rebuild_info (include/cutrace_rebuild.h)"""
+    _fields_ = [("builder", C.c_uint32), ("fell_back", C.c_uint32), ("node_count", C.c_uint32), ("levels", C.c_uint32),
+                ("moved", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 class RayQuery(C.Structure):
     """ctr_ray_query (include/cutrace_rays.h)"""
     _fields_ = [("n_rays", C.c_uint64), ("flags", C.c_uint32), ("min_t", C.c_float), ("max_t", C.c_float),
@@ -202,6 +208,9 @@ HIP_LATER_PROTOS = {
         "ctr_scene_object_count": ([_ptr, _P(_u64)], _int),
         "ctr_scene_get_object": ([_ptr, _u64, _P(Object)], _int),
     },
+    "cutrace_rebuild.h": {
+        "ctr_scene_rebuild_mesh": ([_ptr, _u32, _ptr, _u64, _u32, _P(RebuildInfo), _ptr], _int),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -214,6 +223,8 @@ IMAGES_SYMBOLS = list(HIP_PROTOS["cutrace_images.h"])
 UPDATE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_update.h"])
 EDIT_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_edit.h"])
 OBJECT_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_objects.h"])
+REBUILD_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_rebuild.h"])
+REBUILD_HOST = 1   # CTR_REBUILD_HOST
 
 _host = None
 _hip = None

@@ -16,6 +16,7 @@
 
 #include "cutrace_amd.h"
 #include "guard_scan.h"
+#include "lbvh.h"
 #include "mesh_refit.h"
 #include "scene_device.h"
 #include "scene_flatten.h"
@@ -136,6 +137,15 @@ struct ctr_scene {
   GrowBuf upd_planes{7 * sizeof(double)};          // the guard's plane records as update_tris writes them
   GrowBuf upd_words{sizeof(uint32_t)};             // [0] the finiteness flag, [2..7] the mesh box
   GrowBuf upd_back{1, true};                       // page-locked landing zone of the copy-back, bytes
+  // mesh rebuilds (include/cutrace_rebuild.h, ctr_update.cpp): the device builder's scratch (mesh_build.h), allocated at the first
+  // rebuild; nothing of the scene lives in them
+  GrowBuf rb_keys{sizeof(uint64_t)};               // 2 n: Morton keys, unsorted then sorted
+  GrowBuf rb_index{sizeof(uint32_t)};              // 2 n: file indices, unsorted then sorted; afterwards [0, n) the accepted leaf order
+  GrowBuf rb_temp{1};                              // the sort's temporary storage, bytes
+  GrowBuf rb_bin{sizeof(LbvhNode)};                // the binary radix tree
+  GrowBuf rb_nodes{sizeof(DNode4)};                // the collapsed descriptors, indexed by binary node
+  GrowBuf rb_words{sizeof(float)};                 // [0..5] the centroid bounds, then the per-block partials
+  size_t nodes4_cap = 0;  // DNode4 records dev.nodes4 has room for (0: as ctr_scene_create allocated it); a moved mesh makes it grow
   // edits of the lights and materials (include/cutrace_edit.h, ctr_edit.cpp): records the device arrays have room for
   // (0: as ctr_scene_create allocated them, the count they were created with)
   size_t lights_cap = 0, mats_cap = 0;

@@ -1,5 +1,6 @@
-// ctr_update.cpp — the host half of include/cutrace_update.h: ctr_scene_update_mesh and ctr_scene_mesh_box.  No HIP kernels here:
-// the device half is mesh_update.hip, the arithmetic both sides share is tri_record.h and mesh_refit.h.
+// ctr_update.cpp — the host half of include/cutrace_update.h (ctr_scene_update_mesh, ctr_scene_mesh_box) and of
+// include/cutrace_rebuild.h (ctr_scene_rebuild_mesh).  No HIP kernels here: the device halves are mesh_update.hip and
+// mesh_build.hip, the arithmetic both sides share is tri_record.h, mesh_refit.h and lbvh.h.
 //
 // An update in five steps:
 //   1. arguments and vertices are checked; nothing of the handle has changed when the call fails here
@@ -11,6 +12,15 @@
 //      guard state reset, the merged tree retired
 //   5. upload_dirty and refresh_linear_meshes, the machinery ctr_scene_set_cameras ends with; the guard's plane scan runs on the
 //      device when it is large enough (guard_scan.h), over the planes step 2 left there
+//
+// A rebuild is an update with three steps between 1 and 2:
+//   1a. a tree SHAPE over the new vertices: the device's linear BVH (mesh_build.hip, into scratch buffers of the handle, its
+//       descriptors and sorted indices copied back) or the host's bvh4_build
+//   1b. the host accepts the device's tree (lbvh.h lbvh_accept) or builds one itself; the new level schedule, the room the
+//       tree needs in the device's node array and every buffer of steps 2 .. 5 are allocated.  Still nothing has changed
+//   1c. mesh_rebuilt (scene_flatten.cpp) installs the shape in the host copy; the device receives the descriptors and the
+//       records' new `orig`
+// and steps 2 .. 5 run with the NEW schedule.
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
@@ -22,7 +32,9 @@
 #include <string>
 
 #include "ctr_internal.h"
+#include "cutrace_rebuild.h"
 #include "cutrace_update.h"
+#include "mesh_build.h"
 #include "mesh_refit.h"
 #include "mesh_update.h"
 
@@ -44,99 +56,150 @@ Where where_is(const void *p, size_t bytes, int device) {
 
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-// the mesh's level schedule, on the host and on the device, from the host copy of its tree: once per mesh
+// the level schedule of a tree, on the host and on the device
+int refit_of_tree(const DNode4 *nodes, uint32_t node_count, uint32_t tri_count, const std::string &who, std::unique_ptr<MeshRefit> &out) {
+  auto r = std::make_unique<MeshRefit>();
+  if (!level_schedule(nodes, node_count, tri_count, r->sched)) return fail(CTR_E_INVALID, who + "the mesh's tree is not one the refit can walk");
+  if (int st = r->d_nodes.reserve(r->sched.nodes.size())) return st;
+  HIP_TRY(hipMemcpy(r->d_nodes.p, r->sched.nodes.data(), r->sched.nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  out = std::move(r);
+  return CTR_OK;
+}
+
+// the mesh's level schedule from the host copy of its tree: once per mesh and tree
 int mesh_refit_of(ctr_scene *s, size_t gi, MeshRefit **out) {
   if (s->refit.size() < s->flat.guards.size()) s->refit.resize(s->flat.guards.size());
   if (!s->refit[gi]) {
     const FlatScene &F = s->flat;
     const MeshGuard &g = F.guards[gi];
-    auto r = std::make_unique<MeshRefit>();
-    bool ok = level_schedule(&F.nodes4[g.node_begin], g.node_count, g.tri_count, r->sched);
     // (the kernels index the caller's vertices by a record's `orig`: it must name a triangle of the mesh)
+    bool ok = true;
     for (uint32_t k = 0; ok && k < g.tri_count; k++) ok = F.tris[g.tri_begin + k].orig < g.tri_count;
     if (!ok) return fail(CTR_E_INVALID, "ctr_scene_update_mesh: the mesh's tree is not one the refit can walk");
-    if (int st = r->d_nodes.reserve(r->sched.nodes.size())) return st;
-    HIP_TRY(hipMemcpy(r->d_nodes.p, r->sched.nodes.data(), r->sched.nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    s->refit[gi] = std::move(r);
+    if (int st = refit_of_tree(&F.nodes4[g.node_begin], g.node_count, g.tri_count, "ctr_scene_update_mesh: ", s->refit[gi])) return st;
   }
   *out = s->refit[gi].get();
   return CTR_OK;
 }
 
-// CUTRACE_DEBUG_UPDATE=1: where ctr_scene_update_mesh spends its time (stderr), the time since the previous stamp; the device
-// kernels then get a wait of their own, so that their time is not counted as the copy-back's (scripts/gpu_mesh_update.py)
+// CUTRACE_DEBUG_UPDATE=1: where ctr_scene_update_mesh and ctr_scene_rebuild_mesh spend their time (stderr), the time since the
+// previous stamp; the device kernels then get a wait of their own, so that their time is not counted as the copy-back's
+// (scripts/gpu_mesh_update.py, scripts/gpu_mesh_rebuild.py)
 struct Stamps {
+  const char *call;
   const bool on = getenv("CUTRACE_DEBUG_UPDATE") != nullptr;
   std::chrono::high_resolution_clock::time_point t0 = std::chrono::high_resolution_clock::now();
+  explicit Stamps(const char *call_name) : call(call_name) {}
   void operator()(const char *what) {
     if (!on) return;
     const auto now = std::chrono::high_resolution_clock::now();
-    fprintf(stderr, "cutrace_amd update_mesh: %-24s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t0).count());
+    fprintf(stderr, "cutrace_amd %s: %-24s %8.3f ms\n", call, what, std::chrono::duration<double, std::milli>(now - t0).count());
     t0 = now;
   }
 };
 
-}  // namespace
+// where the parts of the copy-back land in ctr_scene::upd_back, for a mesh of `n` triangles and `node_count` nodes
+struct BackLayout {
+  size_t tris, gn, nodes, planes, box, flag, end;
+  BackLayout(uint32_t n, uint32_t node_count) {
+    tris = 0;
+    gn = tris + align16(n * sizeof(DTri));
+    nodes = gn + align16(n * 4 * sizeof(float));
+    planes = nodes + align16(node_count * sizeof(DNode4));
+    box = planes + align16(n * CTR_PLANE_DOUBLES * sizeof(double));
+    flag = box + 32;
+    end = flag + 16;
+  }
+};
 
-extern "C" {
+// What the two calls share once the arguments are known to name a mesh of the handle
+struct MeshCall {
+  ctr_scene *s;
+  std::string who;
+  size_t gi = 0;
+  uint32_t n = 0;
+  const ctr_triangle *tris = nullptr;
+  Where where = Where::HOST;
+  hipStream_t stream = nullptr;
+  const float *d_verts = nullptr;  // the vertices on the device: the caller's, or upd_verts once upload_verts has run
+  bool uploaded = false;
+  Stamps stamp;
+  MeshCall(ctr_scene *scene, const char *name) : s(scene), who(std::string(name) + ": "), stamp(name + 10 /* past "ctr_scene_" */) {}
+};
 
-int ctr_scene_update_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream) {
-  const std::string who = "ctr_scene_update_mesh: ";
-  if (!s || !tris) return fail(CTR_E_INVALID, who + "null argument");
-  std::lock_guard<std::mutex> lk(s->mtx);
-  FlatScene &F = s->flat;
+// ---- 1. the arguments: `object` is a non-empty mesh of n_tris triangles (the caller holds the handle's lock) ----
+int mesh_arguments(MeshCall &c, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream) {
+  const FlatScene &F = c.s->flat;
   if (object >= F.objs.size() || F.objs[object].type != CTR_OBJ_MESH)
-    return fail(CTR_E_INVALID, who + "object #" + std::to_string(object) + " is not a mesh");
-  if (F.objs[object].tri_count == 0) return fail(CTR_E_INVALID, who + "object #" + std::to_string(object) + " is an empty mesh");
+    return fail(CTR_E_INVALID, c.who + "object #" + std::to_string(object) + " is not a mesh");
+  if (F.objs[object].tri_count == 0) return fail(CTR_E_INVALID, c.who + "object #" + std::to_string(object) + " is an empty mesh");
   if (n_tris != F.objs[object].tri_count)
-    return fail(CTR_E_INVALID, who + std::to_string(n_tris) + " triangles for a mesh of " + std::to_string(F.objs[object].tri_count) +
+    return fail(CTR_E_INVALID, c.who + std::to_string(n_tris) + " triangles for a mesh of " + std::to_string(F.objs[object].tri_count) +
                                    ": the count is fixed");
   size_t gi = 0;
   while (gi < F.guards.size() && F.guards[gi].obj_index != object) gi++;
-  if (gi == F.guards.size() || F.guards[gi].mesh_pos < 0) return fail(CTR_E_INVALID, who + "the mesh has no records");
-  const uint32_t n = (uint32_t)n_tris;
-  const uint32_t tri_begin = F.guards[gi].tri_begin, node_begin = F.guards[gi].node_begin, node_count = F.guards[gi].node_count;
+  if (gi == F.guards.size() || F.guards[gi].mesh_pos < 0) return fail(CTR_E_INVALID, c.who + "the mesh has no records");
+  c.gi = gi;
+  c.n = (uint32_t)n_tris;
+  c.tris = tris;
+  c.stream = (hipStream_t)hip_stream;
+  if (int st = use_device(c.s)) return st;
+  c.where = where_is(tris, c.n * sizeof(ctr_triangle), c.s->device);
+  if (c.where == Where::ELSEWHERE) return fail(CTR_E_INVALID, c.who + "tris is neither host memory nor device memory of the scene's device");
+  return CTR_OK;
+}
 
-  Stamps stamp;
-  if (int st = use_device(s)) return st;
-  const Where where = where_is(tris, n * sizeof(ctr_triangle), s->device);
-  if (where == Where::ELSEWHERE) return fail(CTR_E_INVALID, who + "tris is neither host memory nor device memory of the scene's device");
-  hipStream_t stream = (hipStream_t)hip_stream;
-
-  // ---- 1. the vertices must be finite; buffers (nothing of the scene changes yet) ----
-  MeshRefit *refit = nullptr;
-  if (int st = mesh_refit_of(s, gi, &refit)) return st;
-  const size_t b_tris = 0, b_gn = b_tris + align16(n * sizeof(DTri)), b_nodes = b_gn + align16(n * 4 * sizeof(float)),
-               b_planes = b_nodes + align16(node_count * sizeof(DNode4)), b_box = b_planes + align16(n * CTR_PLANE_DOUBLES * sizeof(double)),
-               b_flag = b_box + 32, b_end = b_flag + 16;
-  if (int st = s->upd_back.reserve(b_end)) return st;
+// ---- 1. the vertices must be finite; the buffers of steps 2 and 3 for a tree of up to `node_count` nodes (nothing of the scene changes) ----
+int vertices_and_buffers(MeshCall &c, uint32_t node_count) {
+  ctr_scene *s = c.s;
+  const uint32_t n = c.n;
+  const BackLayout b(n, node_count);
+  if (int st = s->upd_back.reserve(b.end)) return st;
   if (int st = s->upd_planes.reserve(n)) return st;
   if (int st = s->upd_words.reserve(8)) return st;
   char *back = s->upd_back.as<char>();
   uint32_t *d_flag = s->upd_words.as<uint32_t>();
-  float *d_box = s->upd_words.as<float>() + 2;
-  const float *d_verts = (const float *)tris;
-  if (where == Where::HOST) {
-    const float *v = (const float *)tris;
+  c.d_verts = (const float *)c.tris;
+  if (c.where == Where::HOST) {
+    const float *v = (const float *)c.tris;
     for (size_t i = 0; i < 9 * (size_t)n; i++)
-      if (!std::isfinite(v[i])) return fail(CTR_E_INVALID, who + "triangle " + std::to_string(i / 9) + " has a vertex that is not finite");
+      if (!std::isfinite(v[i])) return fail(CTR_E_INVALID, c.who + "triangle " + std::to_string(i / 9) + " has a vertex that is not finite");
     if (int st = s->upd_verts.reserve(n)) return st;
-    d_verts = s->upd_verts.as<float>();
+    c.d_verts = s->upd_verts.as<float>();
   } else {
     // a small kernel of its own, its one flag word read back before anything is modified
-    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), stream));
-    if (int st = launched(ctr_launch_all_finite(d_verts, 9 * (uint64_t)n, d_flag, stream), "finiteness check launch")) return st;
-    HIP_TRY(hipMemcpyAsync(back + b_flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), c.stream));
+    if (int st = launched(ctr_launch_all_finite(c.d_verts, 9 * (uint64_t)n, d_flag, c.stream), "finiteness check launch")) return st;
+    HIP_TRY(hipMemcpyAsync(back + b.flag, d_flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
     uint32_t flag;
-    memcpy(&flag, back + b_flag, sizeof(flag));
-    if (flag) return fail(CTR_E_INVALID, who + "a vertex is not finite");
+    memcpy(&flag, back + b.flag, sizeof(flag));
+    if (flag) return fail(CTR_E_INVALID, c.who + "a vertex is not finite");
   }
+  return CTR_OK;
+}
 
-  // ---- 2. the device side, on the caller's stream ----
-  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old records (as ctr_scene_set_cameras does)
-  stamp("checks");
-  if (where == Where::HOST) HIP_TRY(hipMemcpyAsync(s->upd_verts.p, tris, n * sizeof(ctr_triangle), hipMemcpyHostToDevice, stream));
+// a host input's vertices go to the device, on the caller's stream (once per call; upd_verts is scratch, not scene)
+int upload_verts(MeshCall &c) {
+  if (c.where == Where::HOST && !c.uploaded)
+    HIP_TRY(hipMemcpyAsync(c.s->upd_verts.p, c.tris, c.n * sizeof(ctr_triangle), hipMemcpyHostToDevice, c.stream));
+  c.uploaded = true;
+  return CTR_OK;
+}
+
+// ---- 2. .. 5.: the device side on the caller's stream, the copy-back, everything derived, the guard ----
+int update_steps(MeshCall &c, const MeshRefit *refit) {
+  ctr_scene *s = c.s;
+  FlatScene &F = s->flat;
+  const uint32_t n = c.n;
+  const uint32_t tri_begin = F.guards[c.gi].tri_begin, node_begin = F.guards[c.gi].node_begin, node_count = F.guards[c.gi].node_count;
+  const BackLayout b(n, node_count);
+  char *back = s->upd_back.as<char>();
+  float *d_box = s->upd_words.as<float>() + 2;
+  const float *d_verts = c.d_verts;
+  hipStream_t stream = c.stream;
+  Stamps &stamp = c.stamp;
+  if (int st = upload_verts(c)) return st;
   DTri *d_recs = const_cast<DTri *>(s->dev.tris) + tri_begin;
   float *d_gn = const_cast<float *>(s->dev.gnorm) + 4 * (size_t)tri_begin;
   DNode4 *d_nodes = (DNode4 *)const_cast<void *>(s->dev.nodes4) + node_begin;  // (the mesh's spare node and guard records are not the kernels' business)
@@ -153,29 +216,172 @@ int ctr_scene_update_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tri
   stamp("upload + device kernels");
 
   // ---- 3. back into the host copy: one wait ----
-  HIP_TRY(hipMemcpyAsync(back + b_tris, d_recs, n * sizeof(DTri), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(back + b_gn, d_gn, n * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(back + b_nodes, d_nodes, node_count * sizeof(DNode4), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(back + b_planes, d_planes, n * CTR_PLANE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipMemcpyAsync(back + b_box, d_box, 6 * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(back + b.tris, d_recs, n * sizeof(DTri), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(back + b.gn, d_gn, n * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(back + b.nodes, d_nodes, node_count * sizeof(DNode4), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(back + b.planes, d_planes, n * CTR_PLANE_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(back + b.box, d_box, 6 * sizeof(float), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  MeshGuard &g = F.guards[gi];
-  memcpy(&F.tris[tri_begin], back + b_tris, n * sizeof(DTri));
-  memcpy(&F.gn[4 * (size_t)tri_begin], back + b_gn, n * 4 * sizeof(float));
-  memcpy(&F.nodes4[node_begin], back + b_nodes, node_count * sizeof(DNode4));
-  memcpy(g.planes.data(), back + b_planes, n * CTR_PLANE_DOUBLES * sizeof(double));
+  MeshGuard &g = F.guards[c.gi];
+  memcpy(&F.tris[tri_begin], back + b.tris, n * sizeof(DTri));
+  memcpy(&F.gn[4 * (size_t)tri_begin], back + b.gn, n * 4 * sizeof(float));
+  memcpy(&F.nodes4[node_begin], back + b.nodes, node_count * sizeof(DNode4));
+  memcpy(g.planes.data(), back + b.planes, n * CTR_PLANE_DOUBLES * sizeof(double));
   float box[6];
-  memcpy(box, back + b_box, sizeof(box));
+  memcpy(box, back + b.box, sizeof(box));
   stamp("copy-back");
 
   // ---- 4., 5. everything derived from them, then the guard ----
-  if (int st = upload_dirty(s, mesh_updated(F, gi, box))) return st;
+  if (int st = upload_dirty(s, mesh_updated(F, c.gi, box))) return st;
   stamp("host records + upload");
   // (the new planes are on the device already, in upd_planes, and the stream has been waited for: the scan takes them from there)
-  if (int st = guard_planes_changed(s, gi, d_planes)) return st;
+  if (int st = guard_planes_changed(s, c.gi, d_planes)) return st;
   const int st = refresh_linear_meshes(s, true);
   stamp("guard");
   return st;
+}
+
+// ---- 1a. the device builder: a tree shape over c.d_verts into scratch, its descriptors and sorted indices back on the host ----
+// sparse: max(n - 1, 1) descriptors indexed by binary node; order: n file indices.  Waits for the stream.
+int device_shape(MeshCall &c, std::vector<DNode4> &sparse, std::vector<uint32_t> &order) {
+  ctr_scene *s = c.s;
+  const uint32_t n = c.n, n_sparse = n > 1 ? n - 1 : 1;
+  size_t temp_bytes = 0;
+  if (int st = launched(ctr_lbvh_sort_temp_bytes(n, &temp_bytes), "radix sort size query")) return st;
+  if (int st = s->rb_keys.reserve(2 * (size_t)n)) return st;
+  if (int st = s->rb_index.reserve(2 * (size_t)n)) return st;
+  if (int st = s->rb_temp.reserve(temp_bytes ? temp_bytes : 16)) return st;
+  if (int st = s->rb_bin.reserve(n_sparse)) return st;
+  if (int st = s->rb_nodes.reserve(n_sparse)) return st;
+  if (int st = s->rb_words.reserve(8 + ctr_lbvh_partial_floats(n))) return st;
+  const size_t b_nodes = 0, b_order = align16(n_sparse * sizeof(DNode4)), b_end = b_order + align16(n * sizeof(uint32_t));
+  if (int st = s->upd_back.reserve(b_end)) return st;
+  hipStream_t stream = c.stream;
+  uint64_t *keys = s->rb_keys.as<uint64_t>(), *keys_sorted = keys + n;
+  uint32_t *index = s->rb_index.as<uint32_t>(), *index_sorted = index + n;
+  float *bounds = s->rb_words.as<float>();
+  if (int st = upload_verts(c)) return st;
+  if (int st = launched(ctr_launch_lbvh_bounds(c.d_verts, n, bounds + 8, bounds, stream), "centroid bounds launch")) return st;
+  if (int st = launched(ctr_launch_lbvh_keys(c.d_verts, n, bounds, keys, index, stream), "morton keys launch")) return st;
+  if (int st = launched(ctr_lbvh_sort(s->rb_temp.p, temp_bytes, keys, keys_sorted, index, index_sorted, n, stream), "radix sort")) return st;
+  if (c.stamp.on) HIP_TRY(hipStreamSynchronize(stream));
+  c.stamp("sort");
+  if (int st = launched(ctr_launch_lbvh_tree(keys_sorted, n, s->rb_bin.as<LbvhNode>(), stream), "radix tree launch")) return st;
+  if (int st = launched(ctr_launch_lbvh_collapse(s->rb_bin.as<LbvhNode>(), keys_sorted, n, BVH_LEAF, s->rb_nodes.as<DNode4>(), stream), "collapse launch")) return st;
+  if (c.stamp.on) HIP_TRY(hipStreamSynchronize(stream));
+  c.stamp("tree + collapse");
+  char *back = s->upd_back.as<char>();
+  HIP_TRY(hipMemcpyAsync(back + b_nodes, s->rb_nodes.p, n_sparse * sizeof(DNode4), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(back + b_order, index_sorted, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  sparse.resize(n_sparse);
+  order.resize(n);
+  memcpy(sparse.data(), back + b_nodes, n_sparse * sizeof(DNode4));
+  memcpy(order.data(), back + b_order, n * sizeof(uint32_t));
+  c.stamp("shape copy-back");
+  return CTR_OK;
+}
+
+// the device's node array gets room for `records` DNode4 (+ the 256 spare bytes ctr_scene_create gives every array): a new
+// allocation that receives the old one's contents — the DEVICE's, which for a linear mesh are not the host copy's.  The caller
+// has waited for the device.
+int nodes4_room(ctr_scene *s, size_t have, size_t records) {
+  if (s->nodes4_cap == 0) s->nodes4_cap = have;
+  if (records <= s->nodes4_cap) return CTR_OK;
+  void *p = nullptr;
+  HIP_TRY(hipMalloc(&p, records * sizeof(DNode4) + 256));
+  const hipError_t e = have ? hipMemcpy(p, s->dev.nodes4, have * sizeof(DNode4), hipMemcpyDeviceToDevice) : hipSuccess;
+  if (e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "node array copy"); }
+  if (s->dev.nodes4) (void)hipFree(const_cast<void *>(s->dev.nodes4));
+  s->dev.nodes4 = p;
+  s->nodes4_cap = records;
+  return CTR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ctr_scene_update_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream) {
+  if (!s || !tris) return fail(CTR_E_INVALID, "ctr_scene_update_mesh: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  MeshCall c(s, "ctr_scene_update_mesh");
+  if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream)) return st;
+  MeshRefit *refit = nullptr;
+  if (int st = mesh_refit_of(s, c.gi, &refit)) return st;
+  if (int st = vertices_and_buffers(c, s->flat.guards[c.gi].node_count)) return st;
+  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old records (as ctr_scene_set_cameras does)
+  c.stamp("checks");
+  return update_steps(c, refit);
+}
+
+int ctr_scene_rebuild_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, uint32_t flags, ctr_rebuild_info *info,
+                           void *hip_stream) {
+  const std::string who = "ctr_scene_rebuild_mesh: ";
+  if (flags & ~CTR_REBUILD_HOST) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(flags & ~CTR_REBUILD_HOST));
+  if (!s || !tris) return fail(CTR_E_INVALID, who + "null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  MeshCall c(s, "ctr_scene_rebuild_mesh");
+  if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream)) return st;
+  FlatScene &F = s->flat;
+  const uint32_t n = c.n;
+  if (int st = vertices_and_buffers(c, n)) return st;  // (a four-wide tree over n triangles has at most n nodes)
+  c.stamp("checks");
+
+  // ---- 1a., 1b. a tree: the device's, accepted; or the host's ----
+  ctr_rebuild_info built{};
+  MeshTree tree;
+  if (!(flags & CTR_REBUILD_HOST)) {
+    std::vector<DNode4> sparse;
+    if (int st = device_shape(c, sparse, tree.order)) return st;
+    if (!lbvh_accept(sparse.data(), (uint32_t)sparse.size(), tree.order.data(), n, BVH_LEAF, tree.nodes)) built.fell_back = 1;
+    c.stamp("host accept");
+  }
+  if ((flags & CTR_REBUILD_HOST) || built.fell_back) {
+    built.builder = 1;
+    std::vector<ctr_triangle> from_device;
+    const ctr_triangle *host_tris = tris;
+    if (c.where == Where::DEVICE) {  // (the finiteness check has waited for whatever produced them)
+      from_device.resize(n);
+      HIP_TRY(hipMemcpy(from_device.data(), tris, n * sizeof(ctr_triangle), hipMemcpyDeviceToHost));
+      host_tris = from_device.data();
+    }
+    tree = host_mesh_tree(host_tris, n);
+    c.stamp("host build");
+  }
+  bool ok = tree.order.size() == n && !tree.nodes.empty();
+  for (uint32_t k = 0; ok && k < n; k++) ok = tree.order[k] < n;
+  if (!ok) return fail(CTR_E_INVALID, who + "the builder's tree is not one the refit can walk");
+  const uint32_t count = (uint32_t)tree.nodes.size();
+  std::unique_ptr<MeshRefit> refit;
+  if (int st = refit_of_tree(tree.nodes.data(), count, n, who, refit)) return st;
+  const bool moves = count > F.guards[c.gi].node_cap;
+  const size_t nodes4_after = F.nodes4.size() + (moves ? (size_t)count + 1u : 0u);
+  if (int st = s->upd_back.reserve(BackLayout(n, count).end)) return st;
+  if (int st = s->rb_index.reserve(n)) return st;
+  if (s->refit.size() < F.guards.size()) s->refit.resize(F.guards.size());
+  F.nodes4.reserve(nodes4_after);
+  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old records, or the node array when it moves
+  if (int st = nodes4_room(s, F.nodes4.size(), nodes4_after)) return st;  // (same contents in another place: the last step that can fail for want of memory)
+
+  // ---- 1c. the shape goes in: host copy, then the device's descriptors and the records' `orig` ----
+  bool moved = false;
+  const std::vector<DirtyRange> dirty = mesh_rebuilt(F, c.gi, tree, &moved);
+  s->refit[c.gi] = std::move(refit);
+  if (int st = upload_dirty(s, dirty)) return st;
+  HIP_TRY(hipMemcpyAsync(s->rb_index.p, tree.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+  if (int st = launched(ctr_launch_set_orig(const_cast<DTri *>(s->dev.tris) + F.guards[c.gi].tri_begin, s->rb_index.as<uint32_t>(), n, c.stream), "set_orig launch"))
+    return st;
+  if (c.stamp.on) HIP_TRY(hipStreamSynchronize(c.stream));
+  c.stamp("install");
+
+  // ---- 2. .. 5. the update's steps, with the new schedule ----
+  if (int st = update_steps(c, s->refit[c.gi].get())) return st;
+  built.node_count = count;
+  built.levels = (uint32_t)s->refit[c.gi]->sched.levels();
+  built.moved = moved ? 1u : 0u;
+  if (info) *info = built;
+  return CTR_OK;
 }
 
 int ctr_scene_mesh_box(const ctr_scene *s, uint32_t object, ctr_vec3 *bb_min, ctr_vec3 *bb_max) {

@@ -32,8 +32,6 @@ std::vector<BvhInput> tri_boxes(const ctr_triangle *src, size_t n) {
   return prims;
 }
 
-struct MeshTree { std::vector<DNode4> nodes; std::vector<uint32_t> order; };
-
 // The meshes' trees, several meshes at a time (a scene of 16 meshes of 1000 triangles: 2.5 -> 0.5 ms of ctr_scene_create; a
 // mesh large enough to matter is built on several threads by the builder itself).  One entry per object, empty for what is
 // not a mesh (or is one with too many triangles: mesh_record rejects it).
@@ -83,7 +81,7 @@ void mesh_record(const ctr_object &o, const ctr_triangle *src, const MeshTree &t
   memset(&F.nodes4.back(), 0, sizeof(DNode4));
   MeshGuard g;
   g.node_begin = O.node_begin;
-  g.node_count = O.node_count;
+  g.node_count = g.node_cap = O.node_count;
   g.tri_begin = O.tri_begin;
   g.tri_count = n;
   g.obj_index = O.index;
@@ -314,6 +312,8 @@ void shading_flags(FlatScene &F) {
   F.fast_pow_ok = fast_pow_in_bar(worst, lambda);
 }
 
+}  // namespace
+
 // FlatScene::ray_slots
 uint32_t ray_stack_slots(const FlatScene &F) {
   uint32_t deepest = 0;
@@ -332,8 +332,6 @@ uint32_t ray_stack_slots(const FlatScene &F) {
   }
   return 3u * (deepest + 1u);
 }
-
-}  // namespace
 
 DNode4 empty_node4() {
   DNode4 N;
@@ -484,6 +482,45 @@ std::vector<DirtyRange> mesh_updated(FlatScene &F, size_t gi, const float *box) 
   // kernel_facts: not usable, so CTR_VAR_MERGE takes the two-level walk)
   F.merged.reserved = F.merged.built = F.merged.usable = false;
   std::vector<ctr_triangle>().swap(F.merged.src);
+  return dirty;
+}
+
+MeshTree host_mesh_tree(const ctr_triangle *tris, size_t n, uint32_t leaf_size) {
+  MeshTree tree;
+  bvh4_build(tri_boxes(tris, n), leaf_size, tree.nodes, tree.order);
+  return tree;
+}
+
+std::vector<DirtyRange> mesh_rebuilt(FlatScene &F, size_t gi, const MeshTree &tree, bool *moved) {
+  MeshGuard &g = F.guards[gi];
+  const uint32_t count = (uint32_t)tree.nodes.size();
+  *moved = count > g.node_cap;
+  if (*moved) {  // a new range at the end: the tree's nodes and, right behind them, its spare node
+    g.node_begin = (uint32_t)F.nodes4.size();
+    g.node_cap = count;
+    F.nodes4.resize(F.nodes4.size() + count + 1u);
+  }
+  std::copy(tree.nodes.begin(), tree.nodes.end(), F.nodes4.begin() + g.node_begin);
+  memset(&F.nodes4[g.node_begin + count], 0, sizeof(DNode4));  // the spare node, unused = all zero (mesh_record)
+  for (uint32_t k = count + 1u; k <= g.node_cap; k++) F.nodes4[g.node_begin + k] = empty_node4();
+  g.node_count = count;
+  std::vector<DirtyRange> dirty{{DirtyRange::NODES4, g.node_begin, (size_t)g.node_cap + 1u, {}}};
+  // the range and the root, wherever a record of the mesh is kept (mesh_updated's list)
+  auto put = [&](DObj &O) { O.node_begin = g.node_begin; O.node_count = count; O.bvh_root = 0; };
+  put(F.objs[g.obj_index]);
+  dirty.push_back({DirtyRange::OBJS, g.obj_index, 1, {}});
+  if (g.mesh_pos >= 0) {
+    put(F.meshes[g.mesh_pos]);
+    dirty.push_back({DirtyRange::MESHES, (size_t)g.mesh_pos, 1, {}});
+  }
+  for (size_t k = F.n_mesh + 1; k < F.meshes.size(); k++)
+    if (F.meshes[k].index == g.obj_index) {
+      put(F.meshes[k]);
+      dirty.push_back({DirtyRange::MESHES, k, 1, {}});
+    }
+  for (uint32_t k = 0; k < g.tri_count; k++) F.tris[g.tri_begin + k].orig = tree.order[k];
+  F.mesh_bytes = F.tris.size() * sizeof(DTri) + F.nodes.size() * sizeof(DNode) + F.nodes4.size() * sizeof(DNode4);
+  F.ray_slots = ray_stack_slots(F);
   return dirty;
 }
 

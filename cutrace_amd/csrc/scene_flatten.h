@@ -25,6 +25,7 @@ constexpr uint32_t BVH_LEAF = CTR_BVH_LEAF;  // triangles per BVH leaf
 // Guard of the BVH culling (guard.h): what it needs to know of one mesh, and what it currently has on the device
 struct MeshGuard {
   uint32_t node_begin = 0, node_count = 0;
+  uint32_t node_cap = 0;  // tree nodes the mesh's range of nodes4 has room for (+ the spare node): the count it was created or moved with (mesh_rebuilt)
   uint32_t tri_begin = 0, tri_count = 0;  // the mesh's DTri range (leaf order); CTR_GUARD_SLOTS spare records follow it
   uint32_t obj_index = 0;                 // position in objs
   int mesh_pos = -1;                      // position in meshes (-1: an empty mesh, never walked)
@@ -91,7 +92,8 @@ struct FlatScene {
   // LDS stack entries per lane that the ray-query walk (ray_query.hip) can need: a node pushes at most three of its
   // children (the fourth is visited next), so the stack holds at most three entries per level above the current node.
   // The depth counts the inner nodes of the longest path of any mesh tree, plus the spare node in front of a guarded
-  // root.  The trees' SHAPES never change after flatten_scene (only boxes and guard leaves do).
+  // root.  A tree's SHAPE changes only in mesh_rebuilt, which computes this anew (ray_stack_slots); boxes and guard leaves do
+  // not count.  The query kernels size their LDS stacks from it per call.
   uint32_t ray_slots = 0;
 };
 
@@ -122,6 +124,26 @@ std::vector<DirtyRange> build_merged_tree(FlatScene &F);
 // tree is retired for the life of the scene (its triangles are stale: no room reserved, nothing built, nothing usable).
 // Returns what the device has to receive.  ray_slots stays: no tree changed its shape.
 std::vector<DirtyRange> mesh_updated(FlatScene &F, size_t gi, const float *box);
+
+// A mesh's tree as a builder hands it over: nodes (node 0 the root, child descriptors relative to it, a parent before its
+// children) and the leaf order, order[k] = the file index of the triangle at leaf position k.
+struct MeshTree { std::vector<DNode4> nodes; std::vector<uint32_t> order; };
+// the host's binned-SAH tree (bvh4_build) over `n` triangles, leaves of at most `leaf_size`: what flatten_scene builds per mesh
+MeshTree host_mesh_tree(const ctr_triangle *tris, size_t n, uint32_t leaf_size = BVH_LEAF);
+// FlatScene::ray_slots of the trees F holds now
+uint32_t ray_stack_slots(const FlatScene &F);
+
+// Another tree SHAPE for mesh guards[gi] (ctr_scene_rebuild_mesh, include/cutrace_rebuild.h): `tree` has passed level_schedule and
+// its order is a permutation of the mesh's triangles.  The mesh owns node_cap + 1 records of nodes4.  A tree that fits is
+// installed in place: its nodes, the spare node right behind the last of them (all zero, as mesh_record leaves it; apply_guards
+// fills it), and empty_node4() in what remains of the range.  A tree that does not fit gets a new range at the END of nodes4,
+// which grows by its nodes and its spare node (*moved = true; the old range is dead, nothing names it any more).  node_begin,
+// node_count and bvh_root = 0 go wherever a record of the mesh keeps them (objs, meshes, the scene-order copy behind the merged
+// pseudo mesh, the MeshGuard); the records' `orig` take the new leaf order; ray_slots and mesh_bytes are derived anew.
+// The nodes' BOXES are whatever `tree` holds and the triangle records are stale but for `orig`: the update's steps follow
+// (update_tris, refit_level with the NEW schedule, mesh_box, then mesh_updated, which also resets the guard state).
+// Returns what the device has to receive of this step: the mesh's node range and its records in objs and meshes.
+std::vector<DirtyRange> mesh_rebuilt(FlatScene &F, size_t gi, const MeshTree &tree, bool *moved);
 
 // The lights, or the materials, of a flattened scene replaced (flatten_scene itself, and ctr_scene_set_lights and
 // ctr_scene_set_materials of include/cutrace_edit.h): the records, and all_opaque, need_cold, any_bounce and fast_pow_ok derived

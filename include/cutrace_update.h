@@ -9,7 +9,7 @@
  * A walk's result is the smallest valid t, ties broken by the triangle's index in the file, whatever the tree looks like.
  * So an updated handle gives, bit for bit, what a freshly created one gives; only the time a walk takes depends on how well
  * the old tree still fits the moved triangles.  When it fits badly — a mesh folded through itself, not a rigid motion —
- * destroy and create remains the answer.
+ * ctr_scene_rebuild_mesh (cutrace_rebuild.h) gives the mesh a new tree on the same handle.
  *
  * Topology is fixed by contract: the triangle count and the file order of the triangles do not change.
  * Not for ctr_multi groups.  CTR_ABI_VERSION is unchanged: the calls are additions.
