@@ -463,6 +463,12 @@ class DeviceScene:
         _check("ctr_debug_last_kernel", _lib.hip_lib().ctr_debug_last_kernel(self._h, C.byref(kv)))
         return int(kv.value)
 
+    def last_shape(self):
+        """The launch shape of the handle's most recent launch (ctr_debug_last_shape): 0 general, 1 the one-mesh build."""
+        shape = C.c_uint32()
+        _check("ctr_debug_last_shape", _lib.hip_lib().ctr_debug_last_shape(self._h, C.byref(shape)))
+        return int(shape.value)
+
     @staticmethod
     def lane_stats(reset=True):
         """Live-lane statistics of the VAR_STATS launches since the last reset (ctr_debug_lane_stats), decoded."""

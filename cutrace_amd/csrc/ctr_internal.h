@@ -115,6 +115,7 @@ struct ctr_scene {
   std::vector<DCam> h_cams;   // host copy of d_cams: the eyes the guard checks (refresh_linear_meshes)
   uint32_t user_variant = CTR_VAR_AUTO;
   bool no_scene_head = false;  // CUTRACE_NO_SCENE_HEAD=1 when the handle was created: launches carry an empty scene head
+  bool no_shape_build = false; // CUTRACE_NO_SHAPE_BUILD=1 when the handle was created: every launch in shape KS_GENERAL (kernel_choice.h)
   // cached device outputs for the host-buffer form: ONE allocation of 7 floats per pixel, a call's buffers are its
   // consecutive parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
   GrowBuf out{7 * sizeof(float)};
@@ -127,6 +128,7 @@ struct ctr_scene {
   unsigned long long *d_counters = nullptr;
   unsigned long long *d_shards = nullptr;  // CTR_SHARDS x CTR_SHARD_WORDS, zero between launches
   uint32_t last_kernel = 0;        // the KV of the most recent launch (ctr_debug_last_kernel)
+  uint32_t last_shape = 0;         // its launch shape, KS_* of kernel_choice.h (ctr_debug_last_shape)
   // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling"; tile_order_policy.h, tile_order_host.cpp)
   OrderState order;
   GrowBuf d_cost{sizeof(uint32_t)}, d_order{sizeof(uint32_t)};  // order.cap tiles each

@@ -177,6 +177,7 @@ void set_root_and_head(const ctr_scene *s, RenderLaunch &L, bool merged) {
   // launch, because the top-level root is final only now, and so that no edit of the arrays (guard selection, merged
   // tree, cameras) can leave a stale one behind
   if (!s->no_scene_head) fill_scene_head(s->flat, L.scene.tlas_root, L.head);
+  L.no_shape = s->no_shape_build ? 1u : 0u;
 }
 
 // What the launch writes on the device: `spx` pixels per output buffer in the handle's `out`; for a direct launch (z: the
@@ -339,6 +340,7 @@ int render_device(ctr_scene *s, const RenderCall &c) {
     std::lock_guard<std::mutex> lk(s->mtx);
     if ((st = attach_order(s, L, big_mesh(s), false))) return st;
     s->last_kernel = L.variant;
+    s->last_shape = ctr_launch_shape(L);
   }
   return launched(ctr_launch_render(L, c.stream), "render kernel launch");
 }
@@ -377,6 +379,7 @@ int render_host(ctr_scene *s, const RenderCall &c) {
     L.uv = s->uv.as<float>();
   }
   set_root_and_head(s, L, choice.merged);
+  s->last_shape = ctr_launch_shape(L);
   if ((st = attach_order(s, L, big_mesh(s), c.count))) return st;
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, 16 * sizeof(unsigned long long), nullptr));
   HIP_TRY(hipEventRecord(s->ev0, nullptr));

@@ -268,6 +268,7 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   s->device = device;
   s->cam = to_dcam(d->cam);
   if (const char *e = getenv("CUTRACE_NO_SCENE_HEAD")) s->no_scene_head = atoi(e) != 0;  // A/B and tests: every record by pointer
+  if (const char *e = getenv("CUTRACE_NO_SHAPE_BUILD")) s->no_shape_build = atoi(e) != 0;  // A/B and tests: the general build of every launch
 
   hipError_t er = hipSuccess;
   for (const SceneArray &a : scene_arrays(s, F)) {
@@ -394,6 +395,13 @@ int ctr_debug_last_kernel(ctr_scene *s, uint32_t *kv) {
   if (!s || !kv) return fail(CTR_E_INVALID, "ctr_debug_last_kernel: null argument");
   std::lock_guard<std::mutex> lk(s->mtx);
   *kv = s->last_kernel;
+  return CTR_OK;
+}
+
+int ctr_debug_last_shape(ctr_scene *s, uint32_t *shape) {
+  if (!s || !shape) return fail(CTR_E_INVALID, "ctr_debug_last_shape: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  *shape = s->last_shape;
   return CTR_OK;
 }
 

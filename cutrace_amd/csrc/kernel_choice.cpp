@@ -1,5 +1,6 @@
 // kernel_choice.cpp — choose_kernel: from the caller's CTR_VAR_* bits, the scene's facts and the entry point to the one build
 // of CTR_RENDER_KERNELS (CTR_LENS_KERNELS for the lens entries) the launch gets, or to the reason why there is none (kernel_choice.h).
+// launch_shape: which launch shape of that build a launch gets, from two facts of its scene.
 #include "kernel_choice.h"
 
 #include "cutrace_amd.h"
@@ -42,4 +43,15 @@ KernelChoice choose_kernel(const KernelFacts &f) {
   // delivery by the kernel: for the variants the library picks by itself, not for the ablation builds
   const bool direct = f.entry == KE_HOST && f.deliverable && !merged && !(u & CTR_VAR_NO_DIRECT) && walk == SHIPPED && pow;
   return {walk | anyhit | pow | occ6 | merge | (direct ? KV_HOSTOUT : 0u), direct, merged, KR_NONE};
+}
+
+uint32_t launch_shape(uint32_t kv, uint32_t n_oloop, bool head_mesh) {
+  if (!head_mesh || n_oloop != 0u) return KS_GENERAL;
+  switch (kv) {
+#define X(k) case (k):
+    CTR_SHAPE_KERNELS(X)
+#undef X
+    return KS_ONE_MESH;
+    default: return KS_GENERAL;
+  }
 }

@@ -57,6 +57,24 @@
   X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS | KV_FASTPOW | KV_ANYHIT)  \
   X(KV_PREFILTER | KV_BVH | KV_RAYS | KV_SS | KV_FASTPOW | KV_ANYHIT | KV_OCC6)
 
+// The launch shape: a second template parameter of render_kernel<KV, SHAPE> beside the build, decided per LAUNCH from facts of the
+// scene the build does not depend on (launch_shape below).  It is not a KV bit: choose_kernel, KernelChoice::kv and
+// ctr_debug_last_kernel say what they said before there were shapes (ctr_debug_last_shape reads the shape back).
+//   KS_GENERAL  : any scene.
+//   KS_ONE_MESH : no sphere and no stand-alone triangle, and exactly one mesh whose record rides in the scene head
+//                 (scene_device.h DSceneHead::mesh): the object loop and the top-level walk are compiled out.  Only code that
+//                 such a scene never runs is removed, so every result has the same bits.
+enum : uint32_t { KS_GENERAL = 0u, KS_ONE_MESH = 1u };
+// The builds that exist in shape KS_ONE_MESH, a list of their own: the default variant (shipped walk, any-hit, fast pow), with
+// or without the 6-wave build, with or without host delivery.  Each is also in CTR_RENDER_KERNELS (its KS_GENERAL twin).
+#define CTR_SHAPE_KERNELS(X)                                                                                                   \
+  X(KV_PREFILTER | KV_BVH | KV_ANYHIT | KV_FASTPOW) X(KV_PREFILTER | KV_BVH | KV_ANYHIT | KV_FASTPOW | KV_OCC6)                \
+  X(KV_PREFILTER | KV_BVH | KV_ANYHIT | KV_FASTPOW | KV_HOSTOUT) X(KV_PREFILTER | KV_BVH | KV_ANYHIT | KV_FASTPOW | KV_HOSTOUT | KV_OCC6)
+// The shape of a launch of build `kv`: n_oloop = spheres and stand-alone triangles of the scene (DScene::n_oloop), head_mesh =
+// the launch's scene head carries the record of the scene's only mesh (render_kernel.hip launch).  KS_ONE_MESH for the builds
+// of CTR_SHAPE_KERNELS with n_oloop == 0 and head_mesh, KS_GENERAL for everything else.
+uint32_t launch_shape(uint32_t kv, uint32_t n_oloop, bool head_mesh);
+
 // The recursion stack of a launch: `frames` frames of `nf` floats per lane (render_kernel.hip KArgs::frames, ::nf).
 struct StackShape {
   uint32_t frames, nf;

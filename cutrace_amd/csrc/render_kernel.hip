@@ -336,7 +336,7 @@ constexpr uint32_t MSP_SHADOW = 0x80000000u, MSP_DONE = 0x40000000u;
 #define MSP_DEPTH(m) ((int)((m) & 0xFFFFu))
 enum { ACT_NONE = 0, ACT_LIGHT = 1, ACT_BOUNCE = 2, ACT_UNWIND = 3 };
 
-template <uint32_t KV>
+template <uint32_t KV, uint32_t SHAPE = KS_GENERAL>
 __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) void render_kernel(KArgs A, float *__restrict__ depth_out,
                                                             float *__restrict__ color_out,
                                                             float *__restrict__ normal_out,
@@ -370,6 +370,13 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   // cast loops anyway.
   constexpr bool RAYS = (KV & KV_RAYS) != 0;
   static_assert(!RAYS || !((KV & (KV_HOSTOUT | KV_STATS | KV_UV | KV_COUNT | KV_IGNTR | KV_MERGE)) != 0), "the lens render leaves through device buffers, three outputs, two-level walk");
+  // "Launch shape" (kernel_choice.h launch_shape): the scene has no sphere and no stand-alone triangle, and exactly one mesh,
+  // whose record is DSceneHead::mesh.  The object loop then runs zero times and the top-level walk consists of that one leaf:
+  // both are compiled out — their loop skeletons, the stack of the walk and the leaf's bookkeeping are scalar instructions every
+  // trip pays for, and the kernel runs at its instruction-issue limit.  Nothing a taken path computes changes.
+  constexpr bool ONE_MESH = SHAPE == KS_ONE_MESH;
+  static_assert(SHAPE == KS_GENERAL || SHAPE == KS_ONE_MESH, "launch shapes: kernel_choice.h");
+  static_assert(!ONE_MESH || (KV & ~(KV_OCC6 | KV_HOSTOUT)) == (KV_PREFILTER | KV_BVH | KV_ANYHIT | KV_FASTPOW), "KS_ONE_MESH: the builds of CTR_SHAPE_KERNELS");
   // wave-level work counters (STATS build only): [0] casts, [1] BVH nodes visited, [2] triangle
   // prefilters, [3] exact tests, [4] mesh entries (AABB ballot != 0), [5] sum of active lanes per cast,
   // and how many of the 64 lanes had a use for the wave-level work: [6] lanes whose ray meets one of the
@@ -570,7 +577,9 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
     const u32x8 hot = *(const CADDR u32x8 *)AK;  // KArgs' hot block
     const CADDR DPlanePair *const k_planes = (const CADDR DPlanePair *)(((uint64_t)hot[1] << 32) | hot[0]);
-    const uint32_t k_plane_recs = hot[2], k_axis_recs = hot[3], k_n_oloop = hot[4], k_mesh = hot[5], k_tlas_root = hot[6];
+    const uint32_t k_plane_recs = hot[2], k_axis_recs = hot[3], k_n_oloop = ONE_MESH ? 0u : hot[4], k_mesh = hot[5];
+    // (ONE_MESH: the top-level item is the leaf the scene head holds, whatever the argument says)
+    const uint32_t k_tlas_root = ONE_MESH ? (BVH_LEAF_FLAG | CTR_TL_HEAD_FLAG) : hot[6];
     const bool k_has_mesh = (hot[7] & 1u) != 0u;
     // the scene head's axis triple, requested with the hot block whether it is filled or not (hot[7] says; constant addresses)
     typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
@@ -865,7 +874,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     CTR_MARK(13);
     const mask_t st_shadow_entry = (STATS && ANYHIT) ? (alive_m & shadow_m) : 0ull;
     const mask_t st_recv_mesh = STATS ? BALLOT(recv_mesh) : 0ull;
-    if (k_mesh != 0u) {
+    if (ONE_MESH || k_mesh != 0u) {
       uint32_t t_pend = k_tlas_root;             // next top-level item: inner node or mesh leaf
       uint32_t t_stack_v = 0, t_sp = 0;        // wave-uniform stack in the lanes of one VGPR
       // ---- mesh::bound_intersects, default_schema.hpp:99-114, for the lanes in `lanes` -> the lanes that pass ----
@@ -924,7 +933,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         //  descent set-up — ~30 vector instructions per cast for nothing, found by the execution profile, scripts/dynamic_mix.py)
         if (t_pend == TL_NONE) break;
         // descend the top-level tree to the next mesh leaf
-        if (!(t_pend & BVH_LEAF_FLAG)) {
+        if (!ONE_MESH && !(t_pend & BVH_LEAF_FLAG)) {
           CTR_MARK(14);  // top-level descent set-up
           const mask_t lv_m = alive_m;
           const float t_lim = anyhit_cast ? light_dist : best;
@@ -989,11 +998,14 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         if (t_pend == TL_NONE) break;
         // (the leaf the scene head holds: its record lies at a constant address of the argument block — no `meshes` to fetch first)
         const CADDR DObj *o_rec;
-        if (t_pend & CTR_TL_HEAD_FLAG) o_rec = &AK->head.mesh;
+        if (ONE_MESH || (t_pend & CTR_TL_HEAD_FLAG)) o_rec = &AK->head.mesh;
         else o_rec = &AK->meshes[t_pend & 0xFFFFFFu];
         const CADDR DObj &O = *o_rec;
         // advance first, so that `continue` below moves on to the next mesh
-        if (t_sp != 0u) {
+        // (ONE_MESH: there is none — no stack, and the loop folds to its one pass)
+        if constexpr (ONE_MESH) {
+          t_pend = TL_NONE;
+        } else if (t_sp != 0u) {
           t_sp--;
           t_pend = (uint32_t)__builtin_amdgcn_readlane((int)t_stack_v, (int)t_sp);
         } else {
@@ -1991,6 +2003,11 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
 // One launch of `kernel` = render_kernel<kv> (ctr_launch_render): the launch's buffers are cross-checked against the build, then
 // up to three kernels go onto the stream — the first order of a new shape, the render, the fold of its counters and the
 // next order (tile_order.hip).
+// the scene head of the launch carries the record of the top-level walk's first leaf: the walk starts there without `meshes`
+bool launch_head_mesh(const RenderLaunch &L) {
+  return L.head.n_mesh == 1u && (L.scene.tlas_root & BVH_LEAF_FLAG) && L.scene.n_mesh != 0u;
+}
+
 int launch(const RenderLaunch &L, uint32_t kv, const void *kernel, hipStream_t stream) {
   KArgs A;
   const DScene &S = L.scene;
@@ -2000,7 +2017,7 @@ int launch(const RenderLaunch &L, uint32_t kv, const void *kernel, hipStream_t s
   A.n_mesh = S.n_mesh;
   // "Scene head": the flags ride in words of the hot block the trip head has anyway
   A.head = L.head;
-  const bool head_mesh = L.head.n_mesh == 1u && (S.tlas_root & BVH_LEAF_FLAG) && S.n_mesh != 0u;
+  const bool head_mesh = launch_head_mesh(L);
   const bool head_axis = L.head.n_axis_recs == 3u && S.n_axis_recs >= 3u && S.n_plane_recs >= 3u;
   A.tlas_root = S.tlas_root | (head_mesh ? CTR_TL_HEAD_FLAG : 0u);
   A.tlas_root2 = S.tlas_root_regular;
@@ -2144,6 +2161,14 @@ extern "C" int ctr_selftest_exact_math(uint64_t *n_mismatch) {
   return CTR_OK;
 }
 
+// The shape of the launch (kernel_choice.h launch_shape), from the facts that are final only here: the launch's scene head and
+// root.  A head-held leaf of a scene with ONE mesh is that mesh's (the merged pseudo mesh, the other head-held leaf, belongs to
+// KV_MERGE builds, which have no shape).
+uint32_t ctr_launch_shape(const RenderLaunch &L) {
+  if (L.no_shape) return KS_GENERAL;
+  return launch_shape(L.variant, L.scene.n_oloop, launch_head_mesh(L) && L.scene.n_mesh == 1u);
+}
+
 // L.variant is the build (kernel_choice.h choose_kernel decides; launch cross-checks the launch's buffers against it).  The
 // switch is what instantiates the kernels — and what makes a table entry listed twice a compile error.
 int ctr_launch_render(const RenderLaunch &L, void *stream) {
@@ -2154,6 +2179,15 @@ int ctr_launch_render(const RenderLaunch &L, void *stream) {
     CTR_LENS_KERNELS(X)
 #undef X
     default: return (int)hipErrorInvalidValue;
+  }
+  // the launch shape (kernel_choice.h): the same build, compiled for what this launch's scene cannot contain
+  if (ctr_launch_shape(L) == KS_ONE_MESH) {
+    switch (L.variant) {
+#define X(kv) case (kv): kernel = (const void *)render_kernel<(kv), KS_ONE_MESH>; break;
+      CTR_SHAPE_KERNELS(X)
+#undef X
+      default: return (int)hipErrorInvalidValue;
+    }
   }
   return launch(L, L.variant, kernel, (hipStream_t)stream);
 }

@@ -319,6 +319,11 @@ int ctr_debug_poison_next_order(ctr_scene *scene);
 /* Diagnostic: which build of the render kernel the handle's most recent launch was (0 before the first) — the library's
  * internal variant bits (KV_*, csrc/scene_device.h; the builds and who picks them: csrc/kernel_choice.h). */
 int ctr_debug_last_kernel(ctr_scene *scene, uint32_t *kv);
+/* Diagnostic: the launch shape of that launch (csrc/kernel_choice.h): 0 = the general build, 1 = the build for a scene of one
+ * mesh, planes and nothing else (no sphere, no stand-alone triangle), which the default variant's launches on such a scene
+ * get — the same results bit for bit.  CUTRACE_NO_SHAPE_BUILD=1 in the environment when a handle is created keeps that
+ * handle's launches in shape 0 (A/B timing, tests). */
+int ctr_debug_last_shape(ctr_scene *scene, uint32_t *shape);
 /* Diagnostic: what each 8x8 tile of the last launch cost (shader-clock ticks / 64; tile index = frame-major,
  * then row-major over the launch's tile grid).  n_tiles receives the count; out may be NULL. */
 int ctr_tile_costs(ctr_scene *scene, uint32_t *out, uint64_t capacity, uint64_t *n_tiles);

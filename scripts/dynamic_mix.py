@@ -9,16 +9,25 @@ priced with the issue costs scripts/valu_issue.hip measured (profiles/r02/valu_i
 Cross-checks against PMC passes of the shipped build (same scene): the VALU total against SQ_INSTS_VALU, the Q count
 against SQ_ACTIVE_INST_VALU - SQ_INSTS_VALU (a transcendental holds the pipe two quad-cycles), SALU against SQ_INSTS_SALU.
 
-usage: dynamic_mix.py <marks.s> <variant> <counts.json> [--pmc counters.json] [--out mix.json]"""
+usage: dynamic_mix.py <marks.s> <variant>[,<shape>] <counts.json> [--pmc counters.json] [--out mix.json]
+(<variant> alone: the general launch shape; "107,1": render_kernel<107u, 1u>, the one-mesh shape of kernel_choice.h)"""
 import json, re, sys
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.abspath(__file__)))
 from valu_mix import classify, F, H, Q
 
 
+def kernel_names(kv):
+    """the mangled names `kv` may stand for.  "107": render_kernel<107u> as it was when the kernel had one template parameter,
+    and render_kernel<107u, 0u> (the general launch shape); "107,1": render_kernel<107u, 1u> (kernel_choice.h KS_ONE_MESH)"""
+    build, _, shape = str(kv).partition(",")
+    pre = "_ZN12_GLOBAL__N_113render_kernelILj%sE" % build
+    return (pre + "Lj%sEEE" % shape,) if shape else (pre + "EE", pre + "Lj0EEE")
+
+
 def kernel_body(path, kv):
-    name = "_ZN12_GLOBAL__N_113render_kernelILj%sEEE" % kv
+    names = kernel_names(kv)
     lines = open(path).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.startswith(name) and ":" in l)
+    start = next(i for i, l in enumerate(lines) if l.startswith(names) and ":" in l)
     end = next(i for i in range(start, len(lines)) if lines[i].startswith("; Occupancy"))
     return lines[start:end]
 
