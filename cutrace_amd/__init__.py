@@ -469,6 +469,14 @@ class DeviceScene:
         _check("ctr_debug_last_shape", _lib.hip_lib().ctr_debug_last_shape(self._h, C.byref(shape)))
         return int(shape.value)
 
+    def room_facts(self):
+        """The room facts of the handle's most recent launch (ctr_debug_room_facts): all zero, or what lets any-hit shadow trips
+        from inside a plane room skip their plane tests."""
+        out = np.zeros(5, np.float32)
+        lights = C.c_uint32()
+        _check("ctr_debug_room_facts", _lib.hip_lib().ctr_debug_room_facts(self._h, out.ctypes.data, C.byref(lights)))
+        return {"c": out[:3].copy(), "r": float(out[3]), "delta": float(out[4]), "lights": int(lights.value)}
+
     @staticmethod
     def lane_stats(reset=True):
         """Live-lane statistics of the VAR_STATS launches since the last reset (ctr_debug_lane_stats), decoded."""
@@ -482,7 +490,8 @@ class DeviceScene:
                "trips_by_live_lanes_1_8_to_57_64": c[64:72], "trips_mixing_kinds": c[76], "waves": c[74],
                "merged_walks": c[78], "merged_walks_redone": c[77],
                "shadow_casts_at_meshes": {"wave_casts": c[80], "receivers_all_off_mesh": c[81], "of_those_unoccluded_by_meshes": c[82],
-                                          "unoccluded_by_meshes_any_receiver": c[83]}}
+                                          "unoccluded_by_meshes_any_receiver": c[83]},
+               "anyhit_shadow_trips": c[88], "anyhit_shadow_trips_without_planes": c[89]}
         kinds = {}
         for d in range(16):
             for name, base in (("radiance", 0), ("shadow", 16)):

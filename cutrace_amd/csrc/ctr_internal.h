@@ -116,6 +116,8 @@ struct ctr_scene {
   uint32_t user_variant = CTR_VAR_AUTO;
   bool no_scene_head = false;  // CUTRACE_NO_SCENE_HEAD=1 when the handle was created: launches carry an empty scene head
   bool no_shape_build = false; // CUTRACE_NO_SHAPE_BUILD=1 when the handle was created: every launch in shape KS_GENERAL (kernel_choice.h)
+  bool no_wall_skip = false;   // CUTRACE_NO_WALL_SKIP=1 when the handle was created: every launch carries zero room facts (scene_device.h)
+  struct RoomWords { float c[3], r, delta; uint32_t lights; } last_room{};  // the room facts of the most recent launch (ctr_debug_room_facts)
   // cached device outputs for the host-buffer form: ONE allocation of 7 floats per pixel, a call's buffers are its
   // consecutive parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
   GrowBuf out{7 * sizeof(float)};

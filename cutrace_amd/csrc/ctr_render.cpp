@@ -178,6 +178,14 @@ void set_root_and_head(const ctr_scene *s, RenderLaunch &L, bool merged) {
   // tree, cameras) can leave a stale one behind
   if (!s->no_scene_head) fill_scene_head(s->flat, L.scene.tlas_root, L.head);
   L.no_shape = s->no_shape_build ? 1u : 0u;
+  // the room facts only where the launch's kernel reads them (render_kernel.hip "room-safe lanes"): the one-mesh shape of the
+  // any-hit builds, which then runs with the code that uses them, and the any-hit statistics builds; zero for every other launch
+  if ((L.variant & KV_ANYHIT) && (ctr_launch_shape(L) == KS_ONE_MESH || (L.variant & KV_STATS))) fill_room_facts(s->flat, L.head, s->no_wall_skip);
+}
+
+// the launch's room facts as the handle keeps them for ctr_debug_room_facts (written under the handle's mutex, like last_kernel)
+ctr_scene::RoomWords room_words(const RenderLaunch &L) {
+  return {{L.head.room_c[0], L.head.room_c[1], L.head.room_c[2]}, L.head.room_r, L.head.room_delta, L.head.room_lights};
 }
 
 // What the launch writes on the device: `spx` pixels per output buffer in the handle's `out`; for a direct launch (z: the
@@ -341,6 +349,7 @@ int render_device(ctr_scene *s, const RenderCall &c) {
     if ((st = attach_order(s, L, big_mesh(s), false))) return st;
     s->last_kernel = L.variant;
     s->last_shape = ctr_launch_shape(L);
+    s->last_room = room_words(L);
   }
   return launched(ctr_launch_render(L, c.stream), "render kernel launch");
 }
@@ -380,6 +389,7 @@ int render_host(ctr_scene *s, const RenderCall &c) {
   }
   set_root_and_head(s, L, choice.merged);
   s->last_shape = ctr_launch_shape(L);
+  s->last_room = room_words(L);
   if ((st = attach_order(s, L, big_mesh(s), c.count))) return st;
   HIP_TRY(hipMemsetAsync(s->d_counters, 0, 16 * sizeof(unsigned long long), nullptr));
   HIP_TRY(hipEventRecord(s->ev0, nullptr));

@@ -269,6 +269,7 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   s->cam = to_dcam(d->cam);
   if (const char *e = getenv("CUTRACE_NO_SCENE_HEAD")) s->no_scene_head = atoi(e) != 0;  // A/B and tests: every record by pointer
   if (const char *e = getenv("CUTRACE_NO_SHAPE_BUILD")) s->no_shape_build = atoi(e) != 0;  // A/B and tests: the general build of every launch
+  s->no_wall_skip = wall_skip_switched_off();  // CUTRACE_NO_WALL_SKIP=1: A/B and tests: no shadow trip skips its plane tests
 
   hipError_t er = hipSuccess;
   for (const SceneArray &a : scene_arrays(s, F)) {
@@ -402,6 +403,16 @@ int ctr_debug_last_shape(ctr_scene *s, uint32_t *shape) {
   if (!s || !shape) return fail(CTR_E_INVALID, "ctr_debug_last_shape: null argument");
   std::lock_guard<std::mutex> lk(s->mtx);
   *shape = s->last_shape;
+  return CTR_OK;
+}
+
+int ctr_debug_room_facts(ctr_scene *s, float *out5, uint32_t *lights) {
+  if (!s || !out5 || !lights) return fail(CTR_E_INVALID, "ctr_debug_room_facts: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  for (int q = 0; q < 3; q++) out5[q] = s->last_room.c[q];
+  out5[3] = s->last_room.r;
+  out5[4] = s->last_room.delta;
+  *lights = s->last_room.lights;
   return CTR_OK;
 }
 

@@ -106,6 +106,8 @@ __device__ unsigned int g_prof[128];  // executions of the CTR_MARK segments, su
 //        map could skip (built, measured and removed in round 4: those are the cheap casts, profiles/r04/exp_occluder_map.txt) —, [83] those of [80] in which no lane met an occluder in the mesh phase, whatever the receivers
 //   [77] casts the merged walk handed back to the two-level walk (a mesh's AABB test failed for a lane the walk had decided,
 //        or a mesh's nearest valid t equalled min_t), [78] casts that went through the merged walk
+//   [88] any-hit shadow trips (trips with a live shadow lane, any-hit builds), [89] those that skipped their plane tests
+//        ("room-safe lanes" in the kernel)
 __device__ unsigned long long g_lane_stats[96];
 
 // ---- execution profile of the source's straight-line segments (scripts/dynamic_mix.py) ----
@@ -330,13 +332,18 @@ static_assert(sizeof(KArgs) % 64 == 0 && offsetof(KArgs, head) % 64 == 0 && offs
 // through the cast loops): low 16 bits = stack depth; bit 31 = a shadow-loop cast, bit 30 = the pixel is finished,
 // neither = a radiance cast.  Every test is a single compare.
 constexpr uint32_t MSP_SHADOW = 0x80000000u, MSP_DONE = 0x40000000u;
+// Room-safe lanes (any-hit builds; DSceneHead::room_*, DESIGN.md "Shadow casts from inside a plane room"): bit 29 says that the
+// hit point the lane's shadow rays start from passed the lane predicate of the launch's room facts — set once per shaded hit,
+// kept through `msp |= MSP_SHADOW` from light to light, gone wherever msp is rebuilt for the next radiance cast (stack depth
+// or MSP_DONE alone).  Below bit 30, so every test here stays the single compare it was.
+constexpr uint32_t MSP_ROOM = 0x20000000u;
 #define MSP_ACTIVE(m) ((int)(m) < 0x40000000)          /* radiance or shadow */
 #define MSP_IS_SHADOW(m) ((int)(m) < 0)
 #define MSP_IS_RADIANCE(m) ((uint32_t)(m) < 0x40000000u)
 #define MSP_DEPTH(m) ((int)((m) & 0xFFFFu))
 enum { ACT_NONE = 0, ACT_LIGHT = 1, ACT_BOUNCE = 2, ACT_UNWIND = 3 };
 
-template <uint32_t KV, uint32_t SHAPE = KS_GENERAL>
+template <uint32_t KV, uint32_t SHAPE = KS_GENERAL, bool ROOM = false>
 __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) void render_kernel(KArgs A, float *__restrict__ depth_out,
                                                             float *__restrict__ color_out,
                                                             float *__restrict__ normal_out,
@@ -376,6 +383,12 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   // trip pays for, and the kernel runs at its instruction-issue limit.  Nothing a taken path computes changes.
   constexpr bool ONE_MESH = SHAPE == KS_ONE_MESH;
   static_assert(SHAPE == KS_GENERAL || SHAPE == KS_ONE_MESH, "launch shapes: kernel_choice.h");
+  // "Room-safe lanes" (MSP_ROOM above; DESIGN.md "Shadow casts from inside a plane room"): the code that lets a shadow trip skip its
+  // plane tests exists only in the instantiations launched for it — ROOM: a one-mesh launch whose scene head carries room facts
+  // (ctr_launch_render picks <KV, KS_ONE_MESH, true> then) — and in the any-hit statistics builds, which count the trips.  Every
+  // other instantiation is, instruction for instruction, what it was without it: a launch that cannot skip pays nothing.
+  static_assert(!ROOM || ONE_MESH, "room-safe lanes: the one-mesh builds");
+  constexpr bool ROOM_CODE = ANYHIT && (ROOM || STATS);
   static_assert(!ONE_MESH || (KV & ~(KV_OCC6 | KV_HOSTOUT)) == (KV_PREFILTER | KV_BVH | KV_ANYHIT | KV_FASTPOW), "KS_ONE_MESH: the builds of CTR_SHAPE_KERNELS");
   // wave-level work counters (STATS build only): [0] casts, [1] BVH nodes visited, [2] triangle
   // prefilters, [3] exact tests, [4] mesh entries (AABB ballot != 0), [5] sum of active lanes per cast,
@@ -587,6 +600,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     const u32x16 hd_ax = *(const CADDR u32x16 *)&AK->head.ax[0][0];  // ax[0..5], ax_index[0..3]
     const u32x2 hd_ix = *(const CADDR u32x2 *)&AK->head.ax_index[4];
     const bool k_head_axis = (hot[7] & 2u) != 0u;
+    const uint32_t hd_room_lights = ROOM_CODE ? AK->head.room_lights : 0u;  // "room-safe lanes" below: zero = no lane is
     TSTAMP(t_trip0);
     CTR_MARK(1);  // trip head: cast set-up
     typedef unsigned long long mask_t;
@@ -647,8 +661,24 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     CTR_MARK(3);  // planes: set-up
     const bool anyhit_cast = ANYHIT && shadow_cast;
     const bool ign_now = IGNTR && first_trip;  // wave-uniform: this trip is the kernel.hpp:52 cast with ignore_transparent = true
+    // Room-safe lanes: a shadow lane whose origin passed the room facts' predicate (MSP_ROOM) and whose light's bit is set in
+    // room_lights casts a ray that no plane of the scene occludes (the facts are zero unless the head's triple holds every
+    // plane).  When every live lane of the trip is one, the plane phase can only leave alive_m and best = INFINITY as they
+    // are — a plane beyond the light would set best >= light_dist, which the continuation reads as "no occluder" as well —
+    // and the whole wave branches over it.  A trip with any other live lane runs the phase for all of them, as before.
+    bool skip_planes = false;  // wave-uniform
+    if constexpr (ROOM_CODE) {
+      if (hd_room_lights != 0u) {  // (the statistics builds run launches without room facts too)
+        const mask_t safe_m = BALLOT((((hd_room_lights >> (li & 31u)) & (msp >> 29)) & 1u) != 0u);
+        skip_planes = (alive_m & ~(shadow_m & safe_m)) == 0ull;
+      }
+      if (STATS && shadow_m != 0ull && lane == 0) {
+        atomicAdd(&g_lane_stats[88], 1ull);
+        atomicAdd(&g_lane_stats[89], skip_planes ? 1ull : 0ull);  // (no branch on the flag under the lane's: the compiler would thread it past the join)
+      }
+    }
     // ---- planes: plane::intersect, default_schema.hpp:189-201, all in lane masks ----
-    {
+    if (!skip_planes) {
       mask_t live_m = alive_m;
       // t0 = num/den is an IEEE division, and it is only worth doing where the quotient can matter.
       // Classification WITHOUT dividing (and without a reciprocal): with num' = num * sign(den) and
@@ -1673,6 +1703,31 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         { float unused_n; const V3 nrm_ = vnormalized_n(normal, unused_n); CTR_MARK(93); set_nn(nrm_); }
         li = 0;
         act = ACT_LIGHT;
+        if constexpr (ROOM_CODE) {
+          // "room-safe lanes": the lane predicate of the room facts for the hit point every shadow ray of this hit starts from,
+          // once for all its lights — the numerators (point - origin).normal of the head's triple exactly as the plane phase
+          // forms them, none above room_delta, and the origin inside the box (a NaN fails a compare; all-zero facts fail the
+          // box: 0 <= 0 needs the origin AT the centre, and then the trip head finds no light's bit).
+          // (the triple's twelve floats are read again here, through a pointer of its own and only where a hit is shaded: kept
+          //  from the trip head they would live in scalar registers through the mesh walk)
+          const CADDR KArgs *AR = AK;
+          asm volatile("" : "+s"(AR));
+          const u32x8 rm_ax_lo = *(const CADDR u32x8 *)&AR->head.ax[0][0];
+          const u32x4 rm_ax_hi = *(const CADDR u32x4 *)&AR->head.ax[4][0];
+          const u32x2 rm_c01 = *(const CADDR u32x2 *)&AR->head.room_c[0];
+          const u32x4 rm_rest = *(const CADDR u32x4 *)&AR->head.room_c[2];  // room_c[2], room_r, room_delta, room_lights
+          auto rm_ax = [&](int i) -> uint32_t { return i < 8 ? rm_ax_lo[i] : rm_ax_hi[i - 8]; };
+          if (rm_rest[3] != 0u) {  // (wave-uniform)
+            auto pr = [&](int k) -> float2_ { const float2_ v = {__uint_as_float(rm_ax(2 * k)), __uint_as_float(rm_ax(2 * k + 1))}; return v; };
+            const float2_ ox = {ro.x, ro.x}, oy = {ro.y, ro.y}, oz = {ro.z, ro.z};
+            const float2_ n0 = (pr(0) - ox) * pr(1), n1 = (pr(2) - oy) * pr(3), n2 = (pr(4) - oz) * pr(5);
+            const float num_max = fmaxf(fmaxf(fmaxf(n0.x, n0.y), n1.x), fmaxf(fmaxf(n1.y, n2.x), n2.y));
+            const float room_r = __uint_as_float(rm_rest[1]);
+            const bool in_box = fabsf(ro.x - __uint_as_float(rm_c01[0])) <= room_r && fabsf(ro.y - __uint_as_float(rm_c01[1])) <= room_r &&
+                                fabsf(ro.z - __uint_as_float(rm_rest[0])) <= room_r;
+            msp |= (in_box && num_max <= __uint_as_float(rm_rest[2])) ? MSP_ROOM : 0u;
+          }
+        }
       }
     } else if (MSP_IS_SHADOW(msp)) {
       // ---- one iteration of shadow_intensity's loop, shading.hpp:32-42 ----
@@ -2182,8 +2237,10 @@ int ctr_launch_render(const RenderLaunch &L, void *stream) {
   }
   // the launch shape (kernel_choice.h): the same build, compiled for what this launch's scene cannot contain
   if (ctr_launch_shape(L) == KS_ONE_MESH) {
+    // ... and, where the scene head carries room facts, with the code that uses them ("room-safe lanes")
+    const bool room = L.head.room_lights != 0u;
     switch (L.variant) {
-#define X(kv) case (kv): kernel = (const void *)render_kernel<(kv), KS_ONE_MESH>; break;
+#define X(kv) case (kv): kernel = room ? (const void *)render_kernel<(kv), KS_ONE_MESH, true> : (const void *)render_kernel<(kv), KS_ONE_MESH>; break;
       CTR_SHAPE_KERNELS(X)
 #undef X
       default: return (int)hipErrorInvalidValue;

@@ -154,10 +154,17 @@ struct alignas(64) DSceneHead {
   uint32_t ax_transparent[6];  // the same of .transparent (KV_IGNTR only)
   uint32_t n_axis_recs;        // plane records the triple stands for: 3, or 0 = not filled
   uint32_t n_mesh;             // 1: `mesh` is meshes[tlas_root & 0xFFFFFF], 0 = not filled
-  uint32_t pad[6];
+  // The room facts of the launch (scene_flatten.h room_facts; DESIGN.md "Shadow casts from inside a plane room"): all zero, or
+  // what makes the lemma true that lets an any-hit shadow trip skip its plane tests.  A lane whose origin o has
+  // |o - room_c|inf <= room_r and (p - o).n <= room_delta for every filled slot of the triple casts a shadow ray that no
+  // plane of the triple occludes, to every point light whose bit is set in room_lights.
+  float room_c[3], room_r;
+  float room_delta;
+  uint32_t room_lights;        // bit i: lights[i], a point light, qualifies (i < 32)
   DObj mesh;
 };
-static_assert(sizeof(DSceneHead) == 192 && offsetof(DSceneHead, mesh) == 128, "DSceneHead: two 64-byte lines of planes, one of mesh");
+static_assert(sizeof(DSceneHead) == 192 && offsetof(DSceneHead, mesh) == 128 && offsetof(DSceneHead, room_c) == 104,
+              "DSceneHead: two 64-byte lines of planes, one of mesh");
 #define CTR_TL_HEAD_FLAG 0x40000000u  /* kernel-side only: the top-level leaf whose record is DSceneHead::mesh */
 
 // The scene on the device, ONCE: the ten arrays of ctr_scene_create's upload, owned by the handle (ctr_internal.h ctr_scene::dev),

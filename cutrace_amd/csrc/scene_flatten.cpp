@@ -675,3 +675,87 @@ void fill_scene_head(const FlatScene &F, uint32_t tlas_root, DSceneHead &H) {
     H.n_mesh = 1u;
   }
 }
+
+// DESIGN.md "Shadow casts from inside a plane room" has the derivation; the names are its names.
+void room_facts(DSceneHead &H, const DLight *lights, size_t n_light, const RoomTuning &tune) {
+  for (int a = 0; a < 3; a++) H.room_c[a] = 0.0f;
+  H.room_r = H.room_delta = 0.0f;
+  H.room_lights = 0u;
+  if (H.n_axis_recs != 3u || n_light == 0 || n_light > 32) return;
+  // the filled slots: axis, point coordinate, normal component
+  struct Slot { int a; double p, n; };
+  Slot slots[6];
+  int n_slots = 0;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int k = 0; k < 6; k++) {
+    if (H.ax_index[k] == CTR_PLANE_PAD) continue;
+    const int a = k / 2;
+    const double p = H.ax[2 * a][k & 1], n = H.ax[2 * a + 1][k & 1];
+    // (magnitudes at which no product or quotient of the kernel's leaves the normal float range)
+    if (!std::isfinite(p) || !(std::fabs(n) >= 1e-6 && std::fabs(n) <= 1e6) || !(std::fabs(p) <= 1e9)) return;
+    slots[n_slots++] = {a, p, n};
+    lo[a] = std::min(lo[a], p); hi[a] = std::max(hi[a], p);
+  }
+  if (n_slots == 0) return;
+  bool any_point = false;
+  for (size_t i = 0; i < n_light; i++) {
+    if (lights[i].type != CTR_LIGHT_POINT) continue;
+    const double v[3] = {lights[i].vx, lights[i].vy, lights[i].vz};
+    if (!(std::fabs(v[0]) <= 1e9 && std::fabs(v[1]) <= 1e9 && std::fabs(v[2]) <= 1e9)) return;  // (also: not finite)
+    for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
+    any_point = true;
+  }
+  if (!any_point) return;
+  // the origin box: centred on the plane points and point lights, twice their largest half extent
+  double half = 0.0;
+  float c[3];
+  for (int a = 0; a < 3; a++) {
+    c[a] = (float)(0.5 * (lo[a] + hi[a]));
+    half = std::max(half, std::max(hi[a] - (double)c[a], (double)c[a] - lo[a]));
+  }
+  const float r = (float)(2.0 * half);
+  if (!(r >= 1e-9f && r <= 1e9f)) return;
+  // what the kernel's float test |o - c| <= r lets through: the subtraction rounds once
+  const double r_eff = (double)r * (1.0 + 0x1p-20);
+  uint32_t mask = 0u;
+  double t_max = 0.0, den_min = INFINITY;
+  for (size_t i = 0; i < n_light; i++) {
+    if (lights[i].type != CTR_LIGHT_POINT) continue;
+    const double v[3] = {lights[i].vx, lights[i].vy, lights[i].vz};
+    double t2 = 0.0;
+    for (int a = 0; a < 3; a++) { const double e = std::fabs(v[a] - (double)c[a]) + r_eff; t2 += e * e; }
+    t_max = std::max(t_max, std::sqrt(t2));
+  }
+  for (size_t i = 0; i < n_light; i++) {
+    if (lights[i].type != CTR_LIGHT_POINT) continue;
+    const double v[3] = {lights[i].vx, lights[i].vy, lights[i].vz};
+    bool ok = true;
+    double den_i = INFINITY;
+    for (int k = 0; k < n_slots && ok; k++) {
+      const Slot &S = slots[k];
+      const double s_l = (v[S.a] - S.p) * S.n;                                        // the light's side of the plane, and how far
+      const double s_max = (std::fabs((double)c[S.a] - S.p) + r_eff) * std::fabs(S.n);  // the same of any origin of the box, at most
+      ok = s_l > 0.0 && s_l >= tune.k * 0x1p-24 * (t_max * std::fabs(S.n) + s_max);    // case b
+      den_i = std::min(den_i, s_l / t_max);                                             // case c: the smallest den of a ray to it
+    }
+    if (ok) { mask |= 1u << i; den_min = std::min(den_min, den_i); }
+  }
+  if (mask == 0u) return;
+  // case c: t0 <= delta / den <= min_t / 2, min_t = (float)1e-3 of every any-hit shadow ray; rounded down
+  const float delta = (float)(0.5 * (double)(float)1e-3 * den_min * (1.0 - 0x1p-20) * tune.delta_scale);
+  if (!(delta >= 1e-30f) || !std::isfinite(delta)) return;
+  for (int a = 0; a < 3; a++) H.room_c[a] = c[a];
+  H.room_r = r;
+  H.room_delta = delta;
+  H.room_lights = mask;
+}
+
+void fill_room_facts(const FlatScene &F, DSceneHead &H, bool switched_off) {
+  if (!switched_off && F.planes.size() == 3u && F.n_axis_recs == 3u && F.all_opaque) room_facts(H, F.lights.data(), F.lights.size());
+  else room_facts(H, nullptr, 0);
+}
+
+bool wall_skip_switched_off() {
+  const char *e = getenv("CUTRACE_NO_WALL_SKIP");
+  return e && atoi(e) != 0;
+}

@@ -184,6 +184,23 @@ __attribute__((visibility("hidden"))) void fill_scene_counts(const FlatScene &F,
 // and of the mesh record behind a leaf root, as far as the scene has them; everything else zero.
 void fill_scene_head(const FlatScene &F, uint32_t tlas_root, DSceneHead &H);
 
+// The room facts of a head whose axis triple is filled (scene_device.h DSceneHead::room_*; DESIGN.md "Shadow casts from inside
+// a plane room"), computed in double from the triple as the head holds it and the `n_light` records of `lights`: the origin box
+// around the triple's plane points and the point lights, the numerator tolerance, and the bit of every point light that lies
+// on the normal side of every filled slot by more than the margin.  All six words zero: no triple in the head, no point light,
+// more than 32 lights, no light that qualifies, or numbers outside the range the derivation covers.  RoomTuning is what
+// scripts/room_facts_check.cpp mutates; the library uses the defaults.
+struct RoomTuning {
+  double k = 16.0;           // case b: s_L >= k * 2^-24 * (T_max * |n| + S_max); the roundings between t0 and light_dist add up to 10 * 2^-24
+  double delta_scale = 1.0;  // case c: room_delta = delta_scale * min_t / 2 * (smallest den)
+};
+void room_facts(DSceneHead &H, const DLight *lights, size_t n_light, const RoomTuning &tune = RoomTuning());
+// ... of a launch of an any-hit build: zero unless the head's triple holds ALL of the scene's planes (three plane records, all
+// of them the axis triple), no material is transparent and the handle's switch is not set
+void fill_room_facts(const FlatScene &F, DSceneHead &H, bool switched_off);
+// CUTRACE_NO_WALL_SKIP=1 in the environment (read when a handle is created): that handle's launches carry zero room facts
+bool wall_skip_switched_off();
+
 // a node whose four slots are empty: a far-away point box and a leaf of no triangles each
 DNode4 empty_node4();
 // slot `c` of `N` gets a box that every ray passes

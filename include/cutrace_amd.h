@@ -324,6 +324,15 @@ int ctr_debug_last_kernel(ctr_scene *scene, uint32_t *kv);
  * get — the same results bit for bit.  CUTRACE_NO_SHAPE_BUILD=1 in the environment when a handle is created keeps that
  * handle's launches in shape 0 (A/B timing, tests). */
 int ctr_debug_last_shape(ctr_scene *scene, uint32_t *shape);
+/* Diagnostic: the room facts of that launch (csrc/scene_device.h DSceneHead::room_*; DESIGN.md "Shadow casts from inside a plane
+ * room").  out5 = the origin box's centre (3), its half width, the numerator tolerance; *lights = the bits of the point lights
+ * that qualify.  Non-zero only for a launch whose kernel reads them — the one-mesh shape (ctr_debug_last_shape 1) of an any-hit
+ * build, or CTR_VAR_STATS on a scene without transparent material — of a scene whose planes are all axis-aligned and
+ * fit one triple (at most two per axis) with at least one point light well inside them: any-hit shadow trips whose lanes all
+ * start inside that room and aim at such a light then skip their plane tests — the same results bit for bit.
+ * CUTRACE_NO_WALL_SKIP=1 in the environment when a handle is created keeps the words of that handle's launches zero (A/B timing,
+ * tests).  In CTR_VAR_STATS launches ctr_debug_lane_stats counts the any-hit shadow trips in [88] and those that skipped in [89]. */
+int ctr_debug_room_facts(ctr_scene *scene, float *out5, uint32_t *lights);
 /* Diagnostic: what each 8x8 tile of the last launch cost (shader-clock ticks / 64; tile index = frame-major,
  * then row-major over the launch's tile grid).  n_tiles receives the count; out may be NULL. */
 int ctr_tile_costs(ctr_scene *scene, uint32_t *out, uint64_t capacity, uint64_t *n_tiles);
