@@ -18,23 +18,6 @@
 #include "ctr_internal.h"
 #include "cutrace_edit.h"
 
-namespace {
-
-// The device array at *dev gets room for `n` records of `rec` bytes.  *cap: the records it has room for (0: `have`, the count
-// it was created with).  Reallocated only when `n` exceeds that, with the 256 spare bytes ctr_scene_create gives every array.
-int room_for(const void **dev, size_t *cap, size_t have, size_t n, size_t rec) {
-  if (*cap == 0) *cap = have;
-  if (n <= *cap) return CTR_OK;
-  void *p = nullptr;
-  HIP_TRY(hipMalloc(&p, n * rec + 256));
-  if (*dev) (void)hipFree(const_cast<void *>(*dev));
-  *dev = p;
-  *cap = n;
-  return CTR_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int ctr_scene_set_lights(ctr_scene *s, const ctr_light *lights, uint64_t n) {
@@ -42,14 +25,13 @@ int ctr_scene_set_lights(ctr_scene *s, const ctr_light *lights, uint64_t n) {
   if (!s || (!lights && n)) return fail(CTR_E_INVALID, who + "null argument");
   for (uint64_t i = 0; i < n; i++)
     if (lights[i].type > CTR_LIGHT_POINT) return fail(CTR_E_INVALID, who + "light #" + std::to_string(i) + ": bad type");
-  std::lock_guard<std::mutex> lk(s->mtx);
+  const Edit edit(s);
   FlatScene &F = s->flat;
-  if (int st = use_device(s)) return st;
-  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old records
-  if (int st = room_for((const void **)&s->dev.lights, &s->lights_cap, F.lights.size(), n, sizeof(DLight))) return st;
+  if (int st = edit.begin()) return st;
+  if (int st = s->d_lights.grow(n, 0)) return st;
   light_records(F, lights, n);
-  if (n) HIP_TRY(hipMemcpy(const_cast<DLight *>(s->dev.lights), F.lights.data(), n * sizeof(DLight), hipMemcpyHostToDevice));
-  return refresh_linear_meshes(s, true);
+  if (n) HIP_TRY(hipMemcpy(s->d_lights.p, F.lights.data(), n * sizeof(DLight), hipMemcpyHostToDevice));
+  return edit.end({}, true);
 }
 
 int ctr_scene_set_materials(ctr_scene *s, const ctr_material *mats, uint64_t n) {
@@ -57,35 +39,31 @@ int ctr_scene_set_materials(ctr_scene *s, const ctr_material *mats, uint64_t n) 
   if (!s || (!mats && n)) return fail(CTR_E_INVALID, who + "null argument");
   for (uint64_t i = 0; i < n; i++)
     if (mats[i].type != CTR_MAT_PHONG) return fail(CTR_E_INVALID, who + "material #" + std::to_string(i) + ": bad type");
-  std::lock_guard<std::mutex> lk(s->mtx);
+  const Edit edit(s);
   FlatScene &F = s->flat;
   for (size_t i = 0; i < F.objs.size(); i++)
     if (F.objs[i].mat >= n) return fail(CTR_E_INVALID, who + "object #" + std::to_string(i) + ": material index out of range");
-  if (int st = use_device(s)) return st;
-  HIP_TRY(hipDeviceSynchronize());
-  if (int st = room_for((const void **)&s->dev.mats, &s->mats_cap, F.mats.size(), n, sizeof(DMat))) return st;
+  if (int st = edit.begin()) return st;
+  if (int st = s->d_mats.grow(n, 0)) return st;
   const std::vector<DirtyRange> dirty = material_records(F, mats, n);
-  if (n) HIP_TRY(hipMemcpy(const_cast<DMat *>(s->dev.mats), F.mats.data(), n * sizeof(DMat), hipMemcpyHostToDevice));
-  if (int st = upload_dirty(s, dirty)) return st;
-  return refresh_linear_meshes(s, true);
+  if (n) HIP_TRY(hipMemcpy(s->d_mats.p, F.mats.data(), n * sizeof(DMat), hipMemcpyHostToDevice));
+  return edit.end(dirty, true);
 }
 
 int ctr_scene_set_objects(ctr_scene *s, const ctr_object *objects, uint64_t n) {
   const std::string who = "ctr_scene_set_objects: ";
   if (!s) return fail(CTR_E_INVALID, who + "null argument");
-  std::lock_guard<std::mutex> lk(s->mtx);
+  const Edit edit(s);
   FlatScene &F = s->flat;
   std::string err;
   if (int st = check_objects(F, objects, n, err)) return fail(st, who + err);
-  if (int st = use_device(s)) return st;
-  HIP_TRY(hipDeviceSynchronize());
+  if (int st = edit.begin()) return st;
   // (room for the most records ANY packing of these planes needs: the count after the edit is known only once the host copy has it)
-  if (int st = room_for((const void **)&s->dev.planes, &s->planes_cap, F.planes.size(), plane_records_at_most(F), sizeof(DPlanePair))) return st;
+  if (int st = s->d_planes.grow(plane_records_at_most(F), 0)) return st;
   const std::vector<DirtyRange> dirty = objects_edited(F, objects, n);
-  // (a no-op while plane_records_at_most holds; the upload below can never be larger than the array whatever that function says)
-  if (int st = room_for((const void **)&s->dev.planes, &s->planes_cap, 0, F.planes.size(), sizeof(DPlanePair))) return st;
-  if (int st = upload_dirty(s, dirty)) return st;
-  return refresh_linear_meshes(s, true);
+  // (holds while plane_records_at_most does; nothing is uploaded past the end of the array whatever that function says)
+  if (F.planes.size() > s->d_planes.cap) return fail(CTR_E_INVALID, who + "more plane records than plane_records_at_most allows");
+  return edit.end(dirty, true);
 }
 
 int ctr_scene_object_count(const ctr_scene *s, uint64_t *n) {

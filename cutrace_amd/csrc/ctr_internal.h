@@ -12,6 +12,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "cutrace_amd.h"
@@ -66,20 +67,35 @@ int check_device_pointers(int device, const std::string &who, const NamedPtr (&p
   return check_device_pointers(device, who, ptrs, N, whose);
 }
 
-// A buffer that only grows: reserve(n) frees and allocates anew when `n` elements exceed the capacity, and is free
-// otherwise.  An allocation that fails leaves capacity 0 and a null pointer, so that the next call comes back here whatever
-// its size.  Owned by the handle; ctr_scene_destroy releases it with the handle (the scene's device being current).
+// Memory the handle owns, in records of `elem` bytes: device memory, or page-locked host memory.  It only grows, and it is
+// released with the handle (ctr_scene_destroy, the scene's device being current).  `tail`: bytes that stay readable behind the
+// last record.
+//   grow(n, keep)   room for `n` records.  Nothing happens when they fit; otherwise a new block of n * elem + tail bytes (never
+//                   zero: n >= 1 here) receives the first `keep` records of the old one, copied where the memory lives (device
+//                   to device: for a linear mesh the device's nodes are the unbounded payload, which the host copy does not
+//                   hold), and only then is the old block freed and pointer and capacity set.  A failure leaves pointer, capacity
+//                   and contents as they were.
+//   reserve(n)      grow(n, 0): the contents may be gone afterwards.  For scratch.
 struct GrowBuf {
   void *p = nullptr;
-  size_t cap = 0;     // elements
-  size_t elem;        // bytes per element
+  size_t cap = 0;     // records
+  size_t elem;        // bytes per record
   bool pinned;        // page-locked host memory instead of device memory
-  GrowBuf(size_t elem_bytes, bool pinned_host = false) : elem(elem_bytes), pinned(pinned_host) {}
+  size_t tail;        // bytes
+  GrowBuf(size_t elem_bytes, bool pinned_host = false, size_t tail_bytes = 0) : elem(elem_bytes), pinned(pinned_host), tail(tail_bytes) {}
   GrowBuf(const GrowBuf &) = delete;
   ~GrowBuf() { release(); }
-  int reserve(size_t n);
+  int grow(size_t n, size_t keep);
+  int reserve(size_t n) { return grow(n, 0); }
   void release();
+  void swap(GrowBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }  // (two buffers of the same kind)
   template <class T> T *as() const { return (T *)p; }
+};
+// One of the scene's ten device arrays.  Each has 256 readable bytes behind its end: the leaf loop requests the three cache lines
+// after a leaf's first triangle ahead of their use, whether the leaf has that many triangles or not (render_kernel.hip, "touch"),
+// and the same kernels read the other nine.  The rule is stated HERE alone.
+struct SceneBuf : GrowBuf {
+  explicit SceneBuf(size_t rec) : GrowBuf(rec, false, 256) {}
 };
 // two buffers that grow as a pair: both hold `n` elements, or the next call tries again
 inline int reserve_both(GrowBuf &a, GrowBuf &b, size_t n) { const int st = a.reserve(n); return st ? st : b.reserve(n); }
@@ -106,10 +122,12 @@ struct MeshRefit {
 struct ctr_scene {
   int device = 0;
   FlatScene flat;             // the host copy of every scene array, and what the guard knows of it (scene_flatten.h)
-  DScene dev{};               // the scene arrays on the device (ctr_scene.cpp scene_arrays: upload, partial re-upload, free);
-                              // its counts and flags are filled per call: device_scene() below
+  // the scene arrays on the device (ctr_scene.cpp scene_arrays: upload and partial re-upload); what a kernel sees of them is
+  // made per call: device_scene() below.  Capacities are what ctr_scene_create allocated, until an edit needs more
+  SceneBuf d_objs{sizeof(DObj)}, d_oloop{sizeof(DObj)}, d_meshes{sizeof(DObj)}, d_planes{sizeof(DPlanePair)}, d_tris{sizeof(DTri)};
+  SceneBuf d_nodes{sizeof(DNode)}, d_nodes4{sizeof(DNode4)}, d_gnorm{4 * sizeof(float)}, d_lights{sizeof(DLight)}, d_mats{sizeof(DMat)};
   DCam cam{};                 // camera 0 (image size of every camera)
-  DCam *d_cams = nullptr;     // device camera array (>= 1 entry)
+  GrowBuf d_cams{sizeof(DCam)};  // device camera array (>= 1 entry)
   uint32_t n_cams = 0;
   uint32_t cams_epoch = 0;    // bumped by ctr_scene_set_cameras / ctr_scene_set_size
   std::vector<DCam> h_cams;   // host copy of d_cams: the eyes the guard checks (refresh_linear_meshes)
@@ -125,10 +143,10 @@ struct ctr_scene {
   GrowBuf img{9};                 // ctr_render_images: the three byte planes [depth8 | color8 | normal8], 9 bytes per pixel
   GrowBuf d_groups{sizeof(uint32_t)};        // host delivery: one completion counter per group of tiles (render_kernel.hip)
   GrowBuf h_groups{sizeof(uint32_t), true};  // page-locked landing zone of the counters (checked after every direct launch)
-  unsigned long long *h_counters = nullptr;  // pinned landing zone of the 16 counter words
+  GrowBuf h_counters{sizeof(unsigned long long), true};  // page-locked landing zone of the 16 counter words (first host-form render)
   unsigned long long last_cnt[16] = {0};     // the counter words of the last host-form render
-  unsigned long long *d_counters = nullptr;
-  unsigned long long *d_shards = nullptr;  // CTR_SHARDS x CTR_SHARD_WORDS, zero between launches
+  GrowBuf d_counters{sizeof(unsigned long long)};  // 16 words
+  GrowBuf d_shards{sizeof(unsigned long long)};    // CTR_SHARDS x CTR_SHARD_WORDS, zero between launches
   uint32_t last_kernel = 0;        // the KV of the most recent launch (ctr_debug_last_kernel)
   uint32_t last_shape = 0;         // its launch shape, KS_* of kernel_choice.h (ctr_debug_last_shape)
   // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling"; tile_order_policy.h, tile_order_host.cpp)
@@ -149,11 +167,6 @@ struct ctr_scene {
   GrowBuf rb_bin{sizeof(LbvhNode)};                // the binary radix tree
   GrowBuf rb_nodes{sizeof(DNode4)};                // the collapsed descriptors, indexed by binary node
   GrowBuf rb_words{sizeof(float)};                 // [0..5] the centroid bounds, then the per-block partials
-  size_t nodes4_cap = 0;  // DNode4 records dev.nodes4 has room for (0: as ctr_scene_create allocated it); a moved mesh makes it grow
-  // edits of the lights and materials (include/cutrace_edit.h, ctr_edit.cpp): records the device arrays have room for
-  // (0: as ctr_scene_create allocated them, the count they were created with)
-  size_t lights_cap = 0, mats_cap = 0;
-  size_t planes_cap = 0;  // the same of the plane records (ctr_scene_set_objects: an edit can re-pack the planes into more records)
   // the guard's plane scan on the device (guard_scan.h, refresh_linear_meshes): everything is allocated at the first scan there
   GrowBuf scan_planes{7 * sizeof(double)};         // all meshes' planes, FlatScene::guards order
   bool scan_planes_live = false;                   // ... are on the device and current (false: the next scan uploads them all)
@@ -169,9 +182,40 @@ struct ctr_scene {
 
 // the scene on the device as a launch or a query sees it now: the handle's arrays, the counts and flags of their host copy
 inline DScene device_scene(const ctr_scene *s) {
-  DScene D = s->dev;
+  DScene D{};
+  D.objs = s->d_objs.as<DObj>();
+  D.oloop = s->d_oloop.as<DObj>();
+  D.meshes = s->d_meshes.as<DObj>();
+  D.planes = s->d_planes.as<DPlanePair>();
+  D.tris = s->d_tris.as<DTri>();
+  D.nodes = s->d_nodes.p;
+  D.nodes4 = s->d_nodes4.p;
+  D.gnorm = s->d_gnorm.as<float>();
+  D.lights = s->d_lights.as<DLight>();
+  D.mats = s->d_mats.as<DMat>();
   fill_scene_counts(s->flat, D);
   return D;
 }
+
+// An edit of the handle, from the first look at its host copy to the guard: the handle's lock is held while this lives.
+//   begin()   before the first write: the scene's device is current and has been waited for, because no launch may still be
+//             reading the old records.  Arguments are checked, and whatever can fail for want of memory is allocated, before
+//             the first write to the handle.
+//   end()     the device receives what the edit changed in the host copy, then the guard is refreshed (may_scan_on_device:
+//             refresh_linear_meshes above)
+struct Edit {
+  ctr_scene *const s;
+  std::lock_guard<std::mutex> lk;
+  explicit Edit(ctr_scene *scene) : s(scene), lk(scene->mtx) {}
+  int begin() const {
+    if (int st = use_device(s)) return st;
+    HIP_TRY(hipDeviceSynchronize());
+    return CTR_OK;
+  }
+  int end(const std::vector<DirtyRange> &dirty, bool may_scan_on_device) const {
+    if (int st = upload_dirty(s, dirty)) return st;
+    return refresh_linear_meshes(s, may_scan_on_device);
+  }
+};
 
 #endif

@@ -156,8 +156,8 @@ int aa_precheck(const ctr_scene *s, KernelEntry entry, uint32_t samples, RenderC
 // everything of the launch that the handle and the call fix before the rows and the build are known
 void fill_launch(const ctr_scene *s, const RenderCall &c, RenderLaunch &L) {
   L.scene = device_scene(s);  // (tlas_root: set_root_and_head, once the launch's build is known, may put the merged tree there)
-  L.cams = s->d_cams;
-  L.shards = s->d_shards;
+  L.cams = s->d_cams.as<DCam>();
+  L.shards = s->d_shards.as<unsigned long long>();
   L.w = s->cam.w;
   L.h = s->cam.h;
   L.first_frame = c.first_frame;
@@ -191,7 +191,7 @@ ctr_scene::RoomWords room_words(const RenderLaunch &L) {
 // What the launch writes on the device: `spx` pixels per output buffer in the handle's `out`; for a direct launch (z: the
 // caller's buffers as the device sees them, else null) also the groups' completion counters.
 int prepare_outputs(ctr_scene *s, RenderLaunch &L, size_t spx, const HostFrame *z) {
-  if (!s->h_counters) HIP_TRY(hipHostMalloc((void **)&s->h_counters, 16 * sizeof(unsigned long long), hipHostMallocDefault));
+  if (int st = s->h_counters.reserve(16)) return st;
   if (int st = s->out.reserve(spx)) return st;
   L.depth = s->out.as<float>();
   L.color = L.depth + spx;
@@ -241,7 +241,7 @@ int images_out(ctr_scene *s, const RenderLaunch &L, const HostImages &o, size_t 
   uint8_t *const img = s->img.as<uint8_t>();
   ImagesLaunch Q{};
   Q.n = px;
-  Q.counters = s->d_counters;
+  Q.counters = s->d_counters.as<unsigned long long>();
   if (o.depth8) { Q.depth = L.depth; Q.depth8 = img; }
   if (o.color8) { Q.color = L.color; Q.color8 = img + 3 * px; }
   if (o.normal8) { Q.normal = L.normal; Q.normal8 = img + 6 * px; }
@@ -290,7 +290,7 @@ int report(ctr_scene *s, const RenderLaunch &L, std::chrono::high_resolution_clo
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
   unsigned long long cnt[16];
-  memcpy(cnt, s->h_counters, sizeof(cnt));
+  memcpy(cnt, s->h_counters.p, sizeof(cnt));
   memcpy(s->last_cnt, cnt, sizeof(cnt));
   if (s->user_variant & CTR_VAR_STATS)
     fprintf(stderr, "cutrace_amd stats: wave_casts=%llu nodes=%llu tri_prefilter=%llu tri_exact=%llu mesh_entries=%llu "
@@ -380,7 +380,7 @@ int render_host(ctr_scene *s, const RenderCall &c) {
   const bool direct = choice.direct;
   const size_t spx = direct ? (size_t)ctr_staging_pixels(L) : (px ? px : 1);  // pixels per output buffer on the device
   if ((st = prepare_outputs(s, L, spx, direct ? &z : nullptr))) return st;
-  L.counters = s->d_counters;
+  L.counters = s->d_counters.as<unsigned long long>();
   if (choice.reject == KR_UV_STATS) return fail(CTR_E_INVALID, "ctr_render_uv / CTR_VAR_IGNORE_TRANSPARENT: not with the counting / statistics variants");
   L.variant = s->last_kernel = choice.kv;
   if (L.variant & KV_UV) {
@@ -391,12 +391,12 @@ int render_host(ctr_scene *s, const RenderCall &c) {
   s->last_shape = ctr_launch_shape(L);
   s->last_room = room_words(L);
   if ((st = attach_order(s, L, big_mesh(s), c.count))) return st;
-  HIP_TRY(hipMemsetAsync(s->d_counters, 0, 16 * sizeof(unsigned long long), nullptr));
+  HIP_TRY(hipMemsetAsync(s->d_counters.p, 0, 16 * sizeof(unsigned long long), nullptr));
   HIP_TRY(hipEventRecord(s->ev0, nullptr));
   if ((st = launched(ctr_launch_render(L, nullptr), "render kernel launch"))) return st;
   HIP_TRY(hipEventRecord(s->ev1, nullptr));
   if (px && !direct && (st = c.images ? images_out(s, L, *c.images, px) : copy_out(s, L, c.out, px))) return st;
-  HIP_TRY(hipMemcpyAsync(s->h_counters, s->d_counters, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
+  HIP_TRY(hipMemcpyAsync(s->h_counters.p, s->d_counters.p, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, nullptr));
   const size_t n_groups = direct ? (size_t)ctr_staging_groups(L) : 0;
   if (direct) HIP_TRY(hipMemcpyAsync(s->h_groups.p, s->d_groups.p, n_groups * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
   HIP_TRY(hipStreamSynchronize(nullptr));

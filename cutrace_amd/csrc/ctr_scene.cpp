@@ -88,10 +88,20 @@ int use_device(const ctr_scene *s) {
 
 void ctr_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
 
-int GrowBuf::reserve(size_t n) {
+int GrowBuf::grow(size_t n, size_t keep) {
   if (n <= cap) return CTR_OK;
+  if (keep > cap) keep = cap;  // (there is no more)
+  const size_t bytes = n * elem + tail;
+  void *q = nullptr;
+  hipError_t e = pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+  if (e != hipSuccess) return hip_fail(e, pinned ? "hipHostMalloc" : "hipMalloc");
+  if (keep) e = hipMemcpy(q, p, keep * elem, pinned ? hipMemcpyHostToHost : hipMemcpyDeviceToDevice);
+  if (e != hipSuccess) {
+    (void)(pinned ? hipHostFree(q) : hipFree(q));
+    return hip_fail(e, "copy into the larger array");
+  }
   release();
-  HIP_TRY(pinned ? hipHostMalloc(&p, n * elem, hipHostMallocDefault) : hipMalloc(&p, n * elem));
+  p = q;
   cap = n;
   return CTR_OK;
 }
@@ -115,20 +125,17 @@ DCam to_dcam(const ctr_camera &c) {
   return cam;
 }
 
-// The scene's ten device arrays, each ONCE: its pointer in the handle's device scene (scene_device.h DScene), its host copy
-// (scene_flatten.h FlatScene), the bytes of the whole array and of one record, and the key under which a DirtyRange names it
-// (-1: never edited after the upload).  ctr_scene_create uploads, upload_dirty re-uploads and ctr_scene_destroy frees by this
-// table.  F: s->flat, or what ctr_scene_create is about to move there.
-struct SceneArray { void **dev; const void *host; size_t bytes, rec; int dirty; };
+// The scene's ten device arrays, each ONCE: the member of the handle that owns it (its record size is the unit of a DirtyRange),
+// its host copy (scene_flatten.h FlatScene) and the bytes of that, and the key under which a DirtyRange names it (-1: never
+// edited through one after the upload).  ctr_scene_create uploads and upload_dirty re-uploads by this table.  F: s->flat, or
+// what ctr_scene_create is about to move there.
+struct SceneArray { GrowBuf *dev; const void *host; size_t bytes; int dirty; };
 std::vector<SceneArray> scene_arrays(ctr_scene *s, const FlatScene &F) {
-  auto row = [](auto &dev, const auto &v, int dirty = -1, size_t rec = 0) {
-    return SceneArray{(void **)&dev, v.data(), v.size() * sizeof(v[0]), rec ? rec : sizeof(v[0]), dirty};
-  };
-  DScene &D = s->dev;
-  return {row(D.objs, F.objs, DirtyRange::OBJS), row(D.oloop, F.oloop, DirtyRange::OLOOP), row(D.meshes, F.meshes, DirtyRange::MESHES),
-          row(D.planes, F.planes, DirtyRange::PLANES), row(D.tris, F.tris, DirtyRange::TRIS), row(D.nodes, F.nodes, DirtyRange::NODES),
-          row(D.nodes4, F.nodes4, DirtyRange::NODES4), row(D.gnorm, F.gn, DirtyRange::GNORM, 4 * sizeof(float)),
-          row(D.lights, F.lights), row(D.mats, F.mats)};
+  auto row = [](GrowBuf &dev, const auto &v, int dirty = -1) { return SceneArray{&dev, v.data(), v.size() * sizeof(v[0]), dirty}; };
+  return {row(s->d_objs, F.objs, DirtyRange::OBJS), row(s->d_oloop, F.oloop, DirtyRange::OLOOP), row(s->d_meshes, F.meshes, DirtyRange::MESHES),
+          row(s->d_planes, F.planes, DirtyRange::PLANES), row(s->d_tris, F.tris, DirtyRange::TRIS), row(s->d_nodes, F.nodes, DirtyRange::NODES),
+          row(s->d_nodes4, F.nodes4, DirtyRange::NODES4), row(s->d_gnorm, F.gn, DirtyRange::GNORM),
+          row(s->d_lights, F.lights), row(s->d_mats, F.mats)};
 }
 
 }  // namespace
@@ -139,8 +146,9 @@ int upload_dirty(ctr_scene *s, const std::vector<DirtyRange> &dirty) {
   for (const DirtyRange &r : dirty)
     for (const SceneArray &a : arrays) {
       if (a.dirty != (int)r.array || !r.count) continue;
-      const void *src = r.payload.empty() ? (const char *)a.host + r.begin * a.rec : (const char *)r.payload.data();
-      HIP_TRY(hipMemcpy((char *)*a.dev + r.begin * a.rec, src, r.count * a.rec, hipMemcpyHostToDevice));
+      const size_t rec = a.dev->elem;
+      const void *src = r.payload.empty() ? (const char *)a.host + r.begin * rec : (const char *)r.payload.data();
+      HIP_TRY(hipMemcpy(a.dev->as<char>() + r.begin * rec, src, r.count * rec, hipMemcpyHostToDevice));
     }
   return CTR_OK;
 }
@@ -224,14 +232,33 @@ int refresh_linear_meshes(ctr_scene *s, bool may_scan_on_device) {
 namespace {
 
 // The merged tree of a scene that has room for it (scene_flatten.h Merged): built, uploaded, guarded.
-int build_merged_tree(ctr_scene *s) {
+int build_merged_tree(const Edit &edit) {
+  ctr_scene *s = edit.s;
   const std::vector<DirtyRange> dirty = ::build_merged_tree(s->flat);
   if (dirty.empty()) return CTR_OK;
   if (int st = upload_dirty(s, dirty)) {
     s->flat.merged.built = false;  // (the device never got it: the next ctr_set_variant builds it again)
     return st;
   }
-  return refresh_linear_meshes(s);
+  return edit.end({}, false);  // (the tree went up above, where a failure has a consequence of its own)
+}
+
+// ctr_scene_create's device half: every array of F, the one camera, the counters and the zeroed shards, the two events
+int upload_scene(ctr_scene *s, const FlatScene &F) {
+  for (const SceneArray &a : scene_arrays(s, F)) {
+    const size_t n = a.bytes / a.dev->elem;
+    if (int st = a.dev->reserve(n ? n : 1)) return st;  // (never hand the kernel a null base pointer)
+    if (a.bytes) HIP_TRY(hipMemcpy(a.dev->p, a.host, a.bytes, hipMemcpyHostToDevice));
+  }
+  const size_t shard_words = (size_t)CTR_SHARDS * CTR_SHARD_WORDS;
+  if (int st = s->d_cams.reserve(1)) return st;
+  HIP_TRY(hipMemcpy(s->d_cams.p, &s->cam, sizeof(DCam), hipMemcpyHostToDevice));
+  if (int st = s->d_counters.reserve(16)) return st;
+  if (int st = s->d_shards.reserve(shard_words)) return st;
+  HIP_TRY(hipMemset(s->d_shards.p, 0, shard_words * sizeof(unsigned long long)));
+  HIP_TRY(hipEventCreate(&s->ev0));
+  HIP_TRY(hipEventCreate(&s->ev1));
+  return CTR_OK;
 }
 
 }  // namespace
@@ -267,26 +294,13 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   auto *s = new ctr_scene();
   s->device = device;
   s->cam = to_dcam(d->cam);
-  if (const char *e = getenv("CUTRACE_NO_SCENE_HEAD")) s->no_scene_head = atoi(e) != 0;  // A/B and tests: every record by pointer
-  if (const char *e = getenv("CUTRACE_NO_SHAPE_BUILD")) s->no_shape_build = atoi(e) != 0;  // A/B and tests: the general build of every launch
-  s->no_wall_skip = wall_skip_switched_off();  // CUTRACE_NO_WALL_SKIP=1: A/B and tests: no shadow trip skips its plane tests
+  s->no_scene_head = env_switch("CUTRACE_NO_SCENE_HEAD");    // every record by pointer
+  s->no_shape_build = env_switch("CUTRACE_NO_SHAPE_BUILD");  // the general build of every launch
+  s->no_wall_skip = env_switch("CUTRACE_NO_WALL_SKIP");      // no shadow trip skips its plane tests
 
-  hipError_t er = hipSuccess;
-  for (const SceneArray &a : scene_arrays(s, F)) {
-    // never hand the kernel a null base pointer: allocate at least one element's worth
-    // (and 256 bytes beyond the end: the leaf loop requests the three cache lines after a leaf's first triangle ahead
-    //  of their use, whether the leaf has that many triangles or not — render_kernel.hip, "touch")
-    if (er == hipSuccess) er = hipMalloc(a.dev, (a.bytes ? a.bytes : 64) + 256);
-    if (er == hipSuccess && a.bytes) er = hipMemcpy(*a.dev, a.host, a.bytes, hipMemcpyHostToDevice);
-  }
-  const size_t shard_bytes = (size_t)CTR_SHARDS * CTR_SHARD_WORDS * sizeof(unsigned long long);
-  if (er != hipSuccess || (er = hipMalloc((void **)&s->d_cams, sizeof(DCam))) != hipSuccess ||
-      (er = hipMemcpy(s->d_cams, &s->cam, sizeof(DCam), hipMemcpyHostToDevice)) != hipSuccess ||
-      (er = hipMalloc((void **)&s->d_counters, 16 * sizeof(unsigned long long))) != hipSuccess ||
-      (er = hipMalloc((void **)&s->d_shards, shard_bytes)) != hipSuccess || (er = hipMemset(s->d_shards, 0, shard_bytes)) != hipSuccess ||
-      (er = hipEventCreate(&s->ev0)) != hipSuccess || (er = hipEventCreate(&s->ev1)) != hipSuccess) {
+  if (int st = upload_scene(s, F)) {
     ctr_scene_destroy(s);
-    return hip_fail(er, "scene upload");
+    return hip_fail((hipError_t)(st - CTR_E_HIP_BASE), "scene upload");  // (every step of it is a call of the runtime)
   }
   create_stamp("device allocation + upload");
   s->n_cams = 1;
@@ -311,30 +325,24 @@ int ctr_scene_set_cameras(ctr_scene *s, const ctr_camera *cams, uint32_t n) {
     dc[i] = to_dcam(cams[i]);
   }
   if (dc[0].w == 0 || dc[0].h == 0) return fail(CTR_E_INVALID, "camera has zero width or height");
-  std::lock_guard<std::mutex> lk(s->mtx);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old array
-  DCam *nd = nullptr;
-  HIP_TRY(hipMalloc((void **)&nd, sizeof(DCam) * n));
-  hipError_t e = hipMemcpy(nd, dc.data(), sizeof(DCam) * n, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(nd); return hip_fail(e, "camera upload"); }
-  if (s->d_cams) (void)hipFree(s->d_cams);
-  s->d_cams = nd;
+  const Edit edit(s);
+  if (int st = edit.begin()) return st;
+  // the new array is complete before the old one is released: a failure leaves the old cameras
+  GrowBuf fresh(sizeof(DCam));
+  if (int st = fresh.grow(n, 0)) return st;
+  const hipError_t e = hipMemcpy(fresh.p, dc.data(), sizeof(DCam) * n, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return hip_fail(e, "camera upload");
+  s->d_cams.swap(fresh);  // (`fresh` takes the old array with it)
   s->n_cams = n;
   s->cams_epoch++;
   s->cam = dc[0];
   s->h_cams = dc;
-  return refresh_linear_meshes(s);
+  return edit.end({}, false);
 }
 
 void ctr_scene_destroy(ctr_scene *s) {
   if (!s) return;
-  (void)hipSetDevice(s->device);
-  for (const SceneArray &a : scene_arrays(s, s->flat))
-    if (*a.dev) (void)hipFree(*a.dev);
-  for (void *p : {(void *)s->d_cams, (void *)s->d_counters, (void *)s->d_shards})
-    if (p) (void)hipFree(p);
-  if (s->h_counters) (void)hipHostFree(s->h_counters);
+  (void)hipSetDevice(s->device);  // (the memory is released by the handle's members: delete, below)
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   delete s;  // (every GrowBuf of the handle releases its memory here)
@@ -349,13 +357,12 @@ int ctr_scene_size(const ctr_scene *s, uint64_t *w, uint64_t *h) {
 
 int ctr_scene_set_size(ctr_scene *s, uint64_t w, uint64_t h) {
   if (!s || w == 0 || h == 0 || w > 0x7FFFFFFFull || h > 0x7FFFFFFFull) return fail(CTR_E_INVALID, "bad size");
-  std::lock_guard<std::mutex> lk(s->mtx);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipDeviceSynchronize());
+  const Edit edit(s);
+  if (int st = edit.begin()) return st;
   std::vector<DCam> dc(s->n_cams);
-  HIP_TRY(hipMemcpy(dc.data(), s->d_cams, sizeof(DCam) * s->n_cams, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dc.data(), s->d_cams.p, sizeof(DCam) * s->n_cams, hipMemcpyDeviceToHost));
   for (DCam &c : dc) { c.w = (uint32_t)w; c.h = (uint32_t)h; }
-  HIP_TRY(hipMemcpy(s->d_cams, dc.data(), sizeof(DCam) * s->n_cams, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(s->d_cams.p, dc.data(), sizeof(DCam) * s->n_cams, hipMemcpyHostToDevice));
   s->cam.w = (uint32_t)w;
   s->cam.h = (uint32_t)h;
   s->cams_epoch++;
@@ -367,14 +374,11 @@ int ctr_set_variant(ctr_scene *s, uint32_t bits) {
   constexpr uint32_t KNOWN = CTR_VAR_NO_PREFILTER | CTR_VAR_NO_ANYHIT | CTR_VAR_NO_CLUSTER | CTR_VAR_STATS | CTR_VAR_EXACT_POW |
                              CTR_VAR_NO_REORDER | CTR_VAR_NO_OCC6 | CTR_VAR_NO_DIRECT | CTR_VAR_IMAGE_ORDER_FIRST | CTR_VAR_MERGE | CTR_VAR_IGNORE_TRANSPARENT;
   if (bits & ~KNOWN) return fail(CTR_E_INVALID, "ctr_set_variant: unknown variant bits " + std::to_string(bits & ~KNOWN));
-  s->user_variant = bits;
-  if ((bits & CTR_VAR_MERGE) && s->flat.merged.reserved && !s->flat.merged.built) {
-    std::lock_guard<std::mutex> lk(s->mtx);
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());
-    return build_merged_tree(s);
-  }
-  return CTR_OK;
+  const Edit edit(s);
+  s->user_variant = bits;  // (kept also when the build below fails)
+  if (!(bits & CTR_VAR_MERGE) || !s->flat.merged.reserved || s->flat.merged.built) return CTR_OK;
+  if (int st = edit.begin()) return st;
+  return build_merged_tree(edit);
 }
 
 int ctr_frame_alloc(uint64_t n_pixels, float **depth, float **color3, float **normal3) {

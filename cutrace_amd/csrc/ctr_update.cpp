@@ -112,8 +112,9 @@ struct BackLayout {
   }
 };
 
-// What the two calls share once the arguments are known to name a mesh of the handle
+// What the two calls share: the edit they are (the handle's lock from here on), and what is known once the arguments name a mesh
 struct MeshCall {
+  const Edit edit;
   ctr_scene *s;
   std::string who;
   size_t gi = 0;
@@ -124,10 +125,10 @@ struct MeshCall {
   const float *d_verts = nullptr;  // the vertices on the device: the caller's, or upd_verts once upload_verts has run
   bool uploaded = false;
   Stamps stamp;
-  MeshCall(ctr_scene *scene, const char *name) : s(scene), who(std::string(name) + ": "), stamp(name + 10 /* past "ctr_scene_" */) {}
+  MeshCall(ctr_scene *scene, const char *name) : edit(scene), s(scene), who(std::string(name) + ": "), stamp(name + 10 /* past "ctr_scene_" */) {}
 };
 
-// ---- 1. the arguments: `object` is a non-empty mesh of n_tris triangles (the caller holds the handle's lock) ----
+// ---- 1. the arguments: `object` is a non-empty mesh of n_tris triangles; the scene's device becomes current ----
 int mesh_arguments(MeshCall &c, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream) {
   const FlatScene &F = c.s->flat;
   if (object >= F.objs.size() || F.objs[object].type != CTR_OBJ_MESH)
@@ -200,9 +201,9 @@ int update_steps(MeshCall &c, const MeshRefit *refit) {
   hipStream_t stream = c.stream;
   Stamps &stamp = c.stamp;
   if (int st = upload_verts(c)) return st;
-  DTri *d_recs = const_cast<DTri *>(s->dev.tris) + tri_begin;
-  float *d_gn = const_cast<float *>(s->dev.gnorm) + 4 * (size_t)tri_begin;
-  DNode4 *d_nodes = (DNode4 *)const_cast<void *>(s->dev.nodes4) + node_begin;  // (the mesh's spare node and guard records are not the kernels' business)
+  DTri *d_recs = s->d_tris.as<DTri>() + tri_begin;
+  float *d_gn = s->d_gnorm.as<float>() + 4 * (size_t)tri_begin;
+  DNode4 *d_nodes = s->d_nodes4.as<DNode4>() + node_begin;  // (the mesh's spare node and guard records are not the kernels' business)
   double *d_planes = s->upd_planes.as<double>();
   if (int st = launched(ctr_launch_update_tris(d_recs, d_gn, d_planes, d_verts, n, stream), "update_tris launch")) return st;
   const LevelSchedule &sched = refit->sched;
@@ -236,7 +237,7 @@ int update_steps(MeshCall &c, const MeshRefit *refit) {
   stamp("host records + upload");
   // (the new planes are on the device already, in upd_planes, and the stream has been waited for: the scan takes them from there)
   if (int st = guard_planes_changed(s, c.gi, d_planes)) return st;
-  const int st = refresh_linear_meshes(s, true);
+  const int st = c.edit.end({}, true);  // (the records went up above, ahead of their stamp)
   stamp("guard");
   return st;
 }
@@ -282,35 +283,18 @@ int device_shape(MeshCall &c, std::vector<DNode4> &sparse, std::vector<uint32_t>
   return CTR_OK;
 }
 
-// the device's node array gets room for `records` DNode4 (+ the 256 spare bytes ctr_scene_create gives every array): a new
-// allocation that receives the old one's contents — the DEVICE's, which for a linear mesh are not the host copy's.  The caller
-// has waited for the device.
-int nodes4_room(ctr_scene *s, size_t have, size_t records) {
-  if (s->nodes4_cap == 0) s->nodes4_cap = have;
-  if (records <= s->nodes4_cap) return CTR_OK;
-  void *p = nullptr;
-  HIP_TRY(hipMalloc(&p, records * sizeof(DNode4) + 256));
-  const hipError_t e = have ? hipMemcpy(p, s->dev.nodes4, have * sizeof(DNode4), hipMemcpyDeviceToDevice) : hipSuccess;
-  if (e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "node array copy"); }
-  if (s->dev.nodes4) (void)hipFree(const_cast<void *>(s->dev.nodes4));
-  s->dev.nodes4 = p;
-  s->nodes4_cap = records;
-  return CTR_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 int ctr_scene_update_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream) {
   if (!s || !tris) return fail(CTR_E_INVALID, "ctr_scene_update_mesh: null argument");
-  std::lock_guard<std::mutex> lk(s->mtx);
   MeshCall c(s, "ctr_scene_update_mesh");
   if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream)) return st;
   MeshRefit *refit = nullptr;
   if (int st = mesh_refit_of(s, c.gi, &refit)) return st;
   if (int st = vertices_and_buffers(c, s->flat.guards[c.gi].node_count)) return st;
-  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old records (as ctr_scene_set_cameras does)
+  if (int st = c.edit.begin()) return st;
   c.stamp("checks");
   return update_steps(c, refit);
 }
@@ -320,7 +304,6 @@ int ctr_scene_rebuild_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tr
   const std::string who = "ctr_scene_rebuild_mesh: ";
   if (flags & ~CTR_REBUILD_HOST) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(flags & ~CTR_REBUILD_HOST));
   if (!s || !tris) return fail(CTR_E_INVALID, who + "null argument");
-  std::lock_guard<std::mutex> lk(s->mtx);
   MeshCall c(s, "ctr_scene_rebuild_mesh");
   if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream)) return st;
   FlatScene &F = s->flat;
@@ -361,8 +344,10 @@ int ctr_scene_rebuild_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tr
   if (int st = s->rb_index.reserve(n)) return st;
   if (s->refit.size() < F.guards.size()) s->refit.resize(F.guards.size());
   F.nodes4.reserve(nodes4_after);
-  HIP_TRY(hipDeviceSynchronize());  // no launch may still be reading the old records, or the node array when it moves
-  if (int st = nodes4_room(s, F.nodes4.size(), nodes4_after)) return st;  // (same contents in another place: the last step that can fail for want of memory)
+  if (int st = c.edit.begin()) return st;  // (no launch may still be reading the node array either, when it moves)
+  // the same contents in another place (the DEVICE's, which for a linear mesh are not the host copy's): the last step that can
+  // fail for want of memory
+  if (int st = s->d_nodes4.grow(nodes4_after, F.nodes4.size())) return st;
 
   // ---- 1c. the shape goes in: host copy, then the device's descriptors and the records' `orig` ----
   bool moved = false;
@@ -370,7 +355,7 @@ int ctr_scene_rebuild_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tr
   s->refit[c.gi] = std::move(refit);
   if (int st = upload_dirty(s, dirty)) return st;
   HIP_TRY(hipMemcpyAsync(s->rb_index.p, tree.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
-  if (int st = launched(ctr_launch_set_orig(const_cast<DTri *>(s->dev.tris) + F.guards[c.gi].tri_begin, s->rb_index.as<uint32_t>(), n, c.stream), "set_orig launch"))
+  if (int st = launched(ctr_launch_set_orig(s->d_tris.as<DTri>() + F.guards[c.gi].tri_begin, s->rb_index.as<uint32_t>(), n, c.stream), "set_orig launch"))
     return st;
   if (c.stamp.on) HIP_TRY(hipStreamSynchronize(c.stream));
   c.stamp("install");

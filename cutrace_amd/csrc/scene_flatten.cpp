@@ -755,7 +755,7 @@ void fill_room_facts(const FlatScene &F, DSceneHead &H, bool switched_off) {
   else room_facts(H, nullptr, 0);
 }
 
-bool wall_skip_switched_off() {
-  const char *e = getenv("CUTRACE_NO_WALL_SKIP");
+bool env_switch(const char *name) {
+  const char *e = getenv(name);
   return e && atoi(e) != 0;
 }

@@ -198,8 +198,9 @@ void room_facts(DSceneHead &H, const DLight *lights, size_t n_light, const RoomT
 // ... of a launch of an any-hit build: zero unless the head's triple holds ALL of the scene's planes (three plane records, all
 // of them the axis triple), no material is transparent and the handle's switch is not set
 void fill_room_facts(const FlatScene &F, DSceneHead &H, bool switched_off);
-// CUTRACE_NO_WALL_SKIP=1 in the environment (read when a handle is created): that handle's launches carry zero room facts
-bool wall_skip_switched_off();
+// A switch of the environment that a handle reads when it is created (A/B runs and tests), NAME=<an integer other than 0>:
+// CUTRACE_NO_SCENE_HEAD, CUTRACE_NO_SHAPE_BUILD, and CUTRACE_NO_WALL_SKIP (that handle's launches carry zero room facts)
+bool env_switch(const char *name);
 
 // a node whose four slots are empty: a far-away point box and a leaf of no triangles each
 DNode4 empty_node4();

@@ -1,8 +1,10 @@
-// edit_check_common.h — what the edit check programs (scene_edit_check.cpp, object_edit_check.cpp) share: a description that owns
-// its arrays, the small guard scenes' triangles, flatten + guard, and the byte-for-byte comparison of two flat scenes.
+// edit_check_common.h — what the edit check programs (scene_edit_check.cpp, object_edit_check.cpp, mesh_update_check.cpp,
+// mesh_rebuild_check.cpp) share: a description that owns its arrays, the triangle sets, flatten + guard, the ONE restatement of
+// ctr_scene_update_mesh on the host copy (update_on_host), and the byte-for-byte comparison of two flat scenes.
 #ifndef CUTRACE_AMD_EDIT_CHECK_COMMON_H
 #define CUTRACE_AMD_EDIT_CHECK_COMMON_H
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -14,12 +16,14 @@
 #include "bvh.h"
 #include "cutrace_host.h"
 #include "guard.h"
+#include "mesh_refit.h"
 #include "scene_flatten.h"
+#include "tri_record.h"
 
 static int fails = 0;
 #define CHECK(c, ...) do { if (!(c)) { if (fails++ < 40) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
-static std::mt19937 rng(23);
+static std::mt19937 rng(23);  // (mesh_update_check.cpp: rng.seed(11) before its first draw)
 static float U(float lo, float hi) { return std::uniform_real_distribution<float>(lo, hi)(rng); }
 
 typedef std::vector<ctr_triangle> Tris;
@@ -137,6 +141,85 @@ static std::vector<DCam> cams_of(const ctr_scene_desc &d) {
 }
 
 static void guard(FlatScene &F, const std::vector<DCam> &cams) { apply_guards(F, plan_guards(F, cams)); }
+
+// ... with one camera at `eye`; returns what the device would have to receive
+static std::vector<DirtyRange> guard(FlatScene &F, const float *eye) {
+  DCam c{};
+  for (int a = 0; a < 3; a++) c.pos[a] = eye[a];
+  return apply_guards(F, plan_guards(F, std::vector<DCam>(1, c)));
+}
+
+// ---- triangle sets (every draw is one of `rng`: a program that reads its own lines seeds it before the first) ----
+static Tris random_tris(size_t n, float spread, float size) {
+  Tris t(n);
+  for (ctr_triangle &q : t) {
+    const ctr_vec3 o{U(-spread, spread), U(-spread, spread), U(-spread, spread)};
+    ctr_vec3 *p[3] = {&q.p1, &q.p2, &q.p3};
+    for (ctr_vec3 *v : p) *v = ctr_vec3{o.x + U(-size, size), o.y + U(-size, size), o.z + U(-size, size)};
+  }
+  return t;
+}
+
+// a rotation about (1, 2, 3) by `angle` plus a per-vertex wobble
+static Tris moved(const Tris &t, float angle, float wobble) {
+  const double k[3] = {1 / std::sqrt(14.0), 2 / std::sqrt(14.0), 3 / std::sqrt(14.0)}, c = std::cos(angle), s = std::sin(angle);
+  auto rot = [&](ctr_vec3 v) {
+    const double d = k[0] * v.x + k[1] * v.y + k[2] * v.z;
+    const double cr[3] = {k[1] * v.z - k[2] * v.y, k[2] * v.x - k[0] * v.z, k[0] * v.y - k[1] * v.x};
+    return ctr_vec3{(float)(v.x * c + cr[0] * s + k[0] * d * (1 - c)) + U(-wobble, wobble), (float)(v.y * c + cr[1] * s + k[1] * d * (1 - c)) + U(-wobble, wobble),
+                    (float)(v.z * c + cr[2] * s + k[2] * d * (1 - c)) + U(-wobble, wobble)};
+  };
+  Tris out(t);
+  for (ctr_triangle &q : out) { q.p1 = rot(q.p1); q.p2 = rot(q.p2); q.p3 = rot(q.p3); }
+  return out;
+}
+
+// `k` of the mesh's triangles (file indices 0 .. k-1) in the plane z = 0.5, the others where they were
+static Tris with_in_plane(const Tris &t, size_t k) {
+  Tris out(t);
+  for (size_t i = 0; i < k && i < out.size(); i++) {
+    const float x = U(-1, 1), y = U(-1, 1);
+    out[i].p1 = ctr_vec3{x, y, 0.5f}; out[i].p2 = ctr_vec3{x + 0.3f, y + 0.05f, 0.5f}; out[i].p3 = ctr_vec3{x + 0.1f, y + 0.35f, 0.5f};
+  }
+  return out;
+}
+
+// ---- the device's half of an update, restated ----
+// the refit of one tree on the host, level by level as the device launches it
+static void refit_on_host(DNode4 *nodes, const LevelSchedule &S, const DTri *recs, const Tris &verts) {
+  for (size_t h = 0; h < S.levels(); h++)
+    for (uint32_t i = S.begin[h]; i < S.begin[h + 1]; i++)
+      for (int c = 0; c < 4; c++) refit_slot(nodes, S.nodes[i], c, recs, &verts[0].p1.x);
+}
+
+// min / max over the vertices of every triangle below descriptor `d`
+static void brute(const std::vector<DNode4> &nodes, uint32_t d, const std::vector<uint32_t> &order, const Tris &verts, float *lo, float *hi) {
+  if (d == BVH_LEAF_FLAG) return;
+  if (d & BVH_LEAF_FLAG) {
+    for (uint32_t k = d & 0xFFFFFFu; k < (d & 0xFFFFFFu) + ((d >> 24) & 0x7Fu); k++) {
+      const float *v = &verts[order[k]].p1.x;
+      for (int j = 0; j < 9; j++) { lo[j % 3] = std::min(lo[j % 3], v[j]); hi[j % 3] = std::max(hi[j % 3], v[j]); }
+    }
+    return;
+  }
+  for (int c = 0; c < 4; c++) brute(nodes, nodes[d].child[c], order, verts, lo, hi);
+}
+
+// ctr_scene_update_mesh on the host copy: what update_tris, refit_level and mesh_box do on the device, then mesh_updated
+static void update_on_host(FlatScene &F, size_t gi, const Tris &nt) {
+  MeshGuard &g = F.guards[gi];
+  for (uint32_t k = 0; k < g.tri_count; k++) {
+    const uint32_t orig = F.tris[g.tri_begin + k].orig;
+    make_tri(nt[orig].p1, nt[orig].p2, nt[orig].p3, orig, F.tris[g.tri_begin + k], &F.gn[4 * (g.tri_begin + orig)]);
+    guard_plane(nt[orig].p1, nt[orig].p2, nt[orig].p3, &g.planes[CTR_PLANE_DOUBLES * k]);
+  }
+  LevelSchedule S;
+  CHECK(level_schedule(&F.nodes4[g.node_begin], g.node_count, g.tri_count, S), "update: no schedule");
+  refit_on_host(&F.nodes4[g.node_begin], S, &F.tris[g.tri_begin], nt);
+  float box[6];
+  refit_mesh_box(F.nodes4[g.node_begin], box);
+  mesh_updated(F, gi, box);
+}
 
 template <class T> static bool same_bytes(const std::vector<T> &a, const std::vector<T> &b) {
   return a.size() == b.size() && (a.empty() || !memcmp(a.data(), b.data(), a.size() * sizeof(T)));

@@ -17,32 +17,6 @@
 
 #include "edit_check_common.h"
 #include "lbvh.h"
-#include "mesh_refit.h"
-#include "tri_record.h"
-
-static Tris random_tris(size_t n, float spread, float size) {
-  Tris t(n);
-  for (ctr_triangle &q : t) {
-    const ctr_vec3 o{U(-spread, spread), U(-spread, spread), U(-spread, spread)};
-    ctr_vec3 *p[3] = {&q.p1, &q.p2, &q.p3};
-    for (ctr_vec3 *v : p) *v = ctr_vec3{o.x + U(-size, size), o.y + U(-size, size), o.z + U(-size, size)};
-  }
-  return t;
-}
-
-// a rotation about (1, 2, 3) by `angle` plus a per-vertex wobble
-static Tris moved(const Tris &t, float angle, float wobble) {
-  const double k[3] = {1 / std::sqrt(14.0), 2 / std::sqrt(14.0), 3 / std::sqrt(14.0)}, c = std::cos(angle), s = std::sin(angle);
-  auto rot = [&](ctr_vec3 v) {
-    const double d = k[0] * v.x + k[1] * v.y + k[2] * v.z;
-    const double cr[3] = {k[1] * v.z - k[2] * v.y, k[2] * v.x - k[0] * v.z, k[0] * v.y - k[1] * v.x};
-    return ctr_vec3{(float)(v.x * c + cr[0] * s + k[0] * d * (1 - c)) + U(-wobble, wobble), (float)(v.y * c + cr[1] * s + k[1] * d * (1 - c)) + U(-wobble, wobble),
-                    (float)(v.z * c + cr[2] * s + k[2] * d * (1 - c)) + U(-wobble, wobble)};
-  };
-  Tris out(t);
-  for (ctr_triangle &q : out) { q.p1 = rot(q.p1); q.p2 = rot(q.p2); q.p3 = rot(q.p3); }
-  return out;
-}
 
 // ---- the device builder's steps, one loop iteration per lane ----
 struct Lbvh {
@@ -80,25 +54,6 @@ static Lbvh lbvh_on_host(const Tris &tris, uint32_t leaf = BVH_LEAF) {
   L.sparse.resize(n > 1 ? n - 1 : 1);
   for (uint32_t i = 0; i < L.sparse.size(); i++) lbvh_collapse(bin.data(), L.keys.data(), n, leaf, i, L.sparse.data());
   return L;
-}
-
-// min / max over the vertices of every triangle below descriptor `d`; counts the triangles it meets
-static void brute(const std::vector<DNode4> &nodes, uint32_t d, const std::vector<uint32_t> &order, const Tris &verts, float *lo, float *hi) {
-  if (d == BVH_LEAF_FLAG) return;
-  if (d & BVH_LEAF_FLAG) {
-    for (uint32_t k = d & 0xFFFFFFu; k < (d & 0xFFFFFFu) + ((d >> 24) & 0x7Fu); k++) {
-      const float *v = &verts[order[k]].p1.x;
-      for (int j = 0; j < 9; j++) { lo[j % 3] = std::min(lo[j % 3], v[j]); hi[j % 3] = std::max(hi[j % 3], v[j]); }
-    }
-    return;
-  }
-  for (int c = 0; c < 4; c++) brute(nodes, nodes[d].child[c], order, verts, lo, hi);
-}
-
-static void refit_on_host(DNode4 *nodes, const LevelSchedule &S, const DTri *recs, const Tris &verts) {
-  for (size_t h = 0; h < S.levels(); h++)
-    for (uint32_t i = S.begin[h]; i < S.begin[h + 1]; i++)
-      for (int c = 0; c < 4; c++) refit_slot(nodes, S.nodes[i], c, recs, &verts[0].p1.x);
 }
 
 static void check_lbvh(const char *what, const Tris &tris) {
@@ -244,28 +199,11 @@ static Scene scene_of(const Tris &a, const Tris &b) {
   return s;
 }
 
-static std::vector<DirtyRange> guard_dirty(FlatScene &F) {
-  DCam c{};
-  for (int a = 0; a < 3; a++) c.pos[a] = EYE[a];
-  return apply_guards(F, plan_guards(F, std::vector<DCam>(1, c)));
-}
-
-// ctr_scene_rebuild_mesh on the host copy: mesh_rebuilt, then what update_tris and refit_level do on the device, then mesh_updated
+// ctr_scene_rebuild_mesh on the host copy: mesh_rebuilt, then the update's steps
 static bool rebuild_on_host(FlatScene &F, size_t gi, const MeshTree &tree, const Tris &nt) {
   bool was_moved = false;
   mesh_rebuilt(F, gi, tree, &was_moved);
-  MeshGuard &g = F.guards[gi];
-  for (uint32_t k = 0; k < g.tri_count; k++) {
-    const uint32_t orig = F.tris[g.tri_begin + k].orig;
-    make_tri(nt[orig].p1, nt[orig].p2, nt[orig].p3, orig, F.tris[g.tri_begin + k], &F.gn[4 * (g.tri_begin + orig)]);
-    guard_plane(nt[orig].p1, nt[orig].p2, nt[orig].p3, &g.planes[CTR_PLANE_DOUBLES * k]);
-  }
-  LevelSchedule S;
-  CHECK(level_schedule(&F.nodes4[g.node_begin], g.node_count, g.tri_count, S), "rebuild: no schedule");
-  refit_on_host(&F.nodes4[g.node_begin], S, &F.tris[g.tri_begin], nt);
-  float box[6];
-  refit_mesh_box(F.nodes4[g.node_begin], box);
-  mesh_updated(F, gi, box);
+  update_on_host(F, gi, nt);
   return was_moved;
 }
 
@@ -330,16 +268,6 @@ static void same_mesh(const char *what, const FlatScene &A, const FlatScene &B, 
   printf("rebuild %-44s guarded %2zu linear %d nodes %4u\n", what, fa.size(), (int)ga.linear, ga.node_count);
 }
 
-// `k` of the mesh's triangles (file indices 0 .. k-1) in the plane z = 0.5, the others where they were
-static Tris with_in_plane(const Tris &t, size_t k) {
-  Tris out(t);
-  for (size_t i = 0; i < k && i < out.size(); i++) {
-    const float x = U(-1, 1), y = U(-1, 1);
-    out[i].p1 = ctr_vec3{x, y, 0.5f}; out[i].p2 = ctr_vec3{x + 0.3f, y + 0.05f, 0.5f}; out[i].p3 = ctr_vec3{x + 0.1f, y + 0.35f, 0.5f};
-  }
-  return out;
-}
-
 static void check_install() {
   Tris a = random_tris(150, 1.5f, 0.3f), b = random_tris(12, 0.5f, 0.4f);
   for (ctr_triangle &t : a) { t.p1.z += 3.f; t.p2.z += 3.f; t.p3.z += 3.f; }  // (off the plane z = 0.5)
@@ -350,11 +278,11 @@ static void check_install() {
   {
     const Scene s = scene_of(a, Tris());
     FlatScene A = flat_of(s.desc), B = flat_of(s.desc);
-    guard_dirty(A);
-    guard_dirty(B);
+    guard(A, EYE);
+    guard(B, EYE);
     const size_t nodes_before = A.nodes4.size();
     const bool mv = rebuild_on_host(A, 0, host_mesh_tree(a.data(), a.size()), a);
-    guard_dirty(A);
+    guard(A, EYE);
     CHECK(!mv && A.nodes4.size() == nodes_before, "in place: the builder's own tree moved");
     same_flat("in place, the builder's own tree", A, B);
     printf("install in place: moved %d\n", (int)mv);
@@ -362,10 +290,10 @@ static void check_install() {
     const Tris am = moved(a, 0.8f, 0.1f);
     const MeshTree T = lbvh_tree(am);
     const bool mv2 = rebuild_on_host(A, 0, T, am);
-    guard_dirty(A);
+    guard(A, EYE);
     const Scene s2 = scene_of(am, Tris());
     FlatScene B2 = flat_of(s2.desc);
-    guard_dirty(B2);
+    guard(B2, EYE);
     CHECK(mv2 == (T.nodes.size() > B.guards[0].node_count), "lbvh: moved %d with %zu nodes for a range of %u", (int)mv2, T.nodes.size(), B.guards[0].node_count);
     same_mesh("one mesh, LBVH tree", A, B2, 0, am);
   }
@@ -373,15 +301,15 @@ static void check_install() {
   // ---- two meshes; leaf size 1: more nodes than the range holds, the mesh moves ----
   const Scene s0 = scene_of(a, b);
   FlatScene A = flat_of(s0.desc);
-  guard_dirty(A);
+  guard(A, EYE);
   CHECK(!build_merged_tree(A).empty() && A.merged.built, "the merged tree of two meshes builds");
-  guard_dirty(A);
+  guard(A, EYE);
   {
     const FlatScene before = A;
     const MeshTree T1 = host_mesh_tree(a.data(), a.size(), 1);
     CHECK(T1.nodes.size() > before.guards[0].node_count, "leaf size 1 gives %zu nodes, no more than %u", T1.nodes.size(), before.guards[0].node_count);
     const bool mv = rebuild_on_host(A, 0, T1, a);
-    guard_dirty(A);
+    guard(A, EYE);
     const MeshGuard &g = A.guards[0], &o = A.guards[1], &o0 = before.guards[1];
     CHECK(mv && g.node_begin == before.nodes4.size() && g.node_count == T1.nodes.size() && g.node_cap == g.node_count &&
           A.nodes4.size() == before.nodes4.size() + T1.nodes.size() + 1u, "moved: range (%u, %u) in an array of %zu, before %zu", g.node_begin, g.node_count, A.nodes4.size(), before.nodes4.size());
@@ -395,12 +323,12 @@ static void check_install() {
     for (uint32_t i = 0; i < g.node_count; i++)
       CHECK(!memcmp(A.nodes4[g.node_begin + i].child, T1.nodes[i].child, 16) && A.nodes4[g.node_begin + i].axis == T1.nodes[i].axis, "moved: node %u is not the builder's", i);
     FlatScene B = flat_of(s0.desc);
-    guard_dirty(B);
+    guard(B, EYE);
     same_mesh("two meshes, leaf size 1: moved", A, B, 0, a);
     printf("install leaf size 1: moved %d nodes %u range %u\n", (int)mv, g.node_count, before.guards[0].node_count);
     // a smaller tree afterwards fits the new range: in place again
     const bool mv2 = rebuild_on_host(A, 0, host_mesh_tree(a.data(), a.size()), a);
-    guard_dirty(A);
+    guard(A, EYE);
     CHECK(!mv2 && A.guards[0].node_begin == g.node_begin && A.guards[0].node_cap == T1.nodes.size(), "a smaller tree after the move moved again");
     same_mesh("two meshes, back to leaf size 4: in place", A, B, 0, a);
   }
@@ -411,7 +339,7 @@ static void check_install() {
       {"70 again: linear payload after refit", with_in_plane(moved(a, 0.1f, 0.0f), 70), true}, {"none in the plane", moved(a, -0.3f, 0.01f), false}};
   for (const Step &st : steps) {
     rebuild_on_host(A, 0, lbvh_tree(st.tris), st.tris);
-    const std::vector<DirtyRange> dirty = guard_dirty(A);
+    const std::vector<DirtyRange> dirty = guard(A, EYE);
     bool payload = false;
     for (const DirtyRange &r : dirty)
       if (r.array == DirtyRange::NODES4 && r.begin == A.guards[0].node_begin && !r.payload.empty()) {
@@ -422,19 +350,19 @@ static void check_install() {
             if (N.child[c] != BVH_LEAF_FLAG) CHECK(N.lo[0][c] == -3.0e38f && N.hi[2][c] == 3.0e38f, "%s: payload slot not unbounded", st.what);
       }
     CHECK(payload == st.linear, "%s: unbounded payload %s", st.what, payload ? "sent" : "not sent");
-    CHECK(guard_dirty(A).empty(), "%s: the same cameras again change nothing", st.what);
+    CHECK(guard(A, EYE).empty(), "%s: the same cameras again change nothing", st.what);
     const Scene s1 = scene_of(st.tris, b);
     FlatScene B = flat_of(s1.desc);
-    guard_dirty(B);
+    guard(B, EYE);
     same_mesh(st.what, A, B, 0, st.tris);
   }
   // ---- the reflective 12-triangle mesh rebuilt: its triangles are mirrors, the virtual eyes follow ----
   const Tris b2 = moved(b, 1.0f, 0.0f);
   rebuild_on_host(A, 1, lbvh_tree(b2), b2);
-  guard_dirty(A);
+  guard(A, EYE);
   const Scene s2 = scene_of(steps[4].tris, b2);
   FlatScene B = flat_of(s2.desc);
-  guard_dirty(B);
+  guard(B, EYE);
   same_mesh("reflective mesh rebuilt", A, B, 1, b2);
   same_mesh("reflective mesh rebuilt: the other mesh", A, B, 0, steps[4].tris);
 }

@@ -12,52 +12,9 @@
 //              mesh_updated and the guard) against a scene flattened from the replaced triangles: per FILE triangle the same
 //              record, normal and plane bytes, the same boxes, the same guarded triangles, and a mesh that is linear before
 //              and after an update gets its unbounded payload again
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
 #include <set>
-#include <vector>
 
-#include "bvh.h"
-#include "cutrace_host.h"
-#include "guard.h"
-#include "mesh_refit.h"
-#include "scene_flatten.h"
-#include "tri_record.h"
-
-static int fails = 0;
-#define CHECK(c, ...) do { if (!(c)) { if (fails++ < 40) { printf("FAIL %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
-
-static std::mt19937 rng(11);
-static float U(float lo, float hi) { return std::uniform_real_distribution<float>(lo, hi)(rng); }
-
-typedef std::vector<ctr_triangle> Tris;
-
-static Tris random_tris(size_t n, float spread, float size) {
-  Tris t(n);
-  for (ctr_triangle &q : t) {
-    const ctr_vec3 o{U(-spread, spread), U(-spread, spread), U(-spread, spread)};
-    ctr_vec3 *p[3] = {&q.p1, &q.p2, &q.p3};
-    for (ctr_vec3 *v : p) *v = ctr_vec3{o.x + U(-size, size), o.y + U(-size, size), o.z + U(-size, size)};
-  }
-  return t;
-}
-
-// a rotation about (1, 2, 3) by `angle` plus a per-vertex wobble
-static Tris moved(const Tris &t, float angle, float wobble) {
-  const double k[3] = {1 / std::sqrt(14.0), 2 / std::sqrt(14.0), 3 / std::sqrt(14.0)}, c = std::cos(angle), s = std::sin(angle);
-  auto rot = [&](ctr_vec3 v) {
-    const double d = k[0] * v.x + k[1] * v.y + k[2] * v.z;
-    const double cr[3] = {k[1] * v.z - k[2] * v.y, k[2] * v.x - k[0] * v.z, k[0] * v.y - k[1] * v.x};
-    return ctr_vec3{(float)(v.x * c + cr[0] * s + k[0] * d * (1 - c)) + U(-wobble, wobble), (float)(v.y * c + cr[1] * s + k[1] * d * (1 - c)) + U(-wobble, wobble),
-                    (float)(v.z * c + cr[2] * s + k[2] * d * (1 - c)) + U(-wobble, wobble)};
-  };
-  Tris out(t);
-  for (ctr_triangle &q : out) { q.p1 = rot(q.p1); q.p2 = rot(q.p2); q.p3 = rot(q.p3); }
-  return out;
-}
+#include "edit_check_common.h"
 
 static std::vector<BvhInput> boxes_of(const Tris &t) {
   std::vector<BvhInput> prims(t.size());
@@ -70,26 +27,6 @@ static std::vector<BvhInput> boxes_of(const Tris &t) {
     }
   }
   return prims;
-}
-
-// the refit of one tree on the host, level by level as the device launches it
-static void refit_on_host(std::vector<DNode4> &nodes, const LevelSchedule &S, const std::vector<DTri> &recs, const Tris &verts) {
-  for (size_t h = 0; h < S.levels(); h++)
-    for (uint32_t i = S.begin[h]; i < S.begin[h + 1]; i++)
-      for (int c = 0; c < 4; c++) refit_slot(nodes.data(), S.nodes[i], c, recs.data(), &verts[0].p1.x);
-}
-
-// min / max over the vertices of every triangle below descriptor `d`
-static void brute(const std::vector<DNode4> &nodes, uint32_t d, const std::vector<uint32_t> &order, const Tris &verts, float *lo, float *hi) {
-  if (d == BVH_LEAF_FLAG) return;
-  if (d & BVH_LEAF_FLAG) {
-    for (uint32_t k = d & 0xFFFFFFu; k < (d & 0xFFFFFFu) + ((d >> 24) & 0x7Fu); k++) {
-      const float *v = &verts[order[k]].p1.x;
-      for (int j = 0; j < 9; j++) { lo[j % 3] = std::min(lo[j % 3], v[j]); hi[j % 3] = std::max(hi[j % 3], v[j]); }
-    }
-    return;
-  }
-  for (int c = 0; c < 4; c++) brute(nodes, nodes[d].child[c], order, verts, lo, hi);
 }
 
 static void check_tree(const char *what, const Tris &tris, bool zero_free) {
@@ -126,7 +63,7 @@ static void check_tree(const char *what, const Tris &tris, bool zero_free) {
   for (uint32_t k = 0; k < n; k++) make_tri(tris[order[k]].p1, tris[order[k]].p2, tris[order[k]].p3, order[k], recs[k], gn);
   // ---- identity refit against the builder's boxes ----
   std::vector<DNode4> same(nodes);
-  refit_on_host(same, S, recs, tris);
+  refit_on_host(same.data(), S, recs.data(), tris);
   size_t value_diff = 0, byte_diff = 0;
   for (uint32_t i = 0; i < nn; i++)
     for (int c = 0; c < 4; c++)
@@ -141,7 +78,7 @@ static void check_tree(const char *what, const Tris &tris, bool zero_free) {
   // ---- refit with moved vertices against brute force ----
   const Tris mv = moved(tris, 0.7f, 0.05f);
   std::vector<DNode4> re(nodes);
-  refit_on_host(re, S, recs, mv);
+  refit_on_host(re.data(), S, recs.data(), mv);
   for (uint32_t i = 0; i < nn; i++)
     for (int c = 0; c < 4; c++) {
       if (re[i].child[c] == BVH_LEAF_FLAG) {
@@ -161,32 +98,6 @@ static void check_tree(const char *what, const Tris &tris, bool zero_free) {
 }
 
 // ---- a small scene: a mesh of `a`, a plane, a reflective mesh of `b`, one light ----
-struct Scene {
-  std::vector<ctr_object> objects;
-  Tris triangles;
-  std::vector<ctr_light> lights;
-  std::vector<ctr_material> materials;
-  ctr_scene_desc desc{};
-  void mesh(const Tris &t, uint64_t mat) {
-    ctr_object o{};
-    o.type = CTR_OBJ_MESH;
-    o.mat_idx = mat;
-    o.tri_begin = triangles.size();
-    o.tri_count = t.size();
-    ctr_mesh_bounds(t.data(), t.size(), &o.v0, &o.v1);
-    triangles.insert(triangles.end(), t.begin(), t.end());
-    objects.push_back(o);
-  }
-  const ctr_scene_desc &finish() {
-    desc.objects = objects.data(); desc.n_objects = objects.size();
-    desc.triangles = triangles.data(); desc.n_triangles = triangles.size();
-    desc.lights = lights.data(); desc.n_lights = lights.size();
-    desc.materials = materials.data(); desc.n_materials = materials.size();
-    desc.cam.w = desc.cam.h = 16;
-    return desc;
-  }
-};
-
 static Scene scene_of(const Tris &a, const Tris &b) {
   Scene s;
   ctr_material m{};
@@ -200,45 +111,11 @@ static Scene scene_of(const Tris &a, const Tris &b) {
   l.v = ctr_vec3{5.f, 6.f, 7.03f};
   s.lights.push_back(l);
   s.mesh(a, 0);
-  ctr_object p{};
-  p.type = CTR_OBJ_PLANE;
-  p.v0 = ctr_vec3{0, -9, 0};
-  p.v1 = ctr_vec3{0, 1, 0};
-  s.objects.push_back(p);
+  s.plane(ctr_vec3{0, -9, 0}, ctr_vec3{0, 1, 0}, 0);
   s.mesh(b, 1);
+  s.cam.w = s.cam.h = 16;
   s.finish();
   return s;
-}
-
-static FlatScene flat_of(const Scene &s) {
-  FlatScene F;
-  std::string err;
-  if (validate_desc(s.desc, err) || flatten_scene(s.desc, F, err)) { printf("FAIL flatten: %s\n", err.c_str()); exit(1); }
-  return F;
-}
-
-static std::vector<DirtyRange> guard(FlatScene &F, const float *eye) {
-  DCam c{};
-  for (int a = 0; a < 3; a++) c.pos[a] = eye[a];
-  return apply_guards(F, plan_guards(F, std::vector<DCam>(1, c)));
-}
-
-// ctr_scene_update_mesh on the host copy: what update_tris and refit_level do on the device, then mesh_updated
-static void update_on_host(FlatScene &F, size_t gi, const Tris &nt) {
-  MeshGuard &g = F.guards[gi];
-  for (uint32_t k = 0; k < g.tri_count; k++) {
-    const uint32_t orig = F.tris[g.tri_begin + k].orig;
-    make_tri(nt[orig].p1, nt[orig].p2, nt[orig].p3, orig, F.tris[g.tri_begin + k], &F.gn[4 * (g.tri_begin + orig)]);
-    guard_plane(nt[orig].p1, nt[orig].p2, nt[orig].p3, &g.planes[CTR_PLANE_DOUBLES * k]);
-  }
-  LevelSchedule S;
-  CHECK(level_schedule(&F.nodes4[g.node_begin], g.node_count, g.tri_count, S), "update: no schedule");
-  for (size_t h = 0; h < S.levels(); h++)
-    for (uint32_t i = S.begin[h]; i < S.begin[h + 1]; i++)
-      for (int c = 0; c < 4; c++) refit_slot(&F.nodes4[g.node_begin], S.nodes[i], c, &F.tris[g.tri_begin], &nt[0].p1.x);
-  float box[6];
-  refit_mesh_box(F.nodes4[g.node_begin], box);
-  mesh_updated(F, gi, box);
 }
 
 // the mesh's records, normals and planes of A and B agree per FILE triangle; its boxes and the scene's agree as values
@@ -291,16 +168,6 @@ static void top_level_holds(const char *what, const FlatScene &F, uint32_t d, fl
   }
 }
 
-// `k` of the mesh's triangles (file indices 0 .. k-1) in the plane z = 0.5, the others where they were
-static Tris with_in_plane(const Tris &t, size_t k) {
-  Tris out(t);
-  for (size_t i = 0; i < k && i < out.size(); i++) {
-    const float x = U(-1, 1), y = U(-1, 1);
-    out[i].p1 = ctr_vec3{x, y, 0.5f}; out[i].p2 = ctr_vec3{x + 0.3f, y + 0.05f, 0.5f}; out[i].p3 = ctr_vec3{x + 0.1f, y + 0.35f, 0.5f};
-  }
-  return out;
-}
-
 static void check_records_and_update() {
   const float eye[3] = {0.3f, 0.2f, 0.5f};
   Tris a = random_tris(150, 1.5f, 0.3f), b = random_tris(12, 0.5f, 0.4f);
@@ -308,7 +175,7 @@ static void check_records_and_update() {
   a.push_back(ctr_triangle{{0.1f, 0.1f, 2.f}, {0.1f, 0.1f, 2.f}, {0.1f, 0.1f, 2.f}});  // zero area: a point, three points of a line
   a.push_back(ctr_triangle{{0, 0, 2.f}, {0.5f, 0.5f, 2.f}, {1, 1, 2.f}});
   const Scene s0 = scene_of(a, b);
-  FlatScene A = flat_of(s0);
+  FlatScene A = flat_of(s0.desc);
   // ---- records: tri_record.h against flatten_scene, byte for byte ----
   size_t bad = 0;
   for (const MeshGuard &g : A.guards) {
@@ -352,7 +219,7 @@ static void check_records_and_update() {
     CHECK(payload == st.linear, "%s: unbounded payload %s", st.what, payload ? "sent" : "not sent");
     CHECK(guard(A, eye).empty(), "%s: the same cameras again change nothing", st.what);
     const Scene s1 = scene_of(st.tris, b);
-    FlatScene B = flat_of(s1);
+    FlatScene B = flat_of(s1.desc);
     guard(B, eye);
     same_mesh(st.what, A, B, 0);
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -369,7 +236,7 @@ static void check_records_and_update() {
   update_on_host(A, 1, b2);
   guard(A, eye);
   const Scene s2 = scene_of(steps[4].tris, b2);
-  FlatScene B = flat_of(s2);
+  FlatScene B = flat_of(s2.desc);
   guard(B, eye);
   same_mesh("reflective mesh moved", A, B, 1);
   same_mesh("reflective mesh moved: the other mesh", A, B, 0);
@@ -378,6 +245,7 @@ static void check_records_and_update() {
 }
 
 int main() {
+  rng.seed(11);  // (this program's own seed: before the first draw)
   auto flat_set = [](size_t n) { Tris t = random_tris(n, 5.f, 0.4f); for (ctr_triangle &q : t) q.p1.x = q.p2.x = q.p3.x = 1.25f; return t; };
   auto cluster = [](size_t n) {  // triangle sizes over many octaves: the SAH tree is too deep, bvh4_build falls back to the depth-bounded rebuild
     Tris t = random_tris(n, 1.f, 0.01f);

@@ -20,29 +20,9 @@
 #include <algorithm>
 
 #include "edit_check_common.h"
-#include "mesh_refit.h"
-#include "tri_record.h"
 
 // material indices every scene here has
 enum { OPAQUE = 0, OTHER = 1, GLASS = 2, MIRROR = 3 };
-
-// ctr_scene_update_mesh on the host copy: what update_tris and refit_level do on the device, then mesh_updated
-static void update_on_host(FlatScene &F, size_t gi, const Tris &nt) {
-  MeshGuard &g = F.guards[gi];
-  for (uint32_t k = 0; k < g.tri_count; k++) {
-    const uint32_t orig = F.tris[g.tri_begin + k].orig;
-    make_tri(nt[orig].p1, nt[orig].p2, nt[orig].p3, orig, F.tris[g.tri_begin + k], &F.gn[4 * (g.tri_begin + orig)]);
-    guard_plane(nt[orig].p1, nt[orig].p2, nt[orig].p3, &g.planes[CTR_PLANE_DOUBLES * k]);
-  }
-  LevelSchedule S;
-  CHECK(level_schedule(&F.nodes4[g.node_begin], g.node_count, g.tri_count, S), "update: no schedule");
-  for (size_t h = 0; h < S.levels(); h++)
-    for (uint32_t i = S.begin[h]; i < S.begin[h + 1]; i++)
-      for (int c = 0; c < 4; c++) refit_slot(&F.nodes4[g.node_begin], S.nodes[i], c, &F.tris[g.tri_begin], &nt[0].p1.x);
-  float box[6];
-  refit_mesh_box(F.nodes4[g.node_begin], box);
-  mesh_updated(F, gi, box);
-}
 
 // what ctr_scene_set_objects does to the host copy: every check before the first write, the records, the guard
 static int set_objects(FlatScene &F, const std::vector<DCam> &cams, const ctr_object *objects, uint64_t n, std::string &err) {

@@ -204,7 +204,7 @@ int scene_mode(const char *path) {
   if (validate_desc(d, err) || flatten_scene(d, F, err)) { printf("invalid: %s\n", err.c_str()); return 2; }
   DSceneHead H;
   fill_scene_head(F, F.tlas_root, H);
-  fill_room_facts(F, H, wall_skip_switched_off());
+  fill_room_facts(F, H, env_switch("CUTRACE_NO_WALL_SKIP"));
   // does the box hold the triple's plane points and the point lights?
   bool holds = true;
   for (int k = 0; k < 6; k++)
