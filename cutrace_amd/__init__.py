@@ -735,9 +735,28 @@ class DeviceScene:
                 self._h, int(obj), C.c_void_p(ptr or None), int(triangles.shape[0]), _lib.REBUILD_HOST if builder == "host" else 0, C.byref(info), raw))
         return {k: int(getattr(info, k)) for k in ("builder", "fell_back", "node_count", "levels", "moved")}
 
+    def replace_mesh(self, obj, triangles, builder="device", stream=None):
+        """rebuild_mesh with ANOTHER triangle count (ctr_scene_replace_mesh, include/cutrace_replace.h): `triangles` is (n, 3, 3)
+        float32 with any n from 1 to 0xFFFFFF — an isosurface extracted anew, a level-of-detail switch, a body that fractures.
+        The same inputs, builders and stream as rebuild_mesh, the same results bit for bit as a scene created with these
+        triangles; the handle keeps its buffers, its tile history and its other meshes.  Returns what was built and what moved:
+        builder, fell_back, node_count, levels as rebuild_mesh; nodes_moved, tris_moved (1: that range of the mesh lives at the
+        end of its array now, with room for twice what it had); tri_cap (the triangles the mesh's range has room for now).
+        n = 0, an object that is not a mesh or is an empty mesh, or a vertex that is not finite raise RuntimeError and leave the
+        scene as it was."""
+        if builder not in ("device", "host"):
+            raise ValueError(f"builder: expected 'device' or 'host', got {builder!r}")
+        dev = self._torch_device()
+        triangles, ptr = self._mesh_triangles(triangles, dev)
+        info = _lib.ReplaceInfo()
+        with _on_stream(dev, stream) as raw:
+            _check("ctr_scene_replace_mesh", _lib.hip_lib().ctr_scene_replace_mesh(
+                self._h, int(obj), C.c_void_p(ptr or None), int(triangles.shape[0]), _lib.REPLACE_HOST if builder == "host" else 0, C.byref(info), raw))
+        return {k: int(getattr(info, k)) for k in ("builder", "fell_back", "node_count", "levels", "nodes_moved", "tris_moved", "tri_cap")}
+
     @staticmethod
     def _mesh_triangles(triangles, dev):
-        """update_mesh's and rebuild_mesh's input, checked: (the array or tensor to keep alive, its address)"""
+        """update_mesh's, rebuild_mesh's and replace_mesh's input, checked: (the array or tensor to keep alive, its address)"""
         import torch
         if isinstance(triangles, torch.Tensor):
             if triangles.device != dev:

@@ -71,6 +71,12 @@ class RebuildInfo(C.Structure):
                 ("moved", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class ReplaceInfo(C.Structure):
+    """ctr_replace_info (include/cutrace_replace.h)"""
+    _fields_ = [("builder", C.c_uint32), ("fell_back", C.c_uint32), ("node_count", C.c_uint32), ("levels", C.c_uint32),
+                ("nodes_moved", C.c_uint32), ("tris_moved", C.c_uint32), ("tri_cap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class RayQuery(C.Structure):
     """ctr_ray_query (include/cutrace_rays.h)"""
     _fields_ = [("n_rays", C.c_uint64), ("flags", C.c_uint32), ("min_t", C.c_float), ("max_t", C.c_float),
@@ -213,6 +219,9 @@ HIP_LATER_PROTOS = {
     "cutrace_rebuild.h": {
         "ctr_scene_rebuild_mesh": ([_ptr, _u32, _ptr, _u64, _u32, _P(RebuildInfo), _ptr], _int),
     },
+    "cutrace_replace.h": {
+        "ctr_scene_replace_mesh": ([_ptr, _u32, _ptr, _u64, _u32, _P(ReplaceInfo), _ptr], _int),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -227,6 +236,8 @@ EDIT_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_edit.h"])
 OBJECT_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_objects.h"])
 REBUILD_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_rebuild.h"])
 REBUILD_HOST = 1   # CTR_REBUILD_HOST
+REPLACE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_replace.h"])
+REPLACE_HOST = 1   # CTR_REPLACE_HOST
 
 _host = None
 _hip = None

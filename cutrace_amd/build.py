@@ -3,7 +3,7 @@
   libcutrace_host.so   g++    host side: JSON loader, STL reader, image writers
   libcutrace_amd.so    hipcc  gfx950 render, ray-query, surface-shading and display-quantise kernels + the C-ABI of include/cutrace_amd.h (csrc/ctr_scene.cpp,
                               csrc/ctr_render.cpp, csrc/ctr_multi.hip), cutrace_rays.h (csrc/ctr_rays.cpp) and cutrace_update.h (csrc/ctr_update.cpp,
-                              csrc/mesh_update.hip), cutrace_rebuild.h (csrc/ctr_update.cpp, csrc/mesh_build.hip) and cutrace_edit.h + cutrace_objects.h (csrc/ctr_edit.cpp, csrc/guard_scan.hip); what they share: csrc/ctr_internal.h
+                              csrc/mesh_update.hip), cutrace_rebuild.h + cutrace_replace.h (csrc/ctr_update.cpp, csrc/mesh_build.hip) and cutrace_edit.h + cutrace_objects.h (csrc/ctr_edit.cpp, csrc/guard_scan.hip); what they share: csrc/ctr_internal.h
   cutrace              hipcc  the drop-in CLI (`cutrace <scene.json>`, reference main.cu)
 
 Everything float-sensitive is compiled with -ffp-contract=off so that each float

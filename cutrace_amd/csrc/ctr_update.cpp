@@ -1,6 +1,7 @@
-// ctr_update.cpp — the host half of include/cutrace_update.h (ctr_scene_update_mesh, ctr_scene_mesh_box) and of
-// include/cutrace_rebuild.h (ctr_scene_rebuild_mesh).  No HIP kernels here: the device halves are mesh_update.hip and
-// mesh_build.hip, the arithmetic both sides share is tri_record.h, mesh_refit.h and lbvh.h.
+// ctr_update.cpp — the host half of include/cutrace_update.h (ctr_scene_update_mesh, ctr_scene_mesh_box), of
+// include/cutrace_rebuild.h (ctr_scene_rebuild_mesh) and of include/cutrace_replace.h (ctr_scene_replace_mesh).  No HIP kernels
+// here: the device halves are mesh_update.hip and mesh_build.hip, the arithmetic both sides share is tri_record.h, mesh_refit.h
+// and lbvh.h.
 //
 // An update in five steps:
 //   1. arguments and vertices are checked; nothing of the handle has changed when the call fails here
@@ -21,6 +22,9 @@
 //   1c. mesh_rebuilt (scene_flatten.cpp) installs the shape in the host copy; the device receives the descriptors and the
 //       records' new `orig`
 // and steps 2 .. 5 run with the NEW schedule.
+//
+// A replace is a rebuild whose triangle count may differ from the mesh's: 1b also works out where the mesh's triangle and node
+// ranges will live (scene_flatten.h replace_room) and grows d_tris, d_gnorm and d_nodes4 for them, and 1c is mesh_replaced.
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
@@ -33,7 +37,9 @@
 
 #include "ctr_internal.h"
 #include "cutrace_rebuild.h"
+#include "cutrace_replace.h"
 #include "cutrace_update.h"
+#include "guard.h"
 #include "mesh_build.h"
 #include "mesh_refit.h"
 #include "mesh_update.h"
@@ -112,7 +118,7 @@ struct BackLayout {
   }
 };
 
-// What the two calls share: the edit they are (the handle's lock from here on), and what is known once the arguments name a mesh
+// What the three calls share: the edit they are (the handle's lock from here on), and what is known once the arguments name a mesh
 struct MeshCall {
   const Edit edit;
   ctr_scene *s;
@@ -128,13 +134,16 @@ struct MeshCall {
   MeshCall(ctr_scene *scene, const char *name) : edit(scene), s(scene), who(std::string(name) + ": "), stamp(name + 10 /* past "ctr_scene_" */) {}
 };
 
-// ---- 1. the arguments: `object` is a non-empty mesh of n_tris triangles; the scene's device becomes current ----
-int mesh_arguments(MeshCall &c, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream) {
+// ---- 1. the arguments: `object` is a non-empty mesh of n_tris triangles — or, with any_count, of any number of them and n_tris a
+// count a mesh may have; the scene's device becomes current ----
+int mesh_arguments(MeshCall &c, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream, bool any_count = false) {
   const FlatScene &F = c.s->flat;
   if (object >= F.objs.size() || F.objs[object].type != CTR_OBJ_MESH)
     return fail(CTR_E_INVALID, c.who + "object #" + std::to_string(object) + " is not a mesh");
   if (F.objs[object].tri_count == 0) return fail(CTR_E_INVALID, c.who + "object #" + std::to_string(object) + " is an empty mesh");
-  if (n_tris != F.objs[object].tri_count)
+  if (any_count && (n_tris == 0 || n_tris > CTR_MESH_TRIS_MAX))
+    return fail(CTR_E_INVALID, c.who + std::to_string(n_tris) + " triangles: a mesh has 1 .. " + std::to_string(CTR_MESH_TRIS_MAX));
+  if (!any_count && n_tris != F.objs[object].tri_count)
     return fail(CTR_E_INVALID, c.who + std::to_string(n_tris) + " triangles for a mesh of " + std::to_string(F.objs[object].tri_count) +
                                    ": the count is fixed");
   size_t gi = 0;
@@ -283,6 +292,97 @@ int device_shape(MeshCall &c, std::vector<DNode4> &sparse, std::vector<uint32_t>
   return CTR_OK;
 }
 
+// What a rebuild or a replace built and moved: the fields of ctr_rebuild_info and ctr_replace_info
+struct Built { uint32_t builder = 0, fell_back = 0, node_count = 0, levels = 0, nodes_moved = 0, tris_moved = 0, tri_cap = 0; };
+
+// ---- a rebuild (the count is the mesh's) or a replace (any count): steps 1 .. 5 ----
+int rebuild_or_replace(MeshCall &c, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, bool host_builder, bool replace, void *hip_stream,
+                       Built &built) {
+  ctr_scene *s = c.s;
+  const std::string &who = c.who;
+  if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream, replace)) return st;
+  FlatScene &F = s->flat;
+  const uint32_t n = c.n;
+  if (int st = vertices_and_buffers(c, n)) return st;  // (a four-wide tree over n triangles has at most n nodes)
+  c.stamp("checks");
+
+  // ---- 1a., 1b. a tree: the device's, accepted; or the host's ----
+  MeshTree tree;
+  if (!host_builder) {
+    std::vector<DNode4> sparse;
+    if (int st = device_shape(c, sparse, tree.order)) return st;
+    if (!lbvh_accept(sparse.data(), (uint32_t)sparse.size(), tree.order.data(), n, BVH_LEAF, tree.nodes)) built.fell_back = 1;
+    c.stamp("host accept");
+  }
+  if (host_builder || built.fell_back) {
+    built.builder = 1;
+    std::vector<ctr_triangle> from_device;
+    const ctr_triangle *host_tris = tris;
+    if (c.where == Where::DEVICE) {  // (the finiteness check has waited for whatever produced them)
+      from_device.resize(n);
+      HIP_TRY(hipMemcpy(from_device.data(), tris, n * sizeof(ctr_triangle), hipMemcpyDeviceToHost));
+      host_tris = from_device.data();
+    }
+    tree = host_mesh_tree(host_tris, n);
+    c.stamp("host build");
+  }
+  bool ok = tree.order.size() == n && !tree.nodes.empty();
+  for (uint32_t k = 0; ok && k < n; k++) ok = tree.order[k] < n;
+  if (!ok) return fail(CTR_E_INVALID, who + "the builder's tree is not one the refit can walk");
+  const uint32_t count = (uint32_t)tree.nodes.size();
+  std::unique_ptr<MeshRefit> refit;
+  if (int st = refit_of_tree(tree.nodes.data(), count, n, who, refit)) return st;
+  // where the mesh's ranges will live: a rebuild moves a tree that does not fit into exactly its room, a replace leaves room to grow
+  const ReplaceRoom room = replace_room(F, c.gi, n, count, replace ? CTR_REPLACE_GROWTH : 1u);
+  if (room.tris_after > CTR_SCENE_TRIS_MAX)
+    return fail(CTR_E_INVALID, who + std::to_string(room.tris_after) + " triangle records: more than the scene's arrays can address");
+  const uint32_t n_before = F.guards[c.gi].tri_count;
+  if (int st = s->upd_back.reserve(BackLayout(n, count).end)) return st;
+  if (int st = s->rb_index.reserve(n)) return st;
+  if (n != n_before && s->scan_planes.cap) {
+    // the guard's scan on the device keeps every mesh's planes in one array, this mesh's in the middle of it: with another count
+    // the array is laid out anew (the next scan uploads it whole), and it and the scan's words get their room here, not there.
+    // (Scratch, not scene: should a later step fail, the cost is that upload.)
+    const uint64_t planes_after = guard_plane_count(F) - n_before + n;
+    s->scan_planes_live = false;
+    if (int st = s->scan_planes.reserve(planes_after)) return st;
+    if (int st = reserve_both(s->scan_words, s->scan_back, guard_scan_words(planes_after))) return st;
+  }
+  if (s->refit.size() < F.guards.size()) s->refit.resize(F.guards.size());
+  F.tris.reserve(room.tris_after);
+  F.gn.reserve(4 * room.tris_after);
+  F.nodes4.reserve(room.nodes4_after);
+  F.guards[c.gi].planes.reserve((size_t)CTR_PLANE_DOUBLES * n);
+  if (int st = c.edit.begin()) return st;  // (no launch may still be reading an array either, when it moves)
+  // The same contents in another place (the DEVICE's, which for a linear mesh are not the host copy's): the last steps that can fail
+  // for want of memory.  An array that grew before a later one failed holds what it held, at another address, and every launch
+  // takes the addresses from the handle anew: harmless.
+  const size_t tris_before = F.tris.size();
+  if (int st = s->d_tris.grow(room.tris_after, tris_before)) return st;
+  if (int st = s->d_gnorm.grow(room.tris_after, tris_before)) return st;
+  if (int st = s->d_nodes4.grow(room.nodes4_after, F.nodes4.size())) return st;
+
+  // ---- 1c. the shape goes in: host copy, then the device's descriptors and the records' `orig` ----
+  bool nodes_moved = false, tris_moved = false;
+  const std::vector<DirtyRange> dirty = replace ? mesh_replaced(F, c.gi, n, tree, &tris_moved, &nodes_moved) : mesh_rebuilt(F, c.gi, tree, &nodes_moved);
+  s->refit[c.gi] = std::move(refit);
+  if (int st = upload_dirty(s, dirty)) return st;
+  HIP_TRY(hipMemcpyAsync(s->rb_index.p, tree.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+  if (int st = launched(ctr_launch_set_orig(s->d_tris.as<DTri>() + F.guards[c.gi].tri_begin, s->rb_index.as<uint32_t>(), n, c.stream), "set_orig launch"))
+    return st;
+  if (c.stamp.on) HIP_TRY(hipStreamSynchronize(c.stream));
+  c.stamp("install");
+
+  // ---- 2. .. 5. the update's steps, with the new schedule ----
+  if (int st = update_steps(c, s->refit[c.gi].get())) return st;
+  built.node_count = count;
+  built.levels = (uint32_t)s->refit[c.gi]->sched.levels();
+  built.nodes_moved = nodes_moved ? 1u : 0u;
+  built.tris_moved = tris_moved ? 1u : 0u;
+  built.tri_cap = F.guards[c.gi].tri_cap;
+  return CTR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -305,67 +405,28 @@ int ctr_scene_rebuild_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tr
   if (flags & ~CTR_REBUILD_HOST) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(flags & ~CTR_REBUILD_HOST));
   if (!s || !tris) return fail(CTR_E_INVALID, who + "null argument");
   MeshCall c(s, "ctr_scene_rebuild_mesh");
-  if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream)) return st;
-  FlatScene &F = s->flat;
-  const uint32_t n = c.n;
-  if (int st = vertices_and_buffers(c, n)) return st;  // (a four-wide tree over n triangles has at most n nodes)
-  c.stamp("checks");
-
-  // ---- 1a., 1b. a tree: the device's, accepted; or the host's ----
-  ctr_rebuild_info built{};
-  MeshTree tree;
-  if (!(flags & CTR_REBUILD_HOST)) {
-    std::vector<DNode4> sparse;
-    if (int st = device_shape(c, sparse, tree.order)) return st;
-    if (!lbvh_accept(sparse.data(), (uint32_t)sparse.size(), tree.order.data(), n, BVH_LEAF, tree.nodes)) built.fell_back = 1;
-    c.stamp("host accept");
+  Built built;
+  if (int st = rebuild_or_replace(c, object, tris, n_tris, (flags & CTR_REBUILD_HOST) != 0, false, hip_stream, built)) return st;
+  if (info) {
+    *info = ctr_rebuild_info{};
+    info->builder = built.builder;
+    info->fell_back = built.fell_back;
+    info->node_count = built.node_count;
+    info->levels = built.levels;
+    info->moved = built.nodes_moved;
   }
-  if ((flags & CTR_REBUILD_HOST) || built.fell_back) {
-    built.builder = 1;
-    std::vector<ctr_triangle> from_device;
-    const ctr_triangle *host_tris = tris;
-    if (c.where == Where::DEVICE) {  // (the finiteness check has waited for whatever produced them)
-      from_device.resize(n);
-      HIP_TRY(hipMemcpy(from_device.data(), tris, n * sizeof(ctr_triangle), hipMemcpyDeviceToHost));
-      host_tris = from_device.data();
-    }
-    tree = host_mesh_tree(host_tris, n);
-    c.stamp("host build");
-  }
-  bool ok = tree.order.size() == n && !tree.nodes.empty();
-  for (uint32_t k = 0; ok && k < n; k++) ok = tree.order[k] < n;
-  if (!ok) return fail(CTR_E_INVALID, who + "the builder's tree is not one the refit can walk");
-  const uint32_t count = (uint32_t)tree.nodes.size();
-  std::unique_ptr<MeshRefit> refit;
-  if (int st = refit_of_tree(tree.nodes.data(), count, n, who, refit)) return st;
-  const bool moves = count > F.guards[c.gi].node_cap;
-  const size_t nodes4_after = F.nodes4.size() + (moves ? (size_t)count + 1u : 0u);
-  if (int st = s->upd_back.reserve(BackLayout(n, count).end)) return st;
-  if (int st = s->rb_index.reserve(n)) return st;
-  if (s->refit.size() < F.guards.size()) s->refit.resize(F.guards.size());
-  F.nodes4.reserve(nodes4_after);
-  if (int st = c.edit.begin()) return st;  // (no launch may still be reading the node array either, when it moves)
-  // the same contents in another place (the DEVICE's, which for a linear mesh are not the host copy's): the last step that can
-  // fail for want of memory
-  if (int st = s->d_nodes4.grow(nodes4_after, F.nodes4.size())) return st;
+  return CTR_OK;
+}
 
-  // ---- 1c. the shape goes in: host copy, then the device's descriptors and the records' `orig` ----
-  bool moved = false;
-  const std::vector<DirtyRange> dirty = mesh_rebuilt(F, c.gi, tree, &moved);
-  s->refit[c.gi] = std::move(refit);
-  if (int st = upload_dirty(s, dirty)) return st;
-  HIP_TRY(hipMemcpyAsync(s->rb_index.p, tree.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
-  if (int st = launched(ctr_launch_set_orig(s->d_tris.as<DTri>() + F.guards[c.gi].tri_begin, s->rb_index.as<uint32_t>(), n, c.stream), "set_orig launch"))
-    return st;
-  if (c.stamp.on) HIP_TRY(hipStreamSynchronize(c.stream));
-  c.stamp("install");
-
-  // ---- 2. .. 5. the update's steps, with the new schedule ----
-  if (int st = update_steps(c, s->refit[c.gi].get())) return st;
-  built.node_count = count;
-  built.levels = (uint32_t)s->refit[c.gi]->sched.levels();
-  built.moved = moved ? 1u : 0u;
-  if (info) *info = built;
+int ctr_scene_replace_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, uint32_t flags, ctr_replace_info *info,
+                           void *hip_stream) {
+  const std::string who = "ctr_scene_replace_mesh: ";
+  if (flags & ~CTR_REPLACE_HOST) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(flags & ~CTR_REPLACE_HOST));
+  if (!s || !tris) return fail(CTR_E_INVALID, who + "null argument");
+  MeshCall c(s, "ctr_scene_replace_mesh");
+  Built built;
+  if (int st = rebuild_or_replace(c, object, tris, n_tris, (flags & CTR_REPLACE_HOST) != 0, true, hip_stream, built)) return st;
+  if (info) *info = ctr_replace_info{built.builder, built.fell_back, built.node_count, built.levels, built.nodes_moved, built.tris_moved, built.tri_cap, 0u};
   return CTR_OK;
 }
 

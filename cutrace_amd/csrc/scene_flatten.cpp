@@ -39,7 +39,7 @@ std::vector<MeshTree> mesh_trees(const ctr_scene_desc &d) {
   std::vector<MeshTree> trees(d.n_objects);
   std::vector<uint64_t> mesh_ids;
   for (uint64_t i = 0; i < d.n_objects; i++)
-    if (d.objects[i].type == CTR_OBJ_MESH && d.objects[i].tri_count <= 0xFFFFFFull) mesh_ids.push_back(i);
+    if (d.objects[i].type == CTR_OBJ_MESH && d.objects[i].tri_count <= CTR_MESH_TRIS_MAX) mesh_ids.push_back(i);
   std::atomic<size_t> next{0};
   auto work = [&] {
     for (size_t k; (k = next.fetch_add(1)) < mesh_ids.size();) {
@@ -83,7 +83,7 @@ void mesh_record(const ctr_object &o, const ctr_triangle *src, const MeshTree &t
   g.node_begin = O.node_begin;
   g.node_count = g.node_cap = O.node_count;
   g.tri_begin = O.tri_begin;
-  g.tri_count = n;
+  g.tri_count = g.tri_cap = n;
   g.obj_index = O.index;
   g.planes = guard_planes(src, order);
   F.guards.push_back(std::move(g));
@@ -141,7 +141,7 @@ int object_records(const ctr_scene_desc &d, const std::vector<MeshTree> &trees, 
       F.gn.resize(4 * F.tris.size());
     } else if (o.type == CTR_OBJ_MESH) {
       F.has_mesh = true;
-      if (o.tri_count > 0xFFFFFFull) {
+      if (o.tri_count > CTR_MESH_TRIS_MAX) {
         err = "object #" + std::to_string(i) + ": mesh has more than 2^24 triangles";
         return CTR_E_INVALID;
       }
@@ -353,7 +353,7 @@ void create_stamp(const char *what) {
 
 int validate_desc(const ctr_scene_desc &d, std::string &err) {
   auto bad = [&](const std::string &msg) { err = msg; return CTR_E_INVALID; };
-  if (d.n_objects > 0xFFFFFFFFull || d.n_triangles > 0x7FFFFFFFull || d.cam.w > 0x7FFFFFFFull ||
+  if (d.n_objects > 0xFFFFFFFFull || d.n_triangles > CTR_SCENE_TRIS_MAX || d.cam.w > 0x7FFFFFFFull ||
       d.cam.h > 0x7FFFFFFFull)
     return bad("scene too large for 32-bit device indices");
   if (d.cam.w * d.cam.h > 0x7FFFFFFFull * 2) return bad("image too large");
@@ -491,22 +491,26 @@ MeshTree host_mesh_tree(const ctr_triangle *tris, size_t n, uint32_t leaf_size) 
   return tree;
 }
 
-std::vector<DirtyRange> mesh_rebuilt(FlatScene &F, size_t gi, const MeshTree &tree, bool *moved) {
+namespace {
+// `tree` becomes the tree of mesh guards[gi]: in place when it fits the mesh's node range, else in a new range at the end of
+// nodes4 with room for `cap_if_moved` nodes and the spare node.  The ranges and the root go wherever a record of the mesh keeps
+// them, the records' `orig` take the leaf order (over the guard's CURRENT triangle range and count).
+std::vector<DirtyRange> install_tree(FlatScene &F, size_t gi, const MeshTree &tree, uint32_t cap_if_moved, bool *moved) {
   MeshGuard &g = F.guards[gi];
   const uint32_t count = (uint32_t)tree.nodes.size();
   *moved = count > g.node_cap;
   if (*moved) {  // a new range at the end: the tree's nodes and, right behind them, its spare node
     g.node_begin = (uint32_t)F.nodes4.size();
-    g.node_cap = count;
-    F.nodes4.resize(F.nodes4.size() + count + 1u);
+    g.node_cap = cap_if_moved;
+    F.nodes4.resize(F.nodes4.size() + cap_if_moved + 1u);
   }
   std::copy(tree.nodes.begin(), tree.nodes.end(), F.nodes4.begin() + g.node_begin);
   memset(&F.nodes4[g.node_begin + count], 0, sizeof(DNode4));  // the spare node, unused = all zero (mesh_record)
   for (uint32_t k = count + 1u; k <= g.node_cap; k++) F.nodes4[g.node_begin + k] = empty_node4();
   g.node_count = count;
   std::vector<DirtyRange> dirty{{DirtyRange::NODES4, g.node_begin, (size_t)g.node_cap + 1u, {}}};
-  // the range and the root, wherever a record of the mesh is kept (mesh_updated's list)
-  auto put = [&](DObj &O) { O.node_begin = g.node_begin; O.node_count = count; O.bvh_root = 0; };
+  // the ranges and the root, wherever a record of the mesh is kept (mesh_updated's list)
+  auto put = [&](DObj &O) { O.tri_begin = g.tri_begin; O.tri_count = g.tri_count; O.node_begin = g.node_begin; O.node_count = count; O.bvh_root = 0; };
   put(F.objs[g.obj_index]);
   dirty.push_back({DirtyRange::OBJS, g.obj_index, 1, {}});
   if (g.mesh_pos >= 0) {
@@ -521,6 +525,53 @@ std::vector<DirtyRange> mesh_rebuilt(FlatScene &F, size_t gi, const MeshTree &tr
   for (uint32_t k = 0; k < g.tri_count; k++) F.tris[g.tri_begin + k].orig = tree.order[k];
   F.mesh_bytes = F.tris.size() * sizeof(DTri) + F.nodes.size() * sizeof(DNode) + F.nodes4.size() * sizeof(DNode4);
   F.ray_slots = ray_stack_slots(F);
+  return dirty;
+}
+}  // namespace
+
+std::vector<DirtyRange> mesh_rebuilt(FlatScene &F, size_t gi, const MeshTree &tree, bool *moved) {
+  return install_tree(F, gi, tree, (uint32_t)tree.nodes.size(), moved);
+}
+
+ReplaceRoom replace_room(const FlatScene &F, size_t gi, uint32_t n, uint32_t node_count, uint32_t growth) {
+  const MeshGuard &g = F.guards[gi];
+  ReplaceRoom r;
+  r.tris_move = n > g.tri_cap;
+  r.tri_cap = r.tris_move ? std::max(n, growth * g.tri_cap) : g.tri_cap;
+  r.tris_after = F.tris.size() + (r.tris_move ? (size_t)r.tri_cap + CTR_GUARD_SLOTS : 0u);
+  r.nodes_move = node_count > g.node_cap;
+  r.node_cap = r.nodes_move ? std::max(node_count, growth * g.node_cap) : g.node_cap;
+  r.nodes4_after = F.nodes4.size() + (r.nodes_move ? (size_t)r.node_cap + 1u : 0u);
+  return r;
+}
+
+size_t live_mesh_bytes(const FlatScene &F) {
+  size_t tris = 0, nodes4 = 0;
+  for (const DObj &O : F.objs) tris += O.type == CTR_OBJ_TRIANGLE;
+  for (const MeshGuard &g : F.guards) {
+    tris += g.tri_count + (g.tri_count ? CTR_GUARD_SLOTS : 0u);
+    nodes4 += g.node_count + 1u;
+  }
+  return tris * sizeof(DTri) + F.nodes.size() * sizeof(DNode) + nodes4 * sizeof(DNode4);
+}
+
+std::vector<DirtyRange> mesh_replaced(FlatScene &F, size_t gi, uint32_t n, const MeshTree &tree, bool *tris_moved, bool *nodes_moved) {
+  MeshGuard &g = F.guards[gi];
+  const ReplaceRoom room = replace_room(F, gi, n, (uint32_t)tree.nodes.size());
+  *tris_moved = room.tris_move;
+  if (room.tris_move) {  // a new range at the end: the records and, right behind them, the spare records
+    DTri zero;
+    memset(&zero, 0, sizeof(zero));
+    g.tri_begin = (uint32_t)F.tris.size();
+    g.tri_cap = room.tri_cap;
+    F.tris.resize(room.tris_after, zero);
+    F.gn.resize(4 * room.tris_after, 0.0f);
+  }
+  F.mesh_tris = F.mesh_tris - g.tri_count + n;
+  g.tri_count = n;
+  g.planes.assign((size_t)CTR_PLANE_DOUBLES * n, 0.0);  // (the update's steps fill them)
+  std::vector<DirtyRange> dirty = install_tree(F, gi, tree, room.node_cap, nodes_moved);
+  F.mesh_bytes = live_mesh_bytes(F);
   return dirty;
 }
 

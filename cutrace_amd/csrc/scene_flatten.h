@@ -20,6 +20,11 @@
 constexpr uint32_t BVH_LEAF = CTR_BVH_LEAF;  // triangles per BVH leaf
 
 #define CTR_GUARD_SLOTS 64u  // spare DTri records per mesh (guard.h)
+// The two limits on triangle counts, stated HERE alone (validate_desc and flatten_scene at create, ctr_scene_replace_mesh later):
+// a leaf descriptor and a merged key keep a triangle's position inside its mesh in 24 bits, and every index into the record
+// array must fit the device's 32-bit arithmetic with room to spare.
+constexpr uint64_t CTR_MESH_TRIS_MAX = 0xFFFFFFull;     // triangles of one mesh
+constexpr uint64_t CTR_SCENE_TRIS_MAX = 0x7FFFFFFFull;  // triangles of a description; records of FlatScene::tris after a replace
 #define CTR_MERGED_SPARE_NODES ((CTR_GUARD_SLOTS + 2u) / 3u)  // the merged tree: three meshes' guard leaves per spare node
 
 // Guard of the BVH culling (guard.h): what it needs to know of one mesh, and what it currently has on the device
@@ -27,6 +32,7 @@ struct MeshGuard {
   uint32_t node_begin = 0, node_count = 0;
   uint32_t node_cap = 0;  // tree nodes the mesh's range of nodes4 has room for (+ the spare node): the count it was created or moved with (mesh_rebuilt)
   uint32_t tri_begin = 0, tri_count = 0;  // the mesh's DTri range (leaf order); CTR_GUARD_SLOTS spare records follow it
+  uint32_t tri_cap = 0;  // triangle records the range has room for, the spare records not counted: the count it was created or moved with (mesh_replaced)
   uint32_t obj_index = 0;                 // position in objs
   int mesh_pos = -1;                      // position in meshes (-1: an empty mesh, never walked)
   std::vector<double> planes;  // per triangle (leaf order): unit normal (3), a point of the plane (3), extent
@@ -144,6 +150,34 @@ uint32_t ray_stack_slots(const FlatScene &F);
 // (update_tris, refit_level with the NEW schedule, mesh_box, then mesh_updated, which also resets the guard state).
 // Returns what the device has to receive of this step: the mesh's node range and its records in objs and meshes.
 std::vector<DirtyRange> mesh_rebuilt(FlatScene &F, size_t gi, const MeshTree &tree, bool *moved);
+
+// Another triangle COUNT for mesh guards[gi] (ctr_scene_replace_mesh, include/cutrace_replace.h): `tree` is a tree over the `n` new
+// triangles (1 .. CTR_MESH_TRIS_MAX) that has passed level_schedule, its order a permutation of them.  The mesh owns tri_cap +
+// CTR_GUARD_SLOTS records of tris / gn and node_cap + 1 records of nodes4.
+//   n <= tri_cap   the triangle range stays where it is; the spare records follow the new count, at tri_begin + n; what lies
+//                  behind them is dead
+//   n >  tri_cap   a new range at the END of tris and gn, of max(n, CTR_REPLACE_GROWTH * tri_cap) + CTR_GUARD_SLOTS records
+//                  (*tris_moved = true; the old range is dead, nothing names it any more)
+// and the node range by the same rule with the same factor (mesh_rebuilt's move, with room to grow into; *nodes_moved).  Nothing
+// else moves: a stand-alone triangle's record between two mesh ranges and the merged tree's room stay where they are.
+// tri_begin and tri_count go wherever a record of the mesh keeps them, next to node_begin, node_count and bvh_root = 0 (objs,
+// meshes, the scene-order copy behind the merged pseudo mesh, the MeshGuard); planes takes the new length; the records' `orig`
+// take the tree's leaf order; mesh_tris and ray_slots are derived anew, and mesh_bytes counts the LIVE records only (the
+// ranges the meshes name, the stand-alone triangles, the top-level tree; not the dead ranges, not the merged tree's room, which
+// mesh_updated retires).  As after mesh_rebuilt the records are stale but for `orig` and the update's steps follow.
+// replace_room says beforehand what the call will do, so that the device arrays can grow before anything is written; `growth`
+// 1 is mesh_rebuilt's rule (a tree that does not fit gets exactly its room).
+// Returns what the device has to receive of this step: the mesh's node range and its records in objs and meshes.
+constexpr uint32_t CTR_REPLACE_GROWTH = 2;
+struct ReplaceRoom {
+  bool tris_move, nodes_move;
+  uint32_t tri_cap, node_cap;        // of the mesh afterwards
+  size_t tris_after, nodes4_after;   // records of FlatScene::tris (gn: four floats each) and ::nodes4 afterwards
+};
+ReplaceRoom replace_room(const FlatScene &F, size_t gi, uint32_t n, uint32_t node_count, uint32_t growth = CTR_REPLACE_GROWTH);
+std::vector<DirtyRange> mesh_replaced(FlatScene &F, size_t gi, uint32_t n, const MeshTree &tree, bool *tris_moved, bool *nodes_moved);
+// FlatScene::mesh_bytes of the live records, as mesh_replaced leaves it
+size_t live_mesh_bytes(const FlatScene &F);
 
 // The lights, or the materials, of a flattened scene replaced (flatten_scene itself, and ctr_scene_set_lights and
 // ctr_scene_set_materials of include/cutrace_edit.h): the records, and all_opaque, need_cold, any_bounce and fast_pow_ok derived
