@@ -13,7 +13,7 @@ import oracle
 
 from cutrace_amd import _lib
 from tests import aa_ref
-from tests.test_abi import declared
+from tests.checkers import declared
 from tests.util import _random_scene, same_bits
 
 ROOT = _lib.ROOT

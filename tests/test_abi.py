@@ -1,17 +1,8 @@
 """The C-ABI libraries load and export every symbol the headers declare (no GPU needed)."""
 import ctypes
-import os
-import re
 
 from cutrace_amd import _lib
-
-ROOT = _lib.ROOT
-
-
-def declared(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(ctr_[a-z0-9_]+)\s*\(", txt)))
+from tests.checkers import declared
 
 
 def test_hip_library_exports_every_declared_symbol():

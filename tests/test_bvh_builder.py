@@ -2,19 +2,11 @@
 primitive in exactly one leaf, leaf sizes, boxes containing what is below them, depth limits the kernel's lane stacks rely
 on (scripts/bvh_check.cpp; the same harness runs under ASan/UBSan in scripts/cpu_sanitize.sh)."""
 import os
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.checkers import CSRC, I_CSRC, I_INCLUDE, check_output, check_program
 
 
-def test_bvh_builders_keep_their_invariants(tmp_path):
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path / "bvh_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "cutrace_amd", "csrc"), "-I" + os.path.join(ROOT, "include"),
-                           "-o", exe, os.path.join(ROOT, "scripts", "bvh_check.cpp"), os.path.join(ROOT, "cutrace_amd", "csrc", "bvh.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "all invariants hold" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
+def test_bvh_builders_keep_their_invariants(tmp_path_factory):
+    exe = check_program(tmp_path_factory, "bvh_check", ("-O2", I_CSRC, I_INCLUDE), (os.path.join(CSRC, "bvh.cpp"),))
+    out = check_output(exe)
+    assert "all invariants hold" in out, out[-2000:]

@@ -15,6 +15,7 @@ import oracle
 
 from tests import aa_ref
 from tests.conftest import load_scene
+from tests.gpu_support import gpu  # noqa: F401  (the fixture)
 from tests.util import _random_scene, assert_parity, hall_of_mirrors_json, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -36,13 +37,6 @@ def host_scene(ca, name):
         s = load_scene(ca, "bunny", w, h)
     assert s.ok
     return s
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
 
 
 _want = {}

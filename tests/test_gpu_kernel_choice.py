@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from tests.conftest import load_scene
-from tests.util import _multi_mesh_scene, corner_meshes, fast_pow_kept, mesh_scene, same_bits
+from tests.gpu_support import expected_kernel
+from tests.util import _multi_mesh_scene, corner_meshes, mesh_scene, same_bits
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,9 +19,6 @@ W = H = 16
 REJECTIONS = {0xF001: "supersampling: no build for", 0xF002: "not with the counting / statistics variants",
               0xF003: "CTR_VAR_IGNORE_TRANSPARENT: host-buffer calls only"}
 ENTRIES = ("render", "render_pinned", "render_uv", "render_ss", "device", "device_ss", "algorithmic_bytes")
-# the fixture's entry axis (KernelEntry) and whether the caller's buffers qualify for delivery by the kernel
-FIXTURE_ENTRY = {"render": (0, 0), "render_pinned": (0, 1), "algorithmic_bytes": (1, 0), "render_uv": (2, 0), "render_ss": (3, 0),
-                 "device": (4, 0), "device_ss": (5, 0)}
 
 
 @pytest.fixture(scope="module")
@@ -31,30 +29,6 @@ def golden():
 def _masks(ca):
     return (0, ca.VAR_NO_OCC6, ca.VAR_EXACT_POW, ca.VAR_NO_PREFILTER | ca.VAR_NO_CLUSTER, ca.VAR_NO_ANYHIT, ca.VAR_STATS, ca.VAR_MERGE,
             ca.VAR_IGNORE_TRANSPARENT, ca.VAR_NO_DIRECT)
-
-
-def _expected(ca, golden, host_scene, mask, entry, bounces):
-    """The fixture row of this call: scene flags by the rules of scene_flatten.cpp lights_and_materials, stack shape from bounces.
-    The fixture's rows have fast_pow_ok true; a scene whose exponents and colours put the fast specular path outside the
-    colour tolerance (tests/util.py fast_pow_kept) gets the row of the same call with VAR_EXACT_POW."""
-    d = host_scene.desc.contents
-    mats = [d.materials[i] for i in range(d.n_materials)]
-    meshes = [d.objects[i].tri_count for i in range(d.n_objects) if d.objects[i].type == 1 and d.objects[i].tri_count]
-    all_opaque = all(m.transparency == 0.0 for m in mats)
-    need_cold = any(m.transparency >= 1e-6 and m.reflexivity >= 1e-6 for m in mats)
-    any_bounce = any(m.transparency >= 1e-6 or m.reflexivity >= 1e-6 for m in mats)
-    flags = (1 if all_opaque else 0) | (2 if sum(meshes) >= 1000 else 0) | (4 if len(meshes) >= 2 else 0)
-    # the stack shape matters only through "the 6-wave build fits" (the fixture's rows of the cold shapes equal those of the
-    # plain ones): stacks of 24 waves plus one parking granule each in granules of 1280 bytes, five per wave at most
-    frames, nf = (bounces if bounces > 0 and any_bounce else 1), (10 if need_cold else 4)
-    fits = (frames * nf * 64 * 4 + 1280 + 1279) // 1280 <= 5
-    bits = (ca.VAR_NO_PREFILTER, ca.VAR_NO_ANYHIT, ca.VAR_NO_CLUSTER, ca.VAR_STATS, ca.VAR_EXACT_POW, ca.VAR_NO_OCC6, ca.VAR_NO_DIRECT,
-            ca.VAR_MERGE, ca.VAR_IGNORE_TRANSPARENT)
-    if not fast_pow_kept(host_scene):   # KernelFacts::fast_pow_ok false: the row of the same call with VAR_EXACT_POW
-        mask |= ca.VAR_EXACT_POW
-    m = sum(1 << k for k, b in enumerate(bits) if mask & b)
-    e, deliverable = FIXTURE_ENTRY[entry]
-    return int(golden[e, m, flags, deliverable, 0 if fits else 1])
 
 
 def _call(ds, entry, bounces, dev):
@@ -96,7 +70,7 @@ def test_every_entry_launches_the_build_the_fixture_names(ca, golden, tmp_path, 
         for bounces in (5, 6):  # the 6-wave build's stacks fit up to 5 frames of a bouncing scene
             for entry in ENTRIES:
                 what = (name, hex(mask), bounces, entry)
-                want = _expected(ca, golden, s, mask, entry, bounces)
+                want = expected_kernel(ca, golden, s, mask, entry, bounces)
                 ds.set_variant(mask)
                 if want in REJECTIONS:
                     with pytest.raises(RuntimeError, match=REJECTIONS[want]):

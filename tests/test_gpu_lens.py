@@ -14,6 +14,7 @@ import cutrace_amd
 from cutrace_amd import _lib, lenses
 from tests import aa_ref, ray_ref, shade_ref
 from tests.conftest import load_scene
+from tests.gpu_support import gpu  # noqa: F401  (the fixture)
 from tests.util import TOL, _random_scene, hall_of_mirrors_json, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -37,13 +38,6 @@ def host_scene(ca, name, w, h):
 
 def cam_of(s):
     return s.desc.contents.cam
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
 
 
 def max_depth_of(counters):

@@ -1,62 +1,21 @@
 """Mesh rebuilds on the GPU (include/cutrace_rebuild.h): a handle whose mesh got new vertices AND a new tree through
 rebuild_mesh — the device's linear BVH or the host's builder — against a handle freshly created from the replaced description.
 Every comparison is BITWISE: a tree cannot change a result, only the time a walk takes.  Frames are 96 x 54 or smaller; the shapes
-are the smallest at which each part can go wrong (tests/test_gpu_mesh_update.py's, whose helpers this file borrows)."""
+are the smallest at which each part can go wrong (tests/test_gpu_mesh_update.py's; the helpers are those of tests/live.py)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from cutrace_amd import _lib, scenes
-from tests import test_gpu_mesh_update as base
-from tests.util import mesh_scene
+from tests.gpu_support import assert_same_frame, gpu, same_tensors  # noqa: F401  (gpu: the fixture)
+from tests.live import (BOUNCES, H, KV_MERGE, W, assert_box, assert_equals_fresh, cluster, desc_tris, frame, in_plane_scene, mesh_objects, moved,
+                        on_a_busy_stream, random_mesh, rays_at_the_mesh, scene_with, staircase, with_in_plane)
+from tests.util import mesh_scene, parse
 
 pytestmark = pytest.mark.gpu
 
-W, H, BOUNCES, KV_MERGE = base.W, base.H, base.BOUNCES, base.KV_MERGE
 f32 = np.float32
-random_mesh, moved, scene_with, desc_tris, mesh_objects, frame = base.random_mesh, base.moved, base.scene_with, base.desc_tris, base.mesh_objects, base.frame
-assert_same_frame, assert_equals_fresh, assert_box = base.assert_same_frame, base.assert_updated_equals_fresh, base.assert_box
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
-
-
-def staircase():
-    """scripts/mesh_rebuild_check.cpp's: 63 tiny triangles, their centroids at 2^-m, m = 0 .. 20, on each coordinate axis of the unit
-    cube.  Every Morton key has a highest bit of its own, one peels off per split, and the device's tree is refused."""
-    out = []
-    for m in range(21):
-        for axis in range(3):
-            c = np.zeros(3, f32)
-            c[axis] = np.ldexp(f32(1), -m)
-            e = np.where(c != 0, np.ldexp(c, -10), np.ldexp(f32(1), -30)).astype(f32)
-            out.append([c - e, c + e, [c[0] + e[0], c[1] - e[1], c[2]]])
-    return np.asarray(out, f32)
-
-
-def cluster(n, seed):
-    """triangle positions and sizes over ten octaves around the origin (scripts/mesh_rebuild_check.cpp "geometric cluster"): a key
-    spends three bits per octave, so the device's tree is several times deeper than the host's and still inside the walk's stack"""
-    rng = np.random.default_rng(seed)
-    t = (rng.uniform(-1, 1, (n, 1, 3)) + rng.uniform(-0.3, 0.3, (n, 3, 3)))     # (large enough for rays to find them)
-    return (t * np.ldexp(1.0, -(np.arange(n) % 10))[:, None, None]).astype(f32)
-
-
-def same_tensors(got, want, what):
-    import torch
-    for k in want:
-        assert torch.equal(got[k].view(torch.int32), want[k].view(torch.int32)), f"{what}: {k}"
-
-
-def rays_at_the_mesh(n, seed, target=1.2):
-    rng = np.random.default_rng(seed)
-    o = (np.array([0.3, 0.8, 4.0]) + rng.uniform(-0.5, 0.5, (n, 3))).astype(f32)
-    return o, (rng.uniform(-target, target, (n, 3)) - o).astype(f32)
 
 
 # ---- 1 ----
@@ -177,10 +136,10 @@ def test_triangles_rebuilt_into_the_eyes_plane_and_out_again(gpu, tmp_path, monk
     monkeypatch.setenv("CUTRACE_GUARD_SCAN", scan)
     w, h = 96, 24
     mesh = moved(random_mesh(100, seed=9, spread=0.8, size=0.25), 0.0, 0.0, shift=(0.0, 1.2, 0.0))   # above the rows' plane
-    upd = gpu.DeviceScene(base._in_plane_scene(gpu, tmp_path, "plane_base", mesh, w, h))
+    upd = gpu.DeviceScene(in_plane_scene(gpu, tmp_path, "plane_base", mesh, w, h))
     upd.render(bounces=2)
     for step, (k, seed) in enumerate(((3, 1), (70, 2), (70, 3), (0, 4))):
-        fresh_scene = base._in_plane_scene(gpu, tmp_path, f"plane_{step}", base._with_in_plane(moved(mesh, 0.05 * step, 0.0), k, h, seed), w, h)
+        fresh_scene = in_plane_scene(gpu, tmp_path, f"plane_{step}", with_in_plane(moved(mesh, 0.05 * step, 0.0), k, h, seed), w, h)
         assert upd.rebuild_mesh(0, desc_tris(fresh_scene, 0))["fell_back"] == 0
         fresh = gpu.DeviceScene(fresh_scene)
         state = upd.guard_state(0)
@@ -250,19 +209,10 @@ def test_merged_tree_is_retired_by_a_rebuild(gpu, tmp_path):
 @pytest.mark.parametrize("builder", ["device", "host"])
 def test_numpy_input_and_tensor_on_its_producing_stream(gpu, tmp_path, builder):
     """both input paths; the tensor is produced on a non-default stream and handed over without a wait in between"""
-    import torch
     mesh = random_mesh(1000, seed=16)
     s = scene_with(gpu, tmp_path, "in", [mesh])
     from_tensor, from_numpy = gpu.DeviceScene(s), gpu.DeviceScene(s)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
-    src = torch.from_numpy(mesh).to(dev)
-    torch.cuda.synchronize(dev)
-    with torch.cuda.stream(stream):
-        t = src
-        for _ in range(20):                                           # (some work for the stream to be busy with)
-            t = t * f32(1.01) + f32(0.001)
-        t = t.contiguous()
+    t, stream = on_a_busy_stream(mesh)
     a = from_tensor.rebuild_mesh(0, t, builder=builder, stream=stream)
     new = t.cpu().numpy()
     b = from_numpy.rebuild_mesh(0, new, builder=builder)
@@ -310,7 +260,7 @@ def test_rejected_rebuilds_leave_the_handle_untouched(gpu, tmp_path):
         untouched(f"flags {flags:#x}")
     empty = str(tmp_path / "empty.stl")
     scenes.write_stl(empty, np.zeros((0, 3, 3), f32))
-    es = base.parse(gpu, mesh_scene(str(tmp_path / "one.stl"), W, H, mesh, extra_objects=[{"type": "mesh", "file": empty, "material": 1}]))
+    es = parse(gpu, mesh_scene(str(tmp_path / "one.stl"), W, H, mesh, extra_objects=[{"type": "mesh", "file": empty, "material": 1}]))
     with pytest.raises(RuntimeError, match="empty mesh"):
         gpu.DeviceScene(es).rebuild_mesh(2, mesh[:1])
     assert ds.rebuild_mesh(0, good)["fell_back"] == 0                 # and the handle still takes a good one

@@ -2,31 +2,21 @@
 replace_mesh — the device's linear BVH or the host's builder — against a handle freshly created from the replaced description.
 Every comparison is BITWISE: neither a tree nor the place of a mesh's records in the scene's arrays can change a result.  Frames are
 96 x 54 or smaller; the counts are the smallest at which each part can go wrong (tests/test_gpu_mesh_update.py's and
-tests/test_gpu_mesh_rebuild.py's, whose helpers this file borrows)."""
+tests/test_gpu_mesh_rebuild.py's; the helpers are those of tests/live.py)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from cutrace_amd import _lib, scenes
-from tests import test_gpu_mesh_rebuild as rebuild
-from tests import test_gpu_mesh_update as base
-from tests.util import mesh_scene
+from tests.gpu_support import assert_same_frame, gpu, same_tensors  # noqa: F401  (gpu: the fixture)
+from tests.live import (BOUNCES, H, KV_MERGE, W, assert_box, assert_equals_fresh, cluster, desc_tris, frame, in_plane_scene, mesh_objects, moved,
+                        on_a_busy_stream, random_mesh, scene_with, staircase, with_in_plane)
+from tests.util import mesh_scene, parse
 
 pytestmark = pytest.mark.gpu
 
-W, H, BOUNCES, KV_MERGE = base.W, base.H, base.BOUNCES, base.KV_MERGE
 f32 = np.float32
-random_mesh, moved, scene_with, desc_tris, mesh_objects, frame = base.random_mesh, base.moved, base.scene_with, base.desc_tris, base.mesh_objects, base.frame
-assert_same_frame, assert_equals_fresh, assert_box = base.assert_same_frame, base.assert_updated_equals_fresh, base.assert_box
-same_tensors, cluster, staircase = rebuild.same_tensors, rebuild.cluster, rebuild.staircase
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
 
 
 def assert_ranges(info, n_before, cap_before, n, what):
@@ -108,7 +98,7 @@ def _mixed_scene(ca, tmp_path, name, a, b):
     extra = [{"type": "triangle", "p1": [-1.6, 0.2, 0.5], "p2": [-0.9, 0.3, 0.8], "p3": [-1.3, 1.1, 0.4], "material": 0},
              {"type": "mesh", "file": stl_b, "material": 1},
              {"type": "sphere", "center": [1.4, 0.1, 0.6], "radius": 0.35, "material": 1}]
-    return base.parse(ca, mesh_scene(str(tmp_path / f"{name}_a.stl"), W, H, a, extra_objects=extra))
+    return parse(ca, mesh_scene(str(tmp_path / f"{name}_a.stl"), W, H, a, extra_objects=extra))
 
 
 def test_mixed_scene_keeps_what_lies_between_and_beside(gpu, tmp_path):
@@ -142,11 +132,11 @@ def test_guard_states_at_changing_counts(gpu, tmp_path, monkeypatch, scan):
     monkeypatch.setenv("CUTRACE_GUARD_SCAN", scan)
     w, h = 96, 24
     lift = dict(shift=(0.0, 1.2, 0.0))                                # above the rows' plane
-    upd = gpu.DeviceScene(base._in_plane_scene(gpu, tmp_path, "plane_base", moved(random_mesh(100, seed=9, spread=0.8, size=0.25), 0.0, 0.0, **lift), w, h))
+    upd = gpu.DeviceScene(in_plane_scene(gpu, tmp_path, "plane_base", moved(random_mesh(100, seed=9, spread=0.8, size=0.25), 0.0, 0.0, **lift), w, h))
     upd.render(bounces=2)
     for step, (n, k, seed) in enumerate(((40, 3, 1), (200, 70, 2), (150, 70, 3), (90, 0, 4))):
         mesh = moved(random_mesh(n, seed=40 + step, spread=0.8, size=0.25), 0.05 * step, 0.0, **lift)
-        fresh_scene = base._in_plane_scene(gpu, tmp_path, f"plane_{step}", base._with_in_plane(mesh, k, h, seed), w, h)
+        fresh_scene = in_plane_scene(gpu, tmp_path, f"plane_{step}", with_in_plane(mesh, k, h, seed), w, h)
         assert upd.replace_mesh(0, desc_tris(fresh_scene, 0))["fell_back"] == 0
         fresh = gpu.DeviceScene(fresh_scene)
         state = upd.guard_state(0)
@@ -221,18 +211,9 @@ def test_merged_tree_is_retired_by_a_replace(gpu, tmp_path):
 @pytest.mark.parametrize("builder", ["device", "host"])
 def test_numpy_input_and_tensor_on_its_producing_stream(gpu, tmp_path, builder):
     """both input paths; the tensor is produced on a non-default stream and handed over without a wait in between"""
-    import torch
     s = scene_with(gpu, tmp_path, "in", [random_mesh(300, seed=15)])
     from_tensor, from_numpy = gpu.DeviceScene(s), gpu.DeviceScene(s)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
-    src = torch.from_numpy(random_mesh(1000, seed=16)).to(dev)
-    torch.cuda.synchronize(dev)
-    with torch.cuda.stream(stream):
-        t = src
-        for _ in range(20):                                           # (some work for the stream to be busy with)
-            t = t * f32(1.01) + f32(0.001)
-        t = t.contiguous()
+    t, stream = on_a_busy_stream(random_mesh(1000, seed=16))
     a = from_tensor.replace_mesh(0, t, builder=builder, stream=stream)
     new = t.cpu().numpy()
     b = from_numpy.replace_mesh(0, new, builder=builder)
@@ -286,7 +267,7 @@ def test_refused_replaces_leave_the_handle_untouched(gpu, tmp_path):
         untouched(f"flags {flags:#x}")
     empty = str(tmp_path / "empty.stl")
     scenes.write_stl(empty, np.zeros((0, 3, 3), f32))
-    es = base.parse(gpu, mesh_scene(str(tmp_path / "one.stl"), W, H, mesh, extra_objects=[{"type": "mesh", "file": empty, "material": 1}]))
+    es = parse(gpu, mesh_scene(str(tmp_path / "one.stl"), W, H, mesh, extra_objects=[{"type": "mesh", "file": empty, "material": 1}]))
     with pytest.raises(RuntimeError, match="empty mesh"):
         gpu.DeviceScene(es).replace_mesh(2, mesh[:1])
     info = ds.replace_mesh(0, good)                                   # and the handle still takes a good one

@@ -3,38 +3,22 @@ were moved or whose objects were given other materials through set_objects / set
 the edited description — depth, normal, colour and ray count BITWISE under the default build and under VAR_EXACT_POW, the handle's
 own VAR_NO_CLUSTER walk, the kernel build, the work counters under VAR_STATS and the guard state.  Every case runs with the guard's
 plane scan on the device and again on the host (CUTRACE_GUARD_SCAN), and the guard states of the two runs are compared.  The
-helpers are those of tests/test_gpu_scene_edit.py.  Every frame is 96 x 54 or smaller."""
-import ctypes as C
+helpers are those of tests/live.py.  Every frame is 96 x 54 or smaller."""
 import json
 
 import numpy as np
 import pytest
 
 from cutrace_amd import _lib, lenses, scenes
-from tests import test_gpu_scene_edit as base
-from tests.util import same_bits
+from tests.gpu_support import FRAME, assert_same_frame, camera_of, gpu, same_tensors  # noqa: F401  (gpu: the fixture)
+from tests.live import (BOUNCES, EYE, GLASS, KV_MERGE, LIGHTS, MATERIALS, MIRROR, OPAQUE, OTHER, ROOM_MESH, ROOM_PLANES, ROOM_SMALL, ROOM_SPHERE, ROOM_TRI,
+                        ROOM_WALL, assert_equals_fresh, assert_queries_equal_fresh, camera, desc_lights, desc_objects, each_scan, frame, guard_tris,
+                        mesh_objects, room_scene, with_objects)
+from tests.util import parse, same_bits
 
 pytestmark = pytest.mark.gpu
 
-BOUNCES = base.BOUNCES
 f32 = np.float32
-OPAQUE, OTHER, GLASS, MIRROR = 0, 1, 2, 3
-MATERIALS = [{"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.0, "phong": 40},
-             {"type": "solid", "color": [0.3, 0.5, 0.9], "specular": 0.2, "reflect": 0.0, "phong": 10},
-             {"type": "solid", "color": [0.9, 0.9, 0.9], "specular": 0.3, "reflect": 0.0, "phong": 20, "transparency": 0.5},   # used by no object at first
-             {"type": "solid", "color": [0.7, 0.7, 0.7], "specular": 0.3, "reflect": 0.4, "phong": 30}]
-LIGHTS = [{"type": "point", "point": [3.0, -1.0, 1.0], "color": [0.9, 0.9, 0.9]}, {"type": "sun", "direction": [0.3, -0.8, 0.5], "color": [0.3, 0.3, 0.3]}]
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
-
-
-def camera(eye, look, w, h):
-    return {"eye": list(eye), "up": [0, 1, 0], "look": list(look), "near_plane": 0.1, "far_plane": 100.0, "width": w, "height": h, "ambient": 0.1}
 
 
 def plain_scene(w=96, h=54):
@@ -50,63 +34,26 @@ def plain_scene(w=96, h=54):
     return {"camera": camera([0.3, 0.2, -0.5], [0.1, 0.0, 1.0], w, h), "lights": LIGHTS, "materials": MATERIALS, "objects": objs}
 
 
-ROOM_MESH, ROOM_SPHERE, ROOM_SMALL, ROOM_TRI, ROOM_WALL = 2, 4, 6, 7, 8
-ROOM_PLANES = (0, 1, 3, 5, 8)
-
-
-def room_scene(tmp_path, name, w=48, h=27):
-    """(b): a box room of five axis-aligned planes, a 70-triangle mesh with five triangles in z = 0.5, a 12-triangle reflecting mesh,
-    a sphere and a stand-alone triangle.  The eye's image in the wall z = -6, once that wall reflects and stands at z = 0, lies in
-    z = 0.5."""
-    big, small = str(tmp_path / f"{name}_70.stl"), str(tmp_path / f"{name}_12.stl")
-    scenes.write_stl(big, base._guard_tris(5, n_other=65, seed=5, zero_area=False))
-    scenes.write_stl(small, base._guard_tris(0, n_other=12, seed=6, zero_area=False) + f32([2.5, 0.0, 0.0]))
-    objs = [{"type": "plane", "point": [-5, 0, 0], "normal": [1, 0, 0], "material": OTHER},
-            {"type": "plane", "point": [5, 0, 0], "normal": [-1, 0, 0], "material": OTHER},
-            {"type": "mesh", "file": big, "material": OPAQUE},
-            {"type": "plane", "point": [0, -3, 0], "normal": [0, 1, 0], "material": OTHER},
-            {"type": "sphere", "center": [-2.0, -1.0, 3.0], "radius": 0.7, "material": OPAQUE},
-            {"type": "plane", "point": [0, 8, 0], "normal": [0, -1, 0], "material": OTHER},
-            {"type": "mesh", "file": small, "material": MIRROR},
-            {"type": "triangle", "p1": [-3, 0, 6], "p2": [-2, 0.5, 6.5], "p3": [-2.5, 2, 6], "material": OPAQUE},
-            {"type": "plane", "point": [0, 0, -6], "normal": [0, 0, 1], "material": OTHER}]
-    return {"camera": camera([0.3, 0.2, -0.5], [0.0, 0.1, 1.0], w, h), "lights": LIGHTS, "materials": MATERIALS, "objects": objs}
-
-
 def two_mesh_scene(tmp_path, name, w=48, h=27):
     """(c): two meshes (the merged tree has its room), a floor and a sphere"""
     paths = [str(tmp_path / f"{name}_{k}.stl") for k in range(2)]
-    scenes.write_stl(paths[0], base._guard_tris(4, n_other=40, seed=1))
-    scenes.write_stl(paths[1], base._guard_tris(3, n_other=40, seed=2, zero_area=False) + f32([0.4, 0.3, 0.0]))
+    scenes.write_stl(paths[0], guard_tris(4, n_other=40, seed=1))
+    scenes.write_stl(paths[1], guard_tris(3, n_other=40, seed=2, zero_area=False) + f32([0.4, 0.3, 0.0]))
     objs = [{"type": "mesh", "file": paths[0], "material": OPAQUE}, {"type": "plane", "point": [0, -1.5, 0], "normal": [0, 1, 0], "material": OTHER},
             {"type": "mesh", "file": paths[1], "material": OTHER}, {"type": "sphere", "center": [1.0, 0.0, 1.0], "radius": 0.5, "material": OPAQUE}]
-    return {"camera": camera(base.EYE, [0.0, 0.0, 0.0], w, h), "lights": LIGHTS, "materials": MATERIALS, "objects": objs}
-
-
-def with_objects(sc, changes):
-    """a copy of the scene with {object index: {field: value}} applied"""
-    out = json.loads(json.dumps(sc))
-    for i, kw in changes.items():
-        out["objects"][i].update(kw)
-    return out
-
-
-def desc_objects(hs):
-    """the description's objects as set_objects takes them (a mesh's tri_begin, v0 and v1 are ignored)"""
-    d = hs.desc.contents
-    return [d.objects[i] for i in range(int(d.n_objects))]
+    return {"camera": camera(EYE, [0.0, 0.0, 0.0], w, h), "lights": LIGHTS, "materials": MATERIALS, "objects": objs}
 
 
 def follow(gpu, upd, sc, what, **kw):
     """`upd` takes the objects of the description `sc`; then everything of assert_equals_fresh.  Returns (guard states, fresh handle)."""
-    fresh_scene = base.parse(gpu, sc)
+    fresh_scene = parse(gpu, sc)
     upd.set_objects(desc_objects(fresh_scene))
-    fresh = kw.pop("fresh", None) or gpu.DeviceScene(fresh_scene)
-    return base.assert_equals_fresh(gpu, upd, fresh_scene, what, fresh=fresh, **kw), fresh
+    fresh = gpu.DeviceScene(fresh_scene)
+    return assert_equals_fresh(gpu, upd, fresh, what, same_trees=True, **kw), fresh
 
 
 def counters_and_frame(gpu, ds, variant=0):
-    f = base.frame(ds, variant | gpu.VAR_STATS)
+    f = frame(ds, variant | gpu.VAR_STATS)
     c = ds.last_counters().copy()
     ds.set_variant(variant)
     return f, c
@@ -126,7 +73,7 @@ def test_a_scene_without_a_mesh(gpu, monkeypatch):
              ("as it was", {})]
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
+        upd = gpu.DeviceScene(parse(gpu, sc))
         upd.render(bounces=BOUNCES)
         seen = []
         for what, changes in steps:
@@ -134,7 +81,7 @@ def test_a_scene_without_a_mesh(gpu, monkeypatch):
             assert states == []
             seen.append(what)
         return seen
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 2. the plane packing
@@ -156,13 +103,13 @@ def test_the_room_planes_are_packed_again(gpu, tmp_path, monkeypatch):
              ("a wall's point beyond 1e37", {0: dict(point=[-5, 2e37, 0])}), ("the planes as they were", {})]
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
+        upd = gpu.DeviceScene(parse(gpu, sc))
         upd.render(bounces=BOUNCES)
         states = []
         for what, changes in steps:
             states += follow(gpu, upd, with_objects(sc, changes), what)[0]
         return states
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 3. a stand-alone triangle: its DObj carries p1 / p3, its normal lives in gn
@@ -180,11 +127,11 @@ def test_a_triangle_moved_uv_and_normal(gpu, monkeypatch):
     d = (aim - o).astype(f32)
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
+        upd = gpu.DeviceScene(parse(gpu, sc))
         upd.render_uv(bounces=BOUNCES)
         states, fresh = follow(gpu, upd, moved, "two triangles moved")
         u, f = upd.render_uv(bounces=BOUNCES), fresh.render_uv(bounces=BOUNCES)
-        for k in ("uv",) + base.FRAME:
+        for k in ("uv",) + FRAME:
             assert same_bits(u[k], f[k]), f"render_uv: {k}"
         cu, cf = upd.cast_rays(o, d), fresh.cast_rays(o, d)
         for k in ("uv", "normal", "prim", "object", "t"):
@@ -192,7 +139,7 @@ def test_a_triangle_moved_uv_and_normal(gpu, monkeypatch):
         hit = cf["object"].cpu().numpy()
         assert (hit == 3).sum() > 100 and (hit == 6).sum() > 100, "the rays must meet the moved triangles"
         return ["two triangles moved", states]
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 4. material reassignment
@@ -214,23 +161,23 @@ def test_objects_take_other_materials(gpu, tmp_path, monkeypatch):
     d = (rng.uniform(-1, 1, (1024, 3)) * [3, 3, 0] + [-1.0, -1.0, 4.0] - o).astype(f32)
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
-        base.frame(upd, gpu.VAR_AUTO)
+        upd = gpu.DeviceScene(parse(gpu, sc))
+        frame(upd, gpu.VAR_AUTO)
         kernel0 = upd.last_kernel()
         states = []
         for what, changes in steps:
             st, fresh = follow(gpu, upd, with_objects(sc, changes), what)
             states += st
-            base.frame(upd, gpu.VAR_AUTO)
+            frame(upd, gpu.VAR_AUTO)
             assert upd.last_kernel() == kernel0, f"{what}: the materials did not change, the kernel build must not"
             cu, cf = upd.cast_rays(o, d, ignore_transparent=True), fresh.cast_rays(o, d, ignore_transparent=True)
             for k in cf:
                 assert torch.equal(cu[k].view(torch.int32), cf[k].view(torch.int32)), f"{what}: cast_rays(ignore_transparent): {k}"
-            u, f = base.frame(upd, gpu.VAR_IGNORE_TRANSPARENT), base.frame(fresh, gpu.VAR_IGNORE_TRANSPARENT)
-            base.assert_same_frame(u, f, f"{what}: VAR_IGNORE_TRANSPARENT")
+            u, f = frame(upd, gpu.VAR_IGNORE_TRANSPARENT), frame(fresh, gpu.VAR_IGNORE_TRANSPARENT)
+            assert_same_frame(u, f, f"{what}: VAR_IGNORE_TRANSPARENT")
             upd.set_variant(0)
         return states
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 5. the moving mirror
@@ -241,7 +188,7 @@ def test_a_mirror_moves_the_eyes_image_into_the_plane_of_triangles_and_out_again
     moved = {ROOM_WALL: dict(material=MIRROR, point=[0, 0, 0])}
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
+        upd = gpu.DeviceScene(parse(gpu, sc))
         upd.render(bounces=BOUNCES)
         assert upd.guard_state(ROOM_MESH) == ([], False)
         states = []
@@ -250,7 +197,7 @@ def test_a_mirror_moves_the_eyes_image_into_the_plane_of_triangles_and_out_again
             states += follow(gpu, upd, with_objects(sc, changes), what)[0]
             assert upd.guard_state(ROOM_MESH) == (want, False), (what, upd.guard_state(ROOM_MESH))
         return states
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 6., 11. the identity edit and the round trip
@@ -261,7 +208,7 @@ def test_identity_edit_and_round_trip(gpu, tmp_path, monkeypatch, which):
     sc = plain_scene(48, 27) if which == "plain" else room_scene(tmp_path, "same") if which == "room" else two_mesh_scene(tmp_path, "same")
 
     def body():
-        hs = base.parse(gpu, sc)
+        hs = parse(gpu, sc)
         upd, untouched = gpu.DeviceScene(hs), gpu.DeviceScene(hs)
         want_frame, want_counters = counters_and_frame(gpu, untouched)
         kernel = untouched.last_kernel()
@@ -274,15 +221,15 @@ def test_identity_edit_and_round_trip(gpu, tmp_path, monkeypatch, which):
                 assert what == "identity" or int(o.tri_begin) == 0
             upd.set_objects(objs)
             got_frame, got_counters = counters_and_frame(gpu, upd)
-            base.assert_same_frame(got_frame, want_frame, f"{which}: {what}")
+            assert_same_frame(got_frame, want_frame, f"{which}: {what}")
             assert np.array_equal(got_counters, want_counters) and upd.last_kernel() == kernel, (which, what)
-            seen.append([upd.guard_state(m) for m in base.mesh_objects(hs)])
-            assert seen[-1] == [untouched.guard_state(m) for m in base.mesh_objects(hs)]
-        for m in base.mesh_objects(hs):                               # a mesh comes back with its box and its count
+            seen.append([upd.guard_state(m) for m in mesh_objects(hs)])
+            assert seen[-1] == [untouched.guard_state(m) for m in mesh_objects(hs)]
+        for m in mesh_objects(hs):                               # a mesh comes back with its box and its count
             o, (lo, hi) = upd.get_object(m), upd.mesh_box(m)
             assert o.v0.tup() == tuple(lo) and o.v1.tup() == tuple(hi) and int(o.tri_count) == int(hs.desc.contents.objects[m].tri_count)
         return [which, seen]
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 7. with the other edits
@@ -291,7 +238,7 @@ def test_update_mesh_then_set_objects_then_set_lights(gpu, tmp_path, monkeypatch
     sc = room_scene(tmp_path, "order")
     final = with_objects(sc, {ROOM_SPHERE: dict(center=[-1.5, -0.5, 2.5]), ROOM_WALL: dict(material=MIRROR, point=[0, 0, 0]), ROOM_MESH: dict(material=OTHER)})
     final["lights"] = [{"type": "point", "point": [2.0, 1.0, -0.2], "color": [0.7, 0.7, 0.7]}]
-    tris = base._guard_tris(5, n_other=65, seed=5, zero_area=False)
+    tris = guard_tris(5, n_other=65, seed=5, zero_area=False)
     tris[:, :, 0] += f32(0.125)                                        # every triangle slides within its plane
     tris[:, :, 1] -= f32(0.0625)
     path = str(tmp_path / "order_moved.stl")
@@ -299,9 +246,9 @@ def test_update_mesh_then_set_objects_then_set_lights(gpu, tmp_path, monkeypatch
     final["objects"][ROOM_MESH]["file"] = path
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
+        upd = gpu.DeviceScene(parse(gpu, sc))
         upd.render(bounces=BOUNCES)
-        fresh_scene = base.parse(gpu, final)
+        fresh_scene = parse(gpu, final)
         upd.update_mesh(ROOM_MESH, tris)
         lo, hi = upd.mesh_box(ROOM_MESH)
         upd.set_objects(desc_objects(fresh_scene))
@@ -309,32 +256,19 @@ def test_update_mesh_then_set_objects_then_set_lights(gpu, tmp_path, monkeypatch
         o = upd.get_object(ROOM_MESH)
         assert same_bits(lo, lo2) and same_bits(hi, hi2), "set_objects must leave the refitted box"
         assert o.v0.tup() == tuple(lo) and o.v1.tup() == tuple(hi) and int(o.mat_idx) == OTHER
-        upd.set_lights(base.desc_lights(fresh_scene))
+        upd.set_lights(desc_lights(fresh_scene))
         # the counters: of a handle created with the final objects and lights whose mesh then got the same vertices (the same refitted tree)
         start = json.loads(json.dumps(final))
         start["objects"][ROOM_MESH]["file"] = sc["objects"][ROOM_MESH]["file"]
-        ref = gpu.DeviceScene(base.parse(gpu, start))
+        ref = gpu.DeviceScene(parse(gpu, start))
         ref.update_mesh(ROOM_MESH, tris)
-        states = base.assert_equals_fresh(gpu, upd, fresh_scene, "update_mesh, set_objects, set_lights", counters_of=ref)
+        states = assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), "update_mesh, set_objects, set_lights", counters_of=ref)
         assert states[0] == ([0, 1, 2, 3, 4], False), states
         return states
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 8. queries and the other renders
-
-def _same(got, want, what):
-    import torch
-    assert set(got) == set(want), what
-    for k in want:
-        a, b = got[k], want[k]
-        if isinstance(b, torch.Tensor):
-            assert a.shape == b.shape and torch.equal(a.view(torch.int32) if b.dtype == torch.float32 else a, b.view(torch.int32) if b.dtype == torch.float32 else b), f"{what}: {k}"
-        elif isinstance(b, np.ndarray):
-            assert a.shape == b.shape and a.tobytes() == b.tobytes(), f"{what}: {k}"
-        elif k not in ("kernel_ms", "total_ms"):
-            assert a == b, f"{what}: {k}"
-
 
 def test_queries_and_the_other_renders_on_an_edited_handle(gpu, tmp_path, monkeypatch):
     import torch
@@ -354,27 +288,24 @@ def test_queries_and_the_other_renders_on_an_edited_handle(gpu, tmp_path, monkey
         return dict(depth=depth, color=color, normal=normal, rays=counters[:1])
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
+        upd = gpu.DeviceScene(parse(gpu, sc))
         upd.render(bounces=BOUNCES)
-        fresh_scene = base.parse(gpu, final)
+        fresh_scene = parse(gpu, final)
         upd.set_objects(desc_objects(fresh_scene))
         fresh = gpu.DeviceScene(fresh_scene)
-        base.assert_queries_equal_fresh(upd, fresh, len(LIGHTS), "edited room")
-        _same(upd.render(bounces=BOUNCES, samples=2), fresh.render(bounces=BOUNCES, samples=2), "render(samples=2)")
+        assert_queries_equal_fresh(upd, fresh, len(LIGHTS), "edited room")
+        same_tensors(upd.render(bounces=BOUNCES, samples=2), fresh.render(bounces=BOUNCES, samples=2), "render(samples=2)")
         o, d = lenses.pinhole(fresh_scene.desc.contents.cam, w, h)
         lu, lf = upd.render_lens(o, d, bounces=BOUNCES), fresh.render_lens(o, d, bounces=BOUNCES)
-        _same(lu, lf, "render_lens")
+        same_tensors(lu, lf, "render_lens")
         plain = fresh.render(bounces=BOUNCES)
         assert same_bits(lf["color"].cpu().numpy().reshape(plain["color"].shape), plain["color"]), "the camera's own rays give the plain frame"
-        _same(upd.render_images(bounces=BOUNCES), fresh.render_images(bounces=BOUNCES), "render_images")
-        cam = gpu.Camera()
-        C.memmove(C.byref(cam), C.byref(fresh_scene.desc.contents.cam), C.sizeof(gpu.Camera))
-        other = gpu.Camera()
-        C.memmove(C.byref(other), C.byref(cam), C.sizeof(gpu.Camera))
+        same_tensors(upd.render_images(bounces=BOUNCES), fresh.render_images(bounces=BOUNCES), "render_images")
+        cam, other = camera_of(gpu, fresh_scene), camera_of(gpu, fresh_scene)
         other.pos = _lib.Vec3(-0.6, 0.5, -0.9)
-        _same(batch(upd, [cam, other]), batch(fresh, [cam, other]), "render_device_batch")
-        return [upd.guard_state(m) for m in base.mesh_objects(fresh_scene)] + [fresh.guard_state(m) for m in base.mesh_objects(fresh_scene)]
-    base.each_scan(monkeypatch, body)
+        same_tensors(batch(upd, [cam, other]), batch(fresh, [cam, other]), "render_device_batch")
+        return [upd.guard_state(m) for m in mesh_objects(fresh_scene)] + [fresh.guard_state(m) for m in mesh_objects(fresh_scene)]
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 9. the merged tree
@@ -385,21 +316,21 @@ def test_the_merged_tree_stays_in_use_across_an_object_edit(gpu, tmp_path, monke
              ("as it was", {})]
 
     def body():
-        upd = gpu.DeviceScene(base.parse(gpu, sc))
+        upd = gpu.DeviceScene(parse(gpu, sc))
         upd.set_variant(gpu.VAR_MERGE)
         upd.render(bounces=2)
-        assert upd.last_kernel() & base.KV_MERGE, "the scene of two meshes walks its merged tree"
+        assert upd.last_kernel() & KV_MERGE, "the scene of two meshes walks its merged tree"
         states = []
         for what, changes in steps:
-            fresh_scene = base.parse(gpu, with_objects(sc, changes))
+            fresh_scene = parse(gpu, with_objects(sc, changes))
             fresh = gpu.DeviceScene(fresh_scene)
             fresh.set_variant(gpu.VAR_MERGE)
             upd.set_objects(desc_objects(fresh_scene))
-            states += base.assert_equals_fresh(gpu, upd, fresh_scene, f"merged tree, {what}", bounces=2, base=gpu.VAR_MERGE, fresh=fresh)
+            states += assert_equals_fresh(gpu, upd, fresh, f"merged tree, {what}", bounces=2, base=gpu.VAR_MERGE, same_trees=True)
             upd.render(bounces=2)
-            assert upd.last_kernel() & base.KV_MERGE, f"{what}: {upd.last_kernel():#x}"
+            assert upd.last_kernel() & KV_MERGE, f"{what}: {upd.last_kernel():#x}"
         return states
-    base.each_scan(monkeypatch, body)
+    each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- 10. every rejection
@@ -408,7 +339,7 @@ def test_every_rejection_raises_and_leaves_the_handle_as_it_was(gpu, tmp_path, m
     sc = room_scene(tmp_path, "reject")
 
     def body():
-        hs = base.parse(gpu, sc)
+        hs = parse(gpu, sc)
         upd = gpu.DeviceScene(hs)
         upd.set_object(ROOM_SPHERE, center=(-1.5, -0.5, 2.5))          # (a handle that has been edited before)
         before, counters = counters_and_frame(gpu, upd)
@@ -434,8 +365,8 @@ def test_every_rejection_raises_and_leaves_the_handle_as_it_was(gpu, tmp_path, m
         with pytest.raises(RuntimeError, match="material index out of range"):
             upd.set_object(ROOM_PLANES[0], material=len(MATERIALS))
         got, got_counters = counters_and_frame(gpu, upd)
-        base.assert_same_frame(got, before, "after the rejected edits")
+        assert_same_frame(got, before, "after the rejected edits")
         assert np.array_equal(got_counters, counters)
         moved = with_objects(sc, {ROOM_SPHERE: dict(center=[-1.5, -0.5, 2.5])})
-        return base.assert_equals_fresh(gpu, upd, base.parse(gpu, moved), "after the rejected edits")
-    base.each_scan(monkeypatch, body)
+        return assert_equals_fresh(gpu, upd, gpu.DeviceScene(parse(gpu, moved)), "after the rejected edits", same_trees=True)
+    each_scan(monkeypatch, body)

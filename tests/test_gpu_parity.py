@@ -5,7 +5,6 @@ from the reference build), and through size-independent properties at full resol
 Bar: depth / normal / which-object are BIT-EXACT (only +,-,*,/,sqrt arithmetic, -ffp-contract=off
 on both sides); colour within 1e-4 per channel (the specular pow() may differ by 1 ulp between
 glibc powf and the device's f64 pow)."""
-import glob
 import os
 
 import numpy as np
@@ -14,13 +13,12 @@ import pytest
 import oracle
 
 from tests.conftest import load_scene
-from tests.test_oracle_golden import GOLD, parse
-from tests.util import (assert_parity, same_bits, uv_close, mesh_scene as _mesh_scene, corner_meshes, _random_scene, _coplanar_scene,
-                        _mirror_coplanar_scene)
+from tests.util import (GOLD, GOLD_SMALL, assert_parity, golden_case, same_bits, uv_close, mesh_scene as _mesh_scene, corner_meshes, _random_scene,
+                        _coplanar_scene, _mirror_coplanar_scene)
 
 pytestmark = pytest.mark.gpu
 
-SMALL = sorted(glob.glob(os.path.join(GOLD, "small_*.npz")))
+SMALL = GOLD_SMALL
 
 
 @pytest.fixture(scope="module")
@@ -34,7 +32,7 @@ def gpu(ca):
 
 @pytest.mark.parametrize("path", SMALL, ids=[os.path.basename(p) for p in SMALL])
 def test_gpu_matches_golden(gpu, path):
-    name, w, h, b = parse(path)
+    name, w, h, b = golden_case(path)
     g = np.load(path)
     s = load_scene(gpu, name, w, h)
     ds = gpu.DeviceScene(s)

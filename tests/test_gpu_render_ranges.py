@@ -26,6 +26,7 @@ import pytest
 import oracle
 from cutrace_amd import lenses
 from tests import aa_ref, ray_ref
+from tests.gpu_support import gpu  # noqa: F401  (the fixture)
 from tests.util import (ALL_MISS_CASE, RANGE_FLAVOURS, RANGE_POW_DEPENDENT, RENDER_RANGE_CASES, TOL, assert_parity, uv_close, f32, pow2, range_case_id, range_fudge,
                         render_range_scene_json, same_bits)
 
@@ -37,13 +38,6 @@ NT = min(os.cpu_count() or 4, 16)
 KV_ANYHIT, KV_OCC6, KV_HOSTOUT, KV_UV, KV_MERGE, KV_IGNTR, KV_SS, KV_RAYS = 2, 64, 128, 256, 512, 1024, 2048, 4096
 CASES = [pytest.param(c, f, id=f"{range_case_id(c)},{f}") for c in RENDER_RANGE_CASES for f in RANGE_FLAVOURS]
 FRAME = ("depth", "normal", "color")
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
 
 
 def host_scene(ca, tmp_path, case, flavour):

@@ -4,148 +4,20 @@ count BITWISE under the default build and under VAR_EXACT_POW, the handle's own 
 counters under VAR_STATS and the guard state.  Every case runs with the guard's plane scan on the device and again on the host
 (CUTRACE_GUARD_SCAN), and the guard states of the two runs are compared.  Every frame is 96 x 54 or smaller."""
 import ctypes as C
-import json
 
 import numpy as np
 import pytest
 
-from cutrace_amd import _lib, scenes
-from tests.util import mesh_scene, same_bits
+from cutrace_amd import _lib
+from tests.gpu_support import assert_same_frame, gpu  # noqa: F401  (gpu: the fixture)
+from tests.live import (BOUNCES, KV_MERGE, OFF, assert_equals_fresh, assert_queries_equal_fresh, base_scene, desc_lights, desc_materials, desc_tris,
+                        each_scan, edited, frame, guard_scene, guard_tris, random_mesh)
+from tests.util import parse
 
 pytestmark = pytest.mark.gpu
 
-W, H = 96, 54
-BOUNCES = 3
-KV_MERGE = 512
-FRAME = ("depth", "normal", "color")
 f32 = np.float32
-EYE = [0.3, 0.8, 4.03]            # in no plane z = const of the meshes below
 POINT, SUN = 1, 0                 # CTR_LIGHT_POINT, CTR_LIGHT_SUN
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
-
-
-def each_scan(monkeypatch, body):
-    """body() with the guard's scan on the device, then on the host; what it returns (the guard states it went through) must
-    be the same both times"""
-    seen = {}
-    for scan in ("device", "host"):
-        monkeypatch.setenv("CUTRACE_GUARD_SCAN", scan)
-        seen[scan] = body()
-    assert seen["device"] == seen["host"], seen
-    assert seen["device"], "the case looked at no guard state"
-
-
-def random_mesh(n, seed, spread=0.9, size=0.3):
-    rng = np.random.default_rng(seed)
-    centre = rng.uniform(-spread, spread, (n, 1, 3))
-    return (centre + rng.uniform(-size, size, (n, 3, 3))).astype(f32)
-
-
-def parse(ca, sc):
-    s = ca.HostScene.parse(sc if isinstance(sc, str) else json.dumps(sc))
-    assert s.ok
-    return s
-
-
-def base_scene(tmp_path, name, tris, extra=(), w=W, h=H):
-    """util.mesh_scene as a dict: the mesh (material 0, reflecting), a floor (material 1), a point light and a sun"""
-    paths = []
-    for k, t in enumerate(extra):
-        paths.append(str(tmp_path / f"{name}_x{k}.stl"))
-        scenes.write_stl(paths[-1], t)
-    return json.loads(mesh_scene(str(tmp_path / f"{name}.stl"), w, h, tris,
-                                 extra_objects=[{"type": "mesh", "file": p, "material": 1} for p in paths]))
-
-
-def edited(sc, **kw):
-    out = json.loads(json.dumps(sc))
-    out.update(kw)
-    return out
-
-
-def desc_lights(hs):
-    d = hs.desc.contents
-    return [d.lights[i] for i in range(int(d.n_lights))]
-
-
-def desc_materials(hs):
-    d = hs.desc.contents
-    return [d.materials[i] for i in range(int(d.n_materials))]
-
-
-def mesh_objects(hs):
-    d = hs.desc.contents
-    return [i for i in range(d.n_objects) if d.objects[i].type == 1]
-
-
-def desc_tris(hs, obj):
-    d = hs.desc.contents
-    o = d.objects[obj]
-    n = int(o.tri_count)
-    raw = C.string_at(C.addressof(d.triangles[int(o.tri_begin)]), n * C.sizeof(_lib.Triangle))
-    return np.frombuffer(raw, f32).reshape(n, 3, 3).copy()
-
-
-def frame(ds, bits, bounces=BOUNCES):
-    ds.set_variant(bits)
-    return ds.render(bounces=bounces)
-
-
-def assert_same_frame(got, want, what):
-    for k in FRAME:
-        assert same_bits(got[k], want[k]), f"{what}: {k} differs in {int((got[k].view(np.uint32) != want[k].view(np.uint32)).sum())} words"
-    assert got["ray_count"] == want["ray_count"], what
-
-
-def assert_equals_fresh(ca, upd, fresh_scene, what, bounces=BOUNCES, base=0, fresh=None, counters_of=None):
-    """the frames, the kernel build, the counters and the guard; returns the guard state of every mesh.  base: variant bits both
-    handles carry throughout (VAR_MERGE).  counters_of: the handle whose counters `upd` must show instead of the fresh one's (a
-    mesh that update_mesh refitted is walked through another tree than a fresh build's: same frame, other work)"""
-    fresh = fresh or ca.DeviceScene(fresh_scene)
-    for bits in (ca.VAR_AUTO, ca.VAR_EXACT_POW):
-        u, f = frame(upd, base | bits, bounces), frame(fresh, base | bits, bounces)
-        assert_same_frame(u, f, f"{what}, variant {bits}: edited vs fresh")
-        assert upd.last_kernel() == fresh.last_kernel(), f"{what}, variant {bits}: kernel {upd.last_kernel():#x} vs fresh {fresh.last_kernel():#x}"
-        assert_same_frame(u, frame(upd, base | bits | ca.VAR_NO_CLUSTER, bounces), f"{what}, variant {bits}: edited vs its own linear walk")
-    u, f = frame(upd, base | ca.VAR_STATS, bounces), frame(fresh, base | ca.VAR_STATS, bounces)
-    assert_same_frame(u, f, f"{what}, VAR_STATS")
-    assert upd.last_kernel() == fresh.last_kernel(), what
-    if counters_of is not None:
-        assert_same_frame(frame(counters_of, base | ca.VAR_STATS, bounces), f, f"{what}, VAR_STATS: the handle that gives the counters")
-    want = (counters_of or fresh).last_counters()
-    assert np.array_equal(upd.last_counters(), want), (what, upd.last_counters(), want)
-    upd.set_variant(base)
-    fresh.set_variant(base)
-    state = [upd.guard_state(m) for m in mesh_objects(fresh_scene)]
-    assert state == [fresh.guard_state(m) for m in mesh_objects(fresh_scene)], what
-    return state
-
-
-def assert_queries_equal_fresh(upd, fresh, n_lights, what):
-    import torch
-    rng = np.random.default_rng(15)
-    n = 1024
-    o = (np.array(EYE) + rng.uniform(-0.5, 0.5, (n, 3))).astype(f32)
-    d = (rng.uniform(-1.2, 1.2, (n, 3)) - o).astype(f32)
-
-    def same(got, want, q):
-        for k in want:
-            assert got[k].shape == want[k].shape and torch.equal(got[k].view(torch.int32), want[k].view(torch.int32)), f"{what}: {q}: {k}"
-    cu, cf = upd.cast_rays(o, d), fresh.cast_rays(o, d)
-    same(cu, cf, "cast_rays")
-    assert torch.equal(upd.shadow(o, d, 50.0), fresh.shadow(o, d, 50.0)), f"{what}: shadow"
-    outs = ("color", "t", "object", "normal")
-    same(upd.shade_rays(o, d, bounces=2, outputs=outs), fresh.shade_rays(o, d, bounces=2, outputs=outs), "shade_rays")
-    args = dict(normals=cf["normal"], view_dirs=torch.from_numpy(d), objects=cf["object"], outputs=("color", "light_shadow"))
-    pu, pf = upd.shade_points(cf["point"], **args), fresh.shade_points(cf["point"], **args)
-    assert tuple(pu["light_shadow"].shape) == (n, n_lights), f"{what}: light_shadow is {tuple(pu['light_shadow'].shape)}"
-    same(pu, pf, "shade_points")
 
 
 # ---------------------------------------------------------------- lights
@@ -185,7 +57,7 @@ def test_edited_lights_equal_a_fresh_handle(gpu, tmp_path, monkeypatch, n):
             upd.set_lights(desc_lights(fresh_scene))
             assert upd.n_lights == len(lights)
             fresh = gpu.DeviceScene(fresh_scene)
-            states.append(assert_equals_fresh(gpu, upd, fresh_scene, f"{n} triangles, {what}", fresh=fresh))
+            states.append(assert_equals_fresh(gpu, upd, fresh, f"{n} triangles, {what}", same_trees=True))
             assert_queries_equal_fresh(upd, fresh, len(lights), f"{n} triangles, {what}")
         return states
     each_scan(monkeypatch, body)
@@ -221,7 +93,7 @@ def test_edited_materials_equal_a_fresh_handle(gpu, tmp_path, monkeypatch):
         for what, idx, kw in steps:
             fresh_scene.set_material(idx, **kw)
             upd.set_material(idx, **kw)
-            states.append(assert_equals_fresh(gpu, upd, fresh_scene, what))
+            states.append(assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), what, same_trees=True))
             frame(upd, gpu.VAR_AUTO)
             kernels[what] = upd.last_kernel()
         assert kernels["floor transmits"] != kernel0, "a transmitting material: the any-hit shadow build must go"
@@ -233,9 +105,9 @@ def test_edited_materials_equal_a_fresh_handle(gpu, tmp_path, monkeypatch):
         # the count 2 -> 3 -> 2, then 1: rejected while the floor uses index 1
         two = desc_materials(fresh_scene)
         upd.set_materials(two + [two[0]])
-        states.append(assert_equals_fresh(gpu, upd, fresh_scene, "three materials, the third unused"))
+        states.append(assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), "three materials, the third unused", same_trees=True))
         upd.set_materials(two)
-        states.append(assert_equals_fresh(gpu, upd, fresh_scene, "two materials again"))
+        states.append(assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), "two materials again", same_trees=True))
         before = frame(upd, gpu.VAR_AUTO)
         with pytest.raises(RuntimeError, match=r"ctr_scene_set_materials failed \(1\).*material index out of range"):
             upd.set_materials(two[:1])
@@ -247,45 +119,13 @@ def test_edited_materials_equal_a_fresh_handle(gpu, tmp_path, monkeypatch):
         with pytest.raises(RuntimeError, match=r"ctr_scene_set_lights failed \(1\).*bad type"):
             upd.set_lights([_lib.Light(2, _lib.Vec3(0, 1, 0), _lib.Vec3(1, 1, 1))])
         assert_same_frame(frame(upd, gpu.VAR_AUTO), before, "after the rejected edits")
-        states.append(assert_equals_fresh(gpu, upd, fresh_scene, "after the rejected edits"))
+        states.append(assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), "after the rejected edits", same_trees=True))
         return states
     each_scan(monkeypatch, body)
 
 
 # ---------------------------------------------------------------- the guard, through a light
 
-def _guard_tris(k, n_other=400, seed=0, zero_area=True):
-    """tests/test_scene_flatten.py's _guard_mesh with tilted fillers: k triangles IN the plane z = 0.5 (file indices 0..k-1),
-    n_other triangles in the planes z = 2 + 0.1 j + 0.2 x, which hold neither EYE nor a light below and are parallel to no sun
-    below, and (zero_area) two triangles of no area in the plane z = 0.5"""
-    rng = np.random.RandomState(seed)
-    tris = []
-    for _ in range(k):
-        c = rng.uniform(-1, 1, 2)
-        tris.append([[c[0] + dx, c[1] + dy, 0.5] for dx, dy in ((0, 0), (0.3, 0.05), (0.1, 0.35))])
-    for j in range(n_other):
-        c = rng.uniform(-1, 1, 2)
-        tris.append([[c[0] + dx, c[1] + dy, 2.0 + 0.1 * j + 0.2 * (c[0] + dx)] for dx, dy in ((0, 0), (0.3, 0.05), (0.1, 0.35))])
-    if zero_area:
-        tris += [[[0.1, 0.1, 0.5]] * 3, [[0, 0, 0.5], [0.5, 0.5, 0.5], [1, 1, 0.5]]]     # a point, three points of a line
-    return np.asarray(tris, f32)
-
-
-def _guard_scene(tmp_path, name, meshes, lights, eye=EYE, w=48, h=27):
-    objs = []
-    for k, t in enumerate(meshes):
-        path = str(tmp_path / f"{name}_{k}.stl")
-        scenes.write_stl(path, t)
-        objs.append({"type": "mesh", "file": path, "material": 0})
-    objs.append({"type": "plane", "point": [0, -1.5, 0], "normal": [0, 1, 0], "material": 1})
-    return {"camera": {"eye": list(eye), "up": [0, 1, 0], "look": [0.0, 0.0, 0.0], "near_plane": 0.1, "far_plane": 100.0, "width": w, "height": h, "ambient": 0.1},
-            "lights": lights,
-            "materials": [{"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.0, "phong": 40},
-                          {"type": "solid", "color": [0.3, 0.5, 0.9], "specular": 0.2, "reflect": 0.0, "phong": 10}],
-            "objects": objs}
-
-
-OFF = [{"type": "point", "point": [3.0, -1.0, 1.0], "color": [0.9, 0.9, 0.9]}]
 IN_POINT = [{"type": "point", "point": [3.0, -1.0, 0.5], "color": [0.9, 0.9, 0.9]}]
 OFF_SUN = [{"type": "sun", "direction": [0.3, -0.8, 0.5], "color": [0.9, 0.9, 0.9]}]
 IN_SUN = [{"type": "sun", "direction": [0.3, -0.8, 0.0], "color": [0.9, 0.9, 0.9]}]      # parallel to z = 0.5, to no filler
@@ -294,7 +134,7 @@ IN_SUN = [{"type": "sun", "direction": [0.3, -0.8, 0.0], "color": [0.9, 0.9, 0.9
 @pytest.mark.parametrize("k", [3, 70])
 def test_a_light_moved_into_the_plane_of_triangles_and_out_again(gpu, tmp_path, monkeypatch, k):
     """guard records (3), the linear fallback (70 > CTR_GUARD_SLOTS) and back to plain culling, through a point light and a sun"""
-    sc = _guard_scene(tmp_path, f"through_{k}", [_guard_tris(k)], OFF)
+    sc = guard_scene(tmp_path, f"through_{k}", [guard_tris(k)], OFF)
     want_in = ([], True) if k > 64 else (list(range(k)), False)
 
     def body():
@@ -307,7 +147,7 @@ def test_a_light_moved_into_the_plane_of_triangles_and_out_again(gpu, tmp_path, 
             fresh_scene = parse(gpu, edited(sc, lights=lights))
             upd.set_lights(desc_lights(fresh_scene))
             assert upd.guard_state(0) == want, f"{k} triangles in the plane, {what}: {upd.guard_state(0)}"
-            states += assert_equals_fresh(gpu, upd, fresh_scene, f"{k} triangles in the plane, {what}", bounces=2)
+            states += assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), f"{k} triangles in the plane, {what}", bounces=2, same_trees=True)
         return states
     each_scan(monkeypatch, body)
 
@@ -341,7 +181,7 @@ def test_every_leaf_position_answers_for_itself(gpu, tmp_path, monkeypatch, size
     for n in sizes:
         meshes.append(_stack(n, first))
         first += n
-    sc = _guard_scene(tmp_path, "stack_" + "_".join(map(str, sizes)), meshes, OFF)
+    sc = guard_scene(tmp_path, "stack_" + "_".join(map(str, sizes)), meshes, OFF)
 
     def body():
         upd = gpu.DeviceScene(parse(gpu, sc))
@@ -354,7 +194,7 @@ def test_every_leaf_position_answers_for_itself(gpu, tmp_path, monkeypatch, size
                 states.append(got)
                 if i in (0, n // 2, n - 1):
                     fresh_scene = parse(gpu, edited(sc, lights=[{"type": "point", "point": [3.0, -1.0, _level(first + i)], "color": [0.9, 0.9, 0.9]}]))
-                    assert_equals_fresh(gpu, upd, fresh_scene, f"meshes {sizes}: mesh {m}, triangle {i}", bounces=1)
+                    assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), f"meshes {sizes}: mesh {m}, triangle {i}", bounces=1, same_trees=True)
             first += n
         return states
     each_scan(monkeypatch, body)
@@ -363,12 +203,12 @@ def test_every_leaf_position_answers_for_itself(gpu, tmp_path, monkeypatch, size
 def test_sixty_four_stay_guarded_sixty_five_go_linear_and_no_light_at_all(gpu, tmp_path, monkeypatch):
     """64 triangles in z = 0.5, 65 in z = 0.8 (and zero-area ones in both, which never count), one elsewhere; then no light at
     all, with the eye in the first plane: the eye is the only probe"""
-    a, b = _guard_tris(64, n_other=1, seed=3), _guard_tris(65, n_other=0, seed=4)
+    a, b = guard_tris(64, n_other=1, seed=3), guard_tris(65, n_other=0, seed=4)
     b[:, :, 2] = f32(0.8)
     mesh = np.concatenate([a, b])
     n_a = len(a)
-    sc = _guard_scene(tmp_path, "slots", [mesh], OFF)
-    sc_eye = _guard_scene(tmp_path, "slots_eye", [mesh], OFF, eye=[0.3, 0.8, 0.5])
+    sc = guard_scene(tmp_path, "slots", [mesh], OFF)
+    sc_eye = guard_scene(tmp_path, "slots_eye", [mesh], OFF, eye=[0.3, 0.8, 0.5])
 
     def body():
         upd = gpu.DeviceScene(parse(gpu, sc))
@@ -378,12 +218,12 @@ def test_sixty_four_stay_guarded_sixty_five_go_linear_and_no_light_at_all(gpu, t
             fresh_scene = parse(gpu, edited(sc, lights=[dict(OFF[0], point=[3.0, -1.0, z])]))
             upd.set_lights(desc_lights(fresh_scene))
             assert upd.guard_state(0) == want, (what, upd.guard_state(0))
-            states += assert_equals_fresh(gpu, upd, fresh_scene, what, bounces=2)
+            states += assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), what, bounces=2, same_trees=True)
         assert n_a == 64 + 1 + 2
         eye = gpu.DeviceScene(parse(gpu, sc_eye))
         eye.set_lights([])
         assert eye.guard_state(0) == (list(range(64)), False), eye.guard_state(0)
-        states += assert_equals_fresh(gpu, eye, parse(gpu, edited(sc_eye, lights=[])), "no light, the eye in the plane", bounces=2)
+        states += assert_equals_fresh(gpu, eye, gpu.DeviceScene(parse(gpu, edited(sc_eye, lights=[]))), "no light, the eye in the plane", bounces=2, same_trees=True)
         return states
     each_scan(monkeypatch, body)
 
@@ -397,13 +237,13 @@ def test_mesh_updates_and_light_edits_in_turn(gpu, tmp_path, monkeypatch):
     other = random_mesh(64, seed=31, spread=0.5) + f32([1.5, 0.5, -1.0])
 
     def tris(step, k):
-        t = _guard_tris(9, n_other=60, seed=30, zero_area=False)             # (shifted below: three points of a line would not stay one)
+        t = guard_tris(9, n_other=60, seed=30, zero_area=False)             # (shifted below: three points of a line would not stay one)
         t[k:9, :, 2] += f32(0.21)                                     # the others: z = 0.71, in nobody's plane
         t[:, :, 0] += f32(0.1 * step)                                 # (every triangle moves within its plane)
         return t
 
     def scene(step, k, lights):
-        return _guard_scene(tmp_path, f"mixed_{step}_{k}", [tris(step, k), other], lights)
+        return guard_scene(tmp_path, f"mixed_{step}_{k}", [tris(step, k), other], lights)
 
     def body():
         upd = gpu.DeviceScene(parse(gpu, scene(0, 0, OFF)))
@@ -423,14 +263,14 @@ def test_mesh_updates_and_light_edits_in_turn(gpu, tmp_path, monkeypatch):
             # the same vertices, so that both walk the same refitted tree
             ref = gpu.DeviceScene(parse(gpu, scene(0, 0, lights)))
             ref.update_mesh(0, desc_tris(fresh_scene, 0))
-            states += assert_equals_fresh(gpu, upd, fresh_scene, what, bounces=2, counters_of=ref)
+            states += assert_equals_fresh(gpu, upd, gpu.DeviceScene(fresh_scene), what, bounces=2, counters_of=ref)
         return states
     each_scan(monkeypatch, body)
 
 
 def test_the_merged_tree_stays_in_use_across_a_light_edit(gpu, tmp_path, monkeypatch):
-    a, b = _guard_tris(4, n_other=40, seed=1), _guard_tris(3, n_other=40, seed=2, zero_area=False) + f32([0.4, 0.3, 0.0])
-    sc = _guard_scene(tmp_path, "merged", [a, b], OFF)
+    a, b = guard_tris(4, n_other=40, seed=1), guard_tris(3, n_other=40, seed=2, zero_area=False) + f32([0.4, 0.3, 0.0])
+    sc = guard_scene(tmp_path, "merged", [a, b], OFF)
 
     def body():
         upd = gpu.DeviceScene(parse(gpu, sc))
@@ -443,7 +283,7 @@ def test_the_merged_tree_stays_in_use_across_a_light_edit(gpu, tmp_path, monkeyp
             upd.set_lights(desc_lights(fresh_scene))
             fresh = gpu.DeviceScene(fresh_scene)
             fresh.set_variant(gpu.VAR_MERGE)
-            states += assert_equals_fresh(gpu, upd, fresh_scene, f"merged tree, light {what}", bounces=2, base=gpu.VAR_MERGE, fresh=fresh)
+            states += assert_equals_fresh(gpu, upd, fresh, f"merged tree, light {what}", bounces=2, base=gpu.VAR_MERGE, same_trees=True)
             assert states[-2:] == want, (what, states[-2:])
             upd.render(bounces=2)
             assert upd.last_kernel() & KV_MERGE, f"light {what}: {upd.last_kernel():#x}"

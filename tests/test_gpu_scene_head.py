@@ -3,7 +3,6 @@ kernel-argument block.  The head holds COPIES of records the kernel otherwise re
 compared three ways: against the oracle (tests/util.assert_parity), bitwise — depth, normal, colour, ray count —
 against a handle created with CUTRACE_NO_SCENE_HEAD=1 (every record by pointer), and, wherever a handle's state
 changed between two renders, bitwise against a fresh handle.  Frames are 64x48 or smaller."""
-import contextlib
 import ctypes as C
 import json
 import os
@@ -13,7 +12,8 @@ import pytest
 
 import oracle
 
-from tests.util import _coplanar_scene, _multi_mesh_scene, assert_parity, same_bits
+from tests.gpu_support import assert_same_frame, env
+from tests.util import _coplanar_scene, _multi_mesh_scene, assert_parity, parse, same_bits
 
 pytestmark = pytest.mark.gpu
 NT = min(os.cpu_count() or 4, 16)
@@ -47,32 +47,6 @@ def room(n_axis=5, n_oblique=0, mesh=True, lights="sun+points", w=W, h=H, eye=No
     return json.dumps({"camera": cam, "lights": LIGHTS[lights], "materials": MATS, "objects": objs})
 
 
-@contextlib.contextmanager
-def head_switched_off():
-    """handles created inside take every record by pointer (the switch is read when a handle is created)"""
-    old = os.environ.get("CUTRACE_NO_SCENE_HEAD")
-    os.environ["CUTRACE_NO_SCENE_HEAD"] = "1"
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ["CUTRACE_NO_SCENE_HEAD"]
-        else:
-            os.environ["CUTRACE_NO_SCENE_HEAD"] = old
-
-
-def scene_of(ca, text):
-    s = ca.HostScene.parse(text)
-    assert s.ok
-    return s
-
-
-def assert_same_frame(a, b, what):
-    for k in ("depth", "normal", "color"):
-        assert same_bits(a[k], b[k]), f"{what}: {k} differs in {int((a[k].view(np.uint32) != b[k].view(np.uint32)).sum())} words"
-    assert a["ray_count"] == b["ray_count"], what
-
-
 def three_ways(ca, s, what, bounces=4, variant=0, render=None, oracle_kw=None, want=None):
     """oracle parity of a handle with the head; the same bits from a handle without it.  Returns the frame."""
     render = render or (lambda ds: ds.render(bounces=bounces))
@@ -80,7 +54,7 @@ def three_ways(ca, s, what, bounces=4, variant=0, render=None, oracle_kw=None, w
     ds.set_variant(variant)
     got = render(ds)
     ds.close()
-    with head_switched_off():
+    with env("CUTRACE_NO_SCENE_HEAD"):
         off = ca.DeviceScene(s)
     off.set_variant(variant)
     ref = render(off)
@@ -97,23 +71,23 @@ def three_ways(ca, s, what, bounces=4, variant=0, render=None, oracle_kw=None, w
 def test_planes(ca, n_axis, n_oblique):
     """0 .. 7 axis-aligned planes (5: the flagship's room; 7: a second triple, read by pointer) and 2 axis + 3 oblique
     planes, of which the head holds the axis triple only"""
-    three_ways(ca, scene_of(ca, room(n_axis, n_oblique)), f"{n_axis} axis + {n_oblique} oblique planes")
+    three_ways(ca, parse(ca, room(n_axis, n_oblique)), f"{n_axis} axis + {n_oblique} oblique planes")
 
 
 @pytest.mark.parametrize("lights", list(LIGHTS))
 def test_lights(ca, lights):
-    three_ways(ca, scene_of(ca, room(lights=lights)), f"lights: {lights}")
+    three_ways(ca, parse(ca, room(lights=lights)), f"lights: {lights}")
 
 
 def test_fudge_zero_takes_the_general_plane_code(ca):
     """fudge = 0: no axis fast path, so the head's triple goes unused although it is filled"""
-    s = scene_of(ca, room())
+    s = parse(ca, room())
     want = oracle.oracle_render(s, fudge=0.0, bounces=3, threads=NT)
     three_ways(ca, s, "fudge 0", render=lambda ds: ds.render(fudge=0.0, bounces=3), want=want)
 
 
 def test_no_mesh(ca):
-    three_ways(ca, scene_of(ca, room(mesh=False)), "no mesh")
+    three_ways(ca, parse(ca, room(mesh=False)), "no mesh")
 
 
 def test_one_mesh_with_guard_records(ca, tmp_path):
@@ -125,14 +99,14 @@ def test_one_mesh_with_guard_records(ca, tmp_path):
 
 @pytest.mark.parametrize("n_mesh", [2, 4])
 def test_several_meshes_read_by_pointer(ca, tmp_path, n_mesh):
-    s = scene_of(ca, _multi_mesh_scene(tmp_path, seed=3 + n_mesh, w=W, h=H, n_mesh=n_mesh))
+    s = parse(ca, _multi_mesh_scene(tmp_path, seed=3 + n_mesh, w=W, h=H, n_mesh=n_mesh))
     three_ways(ca, s, f"{n_mesh} meshes")
 
 
 def test_merged_tree_and_back(ca, tmp_path):
     """CTR_VAR_MERGE with 4 meshes: the head holds the merged pseudo mesh; set_variant to the merged tree and back on ONE
     handle gives what fresh handles give"""
-    s = scene_of(ca, _multi_mesh_scene(tmp_path, seed=11, w=W, h=H, opaque=True, n_mesh=4))
+    s = parse(ca, _multi_mesh_scene(tmp_path, seed=11, w=W, h=H, opaque=True, n_mesh=4))
     want = oracle.oracle_render(s, bounces=4, threads=NT)
     plain = three_ways(ca, s, "4 meshes", want=want)
     merged = three_ways(ca, s, "4 meshes, merged tree", variant=ca.VAR_MERGE, want=want)
@@ -150,7 +124,7 @@ def test_merged_tree_and_back(ca, tmp_path):
 
 def test_ignore_transparent_reads_the_heads_words(ca):
     """CTR_VAR_IGNORE_TRANSPARENT with a transparent plane (slot 1 of the axis triple) and a transparent mesh"""
-    s = scene_of(ca, room(plane_mats=[1, 3, 2, 1, 2], mesh_mat=3))
+    s = parse(ca, room(plane_mats=[1, 3, 2, 1, 2], mesh_mat=3))
     plain = ca.DeviceScene(s).render(bounces=3)
     got = three_ways(ca, s, "ignore transparent", bounces=3, variant=ca.VAR_IGNORE_TRANSPARENT,
                      oracle_kw={"ignore_transparent_primary": True})
@@ -183,8 +157,8 @@ def test_set_cameras_changes_the_guard_selection(ca, tmp_path):
     """render; set_cameras with an eye outside the triangles' plane (the guard records go, bvh_root returns to the root)
     and back into it; every render equals the oracle's, a fresh handle's and a handle's without the head"""
     stl = _eye_plane_mesh(tmp_path)
-    s_in = scene_of(ca, room(mesh_file=stl))
-    s_out = scene_of(ca, room(mesh_file=stl, eye=[1.1, 1.4, 3.6], look=[-0.3, -0.35, -1.0]))
+    s_in = parse(ca, room(mesh_file=stl))
+    s_out = parse(ca, room(mesh_file=stl, eye=[1.1, 1.4, 3.6], look=[-0.3, -0.35, -1.0]))
     cam_in, cam_out = _camera_of(ca, s_in), _camera_of(ca, s_out)
     ds = ca.DeviceScene(s_in)
     first = ds.render(bounces=3)
@@ -199,7 +173,7 @@ def test_set_cameras_changes_the_guard_selection(ca, tmp_path):
     fresh = ca.DeviceScene(s_out)
     assert_same_frame(second, fresh.render(bounces=3), "eye out of the plane: against a fresh handle")
     fresh.close()
-    with head_switched_off():
+    with env("CUTRACE_NO_SCENE_HEAD"):
         off = ca.DeviceScene(s_in)
     assert_same_frame(first, off.render(bounces=3), "eye in the plane: head on / off")
     off.set_cameras([cam_out])
@@ -210,7 +184,7 @@ def test_set_cameras_changes_the_guard_selection(ca, tmp_path):
 def test_batch_of_two_cameras(ca):
     """two frames with different cameras in one launch: one head serves both"""
     import torch
-    a, b = scene_of(ca, room()), scene_of(ca, room(eye=[-0.8, 0.9, 3.5]))
+    a, b = parse(ca, room()), parse(ca, room(eye=[-0.8, 0.9, 3.5]))
     cams = [_camera_of(ca, a), _camera_of(ca, b)]
     want = [oracle.oracle_render(x, bounces=3, threads=NT) for x in (a, b)]
     dev = torch.device("cuda:0")
@@ -230,7 +204,7 @@ def test_batch_of_two_cameras(ca):
     ds = ca.DeviceScene(a)
     got = batch(ds)
     ds.close()
-    with head_switched_off():
+    with env("CUTRACE_NO_SCENE_HEAD"):
         off = ca.DeviceScene(a)
     ref = batch(off)
     off.close()
@@ -248,11 +222,11 @@ def test_batch_of_two_cameras(ca):
 def test_supersampled(ca):
     """s = 2 at 16x16 output pixels"""
     from tests import aa_ref
-    big = scene_of(ca, room(w=32, h=32))
+    big = parse(ca, room(w=32, h=32))
     o = oracle.oracle_render(big, bounces=3, threads=NT)
     want = aa_ref.reduce_frame(o, 2)
     want["ray_count"] = o["ray_count"]
-    three_ways(ca, scene_of(ca, room(w=16, h=16)), "supersampled s=2", render=lambda ds: ds.render(bounces=3, samples=2), want=want)
+    three_ways(ca, parse(ca, room(w=16, h=16)), "supersampled s=2", render=lambda ds: ds.render(bounces=3, samples=2), want=want)
 
 
 def test_host_delivery(ca):
@@ -260,7 +234,7 @@ def test_host_delivery(ca):
     def pinned(ds):
         r = ds.render(bounces=3, pinned=True)
         return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in r.items()}  # (views of the handle's block)
-    s = scene_of(ca, room(w=64, h=16))
+    s = parse(ca, room(w=64, h=16))
     got = three_ways(ca, s, "host delivery", bounces=3, render=pinned)
     ds = ca.DeviceScene(s)
     assert_same_frame(got, ds.render(bounces=3), "host delivery / device buffers")

@@ -28,9 +28,9 @@ import pytest
 import oracle
 from cutrace_amd import lenses
 from tests import aa_ref, ray_ref, shade_ref
-from tests.test_gpu_kernel_choice import _expected
+from tests.gpu_support import expected_kernel, gpu  # noqa: F401  (gpu: the fixture)
 from tests.util import (PHONG_EXPONENTS, PHONG_LIGHTS, PHONG_RAYS_H, PHONG_RAYS_W, SHADING_FRAME_CASES, STACK_CASES, STACK_FLOOR,
-                        TOL, assert_same, f32, fast_pow_kept, light_scale, phong_rays, phong_scene_json, ref_dict, shading_case_id, shading_case_json,
+                        TOL, assert_same, f32, fast_pow_kept, light_scale, parse, phong_rays, phong_scene_json, ref_dict, shading_case_id, shading_case_json,
                         stack_cameras, stack_scene_json, to_np, uv_close)
 
 pytestmark = pytest.mark.gpu
@@ -43,21 +43,8 @@ FRAME_CASES = [pytest.param(c, id=shading_case_id(c)) for c in SHADING_FRAME_CAS
 
 
 @pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
-
-
-@pytest.fixture(scope="module")
 def golden():
     return np.load(os.path.join(ROOT, "tests", "golden", "kernel_choice.npz"))["choice"].reshape(6, 512, 8, 2, 4)
-
-
-def parsed(ca, text):
-    s = ca.HostScene.parse(text)
-    assert s.ok
-    return s
 
 
 def same_bits_nan(a, b):
@@ -104,7 +91,7 @@ def test_frame_case(gpu, golden, tmp_path, case):
     what = shading_case_id(case)
     family = case[0]
     text, bounces = shading_case_json(tmp_path, case)
-    s = parsed(gpu, text)
+    s = parse(gpu, text)
     w, h = s.size
     tol = TOL * max(1.0, light_scale(s))
     kw = dict(fudge=1e-3, bounces=bounces)
@@ -123,7 +110,7 @@ def test_frame_case(gpu, golden, tmp_path, case):
     kv_default = ds.last_kernel()
     print(f"{what}: kernel {kv_default:#x}, {r['ray_count']} casts, Lambda {light_scale(s):.3f}")
     # (outside the fast specular path's domain the launch is the one VAR_EXACT_POW gets: test_gpu_kernel_choice._expected)
-    assert kv_default == _expected(gpu, golden, s, 0, "render", bounces) and bool(kv_default & KV_FASTPOW) == fast_pow_kept(s), hex(kv_default)
+    assert kv_default == expected_kernel(gpu, golden, s, 0, "render", bounces) and bool(kv_default & KV_FASTPOW) == fast_pow_kept(s), hex(kv_default)
     assert bool(kv_default & KV_ANYHIT) == all_opaque, "any-hit only when every transparency is exactly +-0"
     assert_frame(r, want, tol, f"{what}, default build")
     assert r["ray_count"] == want["ray_count"], what
@@ -131,7 +118,7 @@ def test_frame_case(gpu, golden, tmp_path, case):
     for name, var in (("exact pow", exact), ("the reference's walk", exact | gpu.VAR_NO_PREFILTER | gpu.VAR_NO_CLUSTER), ("no any-hit", exact | gpu.VAR_NO_ANYHIT)):
         ds.set_variant(var)
         e = ds.render(**kw)
-        assert ds.last_kernel() == _expected(gpu, golden, s, var, "render", bounces), (what, name, hex(ds.last_kernel()))
+        assert ds.last_kernel() == expected_kernel(gpu, golden, s, var, "render", bounces), (what, name, hex(ds.last_kernel()))
         assert_bits(e, once, f"{what}, {name}, against the oracle with the pow rounded once")
         assert_frame(e, want, tol, f"{what}, {name}")
         assert e["ray_count"] == want["ray_count"], (what, name)
@@ -211,7 +198,7 @@ def test_frame_case(gpu, golden, tmp_path, case):
 @pytest.mark.parametrize("name", list(STACK_CASES))
 def test_stack_queries(gpu, tmp_path, name):
     for camera in stack_cameras(name):
-        s = parsed(gpu, stack_scene_json(tmp_path, name, camera)[0])
+        s = parse(gpu, stack_scene_json(tmp_path, name, camera)[0])
         sc = shade_ref.ShadeScene(s)
         ds = gpu.DeviceScene(s)
         o, d = ray_ref.camera_rays(sc.cam)
@@ -249,7 +236,7 @@ def test_phong_exponent_on_constructed_rays(gpu, tmp_path, e, light):
     max |colour_fast - colour_ref| is printed per exponent (profiles/shading_ranges/fastpow.txt holds the table) and held to
     TOL where the chooser's rule keeps the fast build."""
     what = f"e={e:g} {light}"
-    s = parsed(gpu, phong_scene_json(tmp_path, e, light, w=PHONG_RAYS_W, h=PHONG_RAYS_H))
+    s = parse(gpu, phong_scene_json(tmp_path, e, light, w=PHONG_RAYS_W, h=PHONG_RAYS_H))
     o, d = phong_rays(light)
     dn = ray_ref.vnormalized(d).astype(f32)   # what the lens render makes of its directions
     want = shade_ref.ray_color(shade_ref.ShadeScene(s), o, dn, min_t=1e-3, bounces=2)

@@ -4,46 +4,23 @@ top-level walk are compiled out.  Only code that such a scene never runs is remo
 A created normally, B under CUTRACE_NO_SHAPE_BUILD=1 (read when a handle is created: shape 0) — and compares depth, colour
 and normal BITWISE, the ray count and the build (last_kernel), and reads the shape back (last_shape: 1 for A, 0 for B).
 Scenes and variants the shape is not for must report shape 0 on both.  Frames are 96 x 54 or smaller."""
-import contextlib
-import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 
-from cutrace_amd import _lib, scenes
-from tests.util import _coplanar_scene, same_bits
+from tests.conftest import load_scene
+from tests.gpu_support import LIGHTS_IN, RIGHT, assert_same_frame, camera_of, env, gpu, held, octahedra, room  # noqa: F401  (gpu: the fixture)
+from tests.live import desc_tris
+from tests.util import _coplanar_scene, parse
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-FRAME = ("depth", "color", "normal")
 # scene_device.h KV_*: the default variant, with or without the 6-wave build (64), with or without host delivery (128)
 DEFAULT = 1 | 2 | 8 | 32
 ONE_MESH_BUILDS = {DEFAULT, DEFAULT | 64, DEFAULT | 128, DEFAULT | 64 | 128}
 W, H = 64, 48
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
-
-
-@contextlib.contextmanager
-def env(name):
-    """handles created inside see `name`=1 (both switches are read when a handle is created)"""
-    old = os.environ.get(name)
-    os.environ[name] = "1"
-    try:
-        yield
-    finally:
-        if old is None:
-            del os.environ[name]
-        else:
-            os.environ[name] = old
+LIGHT_BEHIND_WALL = {"type": "point", "point": [-3.0, 0.2, 0.5], "color": [0.7, 0.7, 0.7]}   # the wall x = -1 lies between it and the room
 
 
 def handles(ca, s, variant=0):
@@ -53,17 +30,6 @@ def handles(ca, s, variant=0):
     a.set_variant(variant)
     b.set_variant(variant)
     return a, b
-
-
-def assert_same_frame(a, b, what):
-    for k in FRAME:
-        assert same_bits(a[k], b[k]), f"{what}: {k} differs in {int((a[k].view(np.uint32) != b[k].view(np.uint32)).sum())} words"
-    assert a["ray_count"] == b["ray_count"], what
-
-
-def held(r):
-    """a frame that outlives the handle's next render (a pinned render returns views of the handle's block)"""
-    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in r.items()}
 
 
 def a_against_b(ca, s, what, render, shape=1, variant=0):
@@ -82,63 +48,18 @@ def a_against_b(ca, s, what, render, shape=1, variant=0):
     return got
 
 
-# ---- scenes: the flagship's room (five axis-aligned walls, open towards the camera) around meshes of small octahedra ----
-def octahedra(centres, r=0.12):
-    ax = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float64) * r
-    tris = [[c + ax[i], c + ax[j], c + ax[k]] for c in np.asarray(centres, np.float64) for i in (0, 1) for j in (2, 3) for k in (4, 5)]
-    return np.asarray(tris, f32)
-
-
-RIGHT = [[0.5, -0.5, -0.3], [0.75, -0.2, 0.1], [0.6, 0.3, -0.5], [0.8, 0.5, 0.2], [0.55, 0.0, 0.3], [0.7, -0.7, -0.6]]   # x >= 0.38: the right half
-LIGHTS_IN = [{"type": "point", "point": [0.5, 0.8, 1.5], "color": [0.6, 0.6, 0.6]},
-             {"type": "point", "point": [-0.6, 0.7, 1.0], "color": [0.4, 0.4, 0.5]}]
-LIGHT_BEHIND_WALL = {"type": "point", "point": [-3.0, 0.2, 0.5], "color": [0.7, 0.7, 0.7]}   # the wall x = -1 lies between it and the room
-FLOOR = 4   # index of the floor among the walls
-
-
-def room(tmp_path, name, meshes, w=W, h=H, lights=LIGHTS_IN, sphere=False, transparent=False, floor_y=-1.0, eye=(0.0, 0.0, 2.8)):
-    """(scene JSON, index of the first mesh, index of the floor): the meshes, then the five walls, then — `sphere` — a sphere"""
-    objs = []
-    for k, t in enumerate(meshes):
-        path = str(tmp_path / f"{name}_{k}.stl")
-        scenes.write_stl(path, np.asarray(t, f32))
-        objs.append({"type": "mesh", "file": path, "material": 0})
-    walls = [([-1, 0, 0], [1, 0, 0]), ([0, 0, -1], [0, 0, 1]), ([0, 1, 0], [0, -1, 0]), ([1, 0, 0], [-1, 0, 0]), ([0, floor_y, 0], [0, 1, 0])]
-    objs += [{"type": "plane", "point": p, "normal": n, "material": 1 + i % 2} for i, (p, n) in enumerate(walls)]
-    if sphere:
-        objs.append({"type": "sphere", "center": [-0.5, -0.6, 0.0], "radius": 0.3, "material": 2})
-    mats = [{"type": "solid", "color": [0.8, 0.6, 0.3], "specular": 0.4, "reflect": 0.3, "phong": 40},
-            {"type": "solid", "color": [0.3, 0.5, 0.9], "specular": 0.2, "reflect": 0.1, "phong": 10},
-            {"type": "solid", "color": [0.9, 0.9, 0.9], "specular": 0.5, "reflect": 0.2, "phong": 80, "transparency": 0.5 if transparent else 0.0}]
-    cam = {"eye": list(eye), "up": [0, 1, 0], "look": [0.0, 0.0, -1.0], "near_plane": 0.1, "far_plane": 100.0, "width": w, "height": h, "ambient": 0.1}
-    return json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs}), 0, len(meshes) + FLOOR
-
-
-def parse(ca, text):
-    s = ca.HostScene.parse(text)
-    assert s.ok
-    return s
-
-
-def bunny(ca, w, h):
-    s = ca.HostScene.load("scene/bunny.json")
-    assert s.ok
-    s.set_size(w, h)
-    return s
-
-
 # ---- the flagship scene ----
 @pytest.mark.parametrize("bounces", [0, 1, 5])
 @pytest.mark.parametrize("size", [(96, 54), (37, 21)], ids=["96x54", "37x21"])
 def test_bunny(gpu, size, bounces):
     """whole tiles and a few rows over; partial tiles in both directions"""
-    a_against_b(gpu, bunny(gpu, *size), f"bunny {size} bounces {bounces}", lambda ds: ds.render(bounces=bounces))
+    a_against_b(gpu, load_scene(gpu, "bunny", *size), f"bunny {size} bounces {bounces}", lambda ds: ds.render(bounces=bounces))
 
 
 def test_bunny_five_wave_build(gpu):
     """VAR_NO_OCC6 keeps the default variant's 5-wave build: one of the four, so the shape applies"""
-    a = a_against_b(gpu, bunny(gpu, 96, 54), "bunny, no 6-wave build", lambda ds: ds.render(bounces=5), variant=gpu.VAR_NO_OCC6)
-    b = a_against_b(gpu, bunny(gpu, 96, 54), "bunny", lambda ds: ds.render(bounces=5))
+    a = a_against_b(gpu, load_scene(gpu, "bunny", 96, 54), "bunny, no 6-wave build", lambda ds: ds.render(bounces=5), variant=gpu.VAR_NO_OCC6)
+    b = a_against_b(gpu, load_scene(gpu, "bunny", 96, 54), "bunny", lambda ds: ds.render(bounces=5))
     assert_same_frame(a, b, "5-wave / 6-wave build")
 
 
@@ -177,20 +98,14 @@ def test_mesh_with_guard_records(gpu, tmp_path):
 def test_rows_in_two_parts(gpu):
     """8-row blocks dealt to 2 parts (54 rows: 30 and 24)"""
     for part in (0, 1):
-        a_against_b(gpu, bunny(gpu, 96, 54), f"part {part} of 2", lambda ds: ds.render(bounces=3, rows=(0, 54, 8, part, 2)))
-
-
-def _camera_of(ca, s):
-    c = ca.Camera()
-    C.memmove(C.byref(c), C.byref(s.desc.contents.cam), C.sizeof(ca.Camera))
-    return c
+        a_against_b(gpu, load_scene(gpu, "bunny", 96, 54), f"part {part} of 2", lambda ds: ds.render(bounces=3, rows=(0, 54, 8, part, 2)))
 
 
 def test_batch_of_two_frames_with_part_stride(gpu, tmp_path):
     """render_device_batch: two cameras in one launch, the part rotating from frame to frame (part_stride 1)"""
     import torch
     s = parse(gpu, room(tmp_path, "batch", [octahedra(RIGHT)])[0])
-    cams = [_camera_of(gpu, s), _camera_of(gpu, parse(gpu, room(tmp_path, "batch2", [octahedra(RIGHT)], eye=(-0.4, 0.3, 2.6))[0]))]
+    cams = [camera_of(gpu, s), camera_of(gpu, parse(gpu, room(tmp_path, "batch2", [octahedra(RIGHT)], eye=(-0.4, 0.3, 2.6))[0]))]
     dev = torch.device("cuda:0")
     n_rows = 24   # 48 rows in 8-row blocks, 2 parts: 24 rows each
 
@@ -213,25 +128,17 @@ def test_batch_of_two_frames_with_part_stride(gpu, tmp_path):
 def test_host_call_into_page_locked_and_pageable_buffers(gpu, tmp_path):
     """page-locked buffers: the kernel delivers the frame itself (the KV_HOSTOUT twins, 6-wave for the bunny, 5-wave for 48
     triangles); pageable ones: device buffers and a copy.  All four are the same frame per scene."""
-    for name, s in (("bunny", bunny(gpu, 96, 54)), ("room", parse(gpu, room(tmp_path, "host", [octahedra(RIGHT)])[0]))):
+    for name, s in (("bunny", load_scene(gpu, "bunny", 96, 54)), ("room", parse(gpu, room(tmp_path, "host", [octahedra(RIGHT)])[0]))):
         pinned = a_against_b(gpu, s, f"{name}, page-locked", lambda ds: ds.render(bounces=3, pinned=True))
         pageable = a_against_b(gpu, s, f"{name}, pageable", lambda ds: ds.render(bounces=3))
         assert_same_frame(pinned, pageable, f"{name}: page-locked / pageable")
-    ds = gpu.DeviceScene(bunny(gpu, 96, 54))
+    ds = gpu.DeviceScene(load_scene(gpu, "bunny", 96, 54))
     ds.render(bounces=3, pinned=True)
     assert ds.last_kernel() & 128, "the page-locked call was meant to take the host-delivery build"
     ds.close()
 
 
 # ---- edits of a live one-mesh handle ----
-def desc_tris(hs, obj):
-    """the triangles of mesh `obj` as the description holds them: exactly what a fresh handle is built from"""
-    d = hs.desc.contents
-    o = d.objects[obj]
-    n = int(o.tri_count)
-    return np.frombuffer(C.string_at(C.addressof(d.triangles[int(o.tri_begin)]), n * C.sizeof(_lib.Triangle)), f32).reshape(n, 3, 3).copy()
-
-
 def test_edits_keep_the_shape_and_equal_a_fresh_handle(gpu, tmp_path):
     """update_mesh (refit), rebuild_mesh (a new tree) and a moved plane on ONE handle: still shape 1, and each frame is a
     fresh handle's on the edited scene"""
@@ -276,7 +183,7 @@ def test_scenes_that_stay_in_shape_0(gpu, tmp_path):
 
 
 def test_variants_outside_the_four_builds_stay_in_shape_0(gpu):
-    s = bunny(gpu, 96, 54)
+    s = load_scene(gpu, "bunny", 96, 54)
     want = a_against_b(gpu, s, "default", lambda ds: ds.render(bounces=3))
     for name in ("VAR_STATS", "VAR_NO_PREFILTER", "VAR_NO_ANYHIT", "VAR_EXACT_POW"):
         got = a_against_b(gpu, s, name, lambda ds: ds.render(bounces=3), shape=0, variant=getattr(gpu, name))
@@ -287,7 +194,7 @@ def test_variants_outside_the_four_builds_stay_in_shape_0(gpu):
 def test_no_direct_on_the_host_path_takes_the_twin_without_delivery(gpu):
     """VAR_NO_DIRECT with page-locked buffers: the frame leaves through device buffers, i.e. the launch is the default
     variant's build without KV_HOSTOUT — one of the four builds, for which launch_shape's rule is shape 1"""
-    s = bunny(gpu, 96, 54)
+    s = load_scene(gpu, "bunny", 96, 54)
     got = a_against_b(gpu, s, "VAR_NO_DIRECT", lambda ds: ds.render(bounces=3, pinned=True), variant=gpu.VAR_NO_DIRECT)
     ds = gpu.DeviceScene(s)
     ds.set_variant(gpu.VAR_NO_DIRECT)
@@ -299,7 +206,7 @@ def test_no_direct_on_the_host_path_takes_the_twin_without_delivery(gpu):
 
 def test_a_handle_without_scene_head_stays_in_shape_0(gpu):
     """CUTRACE_NO_SCENE_HEAD=1: the mesh record is read by pointer, which the one-mesh build has no code for"""
-    s = bunny(gpu, 96, 54)
+    s = load_scene(gpu, "bunny", 96, 54)
     with env("CUTRACE_NO_SCENE_HEAD"):
         got = a_against_b(gpu, s, "no scene head", lambda ds: ds.render(bounces=3), shape=0)
     assert_same_frame(got, a_against_b(gpu, s, "default", lambda ds: ds.render(bounces=3)), "no scene head / default")

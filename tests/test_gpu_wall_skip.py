@@ -13,21 +13,15 @@ import pytest
 
 import oracle
 from cutrace_amd import _lib
-from tests.test_gpu_shape_build import LIGHTS_IN, RIGHT, assert_same_frame, bunny, env, held, octahedra, parse, room
-from tests.util import assert_parity
+from tests.conftest import load_scene
+from tests.gpu_support import LIGHTS_IN, RIGHT, assert_same_frame, env, gpu, held, octahedra, room  # noqa: F401  (gpu: the fixture)
+from tests.util import assert_parity, parse
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 W, H = 64, 48
 BOUNCES = 3
-
-
-@pytest.fixture(scope="module")
-def gpu(ca):
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return ca
 
 
 def handles(ca, s, variant=0):
@@ -97,7 +91,7 @@ def point(x, y, z, c=0.5):
 
 # 1
 def test_bunny_room(gpu):
-    s = bunny(gpu, W, H)
+    s = load_scene(gpu, "bunny", W, H)
     _, facts = a_against_b(gpu, s, "bunny")
     assert facts["lights"] == 0xF and facts["delta"] >= 2e-6 and facts["r"] > 0, facts
     trips, without, got = skipped(gpu, s, lambda ds: ds.render(bounces=BOUNCES))
@@ -276,7 +270,7 @@ def test_live_edits_equal_a_fresh_handle(gpu, tmp_path):
 def test_supersampled_lens_and_host_delivery_launches(gpu):
     import torch
     from cutrace_amd import lenses
-    s = bunny(gpu, W, H)
+    s = load_scene(gpu, "bunny", W, H)
     plain, _ = a_against_b(gpu, s, "bunny", with_oracle=False)
     a_against_b(gpu, s, "2 x 2 samples", lambda ds: ds.render(bounces=BOUNCES, samples=2), with_oracle=False)
     pinned, _ = a_against_b(gpu, s, "page-locked buffers", lambda ds: ds.render(bounces=BOUNCES, pinned=True), with_oracle=False)

@@ -13,7 +13,7 @@ import oracle
 
 from cutrace_amd import _lib
 from tests import images_ref as ir
-from tests.test_abi import declared
+from tests.checkers import declared
 
 ROOT = _lib.ROOT
 f32 = np.float32

@@ -3,28 +3,21 @@ nine CTR_VAR_* bits that matter x scene flags x deliverable x stack shape, 196 6
 against what the launch path chose before there was a chooser (tests/golden/kernel_choice.npz, recorded from that code:
 tests/golden/kernel_choice.md)."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.checkers import CHOICE_SOURCES, I_CSRC, I_INCLUDE, ROOT, check_output, check_program
+
 GOLDEN = os.path.join(ROOT, "tests", "golden", "kernel_choice.npz")
 SHAPE = (6, 512, 8, 2, 4)  # entry, user mask, scene flags, deliverable, stack shape
 REJECTED = 0xF000          # + KernelReject; 0xFFFF: the chooser's outputs contradict each other
 
 
-def choices(tmp_path):
+def choices(tmp_path_factory):
     """(cases in SHAPE as uint16, the KVs of CTR_RENDER_KERNELS, cases the tile-order bits changed, cases in which a scene
     outside the fast specular path's domain gets another build than CTR_VAR_EXACT_POW would)"""
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path / "kernel_choice_check")
-    csrc = os.path.join(ROOT, "cutrace_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I" + csrc, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "kernel_choice_check.cpp"), os.path.join(csrc, "kernel_choice.cpp")])
-    words = subprocess.run([exe], capture_output=True, text=True, timeout=600, check=True).stdout.split()
+    exe = check_program(tmp_path_factory, "kernel_choice_check", ("-O2", I_CSRC, I_INCLUDE), CHOICE_SOURCES)
+    words = check_output(exe).split()
     at_list, at_neutral = words.index("list"), words.index("neutral")
     got = np.array([int(x, 16) for x in words[:at_list]], np.uint16)
     assert got.size == int(np.prod(SHAPE))
@@ -32,8 +25,8 @@ def choices(tmp_path):
     return got.reshape(SHAPE), [int(x, 16) for x in words[at_list + 1:at_neutral]], int(words[at_neutral + 1]), int(words[at_slow + 1])
 
 
-def test_every_launch_gets_the_build_it_got_before_the_chooser(tmp_path):
-    got, builds, moved, slowpow = choices(tmp_path)
+def test_every_launch_gets_the_build_it_got_before_the_chooser(tmp_path_factory):
+    got, builds, moved, slowpow = choices(tmp_path_factory)
     want = np.load(GOLDEN)["choice"].reshape(SHAPE)
     diff = np.argwhere(got != want)
     assert diff.size == 0, [(tuple(i), hex(want[tuple(i)]), hex(got[tuple(i)])) for i in diff[:10]]

@@ -12,6 +12,7 @@ import pytest
 
 from cutrace_amd import _lib, lenses
 from tests import ray_ref
+from tests.checkers import CHOICE_SOURCES, I_CSRC, I_INCLUDE, check_output, check_program
 from tests.util import _random_scene, same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,13 +25,8 @@ REJECTING = NO_PREFILTER | NO_CLUSTER | STATS | IGNTR
 
 @pytest.fixture(scope="module")
 def lens_choices(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path_factory.mktemp("lens") / "kernel_choice_lens_check")
-    csrc = os.path.join(ROOT, "cutrace_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I" + csrc, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "kernel_choice_lens_check.cpp"), os.path.join(csrc, "kernel_choice.cpp")])
-    words = subprocess.run([exe], capture_output=True, text=True, timeout=600, check=True).stdout.split()
+    exe = check_program(tmp_path_factory, "kernel_choice_lens_check", ("-O2", I_CSRC, I_INCLUDE), CHOICE_SOURCES)
+    words = check_output(exe).split()
     at = {k: words.index(k) for k in ("list", "render", "reject", "neutral")}
     got = np.array([int(x, 16) for x in words[:at["list"]]], np.uint16)
     assert got.size == int(np.prod(SHAPE))

@@ -5,29 +5,18 @@ it checks.  Plus the declaration of the one entry point and the argument checks 
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 from cutrace_amd import _lib
+from tests.checkers import CSRC, ROOT, check_report, declared
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cutrace_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
     """the lines scripts/mesh_rebuild_check.cpp prints, once for all tests"""
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path_factory.mktemp("mesh_rebuild_check") / "mesh_rebuild_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "mesh_rebuild_check.cpp"), os.path.join(CSRC, "scene_flatten.cpp"),
-                           os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "bvh.cpp"), os.path.join(ROOT, "cutrace_amd", "host", "scene_host.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "all checks hold" in out.stdout, out.stdout[-4000:] + out.stderr[-2000:]
-    return out.stdout.splitlines()
+    return check_report(tmp_path_factory, "mesh_rebuild_check")
 
 
 def _max_levels():
@@ -95,7 +84,6 @@ def test_mesh_rebuilt_on_the_host(report):
 
 
 def test_rebuild_entry_point_is_declared_and_checks_its_arguments_without_a_device():
-    from tests.test_abi import declared
     names = declared("cutrace_rebuild.h")
     assert set(names) == set(_lib.REBUILD_SYMBOLS) == {"ctr_scene_rebuild_mesh"}
     L = _lib.hip_lib()

@@ -12,7 +12,7 @@ TRIANGLE, MESH, PLANE, SPHERE = 0, 1, 2, 3
 
 
 def test_object_entry_points_are_declared_and_check_their_arguments_without_a_device():
-    from tests.test_abi import declared
+    from tests.checkers import declared
     names = declared("cutrace_objects.h")
     assert set(names) == set(_lib.OBJECT_SYMBOLS) == {"ctr_scene_set_objects", "ctr_scene_object_count", "ctr_scene_get_object"}
     assert '#include "cutrace_objects.h"' in open(_lib.ROOT + "/include/cutrace_edit.h").read()   # cutrace_edit.h brings them along

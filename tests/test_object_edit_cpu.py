@@ -1,15 +1,12 @@
 """Host logic (CPU, no GPU) of the object edits (include/cutrace_objects.h): check_objects / objects_edited / object_of of
 scene_flatten.cpp with the guard behind them, run through scripts/object_edit_check.cpp, which states what it checks: every edit
 of its rows applied to ONE flat scene against flatten_scene of the edited description, byte for byte."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cutrace_amd", "csrc")
+from tests.checkers import ROOT, check_report
+
 A, B, C_ = "a: planes, spheres, triangles", "b: box room", "c: two meshes"
 ROWS = [A, B, B + " (merged)", C_, C_ + " (merged)"]
 
@@ -17,15 +14,7 @@ ROWS = [A, B, B + " (merged)", C_, C_ + " (merged)"]
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
     """the lines scripts/object_edit_check.cpp prints, once for all tests"""
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path_factory.mktemp("object_edit_check") / "object_edit_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "object_edit_check.cpp"), os.path.join(CSRC, "scene_flatten.cpp"),
-                           os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "bvh.cpp"), os.path.join(ROOT, "cutrace_amd", "host", "scene_host.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0 and "all checks hold" in out.stdout, out.stdout[-4000:] + out.stderr[-2000:]
-    return out.stdout.splitlines()
+    return check_report(tmp_path_factory, "object_edit_check", cwd=ROOT)
 
 
 def _edits(report):

@@ -4,9 +4,7 @@
  (b) where oracle/_ref exists (the build container; the prebuilt .so also travels to the
      GPU box), bit-for-bit against a live run of that reference build.
 The reference holds no render tests or golden vectors of its own."""
-import glob
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,15 +12,9 @@ import pytest
 import oracle
 
 from tests.conftest import load_scene
-from tests.util import same_bits
+from tests.util import GOLD, GOLD_SMALL, golden_case, same_bits
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SMALL = sorted(glob.glob(os.path.join(GOLD, "small_*.npz")))
-
-
-def parse(path):
-    m = re.match(r"(small|full)_(.+)_(\d+)x(\d+)_b(\d+)\.npz", os.path.basename(path))
-    return m.group(2), int(m.group(3)), int(m.group(4)), int(m.group(5))
+SMALL = GOLD_SMALL
 
 
 def test_golden_fixtures_exist():
@@ -31,7 +23,7 @@ def test_golden_fixtures_exist():
 
 @pytest.mark.parametrize("path", SMALL, ids=[os.path.basename(p) for p in SMALL])
 def test_oracle_matches_golden_bit_for_bit(ca, path):
-    name, w, h, b = parse(path)
+    name, w, h, b = golden_case(path)
     g = np.load(path)
     s = load_scene(ca, name, w, h)
     r = oracle.oracle_render(s, bounces=b, threads=4)

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import oracle
-from tests.test_scene_flatten import harness, run  # noqa: F401  (the fixture that builds scripts/flatten_check.cpp)
+from tests.checkers import harness, run  # noqa: F401  (the fixture that builds scripts/flatten_check.cpp)
 from tests import aa_ref
 from tests.util import (ALL_MISS_CASE, OFFSET_CASES, RANGE_FLAVOURS, RANGE_KINDS, RANGE_POW_DEPENDENT, RENDER_RANGE_CASES, SCALE_EXPONENTS,
                         pow2, range_case_id, range_fudge, render_range_scene_json, same_bits)

@@ -2,39 +2,25 @@
 plane room") on the CPU, through scripts/room_facts_check.cpp, which states what it checks: a search for counter-examples of the
 lemma in float (10^6 origins here; its default from the command line is 2 * 10^7), the two mutations under which the search
 must find some, and the facts of the project's own scenes — where they must be set and where every word must be zero."""
-import ctypes as C
 import json
 import os
 import re
-import shutil
-import subprocess
 
-import numpy as np
 import pytest
 
 import cutrace_amd as ca
-from cutrace_amd import _lib
+from tests.checkers import FLATTEN_SOURCES, HOST_FLAGS, ROOT, check_output, check_program, write_scene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cutrace_amd", "csrc")
 N = 1000000
 
 
 @pytest.fixture(scope="module")
 def checker(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path_factory.mktemp("room_facts_check") / "room_facts_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "room_facts_check.cpp"), os.path.join(CSRC, "scene_flatten.cpp"),
-                           os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "bvh.cpp")])
-    return exe
+    return check_program(tmp_path_factory, "room_facts_check", HOST_FLAGS, FLATTEN_SOURCES)
 
 
 def search(checker, *args):
-    out = subprocess.run([checker, str(N), *args], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    line = out.stdout.strip().splitlines()[-1]
+    line = check_output(checker, [str(N), *args]).strip().splitlines()[-1]
     assert line.startswith("checked "), line
     words = line.split()
     got = {words[i]: int(words[i + 1]) for i in range(1, len(words) - 1) if re.fullmatch(r"\d+", words[i + 1])}
@@ -63,17 +49,6 @@ def test_the_mutations_are_found(checker):
 
 
 # ---- the facts of whole scenes ----
-def write_scene(path, s):
-    """scripts/flatten_check.cpp's scene file of a HostScene"""
-    d = s.desc.contents
-    with open(path, "wb") as f:
-        f.write(np.array([d.n_objects, d.n_triangles, d.n_lights, d.n_materials, 0], "u8").tobytes())
-        for ptr, n, T in ((d.objects, d.n_objects, _lib.Object), (d.triangles, d.n_triangles, _lib.Triangle),
-                          (d.lights, d.n_lights, _lib.Light), (d.materials, d.n_materials, _lib.Material)):
-            f.write(C.string_at(ptr, n * C.sizeof(T)) if n else b"")
-        f.write(bytes(d.cam))
-
-
 def facts(checker, tmp_path, s, switch=False):
     path = str(tmp_path / "scene.bin")
     write_scene(path, s)
@@ -81,9 +56,9 @@ def facts(checker, tmp_path, s, switch=False):
     env.pop("CUTRACE_NO_WALL_SKIP", None)
     if switch:
         env["CUTRACE_NO_WALL_SKIP"] = "1"
-    out = subprocess.run([checker, "scene", path], capture_output=True, text=True, timeout=600, env=env)
-    assert out.returncode == 0 and out.stdout.startswith("facts "), out.stdout[-2000:] + out.stderr[-2000:]
-    w = out.stdout.split()
+    out = check_output(checker, ["scene", path], env=env)
+    assert out.startswith("facts "), out[-2000:]
+    w = out.split()
     return dict(c=[float(x) for x in w[2:5]], r=float(w[6]), delta=float(w[8]), lights=int(w[10], 16), box_holds=int(w[12]),
                 n_axis_recs=int(w[14]), plane_recs=int(w[16]), all_opaque=int(w[18]))
 

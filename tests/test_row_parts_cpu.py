@@ -2,24 +2,13 @@
 ctr_render.cpp, the part sizes of ctr_multi.hip) against its Python statement, cutrace_amd.tiling.part_rows, restricted to the row
 range — every h in 0..40, block_rows in 1..9, n_parts in 1..5, every part, row_begin in {0, block_rows, 2 block_rows} and
 row_end in {h, h - 3 where positive} (scripts/row_parts_check.cpp prints the cases)."""
-import os
-import shutil
-import subprocess
-
-import pytest
-
 from cutrace_amd.tiling import part_rows
+from tests.checkers import I_CSRC, check_output, check_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def test_shared_row_partition_equals_tiling_part_rows(tmp_path):
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path / "row_parts_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "cutrace_amd", "csrc"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "row_parts_check.cpp")])
-    lines = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.splitlines()
+def test_shared_row_partition_equals_tiling_part_rows(tmp_path_factory):
+    exe = check_program(tmp_path_factory, "row_parts_check", ("-O2", "-Wall", I_CSRC))
+    lines = check_output(exe, timeout=60).splitlines()
     seen = set()
     for line in lines:
         h, B, n, p, begin, end, first_block, n_rows = (int(x) for x in line.split())

@@ -3,33 +3,21 @@ scene_flatten.cpp with the guard behind them, and the shared plane scan of cutra
 guard.cpp had before — run through scripts/scene_edit_check.cpp, which states what it checks.  Plus the argument checks of the
 entry points and of the Python methods that need neither a handle nor a device."""
 import ctypes as C
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
 import cutrace_amd
 from cutrace_amd import _lib
+from tests.checkers import ROOT, check_report, declared
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cutrace_amd", "csrc")
 SCENES = ["scene/bunny.json", "scene/mirror.json", "scene/sphere_plane.json", "scene/triangle.json"]
 
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
     """the lines scripts/scene_edit_check.cpp prints, once for all tests"""
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path_factory.mktemp("scene_edit_check") / "scene_edit_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "scene_edit_check.cpp"), os.path.join(CSRC, "scene_flatten.cpp"),
-                           os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "bvh.cpp"), os.path.join(ROOT, "cutrace_amd", "host", "scene_host.cpp")])
-    out = subprocess.run([exe] + SCENES, capture_output=True, text=True, timeout=600, cwd=ROOT)
-    assert out.returncode == 0 and "all checks hold" in out.stdout, out.stdout[-4000:] + out.stderr[-2000:]
-    return out.stdout.splitlines()
+    return check_report(tmp_path_factory, "scene_edit_check", SCENES, cwd=ROOT)
 
 
 def _edits(report):
@@ -88,7 +76,6 @@ def test_shared_scan_text_equals_the_old_loop(report):
 
 
 def test_edit_entry_points_are_declared_and_check_their_arguments_without_a_device():
-    from tests.test_abi import declared
     names = declared("cutrace_edit.h")
     assert set(names) == set(_lib.EDIT_SYMBOLS) == {"ctr_scene_set_lights", "ctr_scene_set_materials", "ctr_scene_light_count",
                                                     "ctr_scene_material_count", "ctr_debug_guard_state"}

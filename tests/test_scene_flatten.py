@@ -2,109 +2,20 @@
 (cutrace_amd/csrc/scene_flatten.cpp) and the guard of the BVH culling (cutrace_amd/csrc/guard.cpp: plan_guards,
 apply_guards) — run through scripts/flatten_check.cpp on the project's own scenes.  Properties that hold by construction,
 no digests."""
-import ctypes as C
 import json
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from cutrace_amd import _lib, scenes
-from tests.util import _random_scene, _multi_mesh_scene
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "cutrace_amd", "csrc")
+import cutrace_amd
+from cutrace_amd import scenes
+from tests.checkers import CSRC, harness, run  # noqa: F401  (harness: the fixture that builds scripts/flatten_check.cpp)
+from tests.util import _random_scene, _multi_mesh_scene, parse
 
 GUARD_SLOTS = 64          # CTR_GUARD_SLOTS
 LEAF, PAD = 0x80000000, 0xFFFFFFFF   # BVH_LEAF_FLAG, CTR_PLANE_PAD
 OBJ_TRIANGLE, OBJ_MESH, OBJ_PLANE, OBJ_SPHERE, OBJ_MERGED = 0, 1, 2, 3, 4
-
-DOBJ = np.dtype([("type", "u4"), ("mat", "u4"), ("tri_begin", "u4"), ("tri_count", "u4"), ("node_begin", "u4"), ("node_count", "u4"),
-                 ("bvh_root", "u4"), ("index", "u4"), ("f", "f4", 8)])
-DTRI = np.dtype([("ab", "f4", (3, 2)), ("p", "f4", 3), ("orig", "u4"), ("n", "f4", 3), ("ke", "f4"), ("ke2", "f4"), ("pad1", "f4")])
-DNODE4 = np.dtype([("lo", "f4", (3, 4)), ("hi", "f4", (3, 4)), ("child", "u4", 4), ("axis", "u4"), ("pad", "u4", 3)])
-DPLANE = np.dtype([("p", "f4", (3, 2)), ("n", "f4", (3, 2)), ("index", "u4", 2), ("transparent", "u4", 2)])
-DMAT = np.dtype([("color", "f4", 3), ("specular", "f4"), ("reflexivity", "f4"), ("phong_exp", "f4"), ("transparency", "f4"), ("pad", "f4")])
-ARRAYS = {"objs": DOBJ, "oloop": DOBJ, "meshes": DOBJ, "planes": DPLANE, "tris": DTRI, "nodes4": DNODE4, "gn": np.dtype("f4"), "mats": DMAT}
-SCALARS = ["n_mesh", "tlas_root", "tlas_begin", "n_axis_recs", "has_mesh", "all_opaque", "need_cold", "any_bounce", "mesh_tris",
-           "mesh_bytes", "ray_slots", "merged_reserved", "merged_tri_begin", "merged_tri_count", "merged_node_begin", "merged_node_cap", "fast_pow_ok"]
-GUARD = ["node_begin", "node_count", "tri_begin", "tri_count", "obj_index", "mesh_pos"]
-
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path_factory.mktemp("flatten_check") / "flatten_check")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-pthread", "-I" + CSRC, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "flatten_check.cpp"), os.path.join(CSRC, "scene_flatten.cpp"),
-                           os.path.join(CSRC, "guard.cpp"), os.path.join(CSRC, "bvh.cpp")])
-    return exe
-
-
-def _typed(name, raw):
-    if name in ARRAYS:
-        return np.frombuffer(raw, ARRAYS[name])
-    if name in ("scalars", "plan"):
-        return np.frombuffer(raw, "u8")
-    if name in ("dirty", "merged_built"):
-        return np.frombuffer(raw, "u8").reshape(-1, 4)
-    if name in ("guards", "guarded", "linear", "merged", "merged_guarded"):
-        return np.frombuffer(raw, "u4")
-    return raw
-
-
-def run(harness, tmp_path, scene, eyes=None, merge=False):
-    """Flattens `scene` (a HostScene) and runs the guard once per camera set of `eyes` (a list of lists of eye positions;
-    default: the scene's own camera).  Returns (flat, stages): the sections after flatten_scene as a dict, and per
-    plan + apply a dict with its plan, dirty ranges, per-mesh guarded / linear lists and the arrays afterwards."""
-    d = scene.desc.contents
-    sets = []
-    for eye_list in ([None] if eyes is None else eyes):
-        arr = (_lib.Camera * len(eye_list or [0]))()
-        for k in range(len(arr)):
-            C.memmove(C.byref(arr[k]), C.byref(d.cam), C.sizeof(_lib.Camera))
-            if eye_list:
-                arr[k].pos = _lib.Vec3(*eye_list[k])
-        sets.append(arr)
-    path = str(tmp_path / "scene.bin")
-    with open(path, "wb") as f:
-        f.write(np.array([d.n_objects, d.n_triangles, d.n_lights, d.n_materials, len(sets)], "u8").tobytes())
-        for ptr, n, T in ((d.objects, d.n_objects, _lib.Object), (d.triangles, d.n_triangles, _lib.Triangle),
-                          (d.lights, d.n_lights, _lib.Light), (d.materials, d.n_materials, _lib.Material)):
-            f.write(C.string_at(ptr, n * C.sizeof(T)) if n else b"")
-        f.write(bytes(d.cam))
-        for arr in sets:
-            f.write(np.array([len(arr)], "u8").tobytes() + bytes(arr))
-    dump = str(tmp_path / "scene.dump")
-    out = subprocess.run([harness, path, dump] + (["merge"] if merge else []), capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and out.stdout.strip() == "ok", out.stdout[-2000:] + out.stderr[-2000:]
-    raw = open(dump, "rb").read()
-    stages, i = [dict(what="flat", guarded=[], linear=[])], 0
-    while i < len(raw):
-        j = raw.index(b"\n", i)
-        name, n = raw[i:j].split()
-        name, n = name.decode(), int(n)
-        if name in ("refresh", "again"):
-            stages.append(dict(what=name, guarded=[], linear=[]))
-        elif name in ("guarded", "linear"):
-            stages[-1][name].append(_typed(name, raw[j + 1:j + 1 + n]))
-        else:
-            stages[-1][name] = _typed(name, raw[j + 1:j + 1 + n])
-        i = j + 1 + n + 1
-    flat = stages[0]
-    flat["scalars"] = dict(zip(SCALARS, (int(x) for x in flat["scalars"])))
-    flat["guards"] = [dict(zip(GUARD, (int(x) for x in g))) for g in flat["guards"].reshape(-1, 6)]
-    return flat, stages[1:]
-
-
-def _parse(text):
-    import cutrace_amd as ca
-    s = ca.HostScene.parse(text)
-    assert s.ok
-    return s
 
 
 # ---------------------------------------------------------------- flatten_scene
@@ -262,11 +173,11 @@ def test_shipped_scenes_flatten_by_the_rules(harness, tmp_path, ca):
 
 @pytest.mark.parametrize("seed", range(12))
 def test_random_scenes_flatten_by_the_rules(harness, tmp_path, seed):
-    s = _parse(_random_scene(seed, extra_planes=seed % 2 == 1))
+    s = parse(cutrace_amd, _random_scene(seed, extra_planes=seed % 2 == 1))
     flat, stages = run(harness, tmp_path, s)
     check_flat(flat, s.desc.contents)
     check_ray_slots(flat, stages)
-    s = _parse(_multi_mesh_scene(tmp_path, seed, opaque=seed % 2 == 0, n_mesh=2 + seed % 4))
+    s = parse(cutrace_amd, _multi_mesh_scene(tmp_path, seed, opaque=seed % 2 == 0, n_mesh=2 + seed % 4))
     flat, stages = run(harness, tmp_path, s, merge=True)
     check_flat(flat, s.desc.contents)
     check_ray_slots(flat, stages)
@@ -338,7 +249,7 @@ LIGHTS = [{"type": "point", "point": [5.0, 6.0, 7.03], "color": [0.8, 0.8, 0.8]}
 
 
 def _scene(objs, mats=MATS, lights=LIGHTS, cam=CAM):
-    return _parse(json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs}))
+    return parse(cutrace_amd, json.dumps({"camera": cam, "lights": lights, "materials": mats, "objects": objs}))
 
 
 def test_plane_records_and_empty_meshes(harness, tmp_path):

@@ -16,20 +16,14 @@ import pytest
 
 import oracle
 from tests import ray_ref, shade_ref
-from tests.test_scene_flatten import harness, run  # noqa: F401  (the fixture that builds scripts/flatten_check.cpp)
+from tests.checkers import harness, run  # noqa: F401  (the fixture that builds scripts/flatten_check.cpp)
 from tests.util import (LIGHT_CASES, LIGHT_SUN_LENGTH_CASES, PHONG_EXPONENTS, PHONG_LIGHTS, PHONG_POINTS, PHONG_RAYS_H, PHONG_RAYS_W, PHONG_THETAS,
                         SHADING_FRAME_CASES, STACK_CASES, fast_pow_kept, STACK_FLOOR, THRESHOLD_MATERIAL, THRESHOLD_MODES, THRESHOLD_VALUES, f32, first_full_sheet,
-                        lights_scene_json, phong_rays, phong_scene_json, same_bits, shading_case_id, shading_case_json, stack_crossings,
+                        lights_scene_json, parse, phong_rays, phong_scene_json, same_bits, shading_case_id, shading_case_json, stack_crossings,
                         stack_cameras, stack_partial_sums, stack_scene_json, threshold_room_json)
 
 FRAME_CASES = [pytest.param(c, id=shading_case_id(c)) for c in SHADING_FRAME_CASES]
 FRAME = ("depth", "normal", "color")
-
-
-def parsed(ca, text):
-    s = ca.HostScene.parse(text)
-    assert s.ok
-    return s
 
 
 def same_bits_nan(a, b):
@@ -44,7 +38,7 @@ def same_bits_nan(a, b):
 @pytest.mark.parametrize("case", FRAME_CASES)
 def test_shade_ref_equals_the_oracle_with_the_pow_rounded_once(ca, tmp_path, case):
     text, bounces = shading_case_json(tmp_path, case)
-    s = parsed(ca, text)
+    s = parse(ca, text)
     sc = shade_ref.ShadeScene(s)
     o, d = ray_ref.camera_rays(sc.cam)
     r = shade_ref.ray_color(sc, o, d, min_t=1e-3, bounces=bounces)
@@ -66,7 +60,7 @@ def test_ref_render_equals_oracle_render(ca, tmp_path, case):
     if oracle.ref_lib() is None:
         pytest.skip("oracle/_ref not built here (needs the reference tree at build time)")
     text, bounces = shading_case_json(tmp_path, case)
-    s = parsed(ca, text)
+    s = parse(ca, text)
     o, r = oracle.oracle_render(s, bounces=bounces), oracle.ref_render(s, bounces=bounces)
     for k in FRAME:
         assert same_bits_nan(o[k], r[k]), k
@@ -86,7 +80,7 @@ def test_the_constructed_rays_sit_in_the_highlight(ca, tmp_path, e, light):
     o, d = phong_rays(light)
     assert o.shape == (PHONG_POINTS * len(PHONG_THETAS), 3) and len(o) == PHONG_RAYS_W * PHONG_RAYS_H
     d = ray_ref.vnormalized(d).astype(f32)
-    s = parsed(ca, phong_scene_json(tmp_path, e, light))
+    s = parse(ca, phong_scene_json(tmp_path, e, light))
     with_spec = shade_ref.ray_color(shade_ref.ShadeScene(s), o, d, bounces=0)
     s.set_material(0, specular=0.0)
     without = shade_ref.ray_color(shade_ref.ShadeScene(s), o, d, bounces=0)
@@ -156,7 +150,7 @@ def occluders(sc, start, nd, light_dist, step):
 def test_the_lower_camera_sees_floor_under_every_occluder_count(ca, tmp_path, name):
     """the floor pixels of the camera under the stack, per light: how many occluders the shadow loop meets on the way to it"""
     text, _ = stack_scene_json(tmp_path, name, "below")
-    s = parsed(ca, text)
+    s = parse(ca, text)
     sc = shade_ref.ShadeScene(s)
     g = oracle.oracle_render(s, bounces=0)
     assert (g["hit_id"] == STACK_FLOOR).all(), "the lower camera sees something else than the floor"
@@ -189,7 +183,7 @@ def test_the_lower_camera_sees_floor_under_every_occluder_count(ca, tmp_path, na
 def test_the_threshold_values_arrive_as_the_floats_they_are(ca):
     for mode in THRESHOLD_MODES:
         for v in THRESHOLD_VALUES:
-            m = parsed(ca, threshold_room_json(mode, v)).desc.contents.materials[THRESHOLD_MATERIAL]
+            m = parse(ca, threshold_room_json(mode, v)).desc.contents.materials[THRESHOLD_MATERIAL]
             for key, field in (("reflect", m.reflexivity), ("transparency", m.transparency)):
                 want = f32(v) if mode in (key, "both") else f32(0.0)
                 assert f32(field).view(np.uint32) == want.view(np.uint32), (mode, v, key)
@@ -203,17 +197,17 @@ def test_the_flattened_facts_follow_exact_zero_and_the_double_comparison(ca, har
     for v in THRESHOLD_VALUES:
         on = float(v) >= 1e-6
         assert on == (v in THRESHOLD_VALUES[4:8])
-        flat, _ = run(harness, tmp_path, parsed(ca, threshold_room_json(mode, v)))
+        flat, _ = run(harness, tmp_path, parse(ca, threshold_room_json(mode, v)))
         got = tuple(flat["scalars"][k] for k in ("all_opaque", "need_cold", "any_bounce"))
         assert got == (int(mode == "reflect" or v == 0), int(mode == "both" and on), 1), (mode, v, got)
         sc = json.loads(threshold_room_json(mode, v))
         sc["materials"][0]["reflect"] = 0.0
-        flat, _ = run(harness, tmp_path, parsed(ca, json.dumps(sc)))
+        flat, _ = run(harness, tmp_path, parse(ca, json.dumps(sc)))
         assert flat["scalars"]["any_bounce"] == int(on), (mode, v)
 
 
 def test_a_sun_of_any_length_gives_one_frame(ca, tmp_path):
-    frames = [oracle.oracle_render(parsed(ca, lights_scene_json(tmp_path, n)), bounces=3) for n in LIGHT_SUN_LENGTH_CASES]
+    frames = [oracle.oracle_render(parse(ca, lights_scene_json(tmp_path, n)), bounces=3) for n in LIGHT_SUN_LENGTH_CASES]
     for f in frames[1:]:
         for k in FRAME:
             assert same_bits(f[k], frames[0][k]), k
@@ -223,7 +217,7 @@ def test_the_restart_step_case_sits_on_the_rounding_of_the_restart(ca, tmp_path)
     """restart_step: under the vertical sun the second sheet is met within an ulp of the restart (float)((double)t1 + 1e-3); on a
     good part of the floor pixels the float sum t1 + 1e-3f is the neighbouring float and would decide the other way"""
     text, _ = stack_scene_json(tmp_path, "restart_step", "above")
-    sc = shade_ref.ShadeScene(parsed(ca, text))
+    sc = shade_ref.ShadeScene(parse(ca, text))
     o, d = ray_ref.camera_rays(sc.cam)
     floor = ray_ref.ray_cast(sc, o, d, f32(1e-3), ignore_transparent=True)
     assert (floor["object"] == STACK_FLOOR).all()
@@ -241,13 +235,13 @@ def test_the_flattened_scene_knows_where_the_fast_specular_path_stays_in_the_bar
     scenes; scene/bunny.json, the benchmark's, keeps the fast build"""
     from tests.conftest import load_scene
     seen = set()
-    scenes = [(f"phong e={e:g} {l}", parsed(ca, phong_scene_json(tmp_path, e, l))) for e in PHONG_EXPONENTS for l in PHONG_LIGHTS]
+    scenes = [(f"phong e={e:g} {l}", parse(ca, phong_scene_json(tmp_path, e, l))) for e in PHONG_EXPONENTS for l in PHONG_LIGHTS]
     scenes += [(n, load_scene(ca, n, 16, 16)) for n in ("bunny", "mirror", "sphere_plane", "triangle")]
-    scenes += [(n, parsed(ca, lights_scene_json(tmp_path, n))) for n in ("n0", "n33", "colours")]
+    scenes += [(n, parse(ca, lights_scene_json(tmp_path, n))) for n in ("n0", "n33", "colours")]
     for name, s in scenes:
         flat, _ = run(harness, tmp_path, s)
         assert flat["scalars"]["fast_pow_ok"] == int(fast_pow_kept(s)), name
         seen.add(fast_pow_kept(s))
         if name == "bunny":
             assert fast_pow_kept(s), "the benchmark's scene would change its build"
-    assert fast_pow_kept(parsed(ca, phong_scene_json(tmp_path, 0.0, "sun"))) and fast_pow_kept(parsed(ca, lights_scene_json(tmp_path, "n0")))
+    assert fast_pow_kept(parse(ca, phong_scene_json(tmp_path, 0.0, "sun"))) and fast_pow_kept(parse(ca, lights_scene_json(tmp_path, "n0")))

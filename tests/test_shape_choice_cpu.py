@@ -2,13 +2,8 @@
 kernel lists x n_oloop in {0, 1} x head_mesh in {0, 1} (scripts/shape_choice_check.cpp).  The one-mesh shape is for exactly
 four builds, the default variant with or without KV_OCC6 and with or without KV_HOSTOUT, on a scene without spheres and
 stand-alone triangles whose only mesh rides in the scene head; everything else stays in shape 0."""
-import os
-import shutil
-import subprocess
+from tests.checkers import CHOICE_SOURCES, I_CSRC, I_INCLUDE, check_output, check_program
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # scene_device.h KV_*
 PREFILTER, ANYHIT, BVH, FASTPOW, OCC6, HOSTOUT = 1, 2, 8, 32, 64, 128
 DEFAULT = PREFILTER | BVH | ANYHIT | FASTPOW
@@ -16,21 +11,16 @@ ONE_MESH_BUILDS = {DEFAULT, DEFAULT | OCC6, DEFAULT | HOSTOUT, DEFAULT | OCC6 | 
 KS_ONE_MESH = 1
 
 
-def answers(tmp_path):
-    if not shutil.which("g++"):
-        pytest.skip("no g++ here")
-    exe = str(tmp_path / "shape_choice_check")
-    csrc = os.path.join(ROOT, "cutrace_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I" + csrc, "-I" + os.path.join(ROOT, "include"), "-o", exe,
-                           os.path.join(ROOT, "scripts", "shape_choice_check.cpp"), os.path.join(csrc, "kernel_choice.cpp")])
-    lines = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True).stdout.split("\n")
+def answers(tmp_path_factory):
+    exe = check_program(tmp_path_factory, "shape_choice_check", ("-O2", I_CSRC, I_INCLUDE), CHOICE_SOURCES)
+    lines = check_output(exe, timeout=60).split("\n")
     at = lines.index("shapes")
     cases = [(int(kv, 16), int(n), int(hm), int(shape)) for kv, n, hm, shape in (l.split() for l in lines[:at])]
     return cases, [int(x, 16) for x in lines[at + 1:] if x]
 
 
-def test_the_one_mesh_shape_is_for_exactly_the_four_default_builds(tmp_path):
-    cases, shaped = answers(tmp_path)
+def test_the_one_mesh_shape_is_for_exactly_the_four_default_builds(tmp_path_factory):
+    cases, shaped = answers(tmp_path_factory)
     builds = sorted(set(kv for kv, _, _, _ in cases))
     assert len(builds) == 43 + 10 and len(cases) == 4 * len(builds)   # CTR_RENDER_KERNELS + CTR_LENS_KERNELS, each case once
     assert len(shaped) == 4 and set(shaped) == ONE_MESH_BUILDS        # CTR_SHAPE_KERNELS: the four, each once

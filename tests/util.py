@@ -1,6 +1,8 @@
 """Shared comparison helpers and scene builders for the parity tests."""
+import glob
 import json
 import os
+import re
 
 import numpy as np
 
@@ -142,7 +144,6 @@ def _coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed):
     and t — the regime in which the reference's float test can report a hit for a ray that passes far from the
     triangle (BVH caveat)."""
     import ctypes as C
-    import json
     from cutrace_amd import _lib, scenes
     rng = np.random.default_rng(seed)
     eye, up, look = (0.3, 0.8, 4.0), (0.0, 1.0, 0.0), (-0.05, -0.15, -1.0)
@@ -171,9 +172,7 @@ def _coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed):
           "objects": [{"type": "mesh", "file": stl, "material": 0},
                       {"type": "plane", "point": [0, -1.0, 0], "normal": [0, 1, 0], "material": 1},
                       {"type": "plane", "point": [0, 0, -6.0], "normal": [0, 0, 1], "material": 1}]}
-    s = ca.HostScene.parse(json.dumps(sc))
-    assert s.ok
-    return s
+    return parse(ca, sc)
 
 
 def _mirror_coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed, transparent, two_mirrors=False):
@@ -184,7 +183,6 @@ def _mirror_coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed, transparent, t
     pass-through rays that continue from an in-plane hit in the same plane) alpha and all three numerators of
     default_schema.hpp:57-78 are rounding noise.  Neither the eye nor any light lies in that plane."""
     import ctypes as C
-    import json
     from cutrace_amd import _lib, scenes
     rng = np.random.default_rng(seed)
     eye, up, look = (0.2, 0.9, 3.5), (0.0, 1.0, 0.0), (0.02, -0.1, -1.0)
@@ -202,7 +200,7 @@ def _mirror_coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed, transparent, t
     for (p_, n_) in mirrors:                              # images of the eye and of the row's plane, mirror after mirror
         nh = n_ / np.linalg.norm(n_)
         t_mirror = np.dot(p_ - E2, nh) / np.dot(v2, nh)   # where the row's central ray meets this mirror
-        assert t_mirror > 0
+        assert t_mirror > 0, f"the row's central ray does not meet the mirror: t = {t_mirror}"
         E2 = E2 - 2.0 * np.dot(E2 - p_, nh) * nh
         R2, v2 = R2 - 2.0 * np.dot(R2, nh) * nh, v2 - 2.0 * np.dot(v2, nh) * nh
     tris = []
@@ -229,9 +227,7 @@ def _mirror_coplanar_scene(ca, tmp_path, w, h, row, n_tris, seed, transparent, t
                       {"type": "plane", "point": [0, -1.5, 0], "normal": [0, 1, 0], "material": 1}] +
                      [{"type": "plane", "point": [float(x) for x in p_], "normal": [float(x) for x in n_], "material": 2}
                       for (p_, n_) in mirrors]}
-    s = ca.HostScene.parse(json.dumps(sc))
-    assert s.ok
-    return s
+    return parse(ca, sc)
 
 
 def _multi_mesh_scene(tmp_path, seed, w=96, h=64, opaque=False, n_mesh=4):
@@ -330,7 +326,8 @@ def refusal(entry, scene, query, what=""):
     query record (None: a null query) on the scene handle with CTR_E_INVALID"""
     import ctypes as C
     from cutrace_amd import _lib
-    assert entry(scene, C.byref(query) if query is not None else None, None) == 1, what
+    status = entry(scene, C.byref(query) if query is not None else None, None)
+    assert status == 1, f"{what}: status {status}, not CTR_E_INVALID (1)"
     return _lib.hip_lib().ctr_last_error().decode()
 
 
@@ -879,3 +876,21 @@ def shading_case_json(tmp_path, case):
     if case[0] == "phong":
         return phong_scene_json(tmp_path, case[1], case[2]), 2
     return lights_scene_json(tmp_path, case[1]), 3
+
+
+# ---- what CPU and GPU tests both need ----
+def parse(ca, sc):
+    """the HostScene of a scene description (JSON text, or the dict of one), which must parse"""
+    s = ca.HostScene.parse(sc if isinstance(sc, str) else json.dumps(sc))
+    assert s.ok, f"the scene description did not parse: status {s.status}"
+    return s
+
+
+GOLD = os.path.join(ROOT, "tests", "golden")
+GOLD_SMALL = sorted(glob.glob(os.path.join(GOLD, "small_*.npz")))   # <scene>_<w>x<h>_b<bounces>: generated by tests/golden/make_golden.py
+
+
+def golden_case(path):
+    """(scene name, width, height, bounces) of a golden file's name"""
+    m = re.match(r"(small|full)_(.+)_(\d+)x(\d+)_b(\d+)\.npz", os.path.basename(path))
+    return m.group(2), int(m.group(3)), int(m.group(4)), int(m.group(5))
