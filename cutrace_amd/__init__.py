@@ -852,6 +852,62 @@ class DeviceScene:
                 raise TypeError(f"set_object: an object of type {int(objs[i].type)} has no field {k!r}")
         self.set_objects(objs)
 
+    # ---- a live object count (include/cutrace_topology.h) ----
+    _OBJECT_KINDS = {"triangle": 0, "plane": 2, "sphere": 3}
+
+    def add_object(self, kind, material=0, **fields):
+        """Append a sphere, a plane or a stand-alone triangle (ctr_scene_add_object): `kind` is "sphere", "plane" or "triangle",
+        the fields are set_object's — center, radius; point, normal; p1, p2, p3 — and `material` an index into the scene's
+        materials.  Returns the new object's index, the object count before the call.  Afterwards every render and query gives,
+        bit for bit, what a scene created with the object appended gives.  A mesh is added by add_mesh."""
+        if kind not in self._OBJECT_KINDS:
+            raise ValueError(f"kind: expected 'sphere', 'plane' or 'triangle', got {kind!r}")
+        if isinstance(material, bool) or not isinstance(material, (int, np.integer)) or material < 0:
+            raise ValueError(f"bad material index {material!r}")
+        o = Object()
+        o.type, o.mat_idx = self._OBJECT_KINDS[kind], int(material)
+        own = self._OBJECT_FIELDS[int(o.type)]
+        for k, v in fields.items():
+            if k not in own:
+                raise TypeError(f"add_object: a {kind} has no field {k!r}")
+            setattr(o, own[k], v if k == "radius" else Vec3(*v))
+        index = C.c_uint64()
+        _check("ctr_scene_add_object", _lib.hip_lib().ctr_scene_add_object(self._h, C.byref(o), C.byref(index)))
+        return int(index.value)
+
+    def add_mesh(self, triangles, material=0, builder="device", stream=None):
+        """Append a mesh (ctr_scene_add_mesh): `triangles`, `builder` and `stream` are replace_mesh's, `material` an index into
+        the scene's materials.  Afterwards every render and query gives, bit for bit, what a scene created with the mesh
+        appended gives.  Returns what was built and where: index (the new object's), builder, fell_back, node_count, levels
+        as replace_mesh; tris_reused, nodes_reused (1: the mesh lives in a range of that array that a removed object left
+        behind); tri_cap (the triangles its range has room for).  n = 0, a material index out of range or a vertex that is not
+        finite raise RuntimeError and leave the scene as it was."""
+        if builder not in ("device", "host"):
+            raise ValueError(f"builder: expected 'device' or 'host', got {builder!r}")
+        if isinstance(material, bool) or not isinstance(material, (int, np.integer)) or material < 0:
+            raise ValueError(f"bad material index {material!r}")
+        dev = self._torch_device()
+        triangles, ptr = self._mesh_triangles(triangles, dev)
+        info = _lib.AddInfo()
+        with _on_stream(dev, stream) as raw:
+            _check("ctr_scene_add_mesh", _lib.hip_lib().ctr_scene_add_mesh(
+                self._h, int(material), C.c_void_p(ptr or None), int(triangles.shape[0]), _lib.ADD_HOST if builder == "host" else 0, C.byref(info), raw))
+        return {k: int(getattr(info, k)) for k in ("index", "builder", "fell_back", "node_count", "levels", "tris_reused", "nodes_reused", "tri_cap")}
+
+    def remove_object(self, i):
+        """Remove object `i`, of any type (ctr_scene_remove_object); the objects behind it move down by one index.  Afterwards
+        every render and query gives, bit for bit, what a scene created without the object gives."""
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < self.object_count():
+            raise ValueError(f"bad object index {i!r}")
+        _check("ctr_scene_remove_object", _lib.hip_lib().ctr_scene_remove_object(self._h, int(i)))
+
+    def room(self):
+        """How much of the scene's triangle and node arrays is in use (ctr_scene_room): tris_live, tris_total, nodes4_live,
+        nodes4_total — the records inside a range some object owns, and the records of the array."""
+        r = _lib.SceneRoom()
+        _check("ctr_scene_room", _lib.hip_lib().ctr_scene_room(self._h, C.byref(r)))
+        return {k: int(getattr(r, k)) for k in ("tris_live", "tris_total", "nodes4_live", "nodes4_total")}
+
     def guard_state(self, obj):
         """Test hook (ctr_debug_guard_state): (file indices of mesh `obj`'s triangles in its guard records, ascending, as a
         list; whether the mesh is walked linearly)."""

@@ -77,6 +77,17 @@ class ReplaceInfo(C.Structure):
                 ("nodes_moved", C.c_uint32), ("tris_moved", C.c_uint32), ("tri_cap", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class AddInfo(C.Structure):
+    """ctr_add_info (include/cutrace_topology.h)"""
+    _fields_ = [("index", C.c_uint32), ("builder", C.c_uint32), ("fell_back", C.c_uint32), ("node_count", C.c_uint32), ("levels", C.c_uint32),
+                ("tris_reused", C.c_uint32), ("nodes_reused", C.c_uint32), ("tri_cap", C.c_uint32)]
+
+
+class SceneRoom(C.Structure):
+    """struct ctr_scene_room (include/cutrace_topology.h)"""
+    _fields_ = [("tris_live", C.c_uint64), ("tris_total", C.c_uint64), ("nodes4_live", C.c_uint64), ("nodes4_total", C.c_uint64)]
+
+
 class RayQuery(C.Structure):
     """ctr_ray_query (include/cutrace_rays.h)"""
     _fields_ = [("n_rays", C.c_uint64), ("flags", C.c_uint32), ("min_t", C.c_float), ("max_t", C.c_float),
@@ -222,6 +233,12 @@ HIP_LATER_PROTOS = {
     "cutrace_replace.h": {
         "ctr_scene_replace_mesh": ([_ptr, _u32, _ptr, _u64, _u32, _P(ReplaceInfo), _ptr], _int),
     },
+    "cutrace_topology.h": {
+        "ctr_scene_add_object": ([_ptr, _P(Object), _P(_u64)], _int),
+        "ctr_scene_add_mesh": ([_ptr, _u64, _ptr, _u64, _u32, _P(AddInfo), _ptr], _int),
+        "ctr_scene_remove_object": ([_ptr, _u64], _int),
+        "ctr_scene_room": ([_ptr, _P(SceneRoom)], _int),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -238,6 +255,8 @@ REBUILD_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_rebuild.h"])
 REBUILD_HOST = 1   # CTR_REBUILD_HOST
 REPLACE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_replace.h"])
 REPLACE_HOST = 1   # CTR_REPLACE_HOST
+TOPOLOGY_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_topology.h"])
+ADD_HOST = 1       # CTR_ADD_HOST
 
 _host = None
 _hip = None

@@ -25,6 +25,11 @@
 //
 // A replace is a rebuild whose triangle count may differ from the mesh's: 1b also works out where the mesh's triangle and node
 // ranges will live (scene_flatten.h replace_room) and grows d_tris, d_gnorm and d_nodes4 for them, and 1c is mesh_replaced.
+//
+// An add (ctr_scene_add_mesh, include/cutrace_topology.h; the other calls of that header are ctr_topology.cpp) is a replace of a mesh
+// that is not there yet: 1 checks a material index where the others look for the mesh, 1b asks add_room, which knows the ranges that
+// removed objects left behind, and also gives d_objs, d_meshes and d_nodes room for one mesh more, 1c is mesh_added, and step 4 is
+// mesh_joined: the top-level tree can be built only once the device has said what the mesh's box is.
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
@@ -38,6 +43,7 @@
 #include "ctr_internal.h"
 #include "cutrace_rebuild.h"
 #include "cutrace_replace.h"
+#include "cutrace_topology.h"
 #include "cutrace_update.h"
 #include "guard.h"
 #include "mesh_build.h"
@@ -130,6 +136,8 @@ struct MeshCall {
   hipStream_t stream = nullptr;
   const float *d_verts = nullptr;  // the vertices on the device: the caller's, or upd_verts once upload_verts has run
   bool uploaded = false;
+  bool adding = false;             // ctr_scene_add_mesh: the mesh is the last of the list once mesh_added has run
+  uint64_t mat_idx = 0;            // ... and this its material
   Stamps stamp;
   MeshCall(ctr_scene *scene, const char *name) : edit(scene), s(scene), who(std::string(name) + ": "), stamp(name + 10 /* past "ctr_scene_" */) {}
 };
@@ -150,6 +158,24 @@ int mesh_arguments(MeshCall &c, uint32_t object, const ctr_triangle *tris, uint6
   while (gi < F.guards.size() && F.guards[gi].obj_index != object) gi++;
   if (gi == F.guards.size() || F.guards[gi].mesh_pos < 0) return fail(CTR_E_INVALID, c.who + "the mesh has no records");
   c.gi = gi;
+  c.n = (uint32_t)n_tris;
+  c.tris = tris;
+  c.stream = (hipStream_t)hip_stream;
+  if (int st = use_device(c.s)) return st;
+  c.where = where_is(tris, c.n * sizeof(ctr_triangle), c.s->device);
+  if (c.where == Where::ELSEWHERE) return fail(CTR_E_INVALID, c.who + "tris is neither host memory nor device memory of the scene's device");
+  return CTR_OK;
+}
+
+// ---- 1. of an add: a material of the scene and a count a mesh may have; the scene's device becomes current ----
+int add_arguments(MeshCall &c, uint64_t mat_idx, const ctr_triangle *tris, uint64_t n_tris, void *hip_stream) {
+  const FlatScene &F = c.s->flat;
+  if (mat_idx >= F.mats.size()) return fail(CTR_E_INVALID, c.who + "material index " + std::to_string(mat_idx) + " out of range");
+  if (n_tris == 0 || n_tris > CTR_MESH_TRIS_MAX)
+    return fail(CTR_E_INVALID, c.who + std::to_string(n_tris) + " triangles: a mesh has 1 .. " + std::to_string(CTR_MESH_TRIS_MAX));
+  if (F.objs.size() >= 0xFFFFFFFFull) return fail(CTR_E_INVALID, c.who + "scene too large for 32-bit device indices");
+  c.adding = true;
+  c.mat_idx = mat_idx;
   c.n = (uint32_t)n_tris;
   c.tris = tris;
   c.stream = (hipStream_t)hip_stream;
@@ -242,7 +268,10 @@ int update_steps(MeshCall &c, const MeshRefit *refit) {
   stamp("copy-back");
 
   // ---- 4., 5. everything derived from them, then the guard ----
-  if (int st = upload_dirty(s, mesh_updated(F, c.gi, box))) return st;
+  const std::vector<DirtyRange> derived = c.adding ? mesh_joined(F, c.gi, box) : mesh_updated(F, c.gi, box);
+  // (holds while a top-level tree over m meshes has fewer than m nodes; nothing is uploaded past the end of an array whatever the builder does)
+  if (F.nodes.size() > s->d_nodes.cap || F.meshes.size() > s->d_meshes.cap) return fail(CTR_E_INVALID, c.who + "a larger top-level tree than its arrays have room for");
+  if (int st = upload_dirty(s, derived)) return st;
   stamp("host records + upload");
   // (the new planes are on the device already, in upd_planes, and the stream has been waited for: the scan takes them from there)
   if (int st = guard_planes_changed(s, c.gi, d_planes)) return st;
@@ -293,14 +322,16 @@ int device_shape(MeshCall &c, std::vector<DNode4> &sparse, std::vector<uint32_t>
 }
 
 // What a rebuild or a replace built and moved: the fields of ctr_rebuild_info and ctr_replace_info
+// (of an add: the two `moved` say that the range is one a removed object left behind)
 struct Built { uint32_t builder = 0, fell_back = 0, node_count = 0, levels = 0, nodes_moved = 0, tris_moved = 0, tri_cap = 0; };
 
-// ---- a rebuild (the count is the mesh's) or a replace (any count): steps 1 .. 5 ----
+// ---- a rebuild (the count is the mesh's), a replace (any count) or — the arguments checked already — an add: steps 1 .. 5 ----
 int rebuild_or_replace(MeshCall &c, uint32_t object, const ctr_triangle *tris, uint64_t n_tris, bool host_builder, bool replace, void *hip_stream,
                        Built &built) {
   ctr_scene *s = c.s;
   const std::string &who = c.who;
-  if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream, replace)) return st;
+  if (!c.adding)
+    if (int st = mesh_arguments(c, object, tris, n_tris, hip_stream, replace)) return st;
   FlatScene &F = s->flat;
   const uint32_t n = c.n;
   if (int st = vertices_and_buffers(c, n)) return st;  // (a four-wide tree over n triangles has at most n nodes)
@@ -333,10 +364,17 @@ int rebuild_or_replace(MeshCall &c, uint32_t object, const ctr_triangle *tris, u
   std::unique_ptr<MeshRefit> refit;
   if (int st = refit_of_tree(tree.nodes.data(), count, n, who, refit)) return st;
   // where the mesh's ranges will live: a rebuild moves a tree that does not fit into exactly its room, a replace leaves room to grow
-  const ReplaceRoom room = replace_room(F, c.gi, n, count, replace ? CTR_REPLACE_GROWTH : 1u);
+  // ... and an add takes the ranges that removed objects left behind before it lets the arrays grow
+  ReplaceRoom room;
+  if (c.adding) {
+    const AddRoom ar = add_room(F, n, count);
+    room = ReplaceRoom{ar.tris_reused, ar.nodes_reused, ar.tri_cap, ar.node_cap, ar.tris_after, ar.nodes4_after};
+  } else {
+    room = replace_room(F, c.gi, n, count, replace ? CTR_REPLACE_GROWTH : 1u);
+  }
   if (room.tris_after > CTR_SCENE_TRIS_MAX)
     return fail(CTR_E_INVALID, who + std::to_string(room.tris_after) + " triangle records: more than the scene's arrays can address");
-  const uint32_t n_before = F.guards[c.gi].tri_count;
+  const uint32_t n_before = c.adding ? 0u : F.guards[c.gi].tri_count;
   if (int st = s->upd_back.reserve(BackLayout(n, count).end)) return st;
   if (int st = s->rb_index.reserve(n)) return st;
   if (n != n_before && s->scan_planes.cap) {
@@ -348,12 +386,26 @@ int rebuild_or_replace(MeshCall &c, uint32_t object, const ctr_triangle *tris, u
     if (int st = s->scan_planes.reserve(planes_after)) return st;
     if (int st = reserve_both(s->scan_words, s->scan_back, guard_scan_words(planes_after))) return st;
   }
-  if (s->refit.size() < F.guards.size()) s->refit.resize(F.guards.size());
+  const size_t n_guards = F.guards.size() + (c.adding ? 1u : 0u);
+  if (s->refit.size() < n_guards) s->refit.resize(n_guards);
   F.tris.reserve(room.tris_after);
   F.gn.reserve(4 * room.tris_after);
   F.nodes4.reserve(room.nodes4_after);
-  F.guards[c.gi].planes.reserve((size_t)CTR_PLANE_DOUBLES * n);
+  if (c.adding) {
+    F.objs.reserve(F.objs.size() + 1);
+    F.guards.reserve(n_guards);
+  } else {
+    F.guards[c.gi].planes.reserve((size_t)CTR_PLANE_DOUBLES * n);
+  }
   if (int st = c.edit.begin()) return st;  // (no launch may still be reading an array either, when it moves)
+  if (c.adding) {
+    // one object more, one mesh more in the top-level tree (a binary tree over m leaves has fewer than m nodes)
+    size_t n_mesh = 1;
+    for (const MeshGuard &g : F.guards) n_mesh += g.tri_count != 0;
+    if (int st = s->d_objs.grow(F.objs.size() + 1, F.objs.size())) return st;
+    if (int st = s->d_meshes.grow(n_mesh, F.meshes.size())) return st;
+    if (int st = s->d_nodes.grow(2 * n_mesh, F.nodes.size())) return st;
+  }
   // The same contents in another place (the DEVICE's, which for a linear mesh are not the host copy's): the last steps that can fail
   // for want of memory.  An array that grew before a later one failed holds what it held, at another address, and every launch
   // takes the addresses from the handle anew: harmless.
@@ -364,7 +416,15 @@ int rebuild_or_replace(MeshCall &c, uint32_t object, const ctr_triangle *tris, u
 
   // ---- 1c. the shape goes in: host copy, then the device's descriptors and the records' `orig` ----
   bool nodes_moved = false, tris_moved = false;
-  const std::vector<DirtyRange> dirty = replace ? mesh_replaced(F, c.gi, n, tree, &tris_moved, &nodes_moved) : mesh_rebuilt(F, c.gi, tree, &nodes_moved);
+  std::vector<DirtyRange> dirty;
+  if (c.adding) {
+    dirty = mesh_added(F, c.mat_idx, n, tree);
+    c.gi = F.guards.size() - 1;
+    tris_moved = room.tris_move;
+    nodes_moved = room.nodes_move;
+  } else {
+    dirty = replace ? mesh_replaced(F, c.gi, n, tree, &tris_moved, &nodes_moved) : mesh_rebuilt(F, c.gi, tree, &nodes_moved);
+  }
   s->refit[c.gi] = std::move(refit);
   if (int st = upload_dirty(s, dirty)) return st;
   HIP_TRY(hipMemcpyAsync(s->rb_index.p, tree.order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
@@ -427,6 +487,19 @@ int ctr_scene_replace_mesh(ctr_scene *s, uint32_t object, const ctr_triangle *tr
   Built built;
   if (int st = rebuild_or_replace(c, object, tris, n_tris, (flags & CTR_REPLACE_HOST) != 0, true, hip_stream, built)) return st;
   if (info) *info = ctr_replace_info{built.builder, built.fell_back, built.node_count, built.levels, built.nodes_moved, built.tris_moved, built.tri_cap, 0u};
+  return CTR_OK;
+}
+
+int ctr_scene_add_mesh(ctr_scene *s, uint64_t mat_idx, const ctr_triangle *tris, uint64_t n_tris, uint32_t flags, ctr_add_info *info, void *hip_stream) {
+  const std::string who = "ctr_scene_add_mesh: ";
+  if (flags & ~CTR_ADD_HOST) return fail(CTR_E_INVALID, who + "unknown flag bits " + std::to_string(flags & ~CTR_ADD_HOST));
+  if (!s || !tris) return fail(CTR_E_INVALID, who + "null argument");
+  MeshCall c(s, "ctr_scene_add_mesh");
+  if (int st = add_arguments(c, mat_idx, tris, n_tris, hip_stream)) return st;
+  Built built;
+  if (int st = rebuild_or_replace(c, 0, tris, n_tris, (flags & CTR_ADD_HOST) != 0, true, hip_stream, built)) return st;
+  if (info)
+    *info = ctr_add_info{s->flat.guards[c.gi].obj_index, built.builder, built.fell_back, built.node_count, built.levels, built.tris_moved, built.nodes_moved, built.tri_cap};
   return CTR_OK;
 }
 

@@ -690,12 +690,203 @@ ctr_object object_of(const FlatScene &F, size_t i) {
 size_t plane_records_at_most(const FlatScene &F) {
   size_t n = 0;
   for (const DObj &O : F.objs) n += O.type == CTR_OBJ_PLANE;
+  return plane_records_at_most(n);
+}
+
+size_t plane_records_at_most(size_t n) {
   // `a` planes on the busiest axis cost 3 * ceil(a / 2) records (planes on the other two axes ride in the same triples), the
   // n - a general ones ceil((n - a) / 2); fewer than three axis-aligned planes: general pairs only.  Not monotonic in `a`: four
   // planes need 7 records with three on one axis beside a general one, 6 with all four on it.
   size_t most = (n + 1) / 2;
   for (size_t a = 3; a <= n; a++) most = std::max(most, 3 * ((a + 1) / 2) + (n - a + 1) / 2);
   return most;
+}
+
+namespace {
+// the merged tree, retired as mesh_updated retires it, and its records behind meshes[n_mesh] dropped: they name objects by index
+void retire_merged(FlatScene &F) {
+  F.merged.reserved = F.merged.built = F.merged.usable = false;
+  std::vector<ctr_triangle>().swap(F.merged.src);
+  F.meshes.resize(F.n_mesh);
+}
+
+// the top-level tree over the meshes' current boxes in scene order, and every guard's place in it; the merged tree is retired
+void top_level_again(FlatScene &F) {
+  F.nodes.clear();
+  F.meshes.clear();
+  F.tlas_root = BVH_LEAF_FLAG;
+  for (int a = 0; a < 3; a++) F.tl_mn[a] = F.tl_mx[a] = 0.0f;
+  F.has_mesh = false;
+  for (const DObj &O : F.objs) F.has_mesh |= O.type == CTR_OBJ_MESH;
+  for (MeshGuard &g : F.guards) g.mesh_pos = -1;
+  top_level(nonempty_meshes(F), F);
+  retire_merged(F);
+}
+
+// the counters flatten_scene ends with, derived anew (mesh_bytes: of the live records, as mesh_replaced leaves it)
+void derived_counters(FlatScene &F) {
+  F.mesh_tris = 0;
+  for (const MeshGuard &g : F.guards) F.mesh_tris += g.tri_count;
+  F.mesh_bytes = live_mesh_bytes(F);
+  F.ray_slots = ray_stack_slots(F);
+}
+
+// every record of the arrays that hold one per object, per plane pair, per mesh or per top-level node
+void whole_lists(const FlatScene &F, std::vector<DirtyRange> &dirty) {
+  dirty.push_back({DirtyRange::OBJS, 0, F.objs.size(), {}});
+  dirty.push_back({DirtyRange::OLOOP, 0, F.oloop.size(), {}});
+  dirty.push_back({DirtyRange::MESHES, 0, F.meshes.size(), {}});
+  dirty.push_back({DirtyRange::PLANES, 0, F.planes.size(), {}});
+  dirty.push_back({DirtyRange::NODES, 0, F.nodes.size(), {}});
+}
+
+void give_back(std::vector<FlatScene::FreeRange> &list, uint32_t begin, uint32_t count) {
+  auto at = list.begin();
+  while (at != list.end() && at->begin < begin) ++at;
+  list.insert(at, FlatScene::FreeRange{begin, count});
+}
+
+// the lowest-addressed freed range of at least `need` records (exactly: of `need` records and no more), or list.size()
+size_t fitting(const std::vector<FlatScene::FreeRange> &list, size_t need, bool exactly = false) {
+  size_t k = 0;
+  while (k < list.size() && (exactly ? list[k].count != need : list[k].count < need)) k++;
+  return k;
+}
+}  // namespace
+
+int check_new_object(const FlatScene &F, const ctr_object &o, std::string &err) {
+  auto bad = [&](const std::string &msg) { err = msg; return CTR_E_INVALID; };
+  if (o.type > CTR_OBJ_SPHERE) return bad("bad type");
+  if (o.type == CTR_OBJ_MESH) return bad("a mesh is added by ctr_scene_add_mesh");
+  if (o.mat_idx >= F.mats.size()) return bad("material index out of range");
+  if (F.objs.size() >= 0xFFFFFFFFull) return bad("scene too large for 32-bit device indices");
+  return CTR_OK;
+}
+
+std::vector<DirtyRange> object_added(FlatScene &F, const ctr_object &o, bool *tri_reused) {
+  std::vector<DirtyRange> dirty;
+  DObj O;
+  memset(&O, 0, sizeof(O));
+  O.type = o.type;
+  O.index = (uint32_t)F.objs.size();
+  if (tri_reused) *tri_reused = false;
+  if (o.type == CTR_OBJ_TRIANGLE) {
+    const size_t k = fitting(F.free_tris, 1, true);
+    if (k < F.free_tris.size()) {
+      O.tri_begin = F.free_tris[k].begin;
+      F.free_tris.erase(F.free_tris.begin() + k);
+      if (tri_reused) *tri_reused = true;
+    } else {
+      O.tri_begin = (uint32_t)F.tris.size();
+      F.tris.emplace_back();
+      F.gn.resize(4 * F.tris.size());
+    }
+    O.tri_count = 1;
+    dirty.push_back({DirtyRange::TRIS, O.tri_begin, 1, {}});
+    dirty.push_back({DirtyRange::GNORM, O.tri_begin, 1, {}});
+  }
+  F.objs.push_back(O);
+  analytic_record(o, F.objs.back(), F);
+  plane_records(F);
+  retire_merged(F);
+  transparency_bits(F);
+  derived_counters(F);
+  whole_lists(F, dirty);
+  return dirty;
+}
+
+AddRoom add_room(const FlatScene &F, uint32_t n, uint32_t node_count) {
+  AddRoom r;
+  const size_t kt = fitting(F.free_tris, (size_t)n + CTR_GUARD_SLOTS), kn = fitting(F.free_nodes4, (size_t)node_count + 1u);
+  r.tris_reused = kt < F.free_tris.size();
+  r.tri_begin = r.tris_reused ? F.free_tris[kt].begin : (uint32_t)F.tris.size();
+  r.tri_cap = r.tris_reused ? F.free_tris[kt].count - CTR_GUARD_SLOTS : n;
+  r.tris_after = F.tris.size() + (r.tris_reused ? 0u : (size_t)n + CTR_GUARD_SLOTS);
+  r.nodes_reused = kn < F.free_nodes4.size();
+  r.node_begin = r.nodes_reused ? F.free_nodes4[kn].begin : (uint32_t)F.nodes4.size();
+  r.node_cap = r.nodes_reused ? F.free_nodes4[kn].count - 1u : node_count;
+  r.nodes4_after = F.nodes4.size() + (r.nodes_reused ? 0u : (size_t)node_count + 1u);
+  return r;
+}
+
+std::vector<DirtyRange> mesh_added(FlatScene &F, uint64_t mat_idx, uint32_t n, const MeshTree &tree) {
+  const AddRoom room = add_room(F, n, (uint32_t)tree.nodes.size());
+  DObj O;
+  memset(&O, 0, sizeof(O));
+  O.type = CTR_OBJ_MESH;
+  O.index = (uint32_t)F.objs.size();
+  O.mat = (uint32_t)mat_idx;
+  F.objs.push_back(O);
+  F.has_mesh = true;
+  transparency_bits(F);
+  // A guard entry of no room takes the freed ranges as its own, and mesh_replaced then finds that the mesh fits them; what is not
+  // reused it moves to the end of the arrays, with exactly the room needed (twice no room is no room).
+  MeshGuard g;
+  g.obj_index = O.index;
+  if (room.tris_reused) {
+    g.tri_begin = room.tri_begin;
+    g.tri_cap = room.tri_cap;
+    F.free_tris.erase(F.free_tris.begin() + fitting(F.free_tris, (size_t)n + CTR_GUARD_SLOTS));
+  }
+  if (room.nodes_reused) {
+    g.node_begin = room.node_begin;
+    g.node_cap = room.node_cap;
+    F.free_nodes4.erase(F.free_nodes4.begin() + fitting(F.free_nodes4, tree.nodes.size() + 1u));
+  }
+  F.guards.push_back(std::move(g));
+  bool tris_moved = false, nodes_moved = false;
+  std::vector<DirtyRange> dirty = mesh_replaced(F, F.guards.size() - 1, n, tree, &tris_moved, &nodes_moved);
+  dirty.push_back({DirtyRange::OBJS, 0, F.objs.size(), {}});
+  return dirty;
+}
+
+std::vector<DirtyRange> mesh_joined(FlatScene &F, size_t gi, const float *box) {
+  for (int q = 0; q < 6; q++) F.objs[F.guards[gi].obj_index].f[q] = box[q];
+  top_level_again(F);
+  std::vector<DirtyRange> dirty;
+  whole_lists(F, dirty);
+  const std::vector<DirtyRange> more = mesh_updated(F, gi, box);
+  dirty.insert(dirty.end(), more.begin(), more.end());
+  derived_counters(F);
+  return dirty;
+}
+
+std::vector<DirtyRange> object_removed(FlatScene &F, size_t i, long *guard_removed) {
+  const DObj gone = F.objs[i];
+  *guard_removed = -1;
+  if (gone.type == CTR_OBJ_TRIANGLE) give_back(F.free_tris, gone.tri_begin, 1);
+  if (gone.type == CTR_OBJ_MESH) {
+    size_t gi = 0;
+    while (gi < F.guards.size() && F.guards[gi].obj_index != i) gi++;
+    if (gi < F.guards.size()) {
+      const MeshGuard &g = F.guards[gi];
+      if (g.tri_cap) give_back(F.free_tris, g.tri_begin, g.tri_cap + CTR_GUARD_SLOTS);
+      give_back(F.free_nodes4, g.node_begin, g.node_cap + 1u);
+      F.guards.erase(F.guards.begin() + gi);
+      *guard_removed = (long)gi;
+    }
+  }
+  F.objs.erase(F.objs.begin() + i);
+  for (size_t k = i; k < F.objs.size(); k++) F.objs[k].index = (uint32_t)k;
+  for (MeshGuard &g : F.guards)
+    if (g.obj_index > i) g.obj_index--;
+  plane_records(F);
+  top_level_again(F);
+  transparency_bits(F);
+  derived_counters(F);
+  std::vector<DirtyRange> dirty;
+  whole_lists(F, dirty);
+  return dirty;
+}
+
+SceneRoom scene_room(const FlatScene &F) {
+  SceneRoom r{0, F.tris.size(), 0, F.nodes4.size()};
+  for (const DObj &O : F.objs) r.tris_live += O.type == CTR_OBJ_TRIANGLE;
+  for (const MeshGuard &g : F.guards) {
+    r.tris_live += g.tri_cap + (g.tri_cap ? CTR_GUARD_SLOTS : 0u);
+    r.nodes4_live += g.node_cap + 1u;
+  }
+  return r;
 }
 
 void fill_scene_counts(const FlatScene &F, DScene &D) {

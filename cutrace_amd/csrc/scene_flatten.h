@@ -95,6 +95,10 @@ struct FlatScene {
   size_t mesh_bytes = 0;    // triangles + BVH nodes
   std::vector<MeshGuard> guards;  // one per mesh object, scene order
   Merged merged;
+  // Ranges of tris / gn and of nodes4 that a removed object left behind (object_removed), lowest address first: what
+  // object_added and mesh_added place a new object in before the arrays grow.  A range is taken whole, never split or merged.
+  struct FreeRange { uint32_t begin, count; };
+  std::vector<FreeRange> free_tris, free_nodes4;
   // LDS stack entries per lane that the ray-query walk (ray_query.hip) can need: a node pushes at most three of its
   // children (the fourth is visited next), so the stack holds at most three entries per level above the current node.
   // The depth counts the inner nodes of the longest path of any mesh tree, plus the spare node in front of a guarded
@@ -209,6 +213,53 @@ ctr_object object_of(const FlatScene &F, size_t i);
 // the most plane records any edit of the scene's planes can need: the maximum, over how many of them share the busiest axis, of
 // that axis's triples plus the general pairs of the rest (for an even count >= 4 one more than every plane on one axis)
 size_t plane_records_at_most(const FlatScene &F);
+size_t plane_records_at_most(size_t n_planes);  // ... of a scene with that many planes
+
+// The object LIST of a flattened scene changes (include/cutrace_topology.h: ctr_scene_add_object, ctr_scene_add_mesh,
+// ctr_scene_remove_object).  Afterwards the host copy is what flatten_scene gives for the edited description — the removed object
+// deleted, an added one appended — but for where the ranges of tris / gn / nodes4 begin, and for the merged tree, which is retired
+// as mesh_updated retires it (scripts/topology_check.cpp compares every array).  What holds an object index or a per-mesh slot, and
+// is therefore written anew, with flatten_scene's own text:
+//   objs            the record erased or appended, DObj::index renumbered
+//   oloop, planes   copies of object records: plane_records (n_axis_recs with them; at most plane_records_at_most of the NEW plane
+//                   set, which the caller gives d_planes room for)
+//   guards          the entry erased or appended, obj_index renumbered, mesh_pos from the new top-level tree.  The caller keeps
+//                   what it indexes by guard in step (ctr_scene::refit, the device scan's flat plane array)
+//   nodes, meshes, n_mesh, tlas_root, tl_mn, tl_mx, has_mesh
+//                   the top-level tree over the meshes' CURRENT boxes in scene order: top_level
+//   merged          retired
+//   mesh_tris, mesh_bytes (live_mesh_bytes), ray_slots, the "material is transparent" bits
+// None of them touches the guard STATE of a mesh that stays (its guard records, spare node and bvh_root travel with its records):
+// a flat mirror that comes or goes moves the eyes' images, so plan_guards / apply_guards (guard.h) follow.
+//
+// Ranges.  A removed mesh's tri_cap + CTR_GUARD_SLOTS triangle records (none for a mesh created empty) and node_cap + 1 nodes, and a
+// removed stand-alone triangle's one record, go on FlatScene::free_tris / free_nodes4.  An added mesh takes, per array, the
+// lowest-addressed freed range with enough room, whole — its tri_cap / node_cap are then the range's — and otherwise a new range at
+// the end with exactly the room it needs; an added stand-alone triangle takes the lowest-addressed freed range of ONE record.
+//
+// check_new_object: what validate_desc checks of an object that ctr_scene_add_object takes (no mesh); F is not written.
+int check_new_object(const FlatScene &F, const ctr_object &o, std::string &err);
+// a sphere, a plane or a stand-alone triangle that passed, appended.  *tri_reused: a triangle's record is a freed one
+std::vector<DirtyRange> object_added(FlatScene &F, const ctr_object &o, bool *tri_reused = nullptr);
+// where mesh_added will put a mesh of `n` triangles under a tree of `node_count` nodes, so that the device arrays can grow first
+struct AddRoom {
+  bool tris_reused, nodes_reused;
+  uint32_t tri_begin, tri_cap, node_begin, node_cap;
+  size_t tris_after, nodes4_after;  // records of FlatScene::tris (gn: four floats each) and ::nodes4 afterwards
+};
+AddRoom add_room(const FlatScene &F, uint32_t n, uint32_t node_count);
+// A mesh of `n` triangles (1 .. CTR_MESH_TRIS_MAX) with material `mat_idx` appended: its object record and MeshGuard (the last of
+// both), its ranges where add_room says, and `tree` installed in them by mesh_replaced.  As after mesh_replaced the records are
+// stale but for `orig`, and the mesh has no box and no place in the top-level tree yet (mesh_pos -1: nothing walks it): the
+// update's steps follow (update_tris, refit_level, mesh_box), then mesh_joined.
+std::vector<DirtyRange> mesh_added(FlatScene &F, uint64_t mat_idx, uint32_t n, const MeshTree &tree);
+// ... and once `box` is known: the box into the mesh's object record, the top-level tree over all meshes, then mesh_updated
+std::vector<DirtyRange> mesh_joined(FlatScene &F, size_t gi, const float *box);
+// object `i` (any type, an empty mesh included) removed.  *guard_removed: the position its MeshGuard had, -1 for what is no mesh
+std::vector<DirtyRange> object_removed(FlatScene &F, size_t i, long *guard_removed);
+// records of tris and nodes4 in all, and inside a range some object owns (capacity plus spare records)
+struct SceneRoom { uint64_t tris_live, tris_total, nodes4_live, nodes4_total; };
+SceneRoom scene_room(const FlatScene &F);
 
 // The counts and flags of a device scene record (scene_device.h DScene) from the host copy its arrays mirror; the ten pointers
 // stay as they are.  Called per launch and per query, so that it is right after build_merged_tree and every guard refresh.

@@ -5,8 +5,8 @@
  *
  * A moving sphere, a sliding or tilting mirror plane, a wall of a room opened, a mesh given another of the materials already
  * loaded do not have to destroy and create the handle: the meshes, their trees, the handle's page-locked buffers, its per-tile
- * cost history and its refit schedules stay.  Topology is fixed, as it is for a mesh update: the number of objects and the type
- * of each stay what ctr_scene_create was given.  What may change:
+ * cost history and its refit schedules stay.  Topology is fixed in THIS call, as it is for a mesh update: the number of objects and
+ * the type of each stay what the handle has (cutrace_topology.h adds and removes objects).  What may change:
  *   sphere               v0 (centre), f0 (radius), mat_idx
  *   plane                v0 (point), v1 (normal), mat_idx
  *   stand-alone triangle v0, v1, v2, mat_idx

@@ -1,5 +1,5 @@
 // edit_check_common.h — what the edit check programs (scene_edit_check.cpp, object_edit_check.cpp, mesh_update_check.cpp,
-// mesh_rebuild_check.cpp, mesh_replace_check.cpp) share: a description that owns its arrays, the triangle sets, flatten + guard, the ONE restatement of
+// mesh_rebuild_check.cpp, mesh_replace_check.cpp, topology_check.cpp) share: a description that owns its arrays, the triangle sets, flatten + guard, the ONE restatement of
 // ctr_scene_update_mesh on the host copy (update_on_host), and the byte-for-byte comparison of two flat scenes.
 #ifndef CUTRACE_AMD_EDIT_CHECK_COMMON_H
 #define CUTRACE_AMD_EDIT_CHECK_COMMON_H
