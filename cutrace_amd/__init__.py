@@ -469,6 +469,13 @@ class DeviceScene:
         _check("ctr_debug_last_shape", _lib.hip_lib().ctr_debug_last_shape(self._h, C.byref(shape)))
         return int(shape.value)
 
+    def last_opaque(self):
+        """The opaque build of the handle's most recent launch (ctr_debug_last_opaque): 0 the code as it is for every scene,
+        1 the one-mesh any-hit build without the pass-through half of the shading."""
+        opaque = C.c_uint32()
+        _check("ctr_debug_last_opaque", _lib.hip_lib().ctr_debug_last_opaque(self._h, C.byref(opaque)))
+        return int(opaque.value)
+
     def room_facts(self):
         """The room facts of the handle's most recent launch (ctr_debug_room_facts): all zero, or what lets any-hit shadow trips
         from inside a plane room skip their plane tests."""

@@ -135,6 +135,7 @@ struct ctr_scene {
   bool no_scene_head = false;  // CUTRACE_NO_SCENE_HEAD=1 when the handle was created: launches carry an empty scene head
   bool no_shape_build = false; // CUTRACE_NO_SHAPE_BUILD=1 when the handle was created: every launch in shape KS_GENERAL (kernel_choice.h)
   bool no_wall_skip = false;   // CUTRACE_NO_WALL_SKIP=1 when the handle was created: every launch carries zero room facts (scene_device.h)
+  bool no_opaque_build = false; // CUTRACE_NO_OPAQUE_BUILD=1 when the handle was created: no launch takes an opaque build (kernel_choice.h KO_*)
   struct RoomWords { float c[3], r, delta; uint32_t lights; } last_room{};  // the room facts of the most recent launch (ctr_debug_room_facts)
   // cached device outputs for the host-buffer form: ONE allocation of 7 floats per pixel, a call's buffers are its
   // consecutive parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
@@ -149,6 +150,7 @@ struct ctr_scene {
   GrowBuf d_shards{sizeof(unsigned long long)};    // CTR_SHARDS x CTR_SHARD_WORDS, zero between launches
   uint32_t last_kernel = 0;        // the KV of the most recent launch (ctr_debug_last_kernel)
   uint32_t last_shape = 0;         // its launch shape, KS_* of kernel_choice.h (ctr_debug_last_shape)
+  uint32_t last_opaque = 0;        // its opaque build, KO_* of kernel_choice.h (ctr_debug_last_opaque)
   // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling"; tile_order_policy.h, tile_order_host.cpp)
   OrderState order;
   GrowBuf d_cost{sizeof(uint32_t)}, d_order{sizeof(uint32_t)};  // order.cap tiles each

@@ -297,6 +297,7 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   s->no_scene_head = env_switch("CUTRACE_NO_SCENE_HEAD");    // every record by pointer
   s->no_shape_build = env_switch("CUTRACE_NO_SHAPE_BUILD");  // the general build of every launch
   s->no_wall_skip = env_switch("CUTRACE_NO_WALL_SKIP");      // no shadow trip skips its plane tests
+  s->no_opaque_build = env_switch("CUTRACE_NO_OPAQUE_BUILD");  // the parent instantiation of every one-mesh launch
 
   if (int st = upload_scene(s, F)) {
     ctr_scene_destroy(s);
@@ -407,6 +408,13 @@ int ctr_debug_last_shape(ctr_scene *s, uint32_t *shape) {
   if (!s || !shape) return fail(CTR_E_INVALID, "ctr_debug_last_shape: null argument");
   std::lock_guard<std::mutex> lk(s->mtx);
   *shape = s->last_shape;
+  return CTR_OK;
+}
+
+int ctr_debug_last_opaque(ctr_scene *s, uint32_t *opaque) {
+  if (!s || !opaque) return fail(CTR_E_INVALID, "ctr_debug_last_opaque: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  *opaque = s->last_opaque;
   return CTR_OK;
 }
 

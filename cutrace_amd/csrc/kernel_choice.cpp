@@ -45,6 +45,10 @@ KernelChoice choose_kernel(const KernelFacts &f) {
   return {walk | anyhit | pow | occ6 | merge | (direct ? KV_HOSTOUT : 0u), direct, merged, KR_NONE};
 }
 
+uint32_t opaque_build(uint32_t kv, uint32_t shape, bool no_opaque) {
+  return !no_opaque && shape == KS_ONE_MESH && (kv & KV_ANYHIT) ? KO_OPAQUE : KO_PARENT;
+}
+
 uint32_t launch_shape(uint32_t kv, uint32_t n_oloop, bool head_mesh) {
   if (!head_mesh || n_oloop != 0u) return KS_GENERAL;
   switch (kv) {

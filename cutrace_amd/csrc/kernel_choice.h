@@ -75,6 +75,17 @@ enum : uint32_t { KS_GENERAL = 0u, KS_ONE_MESH = 1u };
 // of CTR_SHAPE_KERNELS with n_oloop == 0 and head_mesh, KS_GENERAL for everything else.
 uint32_t launch_shape(uint32_t kv, uint32_t n_oloop, bool head_mesh);
 
+// The opaque build: a fourth template parameter of render_kernel<KV, SHAPE, ROOM, OPQ>, decided per LAUNCH like the shape and, like
+// it, not a KV bit (ctr_debug_last_opaque reads it back).  An any-hit build runs only when every material is exactly opaque
+// (choose_kernel), so ray_color's pass-through half never runs in it; the opaque builds of the one-mesh shape compile it out.
+//   KO_PARENT : the code as it was.
+//   KO_OPAQUE : no pass-through state in the continuation; the hit point lives in the ray origin alone.
+enum : uint32_t { KO_PARENT = 0u, KO_OPAQUE = 1u };
+// The opaque build of a launch of build `kv` in shape `shape` (launch_shape); no_opaque: the handle was created under
+// CUTRACE_NO_OPAQUE_BUILD=1.  KO_OPAQUE when the shape is KS_ONE_MESH and the build any-hit (every build of CTR_SHAPE_KERNELS
+// is), KO_PARENT for everything else.  The stack plays no part: an opaque build asks for the LDS of its parent twin.
+uint32_t opaque_build(uint32_t kv, uint32_t shape, bool no_opaque);
+
 // The recursion stack of a launch: `frames` frames of `nf` floats per lane (render_kernel.hip KArgs::frames, ::nf).
 struct StackShape {
   uint32_t frames, nf;
@@ -87,6 +98,9 @@ inline StackShape stack_shape(int bounces, bool any_bounce, bool need_cold) {
 // The 6-waves-per-SIMD build parks 1280 bytes of shading state per wave in LDS (render_kernel PARK); LDS is handed out
 // in granules of 1280 bytes (160 KB / 128), and 24 waves per CU need at most 5 granules each: bounces <= 5 without cold frames
 inline bool occ6_fits(StackShape st) { return (st.bytes_per_wave() + 1280u + 1279u) / 1280u <= 5u; }
+// dynamic LDS of one wave of a launch of build `kv`, in any shape and as the opaque build or not: its stack, and the parking
+// granule of the 6-wave builds
+inline size_t lds_bytes_per_wave(uint32_t kv, StackShape st) { return st.bytes_per_wave() + ((kv & KV_OCC6) ? 1280u : 0u); }
 
 enum KernelEntry {
   KE_HOST,       // ctr_render

@@ -343,7 +343,7 @@ constexpr uint32_t MSP_ROOM = 0x20000000u;
 #define MSP_DEPTH(m) ((int)((m) & 0xFFFFu))
 enum { ACT_NONE = 0, ACT_LIGHT = 1, ACT_BOUNCE = 2, ACT_UNWIND = 3 };
 
-template <uint32_t KV, uint32_t SHAPE = KS_GENERAL, bool ROOM = false>
+template <uint32_t KV, uint32_t SHAPE = KS_GENERAL, bool ROOM = false, uint32_t OPQ = KO_PARENT>
 __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) void render_kernel(KArgs A, float *__restrict__ depth_out,
                                                             float *__restrict__ color_out,
                                                             float *__restrict__ normal_out,
@@ -390,6 +390,16 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   static_assert(!ROOM || ONE_MESH, "room-safe lanes: the one-mesh builds");
   constexpr bool ROOM_CODE = ANYHIT && (ROOM || STATS);
   static_assert(!ONE_MESH || (KV & ~(KV_OCC6 | KV_HOSTOUT)) == (KV_PREFILTER | KV_BVH | KV_ANYHIT | KV_FASTPOW), "KS_ONE_MESH: the builds of CTR_SHAPE_KERNELS");
+  // "Opaque build" (kernel_choice.h KO_*; DESIGN.md "The opaque one-mesh build"): an any-hit build is launched only when every
+  // material's transparency is exactly zero, so ray_color never casts a pass-through child: `do_trans` is false in every lane.
+  // OPAQUE compiles that half of the continuation out — the transparency read and its f64 compare, the six-dword push, the
+  // unwind's pass-through stage — and with it the reasons to keep the incoming direction and a second copy of the hit point
+  // alive across the hit's shadow trips: the radiance ray's direction is `rd` where the hit record needs it, and in the
+  // one-mesh shape (plane or mesh hits only) the hit point is `ro` from the hit record to the bounce.  Nothing a taken path
+  // computes changes.
+  constexpr bool OPAQUE = OPQ != KO_PARENT;
+  static_assert(OPQ == KO_PARENT || OPQ == KO_OPAQUE, "opaque builds: kernel_choice.h");
+  static_assert(!OPAQUE || (ANYHIT && ONE_MESH), "the opaque builds are any-hit one-mesh builds");
   // wave-level work counters (STATS build only): [0] casts, [1] BVH nodes visited, [2] triangle
   // prefilters, [3] exact tests, [4] mesh entries (AABB ballot != 0), [5] sum of active lanes per cast,
   // and how many of the 64 lanes had a use for the wave-level work: [6] lanes whose ray meets one of the
@@ -1620,12 +1630,21 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         mat_i = H.mat;
         if (STATS) recv_mesh = (ht == CTR_OBJ_MESH || ht == CTR_OBJ_TRIANGLE);
         { const CADDR DLight &L0 = k_lights[0]; nl_type = L0.type; nl_v = mk(L0.vx, L0.vy, L0.vz); }
-        pos = vadd(ro, vscale(in_d, best));  // start + dist*dir (triangle/plane hit; shading.hpp:133,143)
+        // (OPAQUE: the direction of the radiance ray just cast is `rd` — every radiance cast starts with rd = in_d and no cast
+        //  writes it — so in_d is not read here, nor after)
+        const V3 hit_d = OPAQUE ? rd : in_d;
+        const V3 hit_pos = vadd(ro, vscale(hit_d, best));  // start + dist*dir (triangle/plane hit; shading.hpp:133,143)
+        if constexpr (!OPAQUE) pos = hit_pos;
         float unused_n0;
-        const V3 hit_dn = vnormalized_n(in_d, unused_n0);
+        const V3 hit_dn = vnormalized_n(hit_d, unused_n0);
         CTR_MARK(92);
         set_in_dn(hit_dn);
-        if (ht == CTR_OBJ_SPHERE) {
+        if constexpr (OPAQUE) {
+          // one-mesh shape: the hit is a plane or the mesh (no sphere, no stand-alone triangle; no uv build), and the hit point
+          // lives in `ro` alone until the bounce
+          ro = hit_pos;
+          normal = ht == CTR_OBJ_PLANE ? mk(hf3, hf4, hf5) : mk(gn0, gn1, gn2);
+        } else if (ht == CTR_OBJ_SPHERE) {
           CTR_MARK(38);
           // default_schema.hpp:245-246: hit uses the NORMALIZED direction
           const V3 hit = vadd(ro, vscale(hit_dn, best));
@@ -1820,28 +1839,36 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
       // shading.hpp:126-150 with rgb = fin
       CTR_MARK(50);
       const CADDR DMat &M = k_mats[mat_i];
-      const float reflective = M.reflexivity, translucent = M.transparency;
+      const float reflective = M.reflexivity, translucent = OPAQUE ? 0.0f : M.transparency;  // (OPAQUE: the lemma; not read)
       const int sp = MSP_DEPTH(msp);
       const bool more = sp < k_bounces;  // `if constexpr (bounces != 0)`
       const bool do_refl = more && (double)reflective >= 1e-6;
-      const bool do_trans = more && (double)translucent >= 1e-6;
+      const bool do_trans = !OPAQUE && more && (double)translucent >= 1e-6;
       if (do_refl || do_trans) {
         CTR_MARK(51);  // push a frame, cast the child
         STK(sp, F_R) = fin.x; STK(sp, F_G) = fin.y; STK(sp, F_B) = fin.z;
         STK(sp, F_MAT) = __uint_as_float(mat_i | (do_refl ? 1u << 30 : 2u << 30));  // the material says reflective / translucent
-        if (do_refl && do_trans) {  // the pass-through child is cast after the reflection returns
-          CTR_MARK(96);
-          STK(sp, F_PX) = pos.x; STK(sp, F_PY) = pos.y; STK(sp, F_PZ) = pos.z;
-          STK(sp, F_DX) = in_d.x; STK(sp, F_DY) = in_d.y; STK(sp, F_DZ) = in_d.z;
+        if constexpr (!OPAQUE) {
+          if (do_refl && do_trans) {  // the pass-through child is cast after the reflection returns
+            CTR_MARK(96);
+            STK(sp, F_PX) = pos.x; STK(sp, F_PY) = pos.y; STK(sp, F_PZ) = pos.z;
+            STK(sp, F_DX) = in_d.x; STK(sp, F_DY) = in_d.y; STK(sp, F_DZ) = in_d.z;
+          }
         }
         CTR_MARK(120);
         msp = (uint32_t)(sp + 1);  // one frame deeper, a radiance cast
-        if (do_refl) {
-          // reflect(nd, nn) = nd - (2*(nn.nd))*nn, vector.hpp:204-206
+        if constexpr (OPAQUE) {
+          // the child is the reflection (do_refl holds here); it starts at the hit point, which `ro` still is
           const V3 nn_ = get_nn(), dn_ = get_in_dn();
-          in_d = vsub(dn_, vscale(nn_, 2.0f * vdot(nn_, dn_)));
+          rd = vsub(dn_, vscale(nn_, 2.0f * vdot(nn_, dn_)));
+        } else {
+          if (do_refl) {
+            // reflect(nd, nn) = nd - (2*(nn.nd))*nn, vector.hpp:204-206
+            const V3 nn_ = get_nn(), dn_ = get_in_dn();
+            in_d = vsub(dn_, vscale(nn_, 2.0f * vdot(nn_, dn_)));
+          }
+          ro = pos; rd = in_d;
         }
-        ro = pos; rd = in_d;
         min_t = A.fudge;
       } else {
         out_rgb = fin;
@@ -1872,6 +1899,11 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         V3 rgb = mk(STK(sp, F_R), STK(sp, F_G), STK(sp, F_B));
         const uint32_t f_mat = __float_as_uint(STK(sp, F_MAT));
         const CADDR DMat &FM = k_mats[f_mat & 0x3FFFFFFFu];
+        if constexpr (OPAQUE) {
+          // every frame waits for its reflection child (stage 1), and no material transmits: shading.hpp:138 alone
+          out_rgb = vadd(rgb, vscale(out_rgb, FM.reflexivity));
+          continue;
+        }
         const float f_transl = FM.transparency;
         if ((f_mat >> 30) == 1u) {
           CTR_MARK(97);
@@ -2128,8 +2160,7 @@ int launch(const RenderLaunch &L, uint32_t kv, const void *kernel, hipStream_t s
     if (L.ss_log2 > 3u || ((TW | TH) & m) || ((L.w | L.h | L.rows.n_rows | L.rows.row_begin | L.rows.row_end | L.rows.block_rows) & m) || L.n_frames != 1)
       return (int)hipErrorInvalidValue;
   }
-  size_t lds_bytes = (size_t)WAVES_PER_WG * stack.bytes_per_wave();
-  if (kv & KV_OCC6) lds_bytes += (size_t)WAVES_PER_WG * 5 * 64 * sizeof(float);  // PARK
+  size_t lds_bytes = (size_t)WAVES_PER_WG * lds_bytes_per_wave(kv, stack);  // (the stack, and PARK's 5 * 64 floats)
   // diagnostic only: extra dynamic LDS per workgroup caps the waves resident per CU (occupancy sweeps)
   if (const char *pad = getenv("CUTRACE_LDS_PAD")) lds_bytes += (size_t)atol(pad);
   const uint64_t waves = ctr_launch_waves(L);
@@ -2224,6 +2255,9 @@ uint32_t ctr_launch_shape(const RenderLaunch &L) {
   return launch_shape(L.variant, L.scene.n_oloop, launch_head_mesh(L) && L.scene.n_mesh == 1u);
 }
 
+// The opaque build of the launch (kernel_choice.h opaque_build), from its build and its shape.
+uint32_t ctr_launch_opaque(const RenderLaunch &L) { return opaque_build(L.variant, ctr_launch_shape(L), L.no_opaque != 0u); }
+
 // L.variant is the build (kernel_choice.h choose_kernel decides; launch cross-checks the launch's buffers against it).  The
 // switch is what instantiates the kernels — and what makes a table entry listed twice a compile error.
 int ctr_launch_render(const RenderLaunch &L, void *stream) {
@@ -2237,12 +2271,16 @@ int ctr_launch_render(const RenderLaunch &L, void *stream) {
   }
   // the launch shape (kernel_choice.h): the same build, compiled for what this launch's scene cannot contain
   if (ctr_launch_shape(L) == KS_ONE_MESH) {
-    // ... and, where the scene head carries room facts, with the code that uses them ("room-safe lanes")
+    const uint32_t opq = ctr_launch_opaque(L);
+    // ... and, where the scene head carries room facts, with the code that uses them ("room-safe lanes"); and as the opaque
+    // build the launch qualifies for ("opaque build")
     const bool room = L.head.room_lights != 0u;
     switch (L.variant) {
-#define X(kv) case (kv): kernel = room ? (const void *)render_kernel<(kv), KS_ONE_MESH, true> : (const void *)render_kernel<(kv), KS_ONE_MESH>; break;
+#define Y(kv, o) (room ? (const void *)render_kernel<(kv), KS_ONE_MESH, true, o> : (const void *)render_kernel<(kv), KS_ONE_MESH, false, o>)
+#define X(kv) case (kv): kernel = opq == KO_OPAQUE ? Y(kv, KO_OPAQUE) : Y(kv, KO_PARENT); break;
       CTR_SHAPE_KERNELS(X)
 #undef X
+#undef Y
       default: return (int)hipErrorInvalidValue;
     }
   }

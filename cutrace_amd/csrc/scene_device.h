@@ -231,6 +231,7 @@ struct RenderLaunch {
   const float *ray_origin, *ray_dir;
   float ray_ambient;
   uint32_t no_shape;  // 1: the launch takes the general build whatever its scene (kernel_choice.h launch_shape; CUTRACE_NO_SHAPE_BUILD)
+  uint32_t no_opaque; // 1: the launch takes no opaque build (kernel_choice.h opaque_build; CUTRACE_NO_OPAQUE_BUILD)
 };
 
 // keeps `msg` for ctr_last_error() (ctr_scene.cpp); used by the other translation units of the library
@@ -239,6 +240,8 @@ void ctr_internal_set_error(const char *msg);
 int ctr_launch_render(const RenderLaunch &L, void *stream);
 // the launch shape ctr_launch_render gives this launch (kernel_choice.h KS_*); L.variant, L.scene and L.head are final
 uint32_t ctr_launch_shape(const RenderLaunch &L);
+// the opaque build ctr_launch_render gives this launch (kernel_choice.h KO_*)
+uint32_t ctr_launch_opaque(const RenderLaunch &L);
 // counters are accumulated in CTR_SHARDS 128-byte shards (see render_kernel.hip) and folded afterwards (tile_order.hip after_render)
 #define CTR_SHARDS 1024
 #define CTR_SHARD_WORDS 16

@@ -324,6 +324,12 @@ int ctr_debug_last_kernel(ctr_scene *scene, uint32_t *kv);
  * get — the same results bit for bit.  CUTRACE_NO_SHAPE_BUILD=1 in the environment when a handle is created keeps that
  * handle's launches in shape 0 (A/B timing, tests). */
 int ctr_debug_last_shape(ctr_scene *scene, uint32_t *shape);
+/* Diagnostic: the opaque build of that launch (csrc/kernel_choice.h KO_*): 0 = the code as it is for every scene, 1 = the build
+ * that a one-mesh launch (shape 1) of an any-hit build gets — such a build runs only when no material transmits, so the
+ * pass-through half of the shading is compiled out of it and its 6-wave form keeps its shading state in registers — the same
+ * results bit for bit.  CUTRACE_NO_OPAQUE_BUILD=1 in the environment when a handle is created keeps that handle's launches
+ * at 0 (A/B timing, tests). */
+int ctr_debug_last_opaque(ctr_scene *scene, uint32_t *opaque);
 /* Diagnostic: the room facts of that launch (csrc/scene_device.h DSceneHead::room_*; DESIGN.md "Shadow casts from inside a plane
  * room").  out5 = the origin box's centre (3), its half width, the numerator tolerance; *lights = the bits of the point lights
  * that qualify.  Non-zero only for a launch whose kernel reads them — the one-mesh shape (ctr_debug_last_shape 1) of an any-hit
