@@ -41,6 +41,11 @@ SHADE_OUTPUTS = ("color", "t", "object", "normal")
 POINTS_LINEAR = 1
 POINTS_EXACT_POW = 2
 POINTS_OUTPUTS = ("color", "light_shadow")
+# ctr_list_hits flags, per-slot outputs and largest max_hits (include/cutrace_hits.h)
+HITS_IGNORE_TRANSPARENT = 1
+HITS_LINEAR = 2
+HITS_OUTPUTS = ("t", "object", "prim", "point", "normal", "uv")
+HITS_MAX = 65535
 # the display planes of render_images / quantise (include/cutrace_images.h)
 IMAGE_PLANES = ("color", "depth", "normal")
 
@@ -572,6 +577,51 @@ class DeviceScene:
             q.d_shadow = out.data_ptr() if n else None
             if n:
                 self._cast(q, (o, d, mx), raw)
+        return out
+
+    # ---- hit lists (ctr_list_hits, include/cutrace_hits.h) ----
+    def list_hits(self, origins, dirs, max_hits, min_t=1e-3, max_t=float("inf"), step=1e-3, ignore_transparent=False, linear=False,
+                  outputs=None, stream=None):
+        """The first `max_hits` hits along every ray (origins[k], dirs[k]): the chain of nearest casts of the reference's
+        shadow_intensity (inc/shading.hpp:22-45), each cast restarting at (float)((double)t + step) behind the last hit and the
+        chain ending at the first cast that hits nothing below max_t.  A dict of tensors on the scene's device: `count` (n,)
+        int32, always, and SLOT-MAJOR per-slot outputs `t` (max_hits, n), `object`, `prim` (max_hits, n) int32, `point`,
+        `normal` (max_hits, n, 3), `uv` (max_hits, n, 2) — or the subset named in `outputs`; outputs=() gives the count alone.
+        hits["point"][j] is the contiguous batch of every ray's j-th hit, as shade_points and cast_rays take it; slots
+        count .. max_hits-1 of a ray hold cast_rays' miss values (t +inf, object and prim -1, zeros).  min_t, max_t: a scalar
+        or (n,) float32.  With the defaults the list is what shadow(origins, dirs, max_t) visits until its sum saturates.
+        t is in the reference's mixed units (a sphere measures along dir/|dir|), and so is step; a surface less than step
+        behind a listed hit is skipped.  Asynchronous on `stream` (default: torch's current stream of the scene's device)."""
+        import torch
+        outputs = HITS_OUTPUTS if outputs is None else _subset("outputs", outputs, HITS_OUTPUTS, allow_empty=True, unique=True)
+        if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+            raise TypeError(f"max_hits: expected an int, got {type(max_hits).__name__}")
+        if not 1 <= max_hits <= HITS_MAX:
+            raise ValueError(f"max_hits: 1 .. {HITS_MAX}, got {max_hits}")
+        step = float(step)
+        if not (0.0 <= step < float("inf")):
+            raise ValueError(f"step: finite and not negative, got {step}")
+        K = int(max_hits)
+        dev = self._torch_device()
+        with _on_stream(dev, stream) as raw:
+            o, d, n = _ray_pair(origins, dirs, dev)
+            q = _lib.HitQuery()
+            q.n_rays, q.max_hits, q.step = n, K, step
+            q.flags = (HITS_IGNORE_TRANSPARENT if ignore_transparent else 0) | (HITS_LINEAR if linear else 0)
+            q.min_t, mn = self._per_ray(min_t, n, "min_t")
+            q.max_t, mx = self._per_ray(max_t, n, "max_t")
+            if outputs and n * K >= 1 << 31:
+                raise ValueError(f"{n} rays x {K} slots: per-slot outputs need n * max_hits below 2^31")
+            out = {"count": torch.empty(n, dtype=torch.int32, device=dev)}
+            for k in outputs:
+                out[k] = torch.empty((K, n) + _RAY_OUT[k][0], dtype=getattr(torch, _RAY_OUT[k][1]), device=dev)
+            if n:
+                q.d_origin, q.d_dir = o.data_ptr(), d.data_ptr()
+                q.d_min_t = mn.data_ptr() if mn is not None else None
+                q.d_max_t = mx.data_ptr() if mx is not None else None
+                for k, v in out.items():
+                    setattr(q, "d_" + k, v.data_ptr())
+                _check("ctr_list_hits", _lib.hip_lib().ctr_list_hits(self._h, C.byref(q), raw))
         return out
 
     def shade_rays(self, origins, dirs, bounces=5, min_t=1e-3, ambient=None, exact_pow=False, linear=False, outputs=None,

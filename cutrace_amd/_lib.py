@@ -110,6 +110,14 @@ class PointQuery(C.Structure):
                 ("d_material", C.c_void_p), ("d_object", C.c_void_p), ("d_color", C.c_void_p), ("d_light_shadow", C.c_void_p)]
 
 
+class HitQuery(C.Structure):
+    """ctr_hit_query (include/cutrace_hits.h)"""
+    _fields_ = [("n_rays", C.c_uint64), ("flags", C.c_uint32), ("max_hits", C.c_uint32), ("min_t", C.c_float), ("max_t", C.c_float),
+                ("step", C.c_double), ("d_origin", C.c_void_p), ("d_dir", C.c_void_p), ("d_min_t", C.c_void_p), ("d_max_t", C.c_void_p),
+                ("d_count", C.c_void_p), ("d_t", C.c_void_p), ("d_object", C.c_void_p), ("d_prim", C.c_void_p), ("d_point", C.c_void_p),
+                ("d_normal", C.c_void_p), ("d_uv", C.c_void_p)]
+
+
 class Lens(C.Structure):
     """ctr_lens (include/cutrace_lens.h)"""
     _fields_ = [("n_rays", C.c_uint64), ("samples", C.c_uint32), ("ambient", C.c_float), ("d_origin", C.c_void_p),
@@ -240,6 +248,9 @@ HIP_LATER_PROTOS = {
         "ctr_scene_remove_object": ([_ptr, _u64], _int),
         "ctr_scene_room": ([_ptr, _P(SceneRoom)], _int),
     },
+    "cutrace_hits.h": {
+        "ctr_list_hits": ([_ptr, _P(HitQuery), _ptr], _int),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -258,6 +269,7 @@ REPLACE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_replace.h"])
 REPLACE_HOST = 1   # CTR_REPLACE_HOST
 TOPOLOGY_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_topology.h"])
 ADD_HOST = 1       # CTR_ADD_HOST
+HITS_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_hits.h"])
 
 _host = None
 _hip = None

@@ -1,18 +1,22 @@
-// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h: ctr_cast_rays, ctr_shade_rays and ctr_shade_points check a query,
-// describe the uploaded scene to the kernel (RayScene, ray_query.h) and launch it (ray_query.hip, ray_shade.hip, ray_points.hip).
+// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h and include/cutrace_hits.h: ctr_cast_rays, ctr_shade_rays, ctr_shade_points
+// and ctr_list_hits check a query, describe the uploaded scene to the kernel (RayScene, ray_query.h) and launch it
+// (ray_query.hip, ray_shade.hip, ray_points.hip, ray_hits.hip).
 #include <hip/hip_runtime_api.h>
 
+#include <cmath>
 #include <string>
 
 #include "ctr_internal.h"
+#include "cutrace_hits.h"
 #include "cutrace_rays.h"
+#include "ray_hits.h"
 #include "ray_points.h"
 #include "ray_query.h"
 #include "ray_shade.h"
 
 namespace {
 
-// What the three entry points check alike, once the query is known not to be null: the record of one call.
+// What the entry points check alike, once the query is known not to be null: the record of one call.
 struct QueryHead {
   const std::string &who;   // "ctr_...: ", the prefix of every message
   uint32_t flags, known;    // the query's flag word, the bits its entry point knows
@@ -171,4 +175,46 @@ extern "C" int ctr_shade_points(ctr_scene *s, const ctr_point_query *q, void *hi
   if (!L.color && !L.light_shadow) return CTR_OK;  // a scene without lights: the rows of d_light_shadow are empty
   if (int st = use_device(s)) return st;
   return launched(ctr_launch_points(L, hip_stream), "surface shading kernel launch");
+}
+
+extern "C" int ctr_list_hits(ctr_scene *s, const ctr_hit_query *q, void *hip_stream) {
+  const std::string who = "ctr_list_hits: ";
+  if (!q) return fail(CTR_E_INVALID, who + "null query");
+  const bool any_slot = q->d_t || q->d_object || q->d_prim || q->d_point || q->d_normal || q->d_uv;
+  std::string broken;
+  if (q->max_hits == 0 || q->max_hits > CTR_HITS_MAX)
+    broken = "max_hits " + std::to_string(q->max_hits) + " outside [1, " + std::to_string(CTR_HITS_MAX) + "]";
+  else if (!(q->step >= 0.0) || std::isinf(q->step)) broken = "step must be finite and not negative";
+  else if (!any_slot && !q->d_count) broken = "no output: d_count or one of the per-slot outputs is required";
+  if (int st = check_query(s, {who, q->flags, CTR_HITS_IGNORE_TRANSPARENT | CTR_HITS_LINEAR, broken, q->n_rays, "n_rays",
+                               q->d_origin && q->d_dir, "null rays"}))
+    return st;
+  if (any_slot && q->n_rays * q->max_hits >= 0x80000000ull)
+    return fail(CTR_E_INVALID, who + "n_rays * max_hits must be below 2^31 with a per-slot output (d_count alone has no such limit)");
+  if (q->n_rays == 0) return CTR_OK;
+  const NamedPtr ptrs[] = {{q->d_origin, "d_origin"}, {q->d_dir, "d_dir"}, {q->d_min_t, "d_min_t"}, {q->d_max_t, "d_max_t"},
+                           {q->d_count, "d_count"}, {q->d_t, "d_t"}, {q->d_object, "d_object"}, {q->d_prim, "d_prim"},
+                           {q->d_point, "d_point"}, {q->d_normal, "d_normal"}, {q->d_uv, "d_uv"}};
+  if (int st = check_device_pointers(s->device, who, ptrs)) return st;
+  if (int st = use_device(s)) return st;
+  HitsLaunch L{};
+  L.scene = ray_scene(s, device_scene(s));
+  L.n_rays = (uint32_t)q->n_rays;
+  L.flags = q->flags;
+  L.max_hits = q->max_hits;
+  L.min_t = q->min_t;
+  L.max_t = q->max_t;
+  L.step = q->step;
+  L.origin = q->d_origin;
+  L.dir = q->d_dir;
+  L.min_t_arr = q->d_min_t;
+  L.max_t_arr = q->d_max_t;
+  L.count = q->d_count;
+  L.t = q->d_t;
+  L.object = q->d_object;
+  L.prim = q->d_prim;
+  L.point = q->d_point;
+  L.normal = q->d_normal;
+  L.uv = q->d_uv;
+  return launched(ctr_launch_hits(L, hip_stream), "hit list kernel launch");
 }

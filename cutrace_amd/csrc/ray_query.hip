@@ -11,7 +11,7 @@
 // aligned: every record is 64 or 128 bytes, every array a hipMalloc), each mesh's four-wide BVH (bvh.h) is walked with
 // a per-lane stack in LDS laid out [entry][lane] (conflict-free whatever depth each lane is at), sized from the
 // scene's deepest mesh tree (scene_flatten.h FlatScene::ray_slots).  No scratch memory.  The walk itself (cast, cast_mesh,
-// tri_hit) lives in ray_walk.h, which the radiance queries (ray_shade.hip) share.
+// tri_hit) lives in ray_walk.h, which the radiance queries (ray_shade.hip) share; the hit record in hit_record.h, which the hit lists (ray_hits.hip) share.
 //
 // Exactness — what each step may and may not shortcut:
 //  * planes, spheres, stand-alone triangles: the reference's arithmetic, operation for operation (-ffp-contract=off,
@@ -36,6 +36,7 @@
 
 #include "bvh.h"
 #include "cutrace_rays.h"
+#include "hit_record.h"
 #include "ray_launch.h"
 #include "ray_query.h"
 #include "ray_walk.h"
@@ -83,48 +84,10 @@ __global__ __launch_bounds__(RQ_THREADS) void ray_query_kernel(RayLaunch L) {
   if (L.object) L.object[i] = hit ? (int32_t)b.obj : -1;
   if (L.prim) L.prim[i] = (hit && b.prim != RQ_NONE) ? (int32_t)b.prim : -1;
   if (!(L.point || L.normal || L.uv)) return;
-  // ---- the hit record: point, normal (per primitive), texture coordinates (ray_cast.hpp:44-47) ----
-  V3 pos = mk(0, 0, 0), nrm = mk(0, 0, 0);
-  float u = 0.0f, v = 0.0f;  // uv{} of kernel.hpp:51 on a miss
-  if (hit) {
-    const float4 *H = S.objs + (size_t)b.obj * 4;
-    const float4 h0 = H[0], h2 = H[2], h3 = H[3];
-    const uint32_t type = bits(h0.x);
-    if (type == CTR_OBJ_SPHERE) {
-      // default_schema.hpp:245-249: the hit uses the NORMALISED direction; uv's delta is the normal again
-      pos = vadd(ro, vscale(vnormalized(rd), b.t));
-      nrm = vnormalized(vsub(pos, mk(h2.x, h2.y, h2.z)));
-      u = 0.5f + (atan2f(nrm.z, nrm.x) / (2.0f * (float)M_PI));
-      v = 0.5f + (asinf(nrm.y) / (float)M_PI);
-    } else {
-      pos = vadd(ro, vscale(rd, b.t));  // start + dist*dir
-      if (type == CTR_OBJ_PLANE) {
-        nrm = mk(h2.w, h3.x, h3.y);
-        // plane::uv_for, default_schema.hpp:169-178
-        const V3 ax1 = vnormalized(mk(nrm.y, -nrm.x, 0.0f));
-        const V3 ax2 = vcross(nrm, ax1);
-        const V3 mod_pt = vsub(mk(h2.x, h2.y, h2.z), pos);
-        u = vdot(ax1, mod_pt);
-        v = vdot(ax2, mod_pt);
-      } else {
-        const float *g = S.gnorm + (size_t)b.tri * 4;
-        nrm = mk(g[0], g[1], g[2]);
-        if (type == CTR_OBJ_MESH) {  // mesh::intersect, default_schema.hpp:138-139
-          u = pos.x;
-          v = pos.y;
-        } else {  // triangle::uv_for, default_schema.hpp:37-46 (p1, p3 in the object record, p2 in its DTri)
-          const float4 *T = S.tris + (size_t)b.tri * 4;
-          const float4 t1 = T[1], t2 = T[2];
-          const V3 p1 = mk(h2.x, h2.y, h2.z), p2 = mk(t1.z, t1.w, t2.x), p3 = mk(h2.w, h3.x, h3.y);
-          const V3 p2p1 = vsub(p2, p1), p3p1 = vsub(p3, p1), xp1 = vsub(pos, p1);
-          const V3 proj_u = vscale(p2p1, vdot(xp1, p2p1) / vdot(p2p1, p2p1));
-          const V3 proj_v = vscale(p3p1, vdot(xp1, p3p1) / vdot(p3p1, p3p1));
-          u = vnorm(proj_u) / vnorm(p2p1);
-          v = vnorm(proj_v) / vnorm(p3p1);
-        }
-      }
-    }
-  }
+  // ---- the hit record: point, normal (per primitive), texture coordinates (hit_record.h) ----
+  const HitRecord r = hit_record(S, ro, rd, b);
+  const V3 pos = r.pos, nrm = r.nrm;
+  const float u = r.u, v = r.v;
   if (L.point) { L.point[i3] = pos.x; L.point[i3 + 1] = pos.y; L.point[i3 + 2] = pos.z; }
   if (L.normal) { L.normal[i3] = nrm.x; L.normal[i3 + 1] = nrm.y; L.normal[i3 + 2] = nrm.z; }
   if (L.uv) { L.uv[2 * (size_t)i] = u; L.uv[2 * (size_t)i + 1] = v; }

@@ -1,6 +1,6 @@
 // ray_walk.h — the per-lane walk of the ray queries: ray_cast (inc/ray_cast.hpp:29-55) of ONE ray by ONE lane.
 //
-// Shared by ray_query.hip (ctr_cast_rays), ray_shade.hip (ctr_shade_rays) and ray_points.hip (ctr_shade_points); what each step may and may not shortcut
+// Shared by ray_query.hip (ctr_cast_rays), ray_shade.hip (ctr_shade_rays), ray_points.hip (ctr_shade_points) and ray_hits.hip (ctr_list_hits); what each step may and may not shortcut
 // is stated at the top of ray_query.hip.  Device code only: include it from a .hip translation unit, after
 // hip_runtime.h.  Everything lives in an unnamed namespace, one copy per translation unit.
 //

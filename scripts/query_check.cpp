@@ -1,10 +1,11 @@
 // query_check.cpp — the host glue of the ray queries that needs no device, as a program of its own (meant for ASan/UBSan; the
 // record of a run: profiles/query_path/sanitizers.txt): the pointer classifier of ctr_scene.cpp and what is written on top of it
 // (memory_kind, is_pinned, all_pinned, check_device_pointers), launched(), walk_stack_bytes and the two *_lds_bytes rules of
-// ray_query.h / ray_shade.hip / ray_points.hip, and the checks ctr_cast_rays, ctr_shade_rays and ctr_shade_points make before
+// ray_query.h / ray_shade.hip / ray_points.hip, and the checks ctr_cast_rays, ctr_shade_rays, ctr_shade_points and ctr_list_hits make before
 // they look at the scene.  Without a device the runtime knows no pointer: everything is HOST_OTHER, which is the path that
-// swallows the runtime's error.  Linked with ctr_scene.cpp, ctr_rays.cpp, the three query .hip files (their host halves are
-// what is checked; no check gets as far as a launch) and the host files those need.
+// swallows the runtime's error.  Linked with ctr_scene.cpp, ctr_rays.cpp, the query .hip files (ray_query, ray_shade, ray_points,
+// and ray_hits since ctr_rays.cpp holds ctr_list_hits: their host halves are what is checked; no check gets as far as a launch) and
+// the host files those need.
 //
 //   query_check        prints "query_check: ok" and returns 0, or says what differed and returns 1
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "ctr_internal.h"
+#include "cutrace_hits.h"
 #include "cutrace_rays.h"
 #include "ray_points.h"
 #include "ray_query.h"
@@ -90,6 +92,16 @@ int main() {
   expect_error(ctr_shade_points(nullptr, &p, nullptr), "ctr_shade_points: null scene");
   p.d_color = some_ptr;
   expect_error(ctr_shade_points(nullptr, &p, nullptr), "ctr_shade_points: d_color needs d_normal and d_view");
+  expect_error(ctr_list_hits(nullptr, nullptr, nullptr), "ctr_list_hits: null query");
+  ctr_hit_query h{};
+  h.n_rays = 2; h.max_hits = 4; h.step = 1e-3; h.d_count = (int32_t *)some_ptr;
+  expect_error(ctr_list_hits(nullptr, &h, nullptr), "ctr_list_hits: null scene");
+  h.max_hits = CTR_HITS_MAX + 1;
+  expect_error(ctr_list_hits(nullptr, &h, nullptr), "ctr_list_hits: max_hits 65536 outside [1, 65535]");
+  h.max_hits = 4; h.step = -1.0;
+  expect_error(ctr_list_hits(nullptr, &h, nullptr), "ctr_list_hits: step must be finite and not negative");
+  h.step = 0.0; h.d_count = nullptr;
+  expect_error(ctr_list_hits(nullptr, &h, nullptr), "ctr_list_hits: no output: d_count or one of the per-slot outputs is required");
 
   if (!failures) printf("query_check: ok\n");
   return failures ? 1 : 0;
