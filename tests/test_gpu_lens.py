@@ -10,12 +10,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-import cutrace_amd
 from cutrace_amd import _lib, lenses
 from tests import aa_ref, ray_ref, shade_ref
-from tests.conftest import load_scene
 from tests.gpu_support import gpu  # noqa: F401  (the fixture)
-from tests.util import TOL, _random_scene, hall_of_mirrors_json, same_bits
+from tests.lens_rays import CastCounter, assert_frames, cam_of, frame_from_rays, host_scene, lens, normalised, plain_device
+from tests.util import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -23,58 +22,6 @@ f32 = np.float32
 KV_OCC6, KV_SS, KV_RAYS = 64, 2048, 4096
 # name -> (w, h, bounces) of the pinhole test; the other tests say their own sizes
 SCENES = {"random3": (21, 13, 5), "random5": (21, 13, 5), "bunny": (40, 24, 5), "mirror": (32, 24, 8)}
-
-
-def host_scene(ca, name, w, h):
-    if name.startswith("random"):
-        s = ca.HostScene.parse(_random_scene(int(name[6:]), w, h))
-    elif name == "hall":
-        s = ca.HostScene.parse(hall_of_mirrors_json(w, h))
-    else:
-        s = load_scene(ca, name, w, h)
-    assert s.ok
-    return s
-
-
-def cam_of(s):
-    return s.desc.contents.cam
-
-
-def max_depth_of(counters):
-    return float(np.array([int(counters[1]) & 0xFFFFFFFF], np.uint32).view(f32)[0])
-
-
-def plain_device(ds, b, rows=None):
-    """ctr_render_device of the handle, as numpy: what render_lens is compared with"""
-    import torch
-    dev = torch.device("cuda", ds.device)
-    n = cutrace_amd.rows_count(ds.h, rows)
-    depth = torch.full((n, ds.w), -1.0, device=dev)
-    color = torch.full((n, ds.w, 3), -1.0, device=dev)
-    normal = torch.full((n, ds.w, 3), -1.0, device=dev)
-    counters = torch.zeros(16, dtype=torch.int64, device=dev)
-    ds.render_device(depth.data_ptr(), color.data_ptr(), normal.data_ptr(), d_counters=counters.data_ptr(),
-                     stream=torch.cuda.current_stream(dev).cuda_stream, bounces=b, rows=rows)
-    torch.cuda.synchronize()
-    c = counters.cpu()
-    return dict(depth=depth.cpu().numpy(), color=color.cpu().numpy(), normal=normal.cpu().numpy(), ray_count=int(c[0]), max_depth=max_depth_of(c))
-
-
-def lens(ds, o, d, **kw):
-    r = ds.render_lens(o, d, **kw)
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
-
-
-def assert_frames(got, want, what, color="bits"):
-    for k in ("depth", "normal"):
-        assert same_bits(got[k], want[k]), f"{what}: {k} differs in {int((got[k].view(np.uint32) != want[k].view(np.uint32)).sum())} words"
-    diff = float(np.abs(got["color"].astype(np.float64) - want["color"].astype(np.float64)).max()) if got["color"].size else 0.0
-    print(f"{what}: colour max|diff| {diff:.3e}")
-    assert not np.isnan(got["color"]).any(), what
-    if color == "bits":
-        assert same_bits(got["color"], want["color"]), f"{what}: colour differs in {int((got['color'].view(np.uint32) != want['color'].view(np.uint32)).sum())} words, max {diff:.3e}"
-    else:
-        assert diff <= TOL, f"{what}: colour max|diff| {diff:.3e}"
 
 
 # ---- 1. the camera through the lens is the render ----
@@ -108,20 +55,6 @@ def other_lenses(cam, w, h):
     """a fisheye with a masked rim, a stereo pair (two origins in one frame), a thin lens (an origin per pixel)"""
     return {"fisheye": lenses.fisheye(cam, w, h, 150.0), "stereo": lenses.stereo(cam, w, h, 0.4),
             "thin": lenses.thin_lens(cam, w, h, 1, 0.15, 4.0, seed=11)}
-
-
-def normalised(d):
-    with np.errstate(all="ignore"):
-        return ray_ref.vnormalized(np.ascontiguousarray(d, f32)).astype(f32)
-
-
-def frame_from_rays(h, w, keep, t, normal, color):
-    """the frame of a per-ray result for the unmasked rays `keep` (flat bool): the miss values elsewhere"""
-    depth = np.full(h * w, np.inf, f32)
-    nrm = np.zeros((h * w, 3), f32)
-    col = np.zeros((h * w, 3), f32)
-    depth[keep], nrm[keep], col[keep] = t, normal, color
-    return dict(depth=depth.reshape(h, w), normal=nrm.reshape(h, w, 3), color=col.reshape(h, w, 3))
 
 
 @pytest.mark.parametrize("name", ["random3", "random5"])
@@ -176,20 +109,6 @@ def test_other_lenses_against_the_linear_radiance_query(gpu, name, w, h, b):
 
 
 # ---- 3. masking ----
-class CastCounter:
-    """counts the rays of every ray_ref.ray_cast call: the casts of tests/shade_ref.py's ray_color"""
-
-    def __init__(self, monkeypatch):
-        self.n = 0
-        real = ray_ref.ray_cast
-
-        def counted(scene, start, dirs, *a, **kw):
-            self.n += len(start)
-            return real(scene, start, dirs, *a, **kw)
-
-        monkeypatch.setattr(ray_ref, "ray_cast", counted)
-
-
 def test_masked_pixels(gpu, monkeypatch):
     """ray_count: the drop equals the cast count of tests/shade_ref.py's ray_color for the masked pixels' camera rays, plus the
     duplicated primary cast of each (the reference's count, not a plain render of those pixels alone: `rows` selects rows,

@@ -25,9 +25,10 @@ import pytest
 
 import oracle
 from cutrace_amd import lenses
-from tests import aa_ref, ray_ref
+from tests import aa_ref
 from tests.gpu_support import gpu  # noqa: F401  (the fixture)
-from tests.util import (ALL_MISS_CASE, RANGE_FLAVOURS, RANGE_POW_DEPENDENT, RENDER_RANGE_CASES, TOL, assert_parity, uv_close, f32, pow2, range_case_id, range_fudge,
+from tests.lens_rays import assert_frames, frame_from_rays, normalised
+from tests.util import (ALL_MISS_CASE, RANGE_FLAVOURS, RANGE_POW_DEPENDENT, RENDER_RANGE_CASES, assert_parity, uv_close, f32, pow2, range_case_id, range_fudge,
                         render_range_scene_json, same_bits)
 
 pytestmark = pytest.mark.gpu
@@ -184,32 +185,6 @@ def test_supersampled_render(gpu, tmp_path, case, flavour):
 
 
 # ---- e. the lens render ----
-def normalised(d):
-    with np.errstate(all="ignore"):
-        return ray_ref.vnormalized(np.ascontiguousarray(d, f32)).astype(f32)
-
-
-def frame_from_rays(h, w, keep, t, normal, color):
-    """the frame of a per-ray result for the unmasked rays `keep` (flat bool): the miss values elsewhere"""
-    depth = np.full(h * w, np.inf, f32)
-    nrm = np.zeros((h * w, 3), f32)
-    col = np.zeros((h * w, 3), f32)
-    depth[keep], nrm[keep], col[keep] = t, normal, color
-    return dict(depth=depth.reshape(h, w), normal=nrm.reshape(h, w, 3), color=col.reshape(h, w, 3))
-
-
-def assert_lens_frame(got, want, what, exact):
-    for k in ("depth", "normal"):
-        assert same_bits(got[k], want[k]), f"{what}: {k} differs in {int((got[k].view(np.uint32) != want[k].view(np.uint32)).sum())} words"
-    assert not np.isnan(got["color"]).any(), what
-    diff = float(np.abs(got["color"].astype(np.float64) - want["color"].astype(np.float64)).max())
-    print(f"{what}: colour max|diff| {diff:.3e}")
-    if exact:
-        assert same_bits(got["color"], want["color"]), f"{what}: colour differs in {int((got['color'].view(np.uint32) != want['color'].view(np.uint32)).sum())} words, max {diff:.3e}"
-    else:
-        assert diff <= TOL, f"{what}: colour max|diff| {diff:.3e}"
-
-
 @pytest.mark.parametrize("case,flavour", CASES)
 def test_lens_render(gpu, tmp_path, case, flavour):
     """pinhole rays: the plain render of the same handle, bit for bit.  A fisheye and a two-samples-per-axis thin lens (aperture
@@ -246,7 +221,7 @@ def test_lens_render(gpu, tmp_path, case, flavour):
             got = as_numpy(ds.render_lens(o, d, fudge=fudge, bounces=BOUNCES, samples=ss))
             kv = ds.last_kernel()
             assert kv & KV_RAYS and bool(kv & KV_SS) == (ss > 1)
-            assert_lens_frame(got, want, f"{what} {lname} exact={exact}", exact)
+            assert_frames(got, want, f"{what} {lname} exact={exact}", color="bits" if exact else "tol")
             if case != ALL_MISS_CASE:
                 assert np.isfinite(got["depth"]).sum() > H * W // 10, f"{what} {lname}: the lens sees too little"
     ds.close()
