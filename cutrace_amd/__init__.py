@@ -46,6 +46,10 @@ HITS_IGNORE_TRANSPARENT = 1
 HITS_LINEAR = 2
 HITS_OUTPUTS = ("t", "object", "prim", "point", "normal", "uv")
 HITS_MAX = 65535
+# ctr_nearest_points flags (include/cutrace_nearest.h) and what DeviceScene.nearest_points returns per point
+NEAREST_LINEAR = 1
+NEAREST_SKIP_PLANES = 2
+NEAREST_OUTPUTS = ("distance", "object", "prim", "point", "normal")
 # the display planes of render_images / quantise (include/cutrace_images.h)
 IMAGE_PLANES = ("color", "depth", "normal")
 
@@ -132,6 +136,11 @@ def _subset(what, names, allowed, allow_empty=False, unique=False):
 # what cast_rays and shade_rays return per ray: (trailing shape, dtype)
 _RAY_OUT = {"t": ((), "float32"), "object": ((), "int32"), "prim": ((), "int32"), "point": ((3,), "float32"),
             "normal": ((3,), "float32"), "uv": ((2,), "float32"), "color": ((3,), "float32")}
+
+
+# what nearest_points returns per point
+_NEAREST_OUT = {"distance": ((), "float32"), "object": ((), "int32"), "prim": ((), "int32"), "point": ((3,), "float32"),
+                "normal": ((3,), "float32")}
 
 
 def _ray_outputs(names, n, dev):
@@ -622,6 +631,43 @@ class DeviceScene:
                 for k, v in out.items():
                     setattr(q, "d_" + k, v.data_ptr())
                 _check("ctr_list_hits", _lib.hip_lib().ctr_list_hits(self._h, C.byref(q), raw))
+        return out
+
+    # ---- nearest points (ctr_nearest_points, include/cutrace_nearest.h) ----
+    def nearest_points(self, points, max_dist=float("inf"), object=None, skip_planes=False, linear=False, outputs=None, stream=None):
+        """The closest surface point to every point of `points` ((n, 3) float32): a dict of tensors on the scene's device,
+        `distance` (n,) (+inf: nothing within max_dist), `object` (n,) int32 (-1), `prim` (n,) int32 (file-order triangle of a
+        mesh, else -1), `point` (n, 3) the closest point, `normal` (n, 3) what cast_rays reports for a hit there — or the subset
+        named in `outputs`.  Among equally near candidates the lower object index wins, inside a mesh the lower file index.
+        max_dist: a scalar >= 0 or (n,) float32 (a NaN or negative entry: that point misses).  object: only this object index
+        (None: every object).  skip_planes: planes are no candidates.  linear=True: no tree, every triangle of every admitted
+        mesh — the same bits, the cross-check.  A point with a NaN or an infinity gets the miss values.  Asynchronous on
+        `stream` (default: torch's current stream of the scene's device)."""
+        import torch
+        outputs = NEAREST_OUTPUTS if outputs is None else _subset("outputs", outputs, NEAREST_OUTPUTS, unique=True)
+        if object is not None and (isinstance(object, bool) or not isinstance(object, (int, np.integer))):
+            raise TypeError(f"object: expected None or an int, got {type(object).__name__}")
+        if object is not None and object < 0:
+            raise ValueError(f"object: None or an index >= 0, got {object}")
+        if isinstance(max_dist, (int, float, np.integer, np.floating)) and not float(max_dist) >= 0.0:
+            raise ValueError(f"max_dist: not negative and not NaN, got {max_dist}")
+        dev = self._torch_device()
+        with _on_stream(dev, stream) as raw:
+            p = _array_check(points, "points", dev, "float32", 3)
+            n = p.shape[0]
+            q = _lib.NearestQuery()
+            q.max_dist, md = self._per_ray(max_dist, n, "max_dist")
+            p = p.to(dev, non_blocking=False).contiguous()
+            q.n_points = n
+            q.flags = (NEAREST_LINEAR if linear else 0) | (NEAREST_SKIP_PLANES if skip_planes else 0)
+            q.object = -1 if object is None else int(object)
+            out = {k: torch.empty((n,) + _NEAREST_OUT[k][0], dtype=getattr(torch, _NEAREST_OUT[k][1]), device=dev) for k in outputs}
+            if n:
+                q.d_point = p.data_ptr()
+                q.d_max_dist = md.data_ptr() if md is not None else None
+                for k, v in out.items():
+                    setattr(q, {"point": "d_nearest"}.get(k, "d_" + k), v.data_ptr())
+                _check("ctr_nearest_points", _lib.hip_lib().ctr_nearest_points(self._h, C.byref(q), raw))
         return out
 
     def shade_rays(self, origins, dirs, bounces=5, min_t=1e-3, ambient=None, exact_pow=False, linear=False, outputs=None,

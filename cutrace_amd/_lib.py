@@ -118,6 +118,13 @@ class HitQuery(C.Structure):
                 ("d_normal", C.c_void_p), ("d_uv", C.c_void_p)]
 
 
+class NearestQuery(C.Structure):
+    """ctr_nearest_query (include/cutrace_nearest.h)"""
+    _fields_ = [("n_points", C.c_uint64), ("flags", C.c_uint32), ("object", C.c_int32), ("max_dist", C.c_float), ("reserved", C.c_uint32),
+                ("d_point", C.c_void_p), ("d_max_dist", C.c_void_p), ("d_distance", C.c_void_p), ("d_object", C.c_void_p),
+                ("d_prim", C.c_void_p), ("d_nearest", C.c_void_p), ("d_normal", C.c_void_p)]
+
+
 class Lens(C.Structure):
     """ctr_lens (include/cutrace_lens.h)"""
     _fields_ = [("n_rays", C.c_uint64), ("samples", C.c_uint32), ("ambient", C.c_float), ("d_origin", C.c_void_p),
@@ -251,6 +258,9 @@ HIP_LATER_PROTOS = {
     "cutrace_hits.h": {
         "ctr_list_hits": ([_ptr, _P(HitQuery), _ptr], _int),
     },
+    "cutrace_nearest.h": {
+        "ctr_nearest_points": ([_ptr, _P(NearestQuery), _ptr], _int),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -270,6 +280,7 @@ REPLACE_HOST = 1   # CTR_REPLACE_HOST
 TOPOLOGY_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_topology.h"])
 ADD_HOST = 1       # CTR_ADD_HOST
 HITS_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_hits.h"])
+NEAREST_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_nearest.h"])
 
 _host = None
 _hip = None

@@ -1,6 +1,6 @@
-// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h and include/cutrace_hits.h: ctr_cast_rays, ctr_shade_rays, ctr_shade_points
-// and ctr_list_hits check a query, describe the uploaded scene to the kernel (RayScene, ray_query.h) and launch it
-// (ray_query.hip, ray_shade.hip, ray_points.hip, ray_hits.hip).
+// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h, include/cutrace_hits.h and include/cutrace_nearest.h: ctr_cast_rays,
+// ctr_shade_rays, ctr_shade_points, ctr_list_hits and ctr_nearest_points check a query, describe the uploaded scene to the kernel
+// (RayScene, ray_query.h) and launch it (ray_query.hip, ray_shade.hip, ray_points.hip, ray_hits.hip, ray_nearest.hip).
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -8,8 +8,10 @@
 
 #include "ctr_internal.h"
 #include "cutrace_hits.h"
+#include "cutrace_nearest.h"
 #include "cutrace_rays.h"
 #include "ray_hits.h"
+#include "ray_nearest.h"
 #include "ray_points.h"
 #include "ray_query.h"
 #include "ray_shade.h"
@@ -217,4 +219,38 @@ extern "C" int ctr_list_hits(ctr_scene *s, const ctr_hit_query *q, void *hip_str
   L.normal = q->d_normal;
   L.uv = q->d_uv;
   return launched(ctr_launch_hits(L, hip_stream), "hit list kernel launch");
+}
+
+extern "C" int ctr_nearest_points(ctr_scene *s, const ctr_nearest_query *q, void *hip_stream) {
+  const std::string who = "ctr_nearest_points: ";
+  if (!q) return fail(CTR_E_INVALID, who + "null query");
+  const char *broken = "";
+  if (!q->d_distance && !q->d_object && !q->d_prim && !q->d_nearest && !q->d_normal)
+    broken = "no output: one of d_distance, d_object, d_prim, d_nearest and d_normal is required";
+  else if (!q->d_max_dist && !(q->max_dist >= 0.0f)) broken = "max_dist must not be negative or NaN";
+  if (int st = check_query(s, {who, q->flags, CTR_NEAREST_LINEAR | CTR_NEAREST_SKIP_PLANES, broken, q->n_points, "n_points",
+                               q->d_point != nullptr, "null d_point"}))
+    return st;
+  const size_t n_obj = s->flat.objs.size();
+  if (q->object < -1 || (q->object >= 0 && (size_t)q->object >= n_obj))
+    return fail(CTR_E_INVALID, who + "object " + std::to_string(q->object) + " outside [-1, " + std::to_string(n_obj) + ")");
+  if (q->n_points == 0) return CTR_OK;
+  const NamedPtr ptrs[] = {{q->d_point, "d_point"}, {q->d_max_dist, "d_max_dist"}, {q->d_distance, "d_distance"}, {q->d_object, "d_object"},
+                           {q->d_prim, "d_prim"}, {q->d_nearest, "d_nearest"}, {q->d_normal, "d_normal"}};
+  if (int st = check_device_pointers(s->device, who, ptrs)) return st;
+  if (int st = use_device(s)) return st;
+  NearestLaunch L{};
+  L.scene = ray_scene(s, device_scene(s));
+  L.n_points = (uint32_t)q->n_points;
+  L.flags = q->flags;
+  L.only = q->object;
+  L.max_dist = q->max_dist;
+  L.point = q->d_point;
+  L.max_dist_arr = q->d_max_dist;
+  L.distance = q->d_distance;
+  L.object = q->d_object;
+  L.prim = q->d_prim;
+  L.nearest = q->d_nearest;
+  L.normal = q->d_normal;
+  return launched(ctr_launch_nearest(L, hip_stream), "nearest point kernel launch");
 }

@@ -1,11 +1,14 @@
 // query_check.cpp — the host glue of the ray queries that needs no device, as a program of its own (meant for ASan/UBSan; the
 // record of a run: profiles/query_path/sanitizers.txt): the pointer classifier of ctr_scene.cpp and what is written on top of it
 // (memory_kind, is_pinned, all_pinned, check_device_pointers), launched(), walk_stack_bytes and the two *_lds_bytes rules of
-// ray_query.h / ray_shade.hip / ray_points.hip, and the checks ctr_cast_rays, ctr_shade_rays, ctr_shade_points and ctr_list_hits make before
-// they look at the scene.  Without a device the runtime knows no pointer: everything is HOST_OTHER, which is the path that
+// ray_query.h / ray_shade.hip / ray_points.hip, and the checks ctr_cast_rays, ctr_shade_rays, ctr_shade_points, ctr_list_hits and
+// ctr_nearest_points make before they look at the scene.  Without a device the runtime knows no pointer: everything is HOST_OTHER, which is the path that
 // swallows the runtime's error.  Linked with ctr_scene.cpp, ctr_rays.cpp, the query .hip files (ray_query, ray_shade, ray_points,
-// and ray_hits since ctr_rays.cpp holds ctr_list_hits: their host halves are what is checked; no check gets as far as a launch) and
-// the host files those need.
+// ray_hits and ray_nearest since ctr_rays.cpp holds ctr_list_hits and ctr_nearest_points: their host halves are what is checked; no
+// check gets as far as a launch) and the host files those need:
+//   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -ffp-contract=off -pthread -Wno-unused-function -Icutrace_amd/csrc -Iinclude
+//     -o query_check scripts/query_check.cpp cutrace_amd/csrc/{ctr_scene.cpp,ctr_rays.cpp,ray_query.hip,ray_shade.hip,ray_points.hip,
+//     ray_hits.hip,ray_nearest.hip,guard_scan.hip,scene_flatten.cpp,guard.cpp,bvh.cpp}
 //
 //   query_check        prints "query_check: ok" and returns 0, or says what differed and returns 1
 #include <cstdio>
@@ -16,6 +19,7 @@
 
 #include "ctr_internal.h"
 #include "cutrace_hits.h"
+#include "cutrace_nearest.h"
 #include "cutrace_rays.h"
 #include "ray_points.h"
 #include "ray_query.h"
@@ -102,6 +106,16 @@ int main() {
   expect_error(ctr_list_hits(nullptr, &h, nullptr), "ctr_list_hits: step must be finite and not negative");
   h.step = 0.0; h.d_count = nullptr;
   expect_error(ctr_list_hits(nullptr, &h, nullptr), "ctr_list_hits: no output: d_count or one of the per-slot outputs is required");
+  expect_error(ctr_nearest_points(nullptr, nullptr, nullptr), "ctr_nearest_points: null query");
+  ctr_nearest_query n{};
+  n.n_points = 2; n.object = -1; n.d_point = some_ptr; n.d_distance = some_ptr;
+  expect_error(ctr_nearest_points(nullptr, &n, nullptr), "ctr_nearest_points: null scene");
+  n.max_dist = -1.0f;
+  expect_error(ctr_nearest_points(nullptr, &n, nullptr), "ctr_nearest_points: max_dist must not be negative or NaN");
+  n.max_dist = 1.0f; n.flags = 4;
+  expect_error(ctr_nearest_points(nullptr, &n, nullptr), "ctr_nearest_points: unknown flag bits 4");
+  n.flags = CTR_NEAREST_LINEAR | CTR_NEAREST_SKIP_PLANES; n.d_distance = nullptr;
+  expect_error(ctr_nearest_points(nullptr, &n, nullptr), "ctr_nearest_points: no output: one of d_distance, d_object, d_prim, d_nearest and d_normal is required");
 
   if (!failures) printf("query_check: ok\n");
   return failures ? 1 : 0;
