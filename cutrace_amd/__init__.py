@@ -498,6 +498,13 @@ class DeviceScene:
         _check("ctr_debug_room_facts", _lib.hip_lib().ctr_debug_room_facts(self._h, out.ctypes.data, C.byref(lights)))
         return {"c": out[:3].copy(), "r": float(out[3]), "delta": float(out[4]), "lights": int(lights.value)}
 
+    def dark_skip(self):
+        """The dark-skip word of the handle's most recent launch (ctr_debug_dark_skip): non-zero when its kernel may leave out the
+        shadow casts of lights whose diffuse and specular factors are both zero at the hit."""
+        word = C.c_uint32()
+        _check("ctr_debug_dark_skip", _lib.hip_lib().ctr_debug_dark_skip(self._h, C.byref(word)))
+        return int(word.value)
+
     @staticmethod
     def lane_stats(reset=True):
         """Live-lane statistics of the VAR_STATS launches since the last reset (ctr_debug_lane_stats), decoded."""
@@ -512,7 +519,8 @@ class DeviceScene:
                "merged_walks": c[78], "merged_walks_redone": c[77],
                "shadow_casts_at_meshes": {"wave_casts": c[80], "receivers_all_off_mesh": c[81], "of_those_unoccluded_by_meshes": c[82],
                                           "unoccluded_by_meshes_any_receiver": c[83]},
-               "anyhit_shadow_trips": c[88], "anyhit_shadow_trips_without_planes": c[89]}
+               "anyhit_shadow_trips": c[88], "anyhit_shadow_trips_without_planes": c[89],
+               "dark_lights": {"lane_light_pairs": c[90], "shadow_trips_all_dark": c[91], "mesh_entries_with_a_dark_lane": c[92]}}
         kinds = {}
         for d in range(16):
             for name, base in (("radiance", 0), ("shadow", 16)):

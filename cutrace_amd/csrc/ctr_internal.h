@@ -135,8 +135,10 @@ struct ctr_scene {
   bool no_scene_head = false;  // CUTRACE_NO_SCENE_HEAD=1 when the handle was created: launches carry an empty scene head
   bool no_shape_build = false; // CUTRACE_NO_SHAPE_BUILD=1 when the handle was created: every launch in shape KS_GENERAL (kernel_choice.h)
   bool no_wall_skip = false;   // CUTRACE_NO_WALL_SKIP=1 when the handle was created: every launch carries zero room facts (scene_device.h)
+  bool no_dark_skip = false;   // CUTRACE_NO_DARK_SKIP=1 when the handle was created: every launch carries a zero dark-skip word (scene_device.h)
   bool no_opaque_build = false; // CUTRACE_NO_OPAQUE_BUILD=1 when the handle was created: no launch takes an opaque build (kernel_choice.h KO_*)
   struct RoomWords { float c[3], r, delta; uint32_t lights; } last_room{};  // the room facts of the most recent launch (ctr_debug_room_facts)
+  uint32_t last_dark_skip = 0;  // its dark-skip word (ctr_debug_dark_skip)
   // cached device outputs for the host-buffer form: ONE allocation of 7 floats per pixel, a call's buffers are its
   // consecutive parts [depth px | color 3 px | normal 3 px] so that a frame can leave in a single D2H transfer
   GrowBuf out{7 * sizeof(float)};

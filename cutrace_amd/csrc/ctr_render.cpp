@@ -182,6 +182,9 @@ void set_root_and_head(const ctr_scene *s, RenderLaunch &L, bool merged) {
   // the room facts only where the launch's kernel reads them (render_kernel.hip "room-safe lanes"): the one-mesh shape of the
   // any-hit builds, which then runs with the code that uses them, and the any-hit statistics builds; zero for every other launch
   if ((L.variant & KV_ANYHIT) && (ctr_launch_shape(L) == KS_ONE_MESH || (L.variant & KV_STATS))) fill_room_facts(s->flat, L.head, s->no_wall_skip);
+  // ... and the dark-skip word where the kernel reads it ("dark lights"): the opaque one-mesh builds, which leave the casts out,
+  // and the any-hit statistics builds, which count them
+  if ((L.variant & KV_ANYHIT) && (ctr_launch_opaque(L) == KO_OPAQUE || (L.variant & KV_STATS))) fill_dark_skip(s->flat, L.head, s->no_dark_skip);
 }
 
 // the launch's room facts as the handle keeps them for ctr_debug_room_facts (written under the handle's mutex, like last_kernel)
@@ -352,6 +355,7 @@ int render_device(ctr_scene *s, const RenderCall &c) {
     s->last_shape = ctr_launch_shape(L);
     s->last_opaque = ctr_launch_opaque(L);
     s->last_room = room_words(L);
+    s->last_dark_skip = (L.head.mesh_dark & CTR_HEAD_DARK) ? 1u : 0u;
   }
   return launched(ctr_launch_render(L, c.stream), "render kernel launch");
 }
@@ -393,6 +397,7 @@ int render_host(ctr_scene *s, const RenderCall &c) {
   s->last_shape = ctr_launch_shape(L);
   s->last_opaque = ctr_launch_opaque(L);
   s->last_room = room_words(L);
+  s->last_dark_skip = (L.head.mesh_dark & CTR_HEAD_DARK) ? 1u : 0u;
   if ((st = attach_order(s, L, big_mesh(s), c.count))) return st;
   HIP_TRY(hipMemsetAsync(s->d_counters.p, 0, 16 * sizeof(unsigned long long), nullptr));
   HIP_TRY(hipEventRecord(s->ev0, nullptr));

@@ -297,6 +297,7 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   s->no_scene_head = env_switch("CUTRACE_NO_SCENE_HEAD");    // every record by pointer
   s->no_shape_build = env_switch("CUTRACE_NO_SHAPE_BUILD");  // the general build of every launch
   s->no_wall_skip = env_switch("CUTRACE_NO_WALL_SKIP");      // no shadow trip skips its plane tests
+  s->no_dark_skip = env_switch("CUTRACE_NO_DARK_SKIP");      // no shadow cast is left out for a light that cannot change the pixel
   s->no_opaque_build = env_switch("CUTRACE_NO_OPAQUE_BUILD");  // the parent instantiation of every one-mesh launch
 
   if (int st = upload_scene(s, F)) {
@@ -425,6 +426,13 @@ int ctr_debug_room_facts(ctr_scene *s, float *out5, uint32_t *lights) {
   out5[3] = s->last_room.r;
   out5[4] = s->last_room.delta;
   *lights = s->last_room.lights;
+  return CTR_OK;
+}
+
+int ctr_debug_dark_skip(ctr_scene *s, uint32_t *word) {
+  if (!s || !word) return fail(CTR_E_INVALID, "ctr_debug_dark_skip: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  *word = s->last_dark_skip;
   return CTR_OK;
 }
 

@@ -108,6 +108,9 @@ __device__ unsigned int g_prof[128];  // executions of the CTR_MARK segments, su
 //        or a mesh's nearest valid t equalled min_t), [78] casts that went through the merged walk
 //   [88] any-hit shadow trips (trips with a live shadow lane, any-hit builds), [89] those that skipped their plane tests
 //        ("room-safe lanes" in the kernel)
+//   [90] (lane, light) pairs whose shadow cast cannot change the pixel ("dark lights" in the kernel; any-hit builds, launches whose
+//        scene head carries the dark-skip word), [91] shadow trips whose live lanes are all such, [92] mesh entries of trips with
+//        at least one such lane
 __device__ unsigned long long g_lane_stats[96];
 
 // ---- execution profile of the source's straight-line segments (scripts/dynamic_mix.py) ----
@@ -245,6 +248,24 @@ __device__ __forceinline__ V3 vnormalized_n(V3 a, float &n) {
   norm_and_inverse(a.x * a.x + a.y * a.y + a.z * a.z, n, inv);
   return vscale(a, inv);
 }
+// The two factors of a light's term (shading.hpp:86-93), each in ONE place: the light set-up tests them for zero before the
+// shadow cast ("dark lights") and the continuation shades with them after it, and both must run the same operations.
+//   fd = max(0, nn.nd)                          nn: normal.normalized(), nd: the shadow ray's direction
+//   fs = pow(max(0, nn.h), phong_exp)           h: the half vector of -incoming->dir.normalized() and nd
+// FAST: the half vector's normalisation with the 1-ulp v_rsq_f32 and exp2(e*log2(x)) on the f32 transcendental pipe (relative
+// error ~1e-6 wherever the result is not negligible; phong_exp == 0 -> 1); else IEEE sqrt + division and the f64 pow rounded
+// once (<= 1 ulp from glibc powf).  Both feed only the colour.
+__device__ __forceinline__ float light_fd(V3 nn_, V3 nd) { return smax(0.0f, vdot(nn_, nd)); }
+template <bool FAST>
+__device__ __forceinline__ float light_fs(V3 nn_, V3 in_dn_, V3 nd, const CADDR DMat &M) {
+  const V3 hsum = vadd(vscale(in_dn_, -1.0f), nd);
+  const V3 hv = FAST ? vscale(hsum, __builtin_amdgcn_rsqf(vdot(hsum, hsum))) : vnormalized(hsum);
+  const float sx = smax(0.0f, vdot(nn_, hv));
+  float fs;
+  if (FAST) fs = (M.phong_exp == 0.0f) ? 1.0f : __builtin_amdgcn_exp2f(M.phong_exp * __builtin_amdgcn_logf(sx));
+  else fs = (float)pow((double)sx, (double)M.phong_exp);
+  return fs;
+}
 // A suspended ray_color activation (shading.hpp:116-154) lives in LDS, never in scratch:
 //   hot  fields 0..3 : rgb so far (3), material index | stage << 30 (stage 1 = waiting for the
 //                      reflection child, 2 = for the pass-through child; the material record says
@@ -337,13 +358,17 @@ constexpr uint32_t MSP_SHADOW = 0x80000000u, MSP_DONE = 0x40000000u;
 // kept through `msp |= MSP_SHADOW` from light to light, gone wherever msp is rebuilt for the next radiance cast (stack depth
 // or MSP_DONE alone).  Below bit 30, so every test here stays the single compare it was.
 constexpr uint32_t MSP_ROOM = 0x20000000u;
+// Dark lights (the DARK builds; CTR_HEAD_DARK of the scene head, DESIGN.md "Dark lights"): bit 28 says that the light the lane's shadow ray
+// goes to cannot change the lane's pixel — set or cleared where the ray is made, so it lasts for that one light; it survives
+// `| MSP_SHADOW` and is gone, like MSP_ROOM, wherever msp is rebuilt.
+constexpr uint32_t MSP_DARK = 0x10000000u;
 #define MSP_ACTIVE(m) ((int)(m) < 0x40000000)          /* radiance or shadow */
 #define MSP_IS_SHADOW(m) ((int)(m) < 0)
 #define MSP_IS_RADIANCE(m) ((uint32_t)(m) < 0x40000000u)
 #define MSP_DEPTH(m) ((int)((m) & 0xFFFFu))
 enum { ACT_NONE = 0, ACT_LIGHT = 1, ACT_BOUNCE = 2, ACT_UNWIND = 3 };
 
-template <uint32_t KV, uint32_t SHAPE = KS_GENERAL, bool ROOM = false, uint32_t OPQ = KO_PARENT>
+template <uint32_t KV, uint32_t SHAPE = KS_GENERAL, bool ROOM = false, uint32_t OPQ = KO_PARENT, bool DARK = false>
 __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) void render_kernel(KArgs A, float *__restrict__ depth_out,
                                                             float *__restrict__ color_out,
                                                             float *__restrict__ normal_out,
@@ -400,6 +425,16 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
   constexpr bool OPAQUE = OPQ != KO_PARENT;
   static_assert(OPQ == KO_PARENT || OPQ == KO_OPAQUE, "opaque builds: kernel_choice.h");
   static_assert(!OPAQUE || (ANYHIT && ONE_MESH), "the opaque builds are any-hit one-mesh builds");
+  // "Dark lights" (MSP_DARK above; DESIGN.md "Dark lights"): in an any-hit build a shadow cast only decides whether the light's
+  // term  fd*ld + fs*ls  is added to `fin` or not.  Where fd and fs are both zero, every colour of the scene is finite and
+  // bounded (CTR_HEAD_DARK of the scene head) and no channel of `fin` is -0, adding the term — a signed zero per channel — leaves
+  // `fin` bit for bit, so the cast cannot be observed: the lane sits the trip out (it is still counted as a cast), and a trip whose
+  // lanes all do goes straight to the continuation.  The code exists only in the instantiations launched for it — DARK: an opaque
+  // build whose scene head carries the fact (ctr_launch_render picks <KV, KS_ONE_MESH, ROOM, KO_OPAQUE, true> then) — and, counting
+  // only, no lane retired, in the any-hit statistics builds, which read the fact from the head.  Every other instantiation is,
+  // instruction for instruction, what it was without it: a launch without the fact pays nothing.
+  static_assert(!DARK || OPAQUE, "dark lights: the opaque builds");
+  constexpr bool DARK_CODE = DARK || (ANYHIT && STATS);
   // wave-level work counters (STATS build only): [0] casts, [1] BVH nodes visited, [2] triangle
   // prefilters, [3] exact tests, [4] mesh entries (AABB ballot != 0), [5] sum of active lanes per cast,
   // and how many of the 64 lanes had a use for the wave-level work: [6] lanes whose ray meets one of the
@@ -650,12 +685,18 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
     // lanes still searching (any-hit mode retires occluded lanes), as a lane MASK: a per-lane bool that crosses blocks
     // is kept as a mask by the compiler anyway, and every BALLOT of it costs two vector instructions to get it back
     mask_t alive_m = active_m;
+    // "dark lights": a dark lane needs no cast; a trip without any other lane skips set-up, planes and mesh in one go
+    mask_t dark_m = 0ull;
+    if constexpr (DARK_CODE) dark_m = BALLOT((msp & MSP_DARK) != 0u);
+    if constexpr (DARK) alive_m &= ~dark_m;
+    const bool all_dark = DARK && alive_m == 0ull;  // wave-uniform
+    if (DARK_CODE && STATS && shadow_m != 0ull && (active_m & ~dark_m) == 0ull && lane == 0) atomicAdd(&g_lane_stats[91], 1ull);
     V3 rinv = mk(0, 0, 0);     // exact 1/dir (IEEE divisions), computed lazily: see the mesh branch
     bool have_rinv = false;    // wave-uniform
     V3 ria = mk(0, 0, 0);
     float ria_big = 0.f;
     float cmax = 0.f;
-    if (k_has_mesh) {
+    if (k_has_mesh && !all_dark) {
       CTR_MARK(2);
       // 1-ulp reciprocals, clamped to +-1e30: an axis-parallel ray (d = 0 -> inf) then gives huge
       // FINITE slab distances with the right signs instead of inf - inf = NaN
@@ -687,6 +728,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         atomicAdd(&g_lane_stats[89], skip_planes ? 1ull : 0ull);  // (no branch on the flag under the lane's: the compiler would thread it past the join)
       }
     }
+    if constexpr (DARK) skip_planes = skip_planes || all_dark;
     // ---- planes: plane::intersect, default_schema.hpp:189-201, all in lane masks ----
     if (!skip_planes) {
       mask_t live_m = alive_m;
@@ -1114,6 +1156,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
           const uint32_t beg = o_tri_begin, cnt = o_tri_count;
           if (COUNT) n_aabb_tris += INVB(bb_m) ? (unsigned long long)cnt : 0ull;
           if (STATS) st[4]++;
+          if (DARK_CODE && STATS && dark_m != 0ull && lane == 0) atomicAdd(&g_lane_stats[92], 1ull);
           uint32_t pl_nodes = 0, pl_tris = 0;  // STATS: this lane's own share of the mesh entry's node visits / triangle tests
           // ---- mesh::intersect, default_schema.hpp:125-144: smallest valid t, FIRST triangle in
           //      file order on ties (strict < over file order)  ==  lexicographic min of (t, orig) ----
@@ -1754,7 +1797,9 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
       { const CADDR DLight &L1 = k_lights[li + 1u]; nl_type = L1.type; nl_v = mk(L1.vx, L1.vy, L1.vz); }
       bool done_shadow;
       float shadow_fac = 0.f;
-      if (was_hit && best < light_dist) {
+      // (a dark lane made no cast: it takes the occluded side, which adds nothing — as the lit side would, bit for bit)
+      const bool dark_lane = DARK && (msp & MSP_DARK) != 0u;
+      if ((was_hit && best < light_dist) || dark_lane) {
         // scenes without any transparency (the any-hit builds) need no material lookup here
         const float trans = ANYHIT ? 0.0f : k_mats[k_objs[bobj].mat].transparency;
         if (!ANYHIT) intensity += (1.0f - trans);
@@ -1778,20 +1823,25 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
           const V3 color = mk(Lg.cx, Lg.cy, Lg.cz);
           const V3 nd = rd;  // the shadow ray's direction IS the normalized direction to the light
           const V3 nn_ = get_nn();
-          const float fd = smax(0.0f, vdot(nn_, nd));
+          float fd, fs;
           const V3 ld = vmul(diffuse, color);
-          const V3 hsum = vadd(vscale(get_in_dn(), -1.0f), nd);
-          // the half vector feeds only the specular colour term: with the fast specular path its
-          // normalisation uses the 1-ulp v_rsq_f32 instead of IEEE sqrt + division
-          const V3 hv = FASTPOW ? vscale(hsum, __builtin_amdgcn_rsqf(vdot(hsum, hsum))) : vnormalized(hsum);
-          const float sx = smax(0.0f, vdot(nn_, hv));
-          float fs;
-          if (FASTPOW) {
-            // exp2(e*log2(x)) on the f32 transcendental pipe: relative error ~1e-6 wherever the
-            // result is not negligible; feeds only the specular colour term (<= 1e-6 absolute)
-            fs = (M.phong_exp == 0.0f) ? 1.0f : __builtin_amdgcn_exp2f(M.phong_exp * __builtin_amdgcn_logf(sx));
+          if constexpr (DARK_CODE) {
+            // the factors the light's set-up tested, by the same functions from the same rd (fd is made again, not kept: a
+            // register through the whole cast would take the 6-wave host-delivery build from 79 to 81 VGPRs, and to 5 waves)
+            fd = light_fd(nn_, nd);
+            fs = light_fs<FASTPOW>(nn_, get_in_dn(), nd, M);
           } else {
-            fs = (float)pow((double)sx, (double)M.phong_exp);  // f64, rounded once: <= 1 ulp from glibc powf
+            // (every other build: light_fd and light_fs written out, as they were — inlined from the functions the compiler
+            //  orders this segment's loads differently, and these builds are to stay what they were instruction for instruction)
+            fd = smax(0.0f, vdot(nn_, nd));
+            const V3 hsum = vadd(vscale(get_in_dn(), -1.0f), nd);
+            const V3 hv = FASTPOW ? vscale(hsum, __builtin_amdgcn_rsqf(vdot(hsum, hsum))) : vnormalized(hsum);
+            const float sx = smax(0.0f, vdot(nn_, hv));
+            if (FASTPOW) {
+              fs = (M.phong_exp == 0.0f) ? 1.0f : __builtin_amdgcn_exp2f(M.phong_exp * __builtin_amdgcn_logf(sx));
+            } else {
+              fs = (float)pow((double)sx, (double)M.phong_exp);  // f64, rounded once: <= 1 ulp from glibc powf
+            }
           }
           const V3 ls = vmul(specular, color);
           fin = vadd(fin, vscale(vadd(vscale(ld, fd), vscale(ls, fs)), 1 - shadow_fac));
@@ -1829,7 +1879,41 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
         light_dist = distance * dir_norm;
         intensity = 0.0f;
         min_t = (float)(0.0 + 1e-3);  // last_hit = 0
-        msp |= MSP_SHADOW;
+        if constexpr (DARK_CODE) {
+          // "dark lights": is this light's term a signed zero that `fin` does not notice?  fd for every lane; fs and the guard on
+          // `fin` only in a wave that has a lane with fd zero, for those lanes.  The bit lasts for one light: it is set or cleared
+          // here, together with MSP_SHADOW.  A DARK build is launched only with the fact; the statistics builds read it (through a
+          // pointer of its own, so that the load stays here).
+          // (msp is written ONCE, after the test: written before it and or-ed into afterwards, the 6-wave host-delivery build
+          //  takes 81 VGPRs instead of 79 and loses its sixth wave)
+          uint32_t hd_dark = 1u;
+          if constexpr (!DARK) {
+            const CADDR KArgs *AD = AK;
+            asm volatile("" : "+s"(AD));
+            hd_dark = AD->head.mesh_dark & CTR_HEAD_DARK;
+          }
+          bool dark = false;
+          if (hd_dark != 0u) {
+            CTR_MARK(121);
+            const V3 nn_ = get_nn();
+            const bool fd_zero = (__float_as_uint(light_fd(nn_, rd)) & 0x7FFFFFFFu) == 0u;  // +0 or -0 as bits: a denormal is not zero
+            if (BALLOT(fd_zero) != 0ull) {
+              CTR_MARK(122);
+              if (fd_zero) {
+                const float fs = light_fs<FASTPOW>(nn_, get_in_dn(), rd, k_mats[mat_i]);
+                dark = (__float_as_uint(fs) & 0x7FFFFFFFu) == 0u && __float_as_uint(fin.x) != 0x80000000u &&
+                       __float_as_uint(fin.y) != 0x80000000u && __float_as_uint(fin.z) != 0x80000000u;
+              }
+              if (STATS) {
+                const mask_t dk_m = BALLOT(dark);
+                if (dk_m != 0ull && lane_now() == (uint32_t)__builtin_ctzll(dk_m)) atomicAdd(&g_lane_stats[90], (unsigned long long)__builtin_popcountll(dk_m));
+              }
+            }
+          }
+          msp = (msp & ~MSP_DARK) | MSP_SHADOW | (dark ? MSP_DARK : 0u);
+        } else {
+          msp |= MSP_SHADOW;
+        }
       } else {
         act = ACT_BOUNCE;  // phong returned `fin`
       }
@@ -2092,7 +2176,7 @@ __global__ __launch_bounds__(WG_THREADS, (KV & KV_OCC6) ? 6 : CTR_MIN_WAVES_EU) 
 // next order (tile_order.hip).
 // the scene head of the launch carries the record of the top-level walk's first leaf: the walk starts there without `meshes`
 bool launch_head_mesh(const RenderLaunch &L) {
-  return L.head.n_mesh == 1u && (L.scene.tlas_root & BVH_LEAF_FLAG) && L.scene.n_mesh != 0u;
+  return (L.head.mesh_dark & CTR_HEAD_MESH) != 0u && (L.scene.tlas_root & BVH_LEAF_FLAG) && L.scene.n_mesh != 0u;
 }
 
 int launch(const RenderLaunch &L, uint32_t kv, const void *kernel, hipStream_t stream) {
@@ -2275,9 +2359,11 @@ int ctr_launch_render(const RenderLaunch &L, void *stream) {
     // ... and, where the scene head carries room facts, with the code that uses them ("room-safe lanes"); and as the opaque
     // build the launch qualifies for ("opaque build")
     const bool room = L.head.room_lights != 0u;
+    // ... and, an opaque build whose scene head carries the dark-skip fact, with the code that leaves those casts out ("dark lights")
+    const bool dark = opq == KO_OPAQUE && (L.head.mesh_dark & CTR_HEAD_DARK) != 0u;
     switch (L.variant) {
-#define Y(kv, o) (room ? (const void *)render_kernel<(kv), KS_ONE_MESH, true, o> : (const void *)render_kernel<(kv), KS_ONE_MESH, false, o>)
-#define X(kv) case (kv): kernel = opq == KO_OPAQUE ? Y(kv, KO_OPAQUE) : Y(kv, KO_PARENT); break;
+#define Y(kv, o, d) (room ? (const void *)render_kernel<(kv), KS_ONE_MESH, true, o, d> : (const void *)render_kernel<(kv), KS_ONE_MESH, false, o, d>)
+#define X(kv) case (kv): kernel = opq == KO_OPAQUE ? (dark ? Y(kv, KO_OPAQUE, true) : Y(kv, KO_OPAQUE, false)) : Y(kv, KO_PARENT, false); break;
       CTR_SHAPE_KERNELS(X)
 #undef X
 #undef Y

@@ -153,7 +153,12 @@ struct alignas(64) DSceneHead {
   uint32_t ax_index[6];        // planes[0].index[0..1], planes[1].index[0..1], planes[2].index[0..1]
   uint32_t ax_transparent[6];  // the same of .transparent (KV_IGNTR only)
   uint32_t n_axis_recs;        // plane records the triple stands for: 3, or 0 = not filled
-  uint32_t n_mesh;             // 1: `mesh` is meshes[tlas_root & 0xFFFFFF], 0 = not filled
+  // one word, two facts (the head has no dword to spare, and a fourth line would move every kernel argument behind it):
+  //   CTR_HEAD_MESH  `mesh` is meshes[tlas_root & 0xFFFFFF] (clear: not filled)
+  //   CTR_HEAD_DARK  the dark-skip fact of the launch (scene_flatten.h fill_dark_skip; DESIGN.md "Dark lights"): every colour of
+  //                  the scene is finite and bounded and no material transmits, so a shadow cast to a light whose diffuse and
+  //                  specular factors are both zero cannot change the pixel; the launch then takes the builds that leave it out
+  uint32_t mesh_dark;
   // The room facts of the launch (scene_flatten.h room_facts; DESIGN.md "Shadow casts from inside a plane room"): all zero, or
   // what makes the lemma true that lets an any-hit shadow trip skip its plane tests.  A lane whose origin o has
   // |o - room_c|inf <= room_r and (p - o).n <= room_delta for every filled slot of the triple casts a shadow ray that no
@@ -163,8 +168,10 @@ struct alignas(64) DSceneHead {
   uint32_t room_lights;        // bit i: lights[i], a point light, qualifies (i < 32)
   DObj mesh;
 };
-static_assert(sizeof(DSceneHead) == 192 && offsetof(DSceneHead, mesh) == 128 && offsetof(DSceneHead, room_c) == 104,
+static_assert(sizeof(DSceneHead) == 192 && offsetof(DSceneHead, mesh) == 128 && offsetof(DSceneHead, room_c) == 104 && offsetof(DSceneHead, mesh_dark) == 100,
               "DSceneHead: two 64-byte lines of planes, one of mesh");
+#define CTR_HEAD_MESH 1u
+#define CTR_HEAD_DARK 0x10000u
 #define CTR_TL_HEAD_FLAG 0x40000000u  /* kernel-side only: the top-level leaf whose record is DSceneHead::mesh */
 
 // The scene on the device, ONCE: the ten arrays of ctr_scene_create's upload, owned by the handle (ctr_internal.h ctr_scene::dev),

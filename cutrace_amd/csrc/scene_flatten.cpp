@@ -310,6 +310,9 @@ void shading_flags(FlatScene &F) {
     worst = std::max(worst, std::fabs((double)m.phong_exp * (double)m.specular) * largest(m.cx, m.cy, m.cz));
   }
   F.fast_pow_ok = fast_pow_in_bar(worst, lambda);
+  const uint32_t facts = shade_facts(F.mats.data(), F.mats.size(), F.lights.data(), F.lights.size());
+  F.shade_finite = (facts & 1u) != 0u;
+  F.shade_bounded = (facts & 2u) != 0u;
 }
 
 }  // namespace
@@ -914,7 +917,7 @@ void fill_scene_head(const FlatScene &F, uint32_t tlas_root, DSceneHead &H) {
   const uint32_t leaf = tlas_root & 0xFFFFFFu;
   if (F.n_mesh != 0u && (tlas_root & BVH_LEAF_FLAG) && leaf < F.meshes.size()) {
     H.mesh = F.meshes[leaf];
-    H.n_mesh = 1u;
+    H.mesh_dark |= CTR_HEAD_MESH;
   }
 }
 
@@ -990,6 +993,22 @@ void room_facts(DSceneHead &H, const DLight *lights, size_t n_light, const RoomT
   H.room_r = r;
   H.room_delta = delta;
   H.room_lights = mask;
+}
+
+uint32_t shade_facts(const DMat *mats, size_t n_mat, const DLight *lights, size_t n_light) {
+  bool finite = true, bounded = true;
+  auto look = [&](float v) {
+    if (!std::isfinite(v)) finite = false;
+    if (!(std::fabs(v) <= CTR_SHADE_BOUND)) bounded = false;  // (a NaN is not bounded either)
+  };
+  for (size_t i = 0; i < n_mat; i++) { look(mats[i].cx); look(mats[i].cy); look(mats[i].cz); look(mats[i].specular); }
+  for (size_t i = 0; i < n_light; i++) { look(lights[i].cx); look(lights[i].cy); look(lights[i].cz); }
+  return (finite ? 1u : 0u) | (bounded ? 2u : 0u);
+}
+
+void fill_dark_skip(const FlatScene &F, DSceneHead &H, bool switched_off) {
+  const bool holds = !switched_off && F.shade_finite && F.shade_bounded && F.all_opaque;
+  H.mesh_dark = (H.mesh_dark & ~CTR_HEAD_DARK) | (holds ? CTR_HEAD_DARK : 0u);
 }
 
 void fill_room_facts(const FlatScene &F, DSceneHead &H, bool switched_off) {

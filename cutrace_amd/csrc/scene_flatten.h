@@ -91,6 +91,10 @@ struct FlatScene {
   // x^e has condition number e, so its error is CTR_FAST_POW_KAPPA * e per unit of specular colour and light colour
   // (fast_pow_in_bar below; DESIGN.md "Shading parameters the kernels are pinned over")
   bool fast_pow_ok = true;
+  // what lets a render skip the shadow casts of lights that cannot change a pixel (shade_facts below; DESIGN.md "Dark lights"):
+  // shade_finite: every material's colour and `specular` and every light's colour is finite; shade_bounded: none of them exceeds
+  // CTR_SHADE_BOUND in magnitude, so no product colour * specular * light colour overflows
+  bool shade_finite = true, shade_bounded = true;
   uint64_t mesh_tris = 0;   // triangles in meshes
   size_t mesh_bytes = 0;    // triangles + BVH nodes
   std::vector<MeshGuard> guards;  // one per mesh object, scene order
@@ -283,8 +287,16 @@ void room_facts(DSceneHead &H, const DLight *lights, size_t n_light, const RoomT
 // ... of a launch of an any-hit build: zero unless the head's triple holds ALL of the scene's planes (three plane records, all
 // of them the axis triple), no material is transparent and the handle's switch is not set
 void fill_room_facts(const FlatScene &F, DSceneHead &H, bool switched_off);
+// The two scene facts behind the dark-light skip (FlatScene::shade_finite, shade_bounded), from the records alone: with both, a
+// light term whose factors fd and fs are zero is a signed zero in every channel — a zero times a FINITE product of colours; a
+// product that overflowed would make it NaN.  bit 0: shade_finite, bit 1: shade_bounded.
+#define CTR_SHADE_BOUND 0x1p40f  /* three factors: 2^120 < FLT_MAX */
+uint32_t shade_facts(const DMat *mats, size_t n_mat, const DLight *lights, size_t n_light);
+// The dark-skip fact of a launch's scene head (scene_device.h CTR_HEAD_DARK in DSceneHead::mesh_dark): set when both facts hold, no
+// material transmits and the handle's switch is not set, else clear
+void fill_dark_skip(const FlatScene &F, DSceneHead &H, bool switched_off);
 // A switch of the environment that a handle reads when it is created (A/B runs and tests), NAME=<an integer other than 0>:
-// CUTRACE_NO_SCENE_HEAD, CUTRACE_NO_SHAPE_BUILD, and CUTRACE_NO_WALL_SKIP (that handle's launches carry zero room facts)
+// CUTRACE_NO_SCENE_HEAD, CUTRACE_NO_SHAPE_BUILD, CUTRACE_NO_WALL_SKIP (that handle's launches carry zero room facts) and CUTRACE_NO_DARK_SKIP (... a zero dark-skip word)
 bool env_switch(const char *name);
 
 // a node whose four slots are empty: a far-away point box and a leaf of no triangles each

@@ -339,6 +339,15 @@ int ctr_debug_last_opaque(ctr_scene *scene, uint32_t *opaque);
  * CUTRACE_NO_WALL_SKIP=1 in the environment when a handle is created keeps the words of that handle's launches zero (A/B timing,
  * tests).  In CTR_VAR_STATS launches ctr_debug_lane_stats counts the any-hit shadow trips in [88] and those that skipped in [89]. */
 int ctr_debug_room_facts(ctr_scene *scene, float *out5, uint32_t *lights);
+/* Diagnostic: the dark-skip word of that launch (csrc/scene_device.h CTR_HEAD_DARK; DESIGN.md "Dark lights").  Non-zero
+ * only for a launch whose kernel reads it — an opaque build (ctr_debug_last_opaque 1), or CTR_VAR_STATS on a scene without
+ * transparent material — of a scene whose material colours, `specular` factors and light colours are all finite and at most
+ * 2^40 in magnitude: a shadow cast to a light whose diffuse and specular factors are both zero at the hit cannot change the
+ * pixel, and the opaque builds leave it out — the same results and ray counts bit for bit.  CUTRACE_NO_DARK_SKIP=1 in the
+ * environment when a handle is created keeps the word of that handle's launches zero (A/B timing, tests).  In CTR_VAR_STATS
+ * launches ctr_debug_lane_stats counts such (lane, light) pairs in [90], the shadow trips whose live lanes are all such in [91]
+ * and the mesh entries of shadow trips with at least one such lane in [92]. */
+int ctr_debug_dark_skip(ctr_scene *scene, uint32_t *word);
 /* Diagnostic: what each 8x8 tile of the last launch cost (shader-clock ticks / 64; tile index = frame-major,
  * then row-major over the launch's tile grid).  n_tiles receives the count; out may be NULL. */
 int ctr_tile_costs(ctr_scene *scene, uint32_t *out, uint64_t capacity, uint64_t *n_tiles);
