@@ -50,6 +50,23 @@ HITS_MAX = 65535
 NEAREST_LINEAR = 1
 NEAREST_SKIP_PLANES = 2
 NEAREST_OUTPUTS = ("distance", "object", "prim", "point", "normal")
+# ctr_count_crossings and ctr_inside_points flags, outputs and largest n_dirs (include/cutrace_inside.h)
+CROSS_LINEAR = 1
+CROSS_SKIP_PLANES = 2
+CROSS_SKIP_TRIANGLES = 4
+CROSS_OUTPUTS = ("count", "signed")
+INSIDE_LINEAR = 1
+INSIDE_OUTPUTS = ("inside", "votes")
+INSIDE_MAX_DIRS = 15
+
+
+def inside_default_dirs():
+    """the library's default directions of inside(): (3, 3) float32 (ctr_inside_default_dirs)"""
+    out = (C.c_float * 9)()
+    _lib.hip_lib().ctr_inside_default_dirs(out)
+    return np.array(out, np.float32).reshape(3, 3)
+
+
 # the display planes of render_images / quantise (include/cutrace_images.h)
 IMAGE_PLANES = ("color", "depth", "normal")
 
@@ -677,6 +694,106 @@ class DeviceScene:
                     setattr(q, {"point": "d_nearest"}.get(k, "d_" + k), v.data_ptr())
                 _check("ctr_nearest_points", _lib.hip_lib().ctr_nearest_points(self._h, C.byref(q), raw))
         return out
+
+    # ---- inside queries (ctr_count_crossings, ctr_inside_points, include/cutrace_inside.h) ----
+    @staticmethod
+    def _object_arg(object):
+        """None or an object index >= 0, as the C-ABI's -1 or index"""
+        if object is not None and (isinstance(object, bool) or not isinstance(object, (int, np.integer))):
+            raise TypeError(f"object: expected None or an int, got {type(object).__name__}")
+        if object is not None and object < 0:
+            raise ValueError(f"object: None or an index >= 0, got {object}")
+        return -1 if object is None else int(object)
+
+    def count_crossings(self, origins, dirs, min_t=0.0, max_t=float("inf"), object=None, skip_planes=False, skip_triangles=False,
+                        linear=False, outputs=("count",), stream=None):
+        """How many surfaces every ray (origins[k], dirs[k]) crosses over the OPEN interval (min_t, max_t): a dict of (n,) int32
+        tensors on the scene's device, `count` and / or `signed` as `outputs` names them.  Every triangle the reference's test
+        accepts there counts 1, every root of a sphere 1, a plane 1; `signed` weights a crossing +1 where the ray leaves through
+        a face whose normal points along it (a sphere's far root, a plane with dir . normal > 0), -1 otherwise: for a closed,
+        outward-oriented mesh and an origin off the surface it is the winding number, and the parity of `count` is containment.
+        The reference's triangle test is inclusive on edges, so ONE ray through an edge or a vertex is not a parity oracle:
+        inside() votes.  min_t, max_t: a scalar or (n,) float32, in the reference's mixed units (a sphere measures along
+        dir/|dir|).  object: only this object index.  skip_planes, skip_triangles: planes / stand-alone triangles are not
+        counted.  linear=True: no tree — the same integers.  A ray with a non-finite origin or a NaN, infinite or zero direction
+        counts 0.  Asynchronous on `stream` (default: torch's current stream of the scene's device)."""
+        import torch
+        outputs = _subset("outputs", outputs, CROSS_OUTPUTS, unique=True)
+        dev = self._torch_device()
+        with _on_stream(dev, stream) as raw:
+            o, d, n = _ray_pair(origins, dirs, dev)
+            q = _lib.CrossingQuery()
+            q.n_rays, q.object = n, self._object_arg(object)
+            q.flags = (CROSS_LINEAR if linear else 0) | (CROSS_SKIP_PLANES if skip_planes else 0) | (CROSS_SKIP_TRIANGLES if skip_triangles else 0)
+            q.min_t, mn = self._per_ray(min_t, n, "min_t")
+            q.max_t, mx = self._per_ray(max_t, n, "max_t")
+            out = {k: torch.empty(n, dtype=torch.int32, device=dev) for k in outputs}
+            if n:
+                q.d_origin, q.d_dir = o.data_ptr(), d.data_ptr()
+                q.d_min_t = mn.data_ptr() if mn is not None else None
+                q.d_max_t = mx.data_ptr() if mx is not None else None
+                for k, v in out.items():
+                    setattr(q, "d_" + k, v.data_ptr())
+                _check("ctr_count_crossings", _lib.hip_lib().ctr_count_crossings(self._h, C.byref(q), raw))
+        return out
+
+    @staticmethod
+    def _dirs_arg(q, dirs):
+        """Fill the query's direction table from `dirs` ((R, 3) floats, R odd, 1 .. 15; None: the default table); returns what
+        must stay alive until the call has returned."""
+        if dirs is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(dirs.cpu() if hasattr(dirs, "cpu") else dirs), np.float32)
+        if a.ndim != 2 or a.shape[1] != 3 or not 1 <= a.shape[0] <= INSIDE_MAX_DIRS or a.shape[0] % 2 == 0:
+            raise ValueError(f"dirs: expected (R, 3) with R odd, 1 .. {INSIDE_MAX_DIRS}, got shape {a.shape}")
+        q.n_dirs, q.dirs = a.shape[0], a.ctypes.data_as(C.POINTER(C.c_float))
+        return a
+
+    def _inside(self, p, object, dirs, linear, out, distance, raw):
+        """ctr_inside_points of the points `p` (on the device, contiguous) into the tensors of `out` and, in place, `distance`"""
+        q = _lib.InsideQuery()
+        q.n_points, q.object, q.flags = p.shape[0], self._object_arg(object), (INSIDE_LINEAR if linear else 0)
+        keep = self._dirs_arg(q, dirs)   # (alive until the call has returned: the library copies the table)
+        if p.shape[0]:
+            q.d_point = p.data_ptr()
+            for k, v in out.items():
+                setattr(q, "d_" + k, v.data_ptr())
+            if distance is not None:
+                q.d_distance = distance.data_ptr()
+            _check("ctr_inside_points", _lib.hip_lib().ctr_inside_points(self._h, C.byref(q), raw))
+        del keep
+
+    def inside(self, points, object=None, dirs=None, linear=False, outputs=("inside",), stream=None):
+        """Whether every point of `points` ((n, 3) float32) lies inside a body of the scene: a dict of (n,) tensors on the scene's
+        device, `inside` (bool) and / or `votes` (uint8) as `outputs` names them.  R rays leave every point, over (0, +inf),
+        counting meshes and spheres only (count_crossings' terms); `votes` is the number of rays with an odd count and a point is
+        inside when that is more than half of R.  dirs: (R, 3), R odd, 1 .. 15 (None: the library's three default directions,
+        inside_default_dirs()).  object: only this mesh or sphere (a plane or a stand-alone triangle raises).  Asking for `votes`
+        casts all R rays of every point; without it a wave stops once all its points are decided.  A point with a NaN or an
+        infinity in it is outside with 0 votes.  Asynchronous on `stream`."""
+        import torch
+        outputs = _subset("outputs", outputs, INSIDE_OUTPUTS, unique=True)
+        dev = self._torch_device()
+        with _on_stream(dev, stream) as raw:
+            p = _array_check(points, "points", dev, "float32", 3).to(dev, non_blocking=False).contiguous()
+            out = {k: torch.empty(p.shape[0], dtype=torch.uint8, device=dev) for k in outputs}
+            self._inside(p, object, dirs, linear, out, None, raw)
+            if "inside" in out:
+                out["inside"] = out["inside"].view(torch.bool)   # the kernel writes 0 or 1
+        return out
+
+    def signed_distance(self, points, object=None, max_dist=float("inf"), dirs=None, linear=False, stream=None):
+        """The distance of every point of `points` ((n, 3) float32) to the nearest mesh, sphere or stand-alone triangle, negative
+        inside a body: (n,) float32 on the scene's device.  nearest_points' distance (skip_planes=True, the same `object`)
+        with inside()'s sign, two launches on one stream.  A point farther than max_dist from everything keeps +inf, whatever
+        its side.  object: only this mesh or sphere.  dirs, linear: as inside()."""
+        dev = self._torch_device()
+        with _on_stream(dev, stream) as raw:
+            p = _array_check(points, "points", dev, "float32", 3).to(dev, non_blocking=False).contiguous()
+            dist = self.nearest_points(p, max_dist=max_dist, object=object, skip_planes=True, linear=linear, outputs=("distance",),
+                                       stream=stream)["distance"]
+            self._inside(p, object, dirs, linear, {}, dist, raw)
+        return dist
 
     def shade_rays(self, origins, dirs, bounces=5, min_t=1e-3, ambient=None, exact_pow=False, linear=False, outputs=None,
                    stream=None):

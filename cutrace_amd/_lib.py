@@ -125,6 +125,20 @@ class NearestQuery(C.Structure):
                 ("d_prim", C.c_void_p), ("d_nearest", C.c_void_p), ("d_normal", C.c_void_p)]
 
 
+class CrossingQuery(C.Structure):
+    """ctr_crossing_query (include/cutrace_inside.h)"""
+    _fields_ = [("n_rays", C.c_uint64), ("flags", C.c_uint32), ("object", C.c_int32), ("min_t", C.c_float), ("max_t", C.c_float),
+                ("d_origin", C.c_void_p), ("d_dir", C.c_void_p), ("d_min_t", C.c_void_p), ("d_max_t", C.c_void_p),
+                ("d_count", C.c_void_p), ("d_signed", C.c_void_p)]
+
+
+class InsideQuery(C.Structure):
+    """ctr_inside_query (include/cutrace_inside.h)"""
+    _fields_ = [("n_points", C.c_uint64), ("flags", C.c_uint32), ("object", C.c_int32), ("n_dirs", C.c_uint32), ("reserved", C.c_uint32),
+                ("dirs", C.POINTER(C.c_float)), ("d_point", C.c_void_p), ("d_inside", C.c_void_p), ("d_votes", C.c_void_p),
+                ("d_distance", C.c_void_p)]
+
+
 class Lens(C.Structure):
     """ctr_lens (include/cutrace_lens.h)"""
     _fields_ = [("n_rays", C.c_uint64), ("samples", C.c_uint32), ("ambient", C.c_float), ("d_origin", C.c_void_p),
@@ -262,6 +276,11 @@ HIP_LATER_PROTOS = {
     "cutrace_nearest.h": {
         "ctr_nearest_points": ([_ptr, _P(NearestQuery), _ptr], _int),
     },
+    "cutrace_inside.h": {
+        "ctr_count_crossings": ([_ptr, _P(CrossingQuery), _ptr], _int),
+        "ctr_inside_points": ([_ptr, _P(InsideQuery), _ptr], _int),
+        "ctr_inside_default_dirs": ([_f32p], None),
+    },
 }
 
 # the symbols each header declares (the tests compare them with the headers)
@@ -282,6 +301,7 @@ TOPOLOGY_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_topology.h"])
 ADD_HOST = 1       # CTR_ADD_HOST
 HITS_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_hits.h"])
 NEAREST_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_nearest.h"])
+INSIDE_SYMBOLS = list(HIP_LATER_PROTOS["cutrace_inside.h"])
 
 _host = None
 _hip = None

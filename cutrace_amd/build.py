@@ -2,7 +2,7 @@
 
   libcutrace_host.so   g++    host side: JSON loader, STL reader, image writers
   libcutrace_amd.so    hipcc  gfx950 render, ray-query, surface-shading and display-quantise kernels + the C-ABI of include/cutrace_amd.h (csrc/ctr_scene.cpp,
-                              csrc/ctr_render.cpp, csrc/ctr_multi.hip), cutrace_rays.h + cutrace_hits.h + cutrace_nearest.h (csrc/ctr_rays.cpp, csrc/ray_hits.hip, csrc/ray_nearest.hip) and cutrace_update.h (csrc/ctr_update.cpp,
+                              csrc/ctr_render.cpp, csrc/ctr_multi.hip), cutrace_rays.h + cutrace_hits.h + cutrace_nearest.h + cutrace_inside.h (csrc/ctr_rays.cpp, csrc/ray_hits.hip, csrc/ray_nearest.hip, csrc/ray_cross.hip) and cutrace_update.h (csrc/ctr_update.cpp,
                               csrc/mesh_update.hip), cutrace_rebuild.h + cutrace_replace.h (csrc/ctr_update.cpp, csrc/mesh_build.hip), cutrace_topology.h (csrc/ctr_topology.cpp, csrc/ctr_update.cpp) and cutrace_edit.h + cutrace_objects.h (csrc/ctr_edit.cpp, csrc/guard_scan.hip); what they share: csrc/ctr_internal.h
   cutrace              hipcc  the drop-in CLI (`cutrace <scene.json>`, reference main.cu)
 
@@ -28,7 +28,7 @@ HOST_SRCS = [os.path.join(HOST, "scene_host.cpp"), os.path.join(HOST, "images.cp
 HIP_SRCS = [os.path.join(CSRC, f) for f in (
     "render_kernel.hip", "ctr_scene.cpp", "ctr_render.cpp", "bvh.cpp", "ctr_multi.hip", "ray_query.hip", "scene_flatten.cpp", "guard.cpp",
     "ray_shade.hip", "ctr_rays.cpp", "kernel_choice.cpp", "frame_images.hip", "tile_order.hip", "tile_order_host.cpp", "ray_points.hip",
-    "mesh_update.hip", "ctr_update.cpp", "guard_scan.hip", "ctr_edit.cpp", "mesh_build.hip", "ctr_topology.cpp", "ray_hits.hip", "ray_nearest.hip")]
+    "mesh_update.hip", "ctr_update.cpp", "guard_scan.hip", "ctr_edit.cpp", "mesh_build.hip", "ctr_topology.cpp", "ray_hits.hip", "ray_nearest.hip", "ray_cross.hip")]
 CLI_SRCS = [os.path.join(HOST, "main.cpp")]
 
 HOST_FLAGS = ["-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-pthread", "-Wall", "-I" + INC]

@@ -1,6 +1,7 @@
-// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h, include/cutrace_hits.h and include/cutrace_nearest.h: ctr_cast_rays,
-// ctr_shade_rays, ctr_shade_points, ctr_list_hits and ctr_nearest_points check a query, describe the uploaded scene to the kernel
-// (RayScene, ray_query.h) and launch it (ray_query.hip, ray_shade.hip, ray_points.hip, ray_hits.hip, ray_nearest.hip).
+// ctr_rays.cpp — the C-ABI of include/cutrace_rays.h, include/cutrace_hits.h, include/cutrace_nearest.h and include/cutrace_inside.h:
+// ctr_cast_rays, ctr_shade_rays, ctr_shade_points, ctr_list_hits, ctr_nearest_points, ctr_count_crossings and ctr_inside_points check a
+// query, describe the uploaded scene to the kernel (RayScene, ray_query.h) and launch it (ray_query.hip, ray_shade.hip, ray_points.hip,
+// ray_hits.hip, ray_nearest.hip, ray_cross.hip).
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -8,8 +9,10 @@
 
 #include "ctr_internal.h"
 #include "cutrace_hits.h"
+#include "cutrace_inside.h"
 #include "cutrace_nearest.h"
 #include "cutrace_rays.h"
+#include "ray_cross.h"
 #include "ray_hits.h"
 #include "ray_nearest.h"
 #include "ray_points.h"
@@ -61,6 +64,14 @@ DScene fill_lit(Launch &L, const ctr_scene *s, uint32_t flags, uint32_t exact_po
 int lds_fail(const std::string &who, const std::string &what, size_t bytes, size_t most, const char *way_out) {
   return fail(CTR_E_INVALID, who + what + " " + std::to_string(bytes) + " bytes of LDS per workgroup, more than " + std::to_string(most) +
                                  " (" + way_out + ")");
+}
+
+// CTR_E_INVALID "<who>object <i> outside [-1, <objects>)" unless `object` is -1 or names an object of the scene
+int check_object(const ctr_scene *s, const std::string &who, int32_t object) {
+  const size_t n_obj = s->flat.objs.size();
+  if (object < -1 || (object >= 0 && (size_t)object >= n_obj))
+    return fail(CTR_E_INVALID, who + "object " + std::to_string(object) + " outside [-1, " + std::to_string(n_obj) + ")");
+  return CTR_OK;
 }
 
 }  // namespace
@@ -231,9 +242,7 @@ extern "C" int ctr_nearest_points(ctr_scene *s, const ctr_nearest_query *q, void
   if (int st = check_query(s, {who, q->flags, CTR_NEAREST_LINEAR | CTR_NEAREST_SKIP_PLANES, broken, q->n_points, "n_points",
                                q->d_point != nullptr, "null d_point"}))
     return st;
-  const size_t n_obj = s->flat.objs.size();
-  if (q->object < -1 || (q->object >= 0 && (size_t)q->object >= n_obj))
-    return fail(CTR_E_INVALID, who + "object " + std::to_string(q->object) + " outside [-1, " + std::to_string(n_obj) + ")");
+  if (int st = check_object(s, who, q->object)) return st;
   if (q->n_points == 0) return CTR_OK;
   const NamedPtr ptrs[] = {{q->d_point, "d_point"}, {q->d_max_dist, "d_max_dist"}, {q->d_distance, "d_distance"}, {q->d_object, "d_object"},
                            {q->d_prim, "d_prim"}, {q->d_nearest, "d_nearest"}, {q->d_normal, "d_normal"}};
@@ -253,4 +262,81 @@ extern "C" int ctr_nearest_points(ctr_scene *s, const ctr_nearest_query *q, void
   L.nearest = q->d_nearest;
   L.normal = q->d_normal;
   return launched(ctr_launch_nearest(L, hip_stream), "nearest point kernel launch");
+}
+
+extern "C" int ctr_count_crossings(ctr_scene *s, const ctr_crossing_query *q, void *hip_stream) {
+  const std::string who = "ctr_count_crossings: ";
+  if (!q) return fail(CTR_E_INVALID, who + "null query");
+  const char *broken = "";
+  if (!q->d_count && !q->d_signed) broken = "no output: one of d_count and d_signed is required";
+  if (int st = check_query(s, {who, q->flags, CTR_CROSS_LINEAR | CTR_CROSS_SKIP_PLANES | CTR_CROSS_SKIP_TRIANGLES, broken, q->n_rays, "n_rays",
+                               q->d_origin && q->d_dir, "null rays"}))
+    return st;
+  if (int st = check_object(s, who, q->object)) return st;
+  if (q->n_rays == 0) return CTR_OK;
+  const NamedPtr ptrs[] = {{q->d_origin, "d_origin"}, {q->d_dir, "d_dir"}, {q->d_min_t, "d_min_t"}, {q->d_max_t, "d_max_t"},
+                           {q->d_count, "d_count"}, {q->d_signed, "d_signed"}};
+  if (int st = check_device_pointers(s->device, who, ptrs)) return st;
+  if (int st = use_device(s)) return st;
+  CrossLaunch L{};
+  L.scene = ray_scene(s, device_scene(s));
+  L.n_rays = (uint32_t)q->n_rays;
+  L.flags = q->flags;
+  L.only = q->object;
+  L.min_t = q->min_t;
+  L.max_t = q->max_t;
+  L.origin = q->d_origin;
+  L.dir = q->d_dir;
+  L.min_t_arr = q->d_min_t;
+  L.max_t_arr = q->d_max_t;
+  L.count = q->d_count;
+  L.sgn = q->d_signed;
+  return launched(ctr_launch_cross(L, hip_stream), "crossing count kernel launch");
+}
+
+extern "C" int ctr_inside_points(ctr_scene *s, const ctr_inside_query *q, void *hip_stream) {
+  const std::string who = "ctr_inside_points: ";
+  if (!q) return fail(CTR_E_INVALID, who + "null query");
+  std::string broken;
+  if (q->n_dirs > CTR_INSIDE_MAX_DIRS || (q->n_dirs && q->n_dirs % 2u == 0u))
+    broken = "n_dirs " + std::to_string(q->n_dirs) + " is not 0 or an odd number up to " + std::to_string(CTR_INSIDE_MAX_DIRS);
+  else if (q->n_dirs && !q->dirs) broken = "null dirs with n_dirs " + std::to_string(q->n_dirs);
+  else if (!q->d_inside && !q->d_votes && !q->d_distance) broken = "no output: one of d_inside, d_votes and d_distance is required";
+  InsideLaunch L{};
+  if (broken.empty()) {
+    L.n_dirs = q->n_dirs ? q->n_dirs : 3u;
+    const float *dirs = q->n_dirs ? q->dirs : CROSS_DEFAULT_DIRS;
+    for (uint32_t k = 0; k < L.n_dirs && broken.empty(); k++) {
+      const float *d = dirs + 3 * k;
+      if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2]) || (d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f))
+        broken = "direction " + std::to_string(k) + " is not finite or is all zero";
+      for (int c = 0; c < 3; c++) L.dirs[3 * k + c] = d[c];
+    }
+  }
+  if (int st = check_query(s, {who, q->flags, CTR_INSIDE_LINEAR, broken, q->n_points, "n_points", q->d_point != nullptr, "null d_point"}))
+    return st;
+  if (int st = check_object(s, who, q->object)) return st;
+  if (q->object >= 0) {
+    const uint32_t type = s->flat.objs[(size_t)q->object].type;
+    if (type != CTR_OBJ_MESH && type != CTR_OBJ_SPHERE)
+      return fail(CTR_E_INVALID, who + "object " + std::to_string(q->object) + " is a " + (type == CTR_OBJ_PLANE ? "plane" : "stand-alone triangle") +
+                                     ": only a mesh or a sphere bounds anything");
+  }
+  if (q->n_points == 0) return CTR_OK;
+  const NamedPtr ptrs[] = {{q->d_point, "d_point"}, {q->d_inside, "d_inside"}, {q->d_votes, "d_votes"}, {q->d_distance, "d_distance"}};
+  if (int st = check_device_pointers(s->device, who, ptrs)) return st;
+  if (int st = use_device(s)) return st;
+  L.scene = ray_scene(s, device_scene(s));
+  L.n_points = (uint32_t)q->n_points;
+  L.flags = q->flags;
+  L.only = q->object;
+  L.point = q->d_point;
+  L.inside = q->d_inside;
+  L.votes = q->d_votes;
+  L.distance = q->d_distance;
+  return launched(ctr_launch_inside(L, hip_stream), "inside kernel launch");
+}
+
+extern "C" void ctr_inside_default_dirs(float out[9]) {
+  for (int k = 0; k < 9; k++) out[k] = CROSS_DEFAULT_DIRS[k];
 }

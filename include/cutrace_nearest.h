@@ -4,7 +4,7 @@
  *
  * The ray queries (cutrace_rays.h, cutrace_hits.h) answer what lies along a ray; this one answers how far a point is from
  * the scene and where the scene is nearest (Embree's rtcPointQuery, Open3D's compute_closest_points): distance fields,
- * snapping, contacts — and, with ctr_list_hits' crossing parity, a sign for the distance.  For point i:
+ * snapping, contacts — and, with ctr_inside_points (cutrace_inside.h), a sign for the distance.  For point i:
  *
  *   every admitted object yields a candidate (d2, q): the squared distance and the closest point on the object
  *       triangle (stand-alone or of a mesh): the closest point of the triangle, Ericson's region test

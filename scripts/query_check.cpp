@@ -1,14 +1,14 @@
 // query_check.cpp — the host glue of the ray queries that needs no device, as a program of its own (meant for ASan/UBSan; the
 // record of a run: profiles/query_path/sanitizers.txt): the pointer classifier of ctr_scene.cpp and what is written on top of it
 // (memory_kind, is_pinned, all_pinned, check_device_pointers), launched(), walk_stack_bytes and the two *_lds_bytes rules of
-// ray_query.h / ray_shade.hip / ray_points.hip, and the checks ctr_cast_rays, ctr_shade_rays, ctr_shade_points, ctr_list_hits and
-// ctr_nearest_points make before they look at the scene.  Without a device the runtime knows no pointer: everything is HOST_OTHER, which is the path that
+// ray_query.h / ray_shade.hip / ray_points.hip, and the checks ctr_cast_rays, ctr_shade_rays, ctr_shade_points, ctr_list_hits,
+// ctr_nearest_points, ctr_count_crossings and ctr_inside_points make before they look at the scene.  Without a device the runtime knows no pointer: everything is HOST_OTHER, which is the path that
 // swallows the runtime's error.  Linked with ctr_scene.cpp, ctr_rays.cpp, the query .hip files (ray_query, ray_shade, ray_points,
-// ray_hits and ray_nearest since ctr_rays.cpp holds ctr_list_hits and ctr_nearest_points: their host halves are what is checked; no
-// check gets as far as a launch) and the host files those need:
+// ray_hits, ray_nearest and ray_cross since ctr_rays.cpp holds ctr_list_hits, ctr_nearest_points, ctr_count_crossings and
+// ctr_inside_points: their host halves are what is checked; no check gets as far as a launch) and the host files those need:
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -ffp-contract=off -pthread -Wno-unused-function -Icutrace_amd/csrc -Iinclude
 //     -o query_check scripts/query_check.cpp cutrace_amd/csrc/{ctr_scene.cpp,ctr_rays.cpp,ray_query.hip,ray_shade.hip,ray_points.hip,
-//     ray_hits.hip,ray_nearest.hip,guard_scan.hip,scene_flatten.cpp,guard.cpp,bvh.cpp}
+//     ray_hits.hip,ray_nearest.hip,ray_cross.hip,guard_scan.hip,scene_flatten.cpp,guard.cpp,bvh.cpp}
 //
 //   query_check        prints "query_check: ok" and returns 0, or says what differed and returns 1
 #include <cstdio>
@@ -19,6 +19,7 @@
 
 #include "ctr_internal.h"
 #include "cutrace_hits.h"
+#include "cutrace_inside.h"
 #include "cutrace_nearest.h"
 #include "cutrace_rays.h"
 #include "ray_points.h"
@@ -116,6 +117,45 @@ int main() {
   expect_error(ctr_nearest_points(nullptr, &n, nullptr), "ctr_nearest_points: unknown flag bits 4");
   n.flags = CTR_NEAREST_LINEAR | CTR_NEAREST_SKIP_PLANES; n.d_distance = nullptr;
   expect_error(ctr_nearest_points(nullptr, &n, nullptr), "ctr_nearest_points: no output: one of d_distance, d_object, d_prim, d_nearest and d_normal is required");
+
+  // ---- the inside queries (include/cutrace_inside.h) ----
+  expect_error(ctr_count_crossings(nullptr, nullptr, nullptr), "ctr_count_crossings: null query");
+  ctr_crossing_query c{};
+  c.n_rays = 2; c.object = -1; c.max_t = 1.0f; c.d_origin = some_ptr; c.d_dir = some_ptr; c.d_count = (int32_t *)some_ptr;
+  expect_error(ctr_count_crossings(nullptr, &c, nullptr), "ctr_count_crossings: null scene");
+  c.flags = 8 | CTR_CROSS_LINEAR;
+  expect_error(ctr_count_crossings(nullptr, &c, nullptr), "ctr_count_crossings: unknown flag bits 8");
+  c.flags = CTR_CROSS_LINEAR | CTR_CROSS_SKIP_PLANES | CTR_CROSS_SKIP_TRIANGLES; c.d_count = nullptr;
+  expect_error(ctr_count_crossings(nullptr, &c, nullptr), "ctr_count_crossings: no output: one of d_count and d_signed is required");
+  c.d_signed = (int32_t *)some_ptr;
+  expect_error(ctr_count_crossings(nullptr, &c, nullptr), "ctr_count_crossings: null scene");
+  expect_error(ctr_inside_points(nullptr, nullptr, nullptr), "ctr_inside_points: null query");
+  ctr_inside_query in{};
+  in.n_points = 2; in.object = -1; in.d_point = some_ptr; in.d_inside = (uint8_t *)some_ptr;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: null scene");
+  in.flags = 2;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: unknown flag bits 2");
+  in.flags = CTR_INSIDE_LINEAR; in.n_dirs = 2;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: n_dirs 2 is not 0 or an odd number up to 15");
+  in.n_dirs = 17;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: n_dirs 17 is not 0 or an odd number up to 15");
+  in.n_dirs = 15;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: null dirs with n_dirs 15");
+  std::vector<float> table(45, 0.5f);   // exactly 15 directions: the copy reads all of them and nothing behind
+  in.dirs = table.data();
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: null scene");
+  table[42] = table[43] = table[44] = 0.0f;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: direction 14 is not finite or is all zero");
+  table[3] = 1.0f / 0.0f;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: direction 1 is not finite or is all zero");
+  in.n_dirs = 1; in.d_inside = nullptr;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: no output: one of d_inside, d_votes and d_distance is required");
+  in.d_distance = some_ptr;
+  expect_error(ctr_inside_points(nullptr, &in, nullptr), "ctr_inside_points: null scene");
+  float def[9];
+  ctr_inside_default_dirs(def);
+  expect(def[0] == 0.3713907f && def[4] == 0.7462025f && def[8] == -0.5345225f, "ctr_inside_default_dirs");
+  for (int k = 0; k < 9; k++) expect(def[k] != 0.0f, "a default direction with a zero component");
 
   if (!failures) printf("query_check: ok\n");
   return failures ? 1 : 0;
