@@ -507,6 +507,13 @@ class DeviceScene:
         _check("ctr_debug_last_opaque", _lib.hip_lib().ctr_debug_last_opaque(self._h, C.byref(opaque)))
         return int(opaque.value)
 
+    def last_phased(self):
+        """Whether the handle's most recent launch ran the phased twin of its opaque build (ctr_debug_last_phased): 1 for every
+        opaque build unless the handle was created under CUTRACE_NO_PHASE_SPLIT=1, else 0."""
+        phased = C.c_uint32()
+        _check("ctr_debug_last_phased", _lib.hip_lib().ctr_debug_last_phased(self._h, C.byref(phased)))
+        return int(phased.value)
+
     def room_facts(self):
         """The room facts of the handle's most recent launch (ctr_debug_room_facts): all zero, or what lets any-hit shadow trips
         from inside a plane room skip their plane tests."""

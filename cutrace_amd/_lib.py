@@ -207,6 +207,7 @@ HIP_PROTOS = {
         "ctr_debug_last_kernel": ([_ptr, _P(_u32)], _int),
         "ctr_debug_last_shape": ([_ptr, _P(_u32)], _int),
         "ctr_debug_last_opaque": ([_ptr, _P(_u32)], _int),
+        "ctr_debug_last_phased": ([_ptr, _P(_u32)], _int),
         "ctr_debug_room_facts": ([_ptr, _ptr, _P(_u32)], _int),
         "ctr_debug_dark_skip": ([_ptr, _P(_u32)], _int),
         "ctr_multi_create": ([_P(SceneDesc), _P(_int), _int, _P(_ptr)], _int),

@@ -137,6 +137,7 @@ struct ctr_scene {
   bool no_wall_skip = false;   // CUTRACE_NO_WALL_SKIP=1 when the handle was created: every launch carries zero room facts (scene_device.h)
   bool no_dark_skip = false;   // CUTRACE_NO_DARK_SKIP=1 when the handle was created: every launch carries a zero dark-skip word (scene_device.h)
   bool no_opaque_build = false; // CUTRACE_NO_OPAQUE_BUILD=1 when the handle was created: no launch takes an opaque build (kernel_choice.h KO_*)
+  bool no_phase_split = false;  // CUTRACE_NO_PHASE_SPLIT=1 when the handle was created: no launch takes a phased build (kernel_choice.h phased_build)
   struct RoomWords { float c[3], r, delta; uint32_t lights; } last_room{};  // the room facts of the most recent launch (ctr_debug_room_facts)
   uint32_t last_dark_skip = 0;  // its dark-skip word (ctr_debug_dark_skip)
   // cached device outputs for the host-buffer form: ONE allocation of 7 floats per pixel, a call's buffers are its
@@ -153,6 +154,7 @@ struct ctr_scene {
   uint32_t last_kernel = 0;        // the KV of the most recent launch (ctr_debug_last_kernel)
   uint32_t last_shape = 0;         // its launch shape, KS_* of kernel_choice.h (ctr_debug_last_shape)
   uint32_t last_opaque = 0;        // its opaque build, KO_* of kernel_choice.h (ctr_debug_last_opaque)
+  uint32_t last_phased = 0;        // 1: it ran the phased twin of that opaque build (ctr_debug_last_phased)
   // tile scheduling feedback (include/cutrace_amd.h "Tile scheduling"; tile_order_policy.h, tile_order_host.cpp)
   OrderState order;
   GrowBuf d_cost{sizeof(uint32_t)}, d_order{sizeof(uint32_t)};  // order.cap tiles each

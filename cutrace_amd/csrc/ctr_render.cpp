@@ -179,6 +179,7 @@ void set_root_and_head(const ctr_scene *s, RenderLaunch &L, bool merged) {
   if (!s->no_scene_head) fill_scene_head(s->flat, L.scene.tlas_root, L.head);
   L.no_shape = s->no_shape_build ? 1u : 0u;
   L.no_opaque = s->no_opaque_build ? 1u : 0u;
+  L.no_phase_split = s->no_phase_split ? 1u : 0u;
   // the room facts only where the launch's kernel reads them (render_kernel.hip "room-safe lanes"): the one-mesh shape of the
   // any-hit builds, which then runs with the code that uses them, and the any-hit statistics builds; zero for every other launch
   if ((L.variant & KV_ANYHIT) && (ctr_launch_shape(L) == KS_ONE_MESH || (L.variant & KV_STATS))) fill_room_facts(s->flat, L.head, s->no_wall_skip);
@@ -354,6 +355,7 @@ int render_device(ctr_scene *s, const RenderCall &c) {
     s->last_kernel = L.variant;
     s->last_shape = ctr_launch_shape(L);
     s->last_opaque = ctr_launch_opaque(L);
+    s->last_phased = ctr_launch_phased(L);
     s->last_room = room_words(L);
     s->last_dark_skip = (L.head.mesh_dark & CTR_HEAD_DARK) ? 1u : 0u;
   }
@@ -396,6 +398,7 @@ int render_host(ctr_scene *s, const RenderCall &c) {
   set_root_and_head(s, L, choice.merged);
   s->last_shape = ctr_launch_shape(L);
   s->last_opaque = ctr_launch_opaque(L);
+  s->last_phased = ctr_launch_phased(L);
   s->last_room = room_words(L);
   s->last_dark_skip = (L.head.mesh_dark & CTR_HEAD_DARK) ? 1u : 0u;
   if ((st = attach_order(s, L, big_mesh(s), c.count))) return st;

@@ -299,6 +299,7 @@ int ctr_scene_create(const ctr_scene_desc *d, int device, ctr_scene **out) {
   s->no_wall_skip = env_switch("CUTRACE_NO_WALL_SKIP");      // no shadow trip skips its plane tests
   s->no_dark_skip = env_switch("CUTRACE_NO_DARK_SKIP");      // no shadow cast is left out for a light that cannot change the pixel
   s->no_opaque_build = env_switch("CUTRACE_NO_OPAQUE_BUILD");  // the parent instantiation of every one-mesh launch
+  s->no_phase_split = env_switch("CUTRACE_NO_PHASE_SPLIT");     // the opaque builds as they are without their phased twins
 
   if (int st = upload_scene(s, F)) {
     ctr_scene_destroy(s);
@@ -416,6 +417,13 @@ int ctr_debug_last_opaque(ctr_scene *s, uint32_t *opaque) {
   if (!s || !opaque) return fail(CTR_E_INVALID, "ctr_debug_last_opaque: null argument");
   std::lock_guard<std::mutex> lk(s->mtx);
   *opaque = s->last_opaque;
+  return CTR_OK;
+}
+
+int ctr_debug_last_phased(ctr_scene *s, uint32_t *phased) {
+  if (!s || !phased) return fail(CTR_E_INVALID, "ctr_debug_last_phased: null argument");
+  std::lock_guard<std::mutex> lk(s->mtx);
+  *phased = s->last_phased;
   return CTR_OK;
 }
 

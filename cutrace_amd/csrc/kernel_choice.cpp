@@ -49,6 +49,8 @@ uint32_t opaque_build(uint32_t kv, uint32_t shape, bool no_opaque) {
   return !no_opaque && shape == KS_ONE_MESH && (kv & KV_ANYHIT) ? KO_OPAQUE : KO_PARENT;
 }
 
+bool phased_build(uint32_t opq, bool no_phase_split) { return !no_phase_split && opq == KO_OPAQUE; }
+
 uint32_t launch_shape(uint32_t kv, uint32_t n_oloop, bool head_mesh) {
   if (!head_mesh || n_oloop != 0u) return KS_GENERAL;
   switch (kv) {

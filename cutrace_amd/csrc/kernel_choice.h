@@ -86,6 +86,14 @@ enum : uint32_t { KO_PARENT = 0u, KO_OPAQUE = 1u };
 // is), KO_PARENT for everything else.  The stack plays no part: an opaque build asks for the LDS of its parent twin.
 uint32_t opaque_build(uint32_t kv, uint32_t shape, bool no_opaque);
 
+// The phased build: a sixth template parameter of render_kernel<KV, SHAPE, ROOM, OPQ, DARK, PHASED>, decided per LAUNCH like the
+// opaque build and, like it, not a KV bit (ctr_debug_last_phased reads it back).  In an opaque build all active lanes of a wave
+// cast for the same reason and towards the same light in every trip (render_kernel.hip "Phased builds"); the phased twin of an
+// opaque build keeps that as scalar state and compiles a radiance trip and a shadow trip apart.
+// The phased build of a launch whose opaque build is `opq` (opaque_build); no_phase_split: the handle was created under
+// CUTRACE_NO_PHASE_SPLIT=1.  True exactly when opq is KO_OPAQUE and the switch is unset.
+bool phased_build(uint32_t opq, bool no_phase_split);
+
 // The recursion stack of a launch: `frames` frames of `nf` floats per lane (render_kernel.hip KArgs::frames, ::nf).
 struct StackShape {
   uint32_t frames, nf;

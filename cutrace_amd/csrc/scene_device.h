@@ -239,6 +239,7 @@ struct RenderLaunch {
   float ray_ambient;
   uint32_t no_shape;  // 1: the launch takes the general build whatever its scene (kernel_choice.h launch_shape; CUTRACE_NO_SHAPE_BUILD)
   uint32_t no_opaque; // 1: the launch takes no opaque build (kernel_choice.h opaque_build; CUTRACE_NO_OPAQUE_BUILD)
+  uint32_t no_phase_split; // 1: the launch takes no phased build (kernel_choice.h phased_build; CUTRACE_NO_PHASE_SPLIT)
 };
 
 // keeps `msg` for ctr_last_error() (ctr_scene.cpp); used by the other translation units of the library
@@ -249,6 +250,8 @@ int ctr_launch_render(const RenderLaunch &L, void *stream);
 uint32_t ctr_launch_shape(const RenderLaunch &L);
 // the opaque build ctr_launch_render gives this launch (kernel_choice.h KO_*)
 uint32_t ctr_launch_opaque(const RenderLaunch &L);
+// 1: ctr_launch_render gives this launch the phased twin of its opaque build (kernel_choice.h phased_build)
+uint32_t ctr_launch_phased(const RenderLaunch &L);
 // counters are accumulated in CTR_SHARDS 128-byte shards (see render_kernel.hip) and folded afterwards (tile_order.hip after_render)
 #define CTR_SHARDS 1024
 #define CTR_SHARD_WORDS 16

@@ -330,6 +330,12 @@ int ctr_debug_last_shape(ctr_scene *scene, uint32_t *shape);
  * results bit for bit.  CUTRACE_NO_OPAQUE_BUILD=1 in the environment when a handle is created keeps that handle's launches
  * at 0 (A/B timing, tests). */
 int ctr_debug_last_opaque(ctr_scene *scene, uint32_t *opaque);
+/* Diagnostic: whether that launch ran the phased twin of its opaque build (csrc/kernel_choice.h phased_build): 1 for every
+ * launch of an opaque build (ctr_debug_last_opaque 1), 0 otherwise.  In an opaque build all active lanes of a wave cast for the
+ * same reason and towards the same light in every trip; the phased twin keeps the kind of the trip as scalar state and holds
+ * a radiance trip and a shadow trip as code of their own — the same results, ray counts and counters bit for bit.
+ * CUTRACE_NO_PHASE_SPLIT=1 in the environment when a handle is created keeps that handle's launches at 0 (A/B timing, tests). */
+int ctr_debug_last_phased(ctr_scene *scene, uint32_t *phased);
 /* Diagnostic: the room facts of that launch (csrc/scene_device.h DSceneHead::room_*; DESIGN.md "Shadow casts from inside a plane
  * room").  out5 = the origin box's centre (3), its half width, the numerator tolerance; *lights = the bits of the point lights
  * that qualify.  Non-zero only for a launch whose kernel reads them — the one-mesh shape (ctr_debug_last_shape 1) of an any-hit

@@ -10,7 +10,8 @@ Cross-checks against PMC passes of the shipped build (same scene): the VALU tota
 against SQ_ACTIVE_INST_VALU - SQ_INSTS_VALU (a transcendental holds the pipe two quad-cycles), SALU against SQ_INSTS_SALU.
 
 usage: dynamic_mix.py <marks.s> <variant>[,<shape>] <counts.json> [--pmc counters.json] [--out mix.json]
-(<variant> alone: the general launch shape; "107,1": render_kernel<107u, 1u>, the one-mesh shape of kernel_choice.h)"""
+(<variant> alone: the general launch shape; "107,1": render_kernel<107u, 1u>, the one-mesh shape of kernel_choice.h;
+"107,1,1,1,1,1": render_kernel<107u, 1u, ROOM, OPQ, DARK, PHASED> spelled out — a phased build's shadow trip has the ids 128 + n)"""
 import json, re, sys
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.abspath(__file__)))
 from valu_mix import classify, F, H, Q
@@ -21,7 +22,10 @@ def kernel_names(kv):
     and render_kernel<107u, 0u> (the general launch shape); "107,1": render_kernel<107u, 1u> (kernel_choice.h KS_ONE_MESH)"""
     build, _, shape = str(kv).partition(",")
     pre = "_ZN12_GLOBAL__N_113render_kernelILj%sE" % build
-    return (pre + "Lj%sEEE" % shape,) if shape else (pre + "EE", pre + "Lj0EEE")
+    if shape.count(",") == 4:   # "107,1,1,1,1,1": render_kernel<107u, 1u, ROOM, OPQ, DARK, PHASED>, e.g. the phased flagship
+        s, room, opq, dark, phased = shape.split(",")
+        return (pre + "Lj%sELb%sELj%sELb%sELb%sEEE" % (s, room, opq, dark, phased),)
+    return (pre + "Lj%sEEE" % shape, pre + "Lj%sELb0ELj0ELb0ELb0EEE" % shape) if shape else (pre + "EE", pre + "Lj0EEE", pre + "Lj0ELb0ELj0ELb0ELb0EEE")
 
 
 def kernel_body(path, kv):

@@ -18,14 +18,14 @@ for name, path, b, wl in todo:
     s = ca.HostScene.load(path)
     ds = ca.DeviceScene(s)
     ds.render(bounces=b)
-    out = np.zeros(128, np.uint64)
+    out = np.zeros(256, np.uint64)  # (ids from 128 on: the shadow copy of a phased build)
     assert L.ctr_debug_profile_read(out.ctypes.data, 1) == 0
     N = 3
     rays = 0
     for _ in range(N):
         rays = ds.render(bounces=b)["ray_count"]
     assert L.ctr_debug_profile_read(out.ctypes.data, 1) == 0
-    per = {str(i): float(out[i]) / N for i in range(128) if out[i]}
+    per = {str(i): float(out[i]) / N for i in range(256) if out[i]}
     json.dump({"workload": wl, "launches": N, "rays": rays, "per_launch": per}, open(os.path.join(ROOT, "gpurun_out", f"profile_counts_{name}.json"), "w"), indent=1)
     print(name, "waves", per.get("0"), "trips", per.get("1"), "nodes", per.get("32"), "prefilters", per.get("23"), "exact", per.get("28"), "unwind", per.get("53"), flush=True)
     ds.close()
